@@ -17,7 +17,15 @@ script itself, which then starts N children BEFORE it touches the GPU and relays
 `--dry-run` rehearses exactly that launch on CPU (gloo, no HIP call, no compute): shard sizes,
 barrier/max timing and the gather, so the N-rank plumbing is testable without GPUs.
 
-Prints ONE JSON line (rank 0) with the contract's fields plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the contract's fields.  A plain run does only what `value` and `ms_per_step` need:
+cards, upload, warm-up, the timed steps, the result line.  `--full` adds everything else the bench measures or checks:
+the rocprofv3 counter passes, the deskew legs, the roofline leg, the accuracy check against the injected angles, the
+CPU baseline with its parity scans and the host-memory end-to-end leg (`roofline`, `cpu_baseline`, `deskew*`,
+`e2e_host*`, `accuracy_ok`).
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the path receives it, rank 0's shard:
+DIR/best_index.npy (arg-max index per scan), DIR/v_sd.npy and DIR/h_sd.npy (the std-dev score of every candidate per
+scan), all float64 (3.3 MB at the default 512 scans).  The cards are seeded, so the same arguments give the same inputs.
 
 roofline: the sweep kernel never moves SURVEY 8(d)'s algorithmic bytes through HBM (the scan is a
 1-bit/px image staged in LDS, 32 px per lane-operation), so that figure is kept as the labelled side
@@ -81,6 +89,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 counter passes")
     ap.add_argument("--no-deskew", action="store_true", help="skip the legs that also produce the deskewed images")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-memory end-to-end leg (e2e_host_images_per_s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks (counter passes, deskew legs, roofline, accuracy, "
+                         "CPU baseline, host-memory leg); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (best_index, v_sd, h_sd; float64 .npy) into DIR")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the N-rank launch (gloo, no GPU work)")
     ap.add_argument("--share-gpus", action="store_true",
                     help="rehearsal on a box with fewer GPUs than ranks: rank r computes on device r %% device_count and the "
@@ -353,6 +366,13 @@ def e2e_host(cards, B, order, repeats=3):
     return out, ref
 
 
+def dump_outputs(d, best, vs, hs):
+    """--dump-outputs: the arrays omr_batch_run_device hands its caller after the last timed step, as float64 .npy"""
+    os.makedirs(d, exist_ok=True)
+    for name, t in (("best_index", best), ("v_sd", vs), ("h_sd", hs)):
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 def pmc_passes(args, cards_path, workdir):
     """HBM + SQ counter passes of the sweep kernel, each a rocprofv3 child running this script with
     --pmc-child on the same cards (started before this process touches the GPU)."""
@@ -408,7 +428,7 @@ def main():
         cards, thetas = make_cards(D, 2 + rank_env * D)  # seed 2 = C2's card
     pmc_res = None
     tmpdir = None
-    if world_env == 1 and not args.pmc_child and not args.no_pmc:
+    if args.full and world_env == 1 and not args.pmc_child and not args.no_pmc:
         tmpdir = tempfile.mkdtemp(prefix="omr_bench_pmc_", dir="/tmp")
         cards_path = os.path.join(tmpdir, "cards.npy")
         np.save(cards_path, cards)
@@ -483,9 +503,24 @@ def main():
         print(json.dumps({"pmc_child": True, "steps": args.steps}))
         return
 
+    if args.dump_outputs and rank == 0:  # before any side leg launches the sweep again
+        dump_outputs(args.dump_outputs, best, vs, hs)
+
     # the path's only exchange: gather of the per-scan results (outside the per-step loop, as in
     # a real batch job where it happens once)
     all_best = odist.gather_results(best.to(xdev), B * world, rank, world)
+
+    if not args.full:
+        batch.close()
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        if rank == 0:
+            out = base_record(args, world, B * world * args.steps / elapsed, elapsed, B, A, G, D,
+                              "scan-lane" if lanes_mode else "run-merging")
+            out["gathered_results"] = int(all_best.numel())
+            print(json.dumps(out))
+        return
 
     # ---- the whole unit of work of the reference (omr.rs:339-452, core/src/main.rs:69-92): the same steps with the
     # deskewed image produced INSIDE the timed region -- sweep -> arg-max -> CONTAIN warp by the detected angle

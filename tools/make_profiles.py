@@ -101,7 +101,7 @@ def hbm_table(fetch_sub, write_sub, f, needles=None, bytes_of=None):
 line = last_json(read("bench_line.json"))
 json.dump(line, open(os.path.join(dst, tag + "_bench_line.json"), "w"), indent=1)
 with open(os.path.join(dst, tag + "_rocprofv3_kernel_stats_bench.md"), "w") as f:
-    f.write("# %s -- `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-pmc`\n\n" % tag + STAMP)
+    f.write("# %s -- `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-pmc`\n\n" % tag + STAMP)
     f.write("Default bench: %d scans per GPU per step (%d distinct cards), %d scans per kernel launch (sweep kernel: %s), 1 sweep "
             "stream + 1 post stream; the `value` leg (angle detection) is followed by the two deskew legs (`deskew_warp_kernel<true>` "
             "= LINEAR, `<false>` = NEAREST; they share the chip with the sweep of the next launch, so their durations here are "

@@ -36,14 +36,14 @@ elif [ "$PART" = "a" ]; then
   rm -f "$OUT/STATUS_$PART"
   # 1. the bench line exactly as the driver runs it (its own FETCH_SIZE / WRITE_SIZE / SQ child passes included)
   rm -f "$OUT/bench_line.json" "$OUT/bench_line.err"; rm -rf "$OUT/bench_pmc" gpurun_out/bench_pmc
-  timeout -k 10 900 python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"; echo "bench_line rc=$?" >> "$OUT/STATUS_$PART"
+  timeout -k 10 900 python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"; echo "bench_line rc=$?" >> "$OUT/STATUS_$PART"
   cp -r gpurun_out/bench_pmc "$OUT/bench_pmc" 2>/dev/null || true
   echo "[profile] bench line done"
   # 2. kernel stats of the same command (no counters in this run).  The cards are made BEFORE the profiled run and
   # handed over by --cards: the program under `--` creates no child process (bench.py's card pool forks workers)
   rm -f "$OUT/cards.npy"
   python3 -c "import sys; sys.argv=['x']; import numpy as np, bench; c,_=bench.make_cards(64, 2); np.save('$OUT/cards.npy', c)" > "$OUT/cards.log" 2>&1; echo "cards rc=$?" >> "$OUT/STATUS_$PART"
-  prof stats --stats -- python3 bench.py --no-cpu-baseline --no-pmc --no-e2e --cards "$OUT/cards.npy"
+  prof stats --stats -- python3 bench.py --full --no-cpu-baseline --no-pmc --no-e2e --cards "$OUT/cards.npy"
   rm -f "$OUT/cards.npy"
   echo "[profile] kernel stats done"
   # 3a. the scan-lane sweep kernel (one launch of 512 scans): timings, counters (tools/pmc_lanes.sh: six passes)
