@@ -194,6 +194,25 @@ int omr_batch_deskew_device(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t 
                             int64_t step_bytes, int32_t n, int32_t black_max, int32_t interp,
                             uint8_t border_value, uint8_t *d_out, int64_t out_stride_bytes,
                             int64_t out_step_bytes, int32_t *d_out_size, int32_t *d_best_idx);
+/* omr_batch_run_device / omr_batch_deskew_device for scans of `channels` interleaved 8-bit channels.
+ * channels = 3: BGR as imread(IMREAD_COLOR) gives it; gray = cvtColor(COLOR_RGB2GRAY) fused into the load
+ * (projection.rs:29-32, quirk B8); a pixel is black iff gray <= black_max.  channels = 1: identical to the
+ * 1-channel entry points.  Other counts: OMR_ERR_NOTIMPL.  black_max outside 0..255: OMR_ERR_BADARG.
+ * Deskew: border_value[0..channels-1] per channel; every output slot holds the largest canvas,
+ * out_step_bytes >= channels * max_cols of omr_batch_deskew_canvas().
+ * Every argument is checked before any device work (step_bytes >= channels * cols included); no gray image is
+ * written.  Scan i's colour canvas is what omr_rotate_device(channels = 3, angle = (best_idx - N) * step, scale 1,
+ * OMR_CLIP_CONTAIN) writes for the same scan, bit for bit; the winners and scores are what the 1-channel entry
+ * points give for omr_rgb_to_gray_device of the scans.  As with omr_batch_deskew_device, the warp stages source
+ * boxes in LDS only when d_scans, scan_stride_bytes and step_bytes are multiples of 4. */
+int omr_batch_run_device_cn(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                            int64_t step_bytes, int32_t channels, int32_t n, int32_t black_max,
+                            int32_t *d_best_idx, double *d_v_sd, double *d_h_sd);
+int omr_batch_deskew_device_cn(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                               int64_t step_bytes, int32_t channels, int32_t n, int32_t black_max,
+                               int32_t interp, const uint8_t border_value[4], uint8_t *d_out,
+                               int64_t out_stride_bytes, int64_t out_step_bytes, int32_t *d_out_size,
+                               int32_t *d_best_idx);
 /* Streams and pinned staging blocks the per-call entry points lease from a bounded per-device pool (a host
  * that runs every task on a fresh OS thread, thread_pool.rs:41-88, must not leak one of each per call):
  * slots that exist, slots idle in the pool, pinned bytes held by idle slots.  Pointers may be NULL. */

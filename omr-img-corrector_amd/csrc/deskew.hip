@@ -391,8 +391,214 @@ __global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const D
     }
 }
 
+// ---- 3 channels (BGR scans; omr_batch_deskew_device_cn).  The same records and the same per-candidate tables: one table lookup
+// and one set of bilinear weights per pixel serve its three channels.  Destination tile DW3_TW x DW3_TH = 64 x 64 pixels (192 x 64
+// bytes), 256 threads, a thread = 4 adjacent pixels (12 bytes: three dword stores) in each of 4 rows 16 apart.  The source box
+// of a 64 x 64 tile at 10 degrees is about 78 x 78 pixels = 234 x 78 bytes = 18.3 KB: DW3_LDS = 24 KB stages every interior
+// tile of an A4 scan up to about +-14 degrees (the gray kernel's 128 x 64 tile would need about 140 x 88 x 3 = 37 KB per box,
+// and twice the staged bytes per stored byte at the edges of a row of tiles is the smaller cost: a box row is 1.2 x the tile's
+// row at 64 pixels against 1.1 x at 128).  p.border holds the border value's three bytes (channel c = byte c).
+#define DW3_TW 64
+#define DW3_TH 64
+#define DW3_LDS 24576
+
+template <bool LINEAR>
+__device__ __forceinline__ int dw3_tap_global(const uint8_t *__restrict__ src, int64_t sstep, int srows, int scols, int Xf, int Yf,
+                                              int c, int border)
+{
+    if (!LINEAR) {
+        const int X = max(-32768, min(32767, Xf >> 10)), Y = max(-32768, min(32767, Yf >> 10));
+        return ((unsigned)X < (unsigned)scols && (unsigned)Y < (unsigned)srows) ? src[(int64_t)Y * sstep + (int64_t)X * 3 + c] : border;
+    }
+    const int X = Xf >> 5, Y = Yf >> 5;
+    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
+    const int fx = X & 31, fy = Y & 31;
+    if (sx >= scols || sx + 1 < 0 || sy >= srows || sy + 1 < 0) return border;
+    const bool in_x0 = sx >= 0 && sx < scols, in_x1 = sx + 1 >= 0 && sx + 1 < scols;
+    const bool in_y0 = sy >= 0 && sy < srows, in_y1 = sy + 1 >= 0 && sy + 1 < srows;
+    const uint8_t *S = src + (int64_t)sy * sstep + (int64_t)sx * 3 + c;
+    const int v0 = in_x0 && in_y0 ? S[0] : border;
+    const int v1 = in_x1 && in_y0 ? S[3] : border;
+    const int v2 = in_x0 && in_y1 ? S[sstep] : border;
+    const int v3 = in_x1 && in_y1 ? S[sstep + 3] : border;
+    const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
+    return dw_sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
+}
+
+// one thread per (scan, tile): the DeskewTile record of a colour tile (bb0, bwb in BYTES of a source row, whole dwords)
+template <bool LINEAR>
+__global__ __launch_bounds__(64) void deskew_tiles3_kernel(const DeskewPass p, DeskewTile *__restrict__ tiles, int ntx, int nty)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x, z = blockIdx.y;
+    if (t >= ntx * nty) return;
+    const int tyi = t / ntx, txi = t - tyi * ntx;
+    const int a = p.best[z];
+    const int drows = p.wsize[2 * a], dcols = p.wsize[2 * a + 1];
+    if (t == 0 && p.out_size) {
+        p.out_size[2 * z] = drows;
+        p.out_size[2 * z + 1] = dcols;
+    }
+    DeskewTile r;
+    r.a = -1, r.bb0 = r.by0 = r.bwb = r.bh = r.a1 = r.b1 = r.last = 0;
+    const int tx0 = txi * DW3_TW, ty0 = tyi * DW3_TH;
+    if (tx0 < dcols && ty0 < drows) {
+        const int32_t *__restrict__ AD = p.adelta + (int64_t)a * p.DC, *__restrict__ BD = p.bdelta + (int64_t)a * p.DC;
+        const int2_t *__restrict__ XY = p.xy0 + (int64_t)a * p.DR;
+        const int rd = LINEAR ? 16 : 512;
+        const int tx1 = min(dcols, tx0 + DW3_TW) - 1, ty1 = min(drows, ty0 + DW3_TH) - 1;
+        const int2_t r0 = XY[ty0], r1 = XY[ty1];
+        const int a0 = AD[tx0], a1 = AD[tx1], b0 = BD[tx0], b1 = BD[tx1];
+        const int cx[4] = {(r0.x + rd + a0) >> 10, (r0.x + rd + a1) >> 10, (r1.x + rd + a0) >> 10, (r1.x + rd + a1) >> 10};
+        const int cy[4] = {(r0.y + rd + b0) >> 10, (r0.y + rd + b1) >> 10, (r1.y + rd + b0) >> 10, (r1.y + rd + b1) >> 10};
+        const int bx0 = min(min(cx[0], cx[1]), min(cx[2], cx[3])) - 1;
+        const int bx1 = max(max(cx[0], cx[1]), max(cx[2], cx[3])) + 1 + (LINEAR ? 1 : 0);
+        const int by0 = min(min(cy[0], cy[1]), min(cy[2], cy[3])) - 1;
+        const int by1 = max(max(cy[0], cy[1]), max(cy[2], cy[3])) + 1 + (LINEAR ? 1 : 0);
+        const bool sane = bx0 > -30000 && bx1 < 30000 && by0 > -30000 && by1 < 30000;
+        const int bb0 = sane ? (bx0 * 3) & ~3 : 0, bb1 = sane ? ((bx1 + 1) * 3 + 3) & ~3 : 0;  // [bb0, bb1): bytes of a row
+        const int bwb = bb1 - bb0, bh = by1 - by0 + 1;
+        // rows that are not whole aligned dwords (pitch, scan stride or address not a multiple of 4): the unstaged path
+        const bool dwords = ((p.sstep | p.scan_stride | (int64_t)(uintptr_t)p.src) & 3) == 0 && (int64_t)p.srows * p.sstep < (int64_t)0x7fffffff;
+        const bool staged = dwords && sane && bwb > 0 && bh > 0 && (int64_t)bwb * bh <= DW3_LDS;
+        const bool all_border = bx1 < 0 || by1 < 0 || bx0 >= p.scols || by0 >= p.srows;
+        r.a = a, r.bb0 = bb0, r.by0 = by0;
+        r.bwb = all_border ? 0 : staged ? bwb : -1;
+        r.bh = bh, r.last = tx1 | (ty1 << 16);
+    }
+    tiles[(int64_t)z * ntx * nty + t] = r;
+}
+
+// grid = 8 * ntx * ceil(nty / 8) * scans workgroups, the gray kernel's order 2 (XCD k warps the tile rows k, k + 8, .. of every
+// scan); the box is staged with dword loads (border bytes outside the image, channel = byte offset mod 3), a tap is LDS reads
+// with no bounds test.
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void deskew_warp3_kernel(const DeskewPass p, const DeskewTile *__restrict__ tiles)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t box[DW3_LDS];
+    const int ntx = p.ntx, nty = p.nty;
+    const int nty8 = (nty + 7) >> 3, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    const int txi = jb % ntx;
+    const int q = jb / ntx, rq = q % nty8;
+    const int z = q / nty8, tyi = rq * 8 + xcd;
+    if (tyi >= nty) return;
+    const DeskewTile *__restrict__ tr = tiles + ((int64_t)z * nty + tyi) * ntx + txi;
+    const int a = tr->a;
+    if (a < 0) return;  // outside this scan's canvas
+    const int bb0 = tr->bb0, by0 = tr->by0, bwb = tr->bwb, bh = tr->bh, last = tr->last;
+    const int tx0 = txi * DW3_TW, ty0 = tyi * DW3_TH;
+    const int tx1 = last & 0xffff, ty1 = last >> 16;
+    const uint8_t *__restrict__ src = p.src + (int64_t)z * p.scan_stride;
+    uint8_t *__restrict__ dst = p.dst + (int64_t)z * p.out_stride;
+    const int32_t *__restrict__ AD = p.adelta + (int64_t)a * p.DC, *__restrict__ BD = p.bdelta + (int64_t)a * p.DC;
+    const int2_t *__restrict__ XY = p.xy0 + (int64_t)a * p.DR;
+    const int rd = LINEAR ? 16 : 512;
+    const int x0 = tx0 + (int)(threadIdx.x & 15) * 4, yq = ty0 + (int)(threadIdx.x >> 4);
+    const uint32_t bd = (uint32_t)p.border & 0xffffffu;
+    const int bc[3] = {(int)(bd & 255u), (int)((bd >> 8) & 255u), (int)(bd >> 16)};
+    // the three dwords of four border pixels: c0 c1 c2 c0 | c1 c2 c0 c1 | c2 c0 c1 c2
+    const uint32_t bpat[3] = {bd | (bd << 24), (bd >> 8) | (bd << 16), (bd >> 16) | (bd << 8)};
+    const bool aligned4 = ((p.dstep | p.out_stride | (int64_t)(uintptr_t)p.dst) & 3) == 0;
+    const bool whole = aligned4 && x0 + 4 <= tx1 + 1;
+    if (bwb == 0) {  // every tap of the tile is border (workgroup-uniform)
+        if (x0 > tx1) return;
+        for (int k = 0; k < DW3_TH / 16; k++) {
+            const int y = yq + 16 * k;
+            if (y > ty1) break;
+            uint8_t *D = dst + (int64_t)y * p.dstep + (int64_t)x0 * 3;
+            if (whole) {
+                ((uint32_t *)D)[0] = bpat[0], ((uint32_t *)D)[1] = bpat[1], ((uint32_t *)D)[2] = bpat[2];
+            } else {
+                for (int j = 0; j < 12 && x0 * 3 + j < (tx1 + 1) * 3; j++) D[j] = (uint8_t)bc[j % 3];
+            }
+        }
+        return;
+    }
+    const bool staged = bwb > 0;
+    if (staged) {
+        const int bq = bwb >> 2, total = bq * bh;
+        const int rowb = p.scols * 3;  // bytes of a source row that hold pixels
+#pragma unroll 4
+        for (int i = threadIdx.x; i < total; i += 256) {
+            const int ly = i / bq, lq = i - ly * bq;
+            const int gy = by0 + ly, gb = bb0 + lq * 4;
+            uint32_t v;
+            if ((unsigned)gy < (unsigned)p.srows && gb >= 0 && gb + 4 <= rowb) {
+                v = *(const uint32_t *)(src + (int64_t)gy * p.sstep + gb);
+            } else {  // the box's edge dwords: border bytes outside the image (byte b of a row = channel b mod 3)
+                v = 0;
+                for (int j = 0; j < 4; j++) {
+                    const int b = gb + j;
+                    uint32_t px = (uint32_t)bc[((b % 3) + 3) % 3];
+                    if ((unsigned)gy < (unsigned)p.srows && b >= 0 && b < rowb) px = src[(int64_t)gy * p.sstep + b];
+                    v |= px << (8 * j);
+                }
+            }
+            *(uint32_t *)&box[i * 4] = v;
+        }
+    }
+    __syncthreads();
+    if (x0 > tx1) return;
+    // the thread's column table entries (x0 + 3 < DC: DC is a multiple of 4, the tables 16-byte aligned); columns past the
+    // tile's last one repeat it, so every sample lies inside the box
+    const int4 adq = *(const int4 *)(AD + x0), bdq = *(const int4 *)(BD + x0);
+    int adv[4] = {adq.x, adq.y, adq.z, adq.w}, bdv[4] = {bdq.x, bdq.y, bdq.z, bdq.w};
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+        const bool past = x0 + j > tx1;
+        adv[j] = past ? adv[j - 1] : adv[j];
+        bdv[j] = past ? bdv[j - 1] : bdv[j];
+    }
+#pragma unroll 1
+    for (int k = 0; k < DW3_TH / 16; k++) {
+        const int y = yq + 16 * k;
+        if (y > ty1) break;
+        const int2_t rw = XY[y];
+        uint32_t o[3];
+        if (!staged) {  // workgroup-uniform: rows that are not whole aligned dwords, or a box too large for LDS
+            uint8_t px[12];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    px[3 * j + c] = (uint8_t)dw3_tap_global<LINEAR>(src, p.sstep, p.srows, p.scols, rw.x + rd + adv[j], rw.y + rd + bdv[j], c, bc[c]);
+#pragma unroll
+            for (int d = 0; d < 3; d++)
+                o[d] = (uint32_t)px[4 * d] | ((uint32_t)px[4 * d + 1] << 8) | ((uint32_t)px[4 * d + 2] << 16) | ((uint32_t)px[4 * d + 3] << 24);
+        } else {
+            uint32_t px[12];
+            const int orgy = rd - (by0 << 10);  // the box's first row rides on Y0 (a multiple of 1024: the fraction bits stay)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int Xf = rw.x + rd + adv[j], Yf = rw.y + orgy + bdv[j];
+                if constexpr (!LINEAR) {
+                    const uint8_t *B = &box[dw_mad24(Yf >> 10, bwb, (Xf >> 10) * 3 - bb0)];
+                    px[3 * j] = B[0], px[3 * j + 1] = B[1], px[3 * j + 2] = B[2];
+                } else {
+                    const int X = Xf >> 5, Y = Yf >> 5;
+                    const int fx = X & 31, fy = Y & 31;
+                    const uint8_t *B = &box[dw_mad24(Y >> 5, bwb, (X >> 5) * 3 - bb0)];
+                    const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
+#pragma unroll
+                    for (int c = 0; c < 3; c++)
+                        px[3 * j + c] = (uint32_t)((B[c] * w0 + B[3 + c] * w1 + B[bwb + c] * w2 + B[bwb + 3 + c] * w3 + (1 << 14)) >> 15);
+                }
+            }
+#pragma unroll
+            for (int d = 0; d < 3; d++) o[d] = px[4 * d] | (px[4 * d + 1] << 8) | (px[4 * d + 2] << 16) | (px[4 * d + 3] << 24);
+        }
+        uint8_t *D = dst + (int64_t)y * p.dstep + (int64_t)x0 * 3;
+        if (whole) {
+            ((uint32_t *)D)[0] = o[0], ((uint32_t *)D)[1] = o[1], ((uint32_t *)D)[2] = o[2];
+        } else {
+            for (int j = 0; j < 12 && x0 * 3 + j < (tx1 + 1) * 3; j++) D[j] = (uint8_t)(o[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+}
+
 size_t deskew_tile_bytes(const DeskewPass &p, int scans)
 {
+    if (p.cn == 3)
+        return sizeof(DeskewTile) * (size_t)((p.DC + DW3_TW - 1) / DW3_TW) * (size_t)((p.DR + DW3_TH - 1) / DW3_TH) * (size_t)scans;
     // (tiles of the LINEAR kernel: the smaller tile, so the buffer serves both)
     constexpr int th = DW_TH_LIN < DW_TH_NN ? DW_TH_LIN : DW_TH_NN;
     return sizeof(DeskewTile) * (size_t)((p.DC + DW_TW - 1) / DW_TW) * (size_t)((p.DR + th - 1) / th) * (size_t)scans;
@@ -409,6 +615,20 @@ hipError_t launch_deskew_warp(const DeskewPass &p0, int scans, int interp, void 
 #endif
     if ((p.DC & 3) != 0 || !d_tiles) return hipErrorInvalidValue;
     DeskewTile *tiles = (DeskewTile *)d_tiles;
+    if (p.cn == 3) {  // BGR scans: 64 x 64 tiles, always the order-2 grid
+        const int ntx = (p.DC + DW3_TW - 1) / DW3_TW, nty = (p.DR + DW3_TH - 1) / DW3_TH;
+        p.ntx = ntx, p.nty = nty;
+        const dim3 grid(8 * ntx * ((nty + 7) / 8) * scans);
+        if (interp == 0) {
+            hipLaunchKernelGGL(deskew_tiles3_kernel<false>, dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
+            hipLaunchKernelGGL(deskew_warp3_kernel<false>, grid, dim3(256), 0, s, p, tiles);
+        } else {
+            hipLaunchKernelGGL(deskew_tiles3_kernel<true>, dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
+            hipLaunchKernelGGL(deskew_warp3_kernel<true>, grid, dim3(256), 0, s, p, tiles);
+        }
+        return hipGetLastError();
+    }
+    if (p.cn > 1) return hipErrorInvalidValue;  // (0 = 1)
     if (interp == 0) {
         constexpr bool LINEAR = false;
         const int ntx = (p.DC + DW_TW - 1) / DW_TW, nty = (p.DR + DW_TH - 1) / DW_TH;

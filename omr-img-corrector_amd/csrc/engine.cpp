@@ -609,13 +609,13 @@ int SweepScratch::create(const SweepTables &t, int scans_per_launch)
 int enqueue_sweep(const SweepTables &t, SweepScratch &s, int kernel_sel, const uint8_t *d_img, int64_t step,
                   int black_max, hipStream_t stream, uint32_t *d_vproj, uint32_t *d_hproj, double *d_v_sd,
                   double *d_h_sd, int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1, bool want_proj,
-                  hipStream_t post_stream, hipEvent_t ev_mid, int scans, int64_t img_stride)
+                  hipStream_t post_stream, hipEvent_t ev_mid, int scans, int64_t img_stride, int cn)
 {
     const SweepDims &d = t.dims;
     if (!d_img) return fail(OMR_ERR_BADARG, "null image");
     if (scans < 1 || scans > s.zmax) return fail(OMR_ERR_BADARG, "%d scans per launch, scratch holds %d", scans, s.zmax);
     if (scans > 1 && (d_vproj || d_hproj)) return fail(OMR_ERR_BADARG, "projections are returned for single-scan launches");
-    if (step < d.cols) return fail(OMR_ERR_BADARG, "step_bytes %lld < cols %d", (long long)step, d.cols);
+    if (step < (int64_t)d.cols * cn) return fail(OMR_ERR_BADARG, "step_bytes %lld < cols %d x %d channels", (long long)step, d.cols, cn);
     // which kernels sweep which candidates
     bool use_runs = false, gather_lds = t.lds_ok;
     const int32_t *glist = nullptr;  // nullptr = every candidate
@@ -645,8 +645,12 @@ int enqueue_sweep(const SweepTables &t, SweepScratch &s, int kernel_sel, const u
     if (n_g > 0 || (use_runs && t.RCHh > 1))
         OMR_HIP(hipMemsetAsync(vp, 0, sizeof(uint32_t) * (size_t)scans * d.A * d.cols, stream));
     if (n_g > 0) OMR_HIP(hipMemsetAsync(hp, 0, sizeof(uint32_t) * (size_t)scans * d.A * d.rows, stream));
-    OMR_HIP(launch_pack_bits(d_img, step, d.rows, d.cols, black_max, s.bits.as<uint32_t>(), d.wpr, stream, scans,
-                             img_stride));
+    if (cn == 1)
+        OMR_HIP(launch_pack_bits(d_img, step, d.rows, d.cols, black_max, s.bits.as<uint32_t>(), d.wpr, stream, scans,
+                                 img_stride));
+    else
+        OMR_HIP(launch_pack_bits_cn(d_img, step, cn, d.rows, d.cols, black_max, s.bits.as<uint32_t>(), d.wpr, stream, scans,
+                                    img_stride));
     if (ev0) OMR_HIP(hipEventRecord(ev0, stream));
     if (use_runs) {
         // the run-merging kernel reads word columns: the bit images once more, transposed
@@ -1055,7 +1059,7 @@ int build_deskew_tables(omr_batch_ctx *ctx)
 }
 
 int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, int64_t step_bytes, int32_t n,
-              int32_t black_max, int32_t *d_best_idx, double *d_v_sd, double *d_h_sd, const DeskewOut *dk)
+              int32_t black_max, int32_t *d_best_idx, double *d_v_sd, double *d_h_sd, const DeskewOut *dk, int cn)
 {
     const int S = (int)ctx->streams.size();
     const int A = ctx->tables.dims.A;
@@ -1087,12 +1091,12 @@ int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, i
         if (lanes)
             rc = slane_enqueue(ctx->slane, *ctx->slane_scratch[set], d_scans + (size_t)i * scan_stride, scan_stride, step_bytes, z,
                                black_max, ctx->streams[k], ctx->post_streams[k], ctx->ev_mid[set],
-                               d_v_sd ? d_v_sd + (size_t)i * A : nullptr, d_h_sd ? d_h_sd + (size_t)i * A : nullptr, best, e0, e1);
+                               d_v_sd ? d_v_sd + (size_t)i * A : nullptr, d_h_sd ? d_h_sd + (size_t)i * A : nullptr, best, e0, e1, cn);
         else
             rc = enqueue_sweep(ctx->tables, *ctx->scratch[set], KERNEL_AUTO, d_scans + (size_t)i * scan_stride,
                                step_bytes, black_max, ctx->streams[k], nullptr, nullptr,
                                d_v_sd ? d_v_sd + (size_t)i * A : nullptr, d_h_sd ? d_h_sd + (size_t)i * A : nullptr, best, e0,
-                               e1, false, ctx->post_streams[k], ctx->ev_mid[set], z, scan_stride);
+                               e1, false, ctx->post_streams[k], ctx->ev_mid[set], z, scan_stride, cn);
         if (rc) return rc;
         if (dk) {  // after the arg-max, on the post stream: overlaps the next group's sweep
             DeskewPass p{};
@@ -1113,6 +1117,7 @@ int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, i
             p.DR = ctx->dk_rows;
             p.border = dk->border;
             p.out_size = dk->d_out_size ? dk->d_out_size + 2 * (size_t)i : nullptr;
+            p.cn = cn;
             // the per-tile records: one buffer per post stream (the warps of a stream run one after the other)
             if (ctx->dk_tiles.size() < ctx->post_streams.size()) ctx->dk_tiles.resize(ctx->post_streams.size());
             if (!ctx->dk_tiles[(size_t)k]) ctx->dk_tiles[(size_t)k].reset(new DevBuf);
@@ -1142,7 +1147,7 @@ int omr_batch_run_device(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t sca
     if (!ctx || !d_scans || n < 0) return fail(OMR_ERR_BADARG, "bad batch arguments");
     std::lock_guard<std::mutex> lk(ctx->mu);
     OMR_HIP(hipSetDevice(ctx->tables.device));
-    return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, d_v_sd, d_h_sd, nullptr);
+    return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, d_v_sd, d_h_sd, nullptr, 1);
 }
 
 }  // extern "C"
@@ -1156,7 +1161,7 @@ int omr::batch_run_device_bits(omr_batch_ctx *ctx, const uint32_t *d_bits, int64
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->lanes <= 0) return fail(OMR_ERR_BADARG, "packed scans need a context in scan-lane mode");
     OMR_HIP(hipSetDevice(ctx->tables.device));
-    return batch_run(ctx, (const uint8_t *)d_bits, scan_stride_bytes, 0, n, /*black_max: packed*/ -1, d_best_idx, d_v_sd, d_h_sd, nullptr);
+    return batch_run(ctx, (const uint8_t *)d_bits, scan_stride_bytes, 0, n, /*black_max: packed*/ -1, d_best_idx, d_v_sd, d_h_sd, nullptr, 1);
 }
 
 extern "C" {
@@ -1188,7 +1193,81 @@ int omr_batch_deskew_device(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t 
         return fail(OMR_ERR_BADARG, "every output slot must hold the largest canvas, %d x %d (omr_batch_deskew_canvas)",
                     ctx->dk_cols, ctx->dk_rows);
     DeskewOut dk{interp, (int)border_value, d_out, out_stride, out_step, d_out_size};
-    return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, nullptr, nullptr, &dk);
+    return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, nullptr, nullptr, &dk, 1);
+}
+
+}  // extern "C"
+
+namespace {
+// the arguments common to both colour entry points; cheap, no device work, the context unchanged
+int check_batch_cn(const omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t step_bytes, int32_t channels, int32_t n,
+                   int32_t black_max)
+{
+    if (!ctx || !d_scans || n < 0) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (channels != 1 && channels != 3) return fail(OMR_ERR_NOTIMPL, "%d channels: batches take 1 or 3 (BGR)", channels);
+    if (black_max < 0 || black_max > 255) return fail(OMR_ERR_BADARG, "black_max %d outside 0..255", black_max);
+    if (step_bytes < (int64_t)ctx->tables.dims.cols * channels)
+        return fail(OMR_ERR_BADARG, "step_bytes %lld < cols %d x %d channels", (long long)step_bytes, ctx->tables.dims.cols, channels);
+    return OMR_OK;
+}
+
+// the largest CONTAIN canvas of the candidate set, from the context's tables or (before they exist) from the host geometry
+// alone: the slot check of omr_batch_deskew_device_cn comes before any device work
+int deskew_canvas_host(const omr_batch_ctx *ctx, int *DR, int *DC)
+{
+    if (ctx->dk_built) {
+        *DR = ctx->dk_rows, *DC = ctx->dk_cols;
+        return OMR_OK;
+    }
+    const SweepDims &d = ctx->tables.dims;
+    int R = 0, Cc = 0;
+    for (int i = 0; i < d.A; i++) {
+        double M[6];
+        int dr, dc;
+        int rc = rotate_geometry(d.rows, d.cols, (double)(i - ctx->N) * ctx->step, 1.0, OMR_CLIP_CONTAIN, M, &dr, &dc);
+        if (rc) return rc;
+        R = std::max(R, dr);
+        Cc = std::max(Cc, dc);
+    }
+    *DR = R, *DC = (Cc + 3) & ~3;  // as build_deskew_tables
+    return OMR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int omr_batch_run_device_cn(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, int64_t step_bytes, int32_t channels,
+                            int32_t n, int32_t black_max, int32_t *d_best_idx, double *d_v_sd, double *d_h_sd)
+{
+    int rc = check_batch_cn(ctx, d_scans, step_bytes, channels, n, black_max);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    OMR_HIP(hipSetDevice(ctx->tables.device));
+    return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, d_v_sd, d_h_sd, nullptr, channels);
+}
+
+int omr_batch_deskew_device_cn(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, int64_t step_bytes,
+                               int32_t channels, int32_t n, int32_t black_max, int32_t interp, const uint8_t border_value[4],
+                               uint8_t *d_out, int64_t out_stride, int64_t out_step, int32_t *d_out_size, int32_t *d_best_idx)
+{
+    int rc = check_batch_cn(ctx, d_scans, step_bytes, channels, n, black_max);
+    if (rc) return rc;
+    if (!d_out || !border_value) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
+        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int DR = 0, DC = 0;
+    if ((rc = deskew_canvas_host(ctx, &DR, &DC))) return rc;
+    if (out_step < (int64_t)DC * channels || out_stride < (int64_t)DR * out_step)
+        return fail(OMR_ERR_BADARG, "every output slot must hold the largest canvas, %d x %d x %d channels (omr_batch_deskew_canvas)",
+                    DC, DR, channels);
+    OMR_HIP(hipSetDevice(ctx->tables.device));
+    if ((rc = build_deskew_tables(ctx))) return rc;
+    // 3 channels: the border's bytes 0..2 packed into DeskewPass::border (channel c = byte c)
+    const int border = channels == 1 ? (int)border_value[0]
+                                     : (int)((uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16));
+    DeskewOut dk{interp, border, d_out, out_stride, out_step, d_out_size};
+    return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, nullptr, nullptr, &dk, channels);
 }
 
 int omr_call_pool_stats(int32_t device, int32_t *live_slots, int32_t *idle_slots, int64_t *idle_pinned_bytes)

@@ -148,7 +148,8 @@ int guard_verdict(const int32_t *flags, size_t n, const char *kernel);
 int enqueue_sweep(const SweepTables &t, SweepScratch &s, int kernel_sel, const uint8_t *d_img, int64_t step,
                   int black_max, hipStream_t stream, uint32_t *d_vproj, uint32_t *d_hproj, double *d_v_sd,
                   double *d_h_sd, int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1, bool want_proj = false,
-                  hipStream_t post_stream = nullptr, hipEvent_t ev_mid = nullptr, int scans = 1, int64_t img_stride = 0);
+                  hipStream_t post_stream = nullptr, hipEvent_t ev_mid = nullptr, int scans = 1, int64_t img_stride = 0,
+                  int cn = 1);  // cn: channels of the scans, 1 or 3 (BGR: gray + threshold fused into the pack, bgr.hpp)
 
 // ---- scan-lane sweep (slane.hpp): lane = scan, for batches of same-shape scans
 struct SlanePlan;
@@ -190,7 +191,7 @@ struct SlaneScratch {
 };
 int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int64_t scan_stride, int64_t step, int nscans,
                   int black_max, hipStream_t stream, hipStream_t post_stream, hipEvent_t ev_mid, double *d_v_sd, double *d_h_sd,
-                  int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1);
+                  int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1, int cn = 1);  // cn: as enqueue_sweep
 
 }  // namespace omr
 

@@ -14,6 +14,7 @@
 // must round exactly like OpenCV's scalar code.
 #include <hip/hip_runtime.h>
 
+#include "bgr.hpp"
 #include "kernels.hpp"
 
 namespace omr {
@@ -98,6 +99,29 @@ hipError_t launch_pack_bits(const uint8_t *d_img, int64_t step, int rows, int co
     dim3 grid((wpr * 32 + 255) / 256, rows, scans);
     hipLaunchKernelGGL(pack_bits_kernel, grid, dim3(256), 0, s, d_img, step, rows, cols, black_max, d_bits, wpr,
                        img_stride);
+    return hipGetLastError();
+}
+
+// BGR scans (3 interleaved channels): a lane turns 32 pixels (96 bytes, six 16-byte loads on the aligned path) into one
+// word of the bit image, gray conversion and threshold fused into the load (bgr.hpp).  No gray image is written.
+__global__ __launch_bounds__(256) void pack_bits_bgr_kernel(const uint8_t *__restrict__ img, int64_t step, int rows, int cols,
+                                                            uint32_t lim, uint32_t *__restrict__ bits, int wpr, int64_t img_stride)
+{
+    img += (int64_t)blockIdx.z * img_stride;  // blockIdx.z = scan of the launch
+    bits += (int64_t)blockIdx.z * rows * wpr;
+    const int y = blockIdx.y;
+    const int w = blockIdx.x * 256 + threadIdx.x;  // word of the row
+    if (w >= wpr) return;
+    bits[(int64_t)y * wpr + w] = bgr_pack32(img + (int64_t)y * step + (int64_t)w * 96, min(32, cols - w * 32), lim);
+}
+
+hipError_t launch_pack_bits_cn(const uint8_t *d_img, int64_t step, int cn, int rows, int cols, int black_max, uint32_t *d_bits,
+                               int wpr, hipStream_t s, int scans, int64_t img_stride)
+{
+    if (cn == 1) return launch_pack_bits(d_img, step, rows, cols, black_max, d_bits, wpr, s, scans, img_stride);
+    if (cn != 3 || black_max < 0 || black_max > 255) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_bits_bgr_kernel, dim3((wpr + 255) / 256, rows, scans), dim3(256), 0, s, d_img, step, rows, cols,
+                       (uint32_t)(black_max + 1) << 15, d_bits, wpr, img_stride);
     return hipGetLastError();
 }
 

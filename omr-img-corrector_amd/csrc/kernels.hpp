@@ -28,6 +28,11 @@ struct LdsTile {
 // `scans` images img_stride bytes apart -> `scans` bit images, packed one after the other.
 hipError_t launch_pack_bits(const uint8_t *d_img, int64_t step, int rows, int cols, int black_max,
                             uint32_t *d_bits, int wpr, hipStream_t s, int scans = 1, int64_t img_stride = 0);
+// the same for scans of cn interleaved 8-bit channels: 1 = launch_pack_bits; 3 = BGR, black iff cvtColor(COLOR_RGB2GRAY)
+// of the pixel (quirk B8: BGR memory order, R weight on byte 0) <= black_max, 0..255 (bgr.hpp); other counts:
+// hipErrorInvalidValue
+hipError_t launch_pack_bits_cn(const uint8_t *d_img, int64_t step, int cn, int rows, int cols, int black_max, uint32_t *d_bits,
+                               int wpr, hipStream_t s, int scans = 1, int64_t img_stride = 0);
 
 // OpenCV hal::warpAffine fixed-point tables for A inverse matrices.
 // adelta/bdelta: [A][cols]; xy0: [A][rows] (X0, Y0 incl. round_delta). *d_overflow != 0 when a
@@ -162,7 +167,7 @@ hipError_t launch_warp_linear(const uint8_t *d_src, int64_t sstep, int srows, in
 
 // ---- batched final deskew (deskew.hip): scan z is rotated by the candidate best[z]'s angle, CONTAIN geometry
 struct DeskewPass {
-    const uint8_t *src;       // scans, 1 channel: scan_stride bytes apart, sstep bytes per row
+    const uint8_t *src;       // scans, cn channels: scan_stride bytes apart, sstep bytes per row
     int64_t scan_stride, sstep;
     int32_t srows, scols;
     uint8_t *dst;             // canvases: out_stride bytes apart, dstep bytes per row, each holds DR x DC pixels
@@ -175,6 +180,8 @@ struct DeskewPass {
     int32_t border;           // border value (0..255)
     int32_t *out_size;        // [scans][2] canvas rows, cols of every scan (device), or null
     int32_t order, ntx, nty;  // (set by launch_deskew_warp) the workgroup order and the tiles across / down the largest canvas
+    int32_t cn;               // channels of the scans and canvases: 1, or 3 (BGR; border then holds one byte per channel,
+                              // channel c = byte c).  (Fills the struct's tail padding: the 1-channel kernels' arguments keep their offsets.)
 };
 // d_tiles: deskew_tile_bytes(p, scans) bytes of scratch (the per-tile records made by the launch's first kernel)
 size_t deskew_tile_bytes(const DeskewPass &p, int scans);

@@ -250,6 +250,10 @@ hipError_t launch_slane_build_scan(const SlaneBuild &b, int ntasks, hipStream_t 
 hipError_t launch_slane_build_emit(const SlaneBuild &b, int ntasks, hipStream_t s);   // -> prog (needs cls, seg_off, fet_off)
 hipError_t launch_slane_pack(const uint8_t *d_img, int64_t scan_stride, int64_t step, const SlaneGeom &g, int nscans,
                              int black_max, uint32_t *d_bits, hipStream_t s);
+// the same for scans of cn interleaved channels: 1 = launch_slane_pack, 3 = BGR (gray + threshold fused into the load, bgr.hpp;
+// black_max 0..255); other counts: hipErrorInvalidValue
+hipError_t launch_slane_pack_cn(const uint8_t *d_img, int64_t scan_stride, int64_t step, int cn, const SlaneGeom &g, int nscans,
+                                int black_max, uint32_t *d_bits, hipStream_t s);
 // scans that arrive packed to 1 bit per pixel: [scan][rows][NW] dwords, bit i of word c = pixel 32 c + i is black
 hipError_t launch_slane_pack_bits(const uint32_t *d_packed, int64_t scan_stride_dwords, const SlaneGeom &g, int nscans,
                                   uint32_t *d_bits, hipStream_t s);

@@ -75,6 +75,10 @@ SYMBOLS = {
     "omr_batch_deskew_canvas": (C.c_int, [C.c_void_p, i32p, i32p]),
     "omr_batch_deskew_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_uint8, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "omr_batch_run_device_cn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_batch_deskew_device_cn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, u8p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "omr_call_pool_stats": (C.c_int, [C.c_int32, i32p, i32p, C.POINTER(C.c_int64)]),
     "omr_host_batch_create": (C.c_int, [C.c_int32, C.c_int32, C.c_uint16, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "omr_host_batch_destroy": (None, [C.c_void_p]),

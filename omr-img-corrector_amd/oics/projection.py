@@ -164,6 +164,21 @@ class Batch:
         check(lib().omr_batch_deskew_device(self.handle, d_scans, scan_stride, step_bytes, n, black_max, interp, border,
                                             d_out, out_stride, out_step, d_out_size, d_best))
 
+    def run_device_cn(self, d_scans, scan_stride, step_bytes, channels, n, black_max, d_best, d_v_sd=None, d_h_sd=None):
+        """run_device for scans of `channels` interleaved channels (3 = BGR: gray = cvtColor(COLOR_RGB2GRAY) of the BGR bytes,
+        quirk B8, fused into the load; 1 = run_device)"""
+        check(lib().omr_batch_run_device_cn(self.handle, d_scans, scan_stride, step_bytes, channels, n, black_max, d_best,
+                                            d_v_sd, d_h_sd))
+
+    def deskew_device_cn(self, d_scans, scan_stride, step_bytes, channels, n, black_max, interp, border, d_out, out_stride,
+                         out_step, d_out_size=None, d_best=None):
+        """deskew_device for scans of `channels` interleaved channels; border = one value per channel (a sequence) or
+        one for all; every slot holds the largest canvas with channels * max_cols bytes per row at least"""
+        bv = [int(border)] * 4 if isinstance(border, int) else [int(v) for v in border] + [0] * (4 - len(border))
+        arr = (C.c_uint8 * 4)(*bv[:4])
+        check(lib().omr_batch_deskew_device_cn(self.handle, d_scans, scan_stride, step_bytes, channels, n, black_max, interp,
+                                               arr, d_out, out_stride, out_step, d_out_size, d_best))
+
     def sync(self):
         check(lib().omr_batch_sync(self.handle))
 

@@ -102,6 +102,34 @@ def make_card(rows, cols, seed, skew=None, noise_sigma=4.0):
     return np.clip(np.rint(rot), 0, 255).astype(np.uint8), theta
 
 
+def make_color_card(rows, cols, seed, skew=None):
+    """A colour (BGR, OpenCV's memory order) card whose inks expose channel-order bugs.  Returns (u8 [rows, cols, 3], skew).
+
+    Tinted paper, BGR (250, 238, 222), per-channel noise, and the card's black split between two inks that the
+    reference's gray formula -- cvtColor(COLOR_RGB2GRAY) on BGR bytes (quirk B8: R weight on byte 0) -- and true BGR
+    weights classify the opposite way at 127: BGR (40, 140, 250), an orange, is black to the quirk formula (gray ~123)
+    and white to true weights (~161); BGR (250, 120, 40), a blue, is white to the quirk formula (~150) and black to
+    true weights (~111).  The bubble grid's left half is orange, its right half blue; frame, marks and text stay
+    near-black."""
+    g, theta = make_card(rows, cols, seed, skew, noise_sigma=0.0)
+    rng = np.random.Generator(np.random.PCG64(seed + 0x5eed))
+    ink = g.astype(np.float32) / 255.0  # 1 = paper, 0 = ink, bilinear edges in between
+    paper = np.array([250.0, 238.0, 222.0], np.float32)
+    orange = np.array([40.0, 140.0, 250.0], np.float32)
+    blue = np.array([250.0, 120.0, 40.0], np.float32)
+    dark = np.array([20.0, 24.0, 30.0], np.float32)
+    s = min(cols / 2480.0, rows / 3508.0)
+    m = max(1, int(round(90 * s)))
+    inner = np.zeros((rows, cols), bool)
+    inner[m + max(2, int(round(20 * s))):rows - m - max(2, int(round(20 * s))), m + max(2, int(round(180 * s))):cols - m - max(2, int(round(20 * s)))] = True
+    left = np.zeros((rows, cols), bool)
+    left[:, :cols // 2] = True
+    col_ink = np.where((inner & left)[..., None], orange, np.where(inner[..., None], blue, dark))
+    out = ink[..., None] * paper + (1.0 - ink[..., None]) * col_ink
+    out = out + rng.normal(0.0, 3.0, out.shape).astype(np.float32)
+    return np.ascontiguousarray(np.clip(np.rint(out), 0, 255).astype(np.uint8)), theta
+
+
 def make_binary_card(rows, cols, seed, skew=None):
     """Card already binarised like transfer.rs:294-301 (0 / 255)."""
     g, theta = make_card(rows, cols, seed, skew)
