@@ -438,6 +438,53 @@ int omr_correct_default(const omr_image *src_bgr, uint16_t projection_max_angle,
                         double hough_max_line_gap, double *rotate_angle, int32_t *need_check,
                         omr_image_owned *rotated);
 
+/* ---- correct_default for batches of sheets ------------------------------
+ * A context for repeated batches of one shape (rows x cols x channels) and one parameter set of omr_correct_default.
+ * For every sheet that omr_correct_default accepts, the batch gives its results bit for bit: rotate_angle (as f64
+ * bits), need_check and the rotated canvas (NEAREST, white border, CONTAIN, scale 1: size and every byte).
+ * channels: 3 (BGR, as imread(IMREAD_COLOR) gives it) or 1 (the gray convenience omr_correct_default also accepts);
+ * 4 is OMR_ERR_NOTIMPL, 2 is OMR_ERR_ASSERT as per call.  max_scans = the largest n a run may carry (1..65535). */
+typedef struct omr_correct_batch omr_correct_batch;
+int omr_correct_batch_create(int32_t rows, int32_t cols, int32_t channels, uint16_t projection_max_angle,
+                             double projection_angle_step, int32_t projection_max_width,
+                             int32_t projection_max_height, double hough_min_line_length,
+                             double hough_max_line_gap, int32_t device, int32_t max_scans,
+                             omr_correct_batch **out);
+void omr_correct_batch_destroy(omr_correct_batch *cb);
+/* Largest CONTAIN canvas any angle can give at rows x cols (cols rounded up to 4, as the batch warp's tables).
+ * A pure function: no device needed. */
+int omr_correct_batch_canvas(int32_t rows, int32_t cols, int32_t *max_rows, int32_t *max_cols);
+/* n device-resident sheets (sheet i at d_scans + i * scan_stride_bytes, rows step_bytes apart) -> per sheet the
+ * decision (host arrays of n: rotate_angle, need_check, scan_rc) and, when d_out != NULL, the rotated sheet: its
+ * canvas fills the top-left of d_out + i * out_stride_bytes (rows out_step_bytes apart; every slot holds
+ * omr_correct_batch_canvas() x channels) and its size lands in the host array out_size[2 i] (rows), [2 i + 1] (cols),
+ * which may be NULL.  scan_rc[i] is what omr_correct_default returns for sheet i: 0, OMR_ERR_ASSERT when the Hough
+ * fallback finds no segment (the reference panics there, quirk B11), OMR_ERR_NOMEM when it finds more segments than the
+ * HoughLinesP buffer holds (65536); such a sheet gets no canvas and size 0 x 0, the other sheets' results stand.  The
+ * sheets that are not Believed go through the Hough pass at most 256 at a time (a packed copy of them is the context's
+ * largest buffer, up to 256 sheets).  The return value is for errors of the whole call; every argument is checked before
+ * any device work.  Synchronous: the decision needs the host, and the call returns when everything is done.
+ * Performance note: as for omr_batch_deskew_device_cn, the warp stages source boxes in LDS only when d_scans,
+ * scan_stride_bytes and step_bytes are multiples of 4. */
+int omr_correct_batch_run_device(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                                 int64_t step_bytes, int32_t n, double *rotate_angle, int32_t *need_check,
+                                 int32_t *scan_rc, uint8_t *d_out, int64_t out_stride_bytes,
+                                 int64_t out_step_bytes, int32_t *out_size);
+/* Host images of any shapes, bucketed by (rows, cols, channels) as omr_sweep_batch does, on the current device;
+ * results land at the sheets' own positions.  rotated (n owned images, omr_image_free each) may be NULL; a sheet
+ * with scan_rc[i] != 0 gets an empty image (data NULL) -- a shape whose projection size truncates to 0 gives every
+ * one of its sheets OMR_ERR_ASSERT, as per call.  Runs of up to 256 sheets per shape go through a context the library
+ * keeps for later calls with the same device, shape and parameters (the last 4 are kept); uploads and the copies of
+ * the rotated sheets into fresh host images run on up to 16 host threads.  On an error of the whole call no image is
+ * returned.  Today this form is SLOWER than omr_correct_default from 16 host threads when the rotated images are
+ * wanted (about 650 sheets/s against 825 on 1150 x 1240 sheets, 3 183 at A4: profiles/r06_correct_batch.md); the
+ * device-resident omr_correct_batch_run_device is the fast path. */
+int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t projection_max_angle,
+                              double projection_angle_step, int32_t projection_max_width,
+                              int32_t projection_max_height, double hough_min_line_length,
+                              double hough_max_line_gap, double *rotate_angle, int32_t *need_check,
+                              int32_t *scan_rc, omr_image_owned *rotated);
+
 /* ---- FFT deskew path ------------------------------------------------------
  * The 2-D DFT is float32 like the reference's (dft on CV_32F); it is a different factorisation than
  * OpenCV's (radix-2 Stockham / Bluestein chirp-z in LDS), so the 8-bit spectrum pictures agree with

@@ -1,0 +1,705 @@
+// correct_batch.cpp -- correct_default (omr.rs:339-448) for batches of sheets on the device:
+//
+//   front end   one launch per stage over the batch (correct_front.hip): gray + erode x3 (+ integer INTER_AREA shrink)
+//               fused; fractional shrinks through the context's resizeArea_ tap tables; enlargement (quirk B7) through
+//               the per-call stage kernel, sheet by sheet
+//   sweep       the context's omr_batch_ctx at the resize scale (quirk B4), black_max 127 (omr.rs:129-139); the scores
+//               go to the host, where omr_select_projection_result decides every sheet (omr.rs:147-221)
+//   Hough       only the sheets that are not Believed: one batched Canny + HoughLinesP pass on a gather of their
+//               colour sheets, then line_angles -> vote_counts -> select_omr_rs and the omr.rs:351-399 decision per sheet
+//   warp        the batch colour warp (deskew.hip) with a per-call candidate set made of the decided angles: NEAREST,
+//               white border, CONTAIN, scale 1.  The Believed sheets' warp runs on a stream of its own while the Hough
+//               pass runs.
+//
+// Every per-sheet result is omr_correct_default's for the same sheet, bit for bit.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <chrono>
+#include <list>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <tuple>
+#include <vector>
+
+#include "../../include/omrdeskew.h"
+#include "engine.hpp"
+#include "hough_host.hpp"
+
+using namespace omr;
+using namespace omr::hh;
+
+namespace omr {
+// correct_front.hip
+hipError_t launch_front(const uint8_t *d_src, int64_t scan_stride, int64_t sstep, int cn, int rows, int cols, int n,
+                        uint8_t *d_dst, int64_t out_stride, int64_t dstep, int kx, int ky, hipStream_t s);
+hipError_t launch_area_general_batch(const uint8_t *d_src, int64_t scan_stride, int64_t sstep, int n, uint8_t *d_dst,
+                                     int64_t out_stride, int64_t dstep, int drows, int dcols, const AreaTap *d_xtab,
+                                     const int32_t *d_xofs, const AreaTap *d_ytab, const int32_t *d_yofs, hipStream_t s);
+}  // namespace omr
+
+namespace {
+
+enum FrontMode {
+    FRONT_AREA_FUSED = 0,  // integer factors <= 64: gray + erode + resizeAreaFast_ in one kernel
+    FRONT_AREA_INT = 1,    // integer factors > 64: eroded sheets, then the per-call resizeAreaFast_ kernel per sheet
+    FRONT_AREA_GENERAL = 2,  // fractional shrink: eroded sheets, then resizeArea_ with the context's tap tables
+    FRONT_LINEAR = 3,        // an axis enlarges (quirk B7): eroded sheets, then the per-call bilinear kernel per sheet
+};
+const int kChunk = 256;  // sheets per front-end / warp launch when a full-size intermediate is needed
+
+// the decided angles of one warp phase as a candidate set of the batch warp
+struct WarpSet {
+    DevBuf minv, size, adelta, bdelta, xy0, best, ovf, tiles;
+    std::vector<double> h_minv;
+    std::vector<int32_t> h_size, h_best;
+};
+
+// Largest CONTAIN canvas over every angle: ceil(rows |sin| + cols |cos|) <= ceil(sqrt(rows^2 + cols^2)) on both axes,
+// and floor(sqrt) + 1 bounds that with room for the rounding of the f64 expression.  Cols rounded up to 4 (the warp's
+// tables).
+void canvas_of(int rows, int cols, int *R, int *C)
+{
+    const int64_t d2 = (int64_t)rows * rows + (int64_t)cols * cols;
+    int64_t r = (int64_t)sqrt((double)d2);
+    while (r * r > d2) r--;
+    while ((r + 1) * (r + 1) <= d2) r++;
+    *R = (int)(r + 1);
+    *C = (int)((r + 1 + 3) & ~3);
+}
+
+}  // namespace
+
+struct omr_correct_batch {
+    int device = 0, rows = 0, cols = 0, cn = 0, max_scans = 0;
+    uint16_t max_angle = 0;
+    double step = 0, hough_min = 0, hough_gap = 0;
+    int N = 0, A = 0;
+    double scale = 1;
+    int dr = 0, dc = 0;  // projection-size image
+    int mode = FRONT_AREA_FUSED, kx = 1, ky = 1;
+    int64_t small_step = 0, small_stride = 0, er_stride = 0;
+    int DR = 0, DC = 0;  // largest canvas
+    omr_batch_ctx *sweep = nullptr;
+    hipStream_t s = nullptr, sw = nullptr;  // front end / sweep hand-off / Hough, and the warp
+    DevBuf small, eroded, best, vsd, hsd, gather, xt, xo, yt, yo;
+    double *h_vsd = nullptr, *h_hsd = nullptr;  // pinned
+    WarpSet warp[2];                            // [0] Believed sheets, [1] the rest
+    std::mutex mu;
+    ~omr_correct_batch()
+    {
+        if (s) (void)hipStreamSynchronize(s);
+        if (sw) (void)hipStreamSynchronize(sw);
+        if (sweep) omr_batch_destroy(sweep);
+        if (h_vsd) (void)hipHostFree(h_vsd);
+        if (h_hsd) (void)hipHostFree(h_hsd);
+        if (s) (void)hipStreamDestroy(s);
+        if (sw) (void)hipStreamDestroy(sw);
+    }
+};
+
+namespace {
+
+int check_shape(int rows, int cols, int cn)
+{
+    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_ASSERT, "empty image");
+    if (rows >= 32767 || cols >= 32767) return fail(OMR_ERR_ASSERT, "image dimension >= SHRT_MAX");
+    if (cn == 4) return fail(OMR_ERR_NOTIMPL, "4-channel batches are not implemented (1 or 3 channels)");
+    if (cn == 2) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
+    if (cn != 1 && cn != 3) return fail(OMR_ERR_ASSERT, "Canny / HoughLinesP take 1, 3 or 4 channels, got %d", cn);
+    return OMR_OK;
+}
+
+// resize_ptr's dispatch (oics_host.cpp) for INTER_AREA from rows x cols to dr x dc
+void front_mode(omr_correct_batch *cb)
+{
+    const double scale_x = 1. / ((double)cb->dc / cb->cols), scale_y = 1. / ((double)cb->dr / cb->rows);
+    const int iscale_x = (int)lrint(scale_x), iscale_y = (int)lrint(scale_y);
+    const bool fast = fabs(scale_x - iscale_x) < 2.220446049250313e-16 && fabs(scale_y - iscale_y) < 2.220446049250313e-16;
+    if (cb->dr == cb->rows && cb->dc == cb->cols) {  // a copy: resizeAreaFast_ with factor 1 is the identity
+        cb->mode = FRONT_AREA_FUSED, cb->kx = cb->ky = 1;
+    } else if (!(scale_x >= 1 && scale_y >= 1)) {
+        cb->mode = FRONT_LINEAR;
+    } else if (fast) {
+        cb->kx = iscale_x, cb->ky = iscale_y;
+        cb->mode = cb->kx <= 64 && cb->ky <= 64 ? FRONT_AREA_FUSED : FRONT_AREA_INT;
+    } else {
+        cb->mode = FRONT_AREA_GENERAL;
+    }
+}
+
+int upload_vec(DevBuf *b, const void *p, size_t bytes, hipStream_t s)
+{
+    if (b->bytes < bytes) {
+        NoPoolScope owned;
+        b->release();
+        OMR_HIP(b->alloc(bytes));
+    }
+    OMR_HIP(hipMemcpyAsync(b->p, p, bytes, hipMemcpyHostToDevice, s));
+    return OMR_OK;
+}
+
+int grow(DevBuf *b, size_t bytes)
+{
+    if (b->bytes >= bytes) return OMR_OK;
+    NoPoolScope owned;
+    b->release();
+    OMR_HIP(b->alloc(bytes));
+    return OMR_OK;
+}
+
+// Rotate the listed sheets (ascending) by angle[i] on stream s: the distinct angles become the candidate set of the batch
+// warp, sheet i's entry best[i].  Sizes go to out_size (host, may be NULL).
+int warp_phase(omr_correct_batch *cb, WarpSet &w, const std::vector<int> &sheets, const double *angle, const uint8_t *d_scans,
+               int64_t scan_stride, int64_t step, uint8_t *d_out, int64_t out_stride, int64_t out_step, int32_t *out_size,
+               hipStream_t s)
+{
+    if (sheets.empty()) return OMR_OK;
+    std::map<uint64_t, int> index;  // angle bits -> candidate
+    w.h_minv.clear();
+    w.h_size.clear();
+    w.h_best.assign((size_t)cb->max_scans, 0);
+    for (int i : sheets) {
+        uint64_t bits;
+        memcpy(&bits, &angle[i], sizeof bits);
+        auto it = index.find(bits);
+        if (it == index.end()) {
+            double M[6], Mi[6];
+            int r, c;
+            int rc = rotate_geometry(cb->rows, cb->cols, angle[i], 1.0, OMR_CLIP_CONTAIN, M, &r, &c);
+            if (rc) return rc;
+            if (r > cb->DR || c > cb->DC) return fail(OMR_ERR_ASSERT, "canvas %d x %d exceeds the context's %d x %d", r, c, cb->DR, cb->DC);
+            invert_affine(M, Mi);
+            w.h_minv.insert(w.h_minv.end(), Mi, Mi + 6);
+            w.h_size.push_back(r);
+            w.h_size.push_back(c);
+            it = index.emplace(bits, (int)index.size()).first;
+        }
+        w.h_best[(size_t)i] = it->second;
+        if (out_size) {
+            out_size[2 * (size_t)i] = w.h_size[2 * (size_t)it->second];
+            out_size[2 * (size_t)i + 1] = w.h_size[2 * (size_t)it->second + 1];
+        }
+    }
+    const int A = (int)index.size();
+    int rc;
+    if ((rc = upload_vec(&w.minv, w.h_minv.data(), sizeof(double) * w.h_minv.size(), s))) return rc;
+    if ((rc = upload_vec(&w.size, w.h_size.data(), sizeof(int32_t) * w.h_size.size(), s))) return rc;
+    if ((rc = upload_vec(&w.best, w.h_best.data(), sizeof(int32_t) * w.h_best.size(), s))) return rc;
+    if ((rc = grow(&w.adelta, sizeof(int32_t) * (size_t)A * cb->DC))) return rc;
+    if ((rc = grow(&w.bdelta, sizeof(int32_t) * (size_t)A * cb->DC))) return rc;
+    if ((rc = grow(&w.xy0, sizeof(int2_t) * (size_t)A * cb->DR))) return rc;
+    if ((rc = grow(&w.ovf, sizeof(int32_t)))) return rc;
+    OMR_HIP(hipMemsetAsync(w.ovf.p, 0, sizeof(int32_t), s));
+    SweepDims td{cb->DR, cb->DC, A, 0};
+    OMR_HIP(launch_tables(w.minv.as<double>(), td, 0, w.adelta.as<int32_t>(), w.bdelta.as<int32_t>(), w.xy0.as<int2_t>(),
+                          w.ovf.as<int32_t>(), s));
+    {  // as build_deskew_tables: no canvas is written from tables that left warpAffine's 32-bit fixed-point range
+        int32_t h_ovf = 0;
+        OMR_HIP(hipMemcpyAsync(&h_ovf, w.ovf.p, sizeof h_ovf, hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+        if (h_ovf) return fail(OMR_ERR_BADARG, "affine map leaves the 32-bit fixed-point range of warpAffine");
+    }
+    DeskewPass p{};
+    p.scan_stride = scan_stride;
+    p.sstep = step;
+    p.srows = cb->rows;
+    p.scols = cb->cols;
+    p.out_stride = out_stride;
+    p.dstep = out_step;
+    p.wsize = w.size.as<int32_t>();
+    p.adelta = w.adelta.as<int32_t>();
+    p.bdelta = w.bdelta.as<int32_t>();
+    p.xy0 = w.xy0.as<int2_t>();
+    p.DC = cb->DC;
+    p.DR = cb->DR;
+    p.border = cb->cn == 1 ? 255 : 0xffffff;  // omr.rs:438: Scalar(255, 255, 255, 0)
+    p.out_size = nullptr;
+    p.cn = cb->cn;
+    if ((rc = grow(&w.tiles, deskew_tile_bytes(p, kChunk)))) return rc;
+    // one launch per run of consecutive sheets (at most kChunk of them)
+    for (size_t j = 0; j < sheets.size();) {
+        size_t e = j + 1;
+        while (e < sheets.size() && sheets[e] == sheets[e - 1] + 1 && (int)(e - j) < kChunk) e++;
+        const int i0 = sheets[j];
+        p.src = d_scans + (size_t)i0 * scan_stride;
+        p.dst = d_out + (size_t)i0 * out_stride;
+        p.best = w.best.as<int32_t>() + i0;
+        OMR_HIP(launch_deskew_warp(p, (int)(e - j), OMR_INTER_NEAREST, w.tiles.p, s));
+        j = e;
+    }
+    return OMR_OK;
+}
+
+// the front end of n sheets -> cb->small (projection-size images)
+int front_end(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n)
+{
+    hipStream_t s = cb->s;
+    if (cb->mode == FRONT_AREA_FUSED) {
+        OMR_HIP(launch_front(d_scans, scan_stride, step, cb->cn, cb->rows, cb->cols, n, cb->small.as<uint8_t>(), cb->small_stride,
+                             cb->small_step, cb->kx, cb->ky, s));
+        return OMR_OK;
+    }
+    for (int i0 = 0; i0 < n; i0 += kChunk) {
+        const int z = std::min(kChunk, n - i0);
+        int rc = grow(&cb->eroded, (size_t)z * cb->er_stride);
+        if (rc) return rc;
+        uint8_t *er = cb->eroded.as<uint8_t>();
+        uint8_t *sm = cb->small.as<uint8_t>() + (size_t)i0 * cb->small_stride;
+        OMR_HIP(launch_front(d_scans + (size_t)i0 * scan_stride, scan_stride, step, cb->cn, cb->rows, cb->cols, z, er, cb->er_stride,
+                             cb->cols, 0, 0, s));
+        if (cb->mode == FRONT_AREA_GENERAL) {
+            OMR_HIP(launch_area_general_batch(er, cb->er_stride, cb->cols, z, sm, cb->small_stride, cb->small_step, cb->dr, cb->dc,
+                                              cb->xt.as<AreaTap>(), cb->xo.as<int32_t>(), cb->yt.as<AreaTap>(), cb->yo.as<int32_t>(),
+                                              s));
+        } else {
+            for (int j = 0; j < z; j++) {
+                const uint8_t *e = er + (size_t)j * cb->er_stride;
+                uint8_t *d = sm + (size_t)j * cb->small_stride;
+                if (cb->mode == FRONT_LINEAR)
+                    OMR_HIP(launch_resize_linear(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc, true, s));
+                else
+                    OMR_HIP(launch_resize_area_int_fast(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc,
+                                                        cb->kx, cb->ky, s));
+            }
+        }
+    }
+    return OMR_OK;
+}
+
+int run_locked(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n, double *rotate_angle,
+               int32_t *need_check, int32_t *scan_rc, uint8_t *d_out, int64_t out_stride, int64_t out_step, int32_t *out_size)
+{
+    const int A = cb->A;
+    int rc;
+    // 1. front end -> projection-size images
+    if ((rc = front_end(cb, d_scans, scan_stride, step, n))) return rc;
+    OMR_HIP(hipStreamSynchronize(cb->s));  // the sweep runs on the batch context's own streams
+    // 2. sweep at the resize scale, scores to the host, omr.rs:147-221 per sheet
+    if ((rc = omr_batch_run_device(cb->sweep, cb->small.as<uint8_t>(), cb->small_stride, cb->small_step, n, 127,
+                                   cb->best.as<int32_t>(), cb->vsd.as<double>(), cb->hsd.as<double>())))
+        return rc;
+    if ((rc = omr_batch_sync(cb->sweep))) return rc;
+    OMR_HIP(hipMemcpyAsync(cb->h_vsd, cb->vsd.p, sizeof(double) * (size_t)n * A, hipMemcpyDeviceToHost, cb->s));
+    OMR_HIP(hipMemcpyAsync(cb->h_hsd, cb->hsd.p, sizeof(double) * (size_t)n * A, hipMemcpyDeviceToHost, cb->s));
+    OMR_HIP(hipStreamSynchronize(cb->s));
+    std::vector<double> pa((size_t)n), pc((size_t)n * (A + 1));
+    std::vector<int32_t> pst((size_t)n), pn((size_t)n);
+    std::vector<int> believed, rest;
+    for (int i = 0; i < n; i++) {
+        if ((rc = omr_select_projection_result(cb->h_vsd + (size_t)i * A, cb->h_hsd + (size_t)i * A, A, cb->N, cb->step, &pa[i],
+                                               &pst[i], &pc[(size_t)i * (A + 1)], A + 1, &pn[i])))
+            return rc;
+        scan_rc[i] = OMR_OK;
+        if (pst[i] == OMR_STATUS_BELIEVED) {
+            rotate_angle[i] = pa[i];
+            need_check[i] = 0;
+            believed.push_back(i);
+        } else {
+            rest.push_back(i);
+        }
+        if (out_size) out_size[2 * (size_t)i] = out_size[2 * (size_t)i + 1] = 0;
+    }
+    // 3. the Believed sheets' warp, on its own stream, beside the Hough pass
+    if (d_out && (rc = warp_phase(cb, cb->warp[0], believed, rotate_angle, d_scans, scan_stride, step, d_out, out_stride, out_step,
+                                  out_size, cb->sw)))
+        return rc;
+    // 4. Hough on a gather of the other sheets (packed, at most kChunk at a time), omr.rs:351-399 per sheet
+    if (!rest.empty()) {
+        const int64_t row = (int64_t)cb->cols * cb->cn, gstride = row * cb->rows;
+        HoughParams hp;
+        hp.min_line_length = cb->hough_min;
+        hp.max_line_gap = cb->hough_gap;
+        std::vector<int> decided;
+        for (size_t j0 = 0; j0 < rest.size(); j0 += kChunk) {
+            const int m = (int)std::min(rest.size() - j0, (size_t)kChunk);
+            if ((rc = grow(&cb->gather, (size_t)m * gstride))) return rc;
+            for (int j = 0; j < m; j++)
+                OMR_HIP(hipMemcpy2DAsync(cb->gather.as<uint8_t>() + (size_t)j * gstride, (size_t)row,
+                                         d_scans + (size_t)rest[j0 + j] * scan_stride, (size_t)step, (size_t)row, (size_t)cb->rows,
+                                         hipMemcpyDeviceToDevice, cb->s));
+            std::vector<std::vector<int32_t>> lines;
+            std::vector<int> sheet_rc((size_t)m, OMR_OK);
+            {
+                PoolScope scratch(cb->s);  // the pass's own buffers come from the block cache
+                rc = edges_lines_device(cb->gather.as<uint8_t>(), gstride, row, cb->rows, cb->cols, cb->cn, m, hp, cb->s, &lines);
+                if (rc == OMR_ERR_NOMEM) {  // a sheet with more segments than the buffer holds: the per-call function fails on that
+                    lines.assign((size_t)m, {});  // sheet alone, so the chunk is redone sheet by sheet
+                    for (int j = 0; j < m; j++) {
+                        std::vector<std::vector<int32_t>> one;
+                        const int r1 = edges_lines_device(cb->gather.as<uint8_t>() + (size_t)j * gstride, gstride, row, cb->rows,
+                                                          cb->cols, cb->cn, 1, hp, cb->s, &one);
+                        if (r1 == OMR_ERR_NOMEM) sheet_rc[(size_t)j] = r1;
+                        else if (r1) return r1;
+                        else lines[(size_t)j] = std::move(one[0]);
+                    }
+                    rc = OMR_OK;
+                }
+                if (rc) return rc;
+            }
+            for (int j = 0; j < m; j++) {
+                const int i = rest[j0 + j];
+                std::vector<float> ang;
+                std::vector<int32_t> cnt;
+                double ea = 0;
+                int32_t est = 0, en = 0;
+                if (sheet_rc[(size_t)j] == OMR_OK) {
+                    line_angles(lines[(size_t)j], &ang);
+                    {
+                        PoolScope scratch(cb->s);
+                        if ((rc = vote_counts(ang, true, cb->s, &cnt))) return rc;
+                    }
+                    sheet_rc[(size_t)j] = select_omr_rs(ang, cnt, &ea, &est, nullptr, 0, &en);  // no segment: -215 (quirk B11)
+                }
+                if (sheet_rc[(size_t)j] != OMR_OK) {
+                    scan_rc[i] = sheet_rc[(size_t)j];
+                    rotate_angle[i] = 0.0;
+                    need_check[i] = 0;
+                    continue;
+                }
+                omr_correct_default_decision(pa[i], pst[i], &pc[(size_t)i * (A + 1)], std::min<int32_t>(pn[i], A + 1), ea,
+                                             &rotate_angle[i], &need_check[i]);
+                decided.push_back(i);
+            }
+        }
+        clear_error();
+        // 5. their warp, behind the Believed sheets' on the warp stream
+        if (d_out && (rc = warp_phase(cb, cb->warp[1], decided, rotate_angle, d_scans, scan_stride, step, d_out, out_stride,
+                                      out_step, out_size, cb->sw)))
+            return rc;
+    }
+    OMR_HIP(hipStreamSynchronize(cb->sw));
+    return OMR_OK;
+}
+
+}  // namespace
+
+namespace {
+
+// ---- the host-image form: contexts kept per (device, shape, parameters), transfers spread over host threads ---------
+struct HostArgs {
+    const omr_image *srcs;
+    uint16_t max_angle;
+    double step;
+    int32_t max_w, max_h;
+    double hmin, hgap;
+    double *angle;
+    int32_t *need_check, *scan_rc;
+    omr_image_owned *rotated;
+    int device;
+};
+
+struct CtxKey {
+    int device, rows, cols, cn;
+    uint16_t max_angle;
+    double step;
+    int32_t max_w, max_h;
+    double hmin, hgap;
+    bool operator==(const CtxKey &o) const
+    {
+        return device == o.device && rows == o.rows && cols == o.cols && cn == o.cn && max_angle == o.max_angle &&
+               step == o.step && max_w == o.max_w && max_h == o.max_h && hmin == o.hmin && hgap == o.hgap;
+    }
+};
+std::mutex g_ctx_mu;
+std::list<std::pair<CtxKey, std::shared_ptr<omr_correct_batch>>> g_ctx;  // most recent first, at most kCachedContexts
+const size_t kCachedContexts = 4;
+
+// a context of kChunk sheets for this key: from the cache, or made and cached (the app calls with one parameter set)
+int cached_context(const CtxKey &k, std::shared_ptr<omr_correct_batch> *out)
+{
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        for (auto it = g_ctx.begin(); it != g_ctx.end(); ++it)
+            if (it->first == k) {
+                *out = it->second;
+                g_ctx.splice(g_ctx.begin(), g_ctx, it);
+                return OMR_OK;
+            }
+    }
+    omr_correct_batch *raw = nullptr;
+    int rc = omr_correct_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.max_w, k.max_h, k.hmin, k.hgap, k.device, kChunk,
+                                      &raw);
+    if (rc) return rc;
+    std::shared_ptr<omr_correct_batch> sp(raw, omr_correct_batch_destroy);
+    std::lock_guard<std::mutex> lk(g_ctx_mu);
+    g_ctx.emplace_front(k, sp);
+    while (g_ctx.size() > kCachedContexts) g_ctx.pop_back();
+    *out = sp;
+    return OMR_OK;
+}
+
+// fn(t, lo, hi) on T host threads over [0, m) in contiguous slices; the first error wins.  Every thread leases its own stream
+// and pinned staging block (HStream), so pageable copies and the page faults of fresh result images run side by side.
+template <class F>
+int on_threads(int m, F fn)
+{
+    const int T = (int)std::max(1u, std::min<unsigned>((unsigned)m, std::min(std::thread::hardware_concurrency(), 16u)));
+    std::vector<int> rcs((size_t)T, OMR_OK);
+    std::vector<std::string> errs((size_t)T);
+    std::vector<std::thread> pool;
+    int dev = 0;
+    OMR_HIP(hipGetDevice(&dev));
+    for (int t = 0; t < T; t++)
+        pool.emplace_back([&, t]() {
+            if (hipSetDevice(dev) != hipSuccess) {
+                rcs[(size_t)t] = fail(OMR_ERR_GPU, "hipSetDevice failed");
+            } else {
+                HStream st;
+                int rc = st.create();
+                if (!rc) rc = fn(st.s, (int)((int64_t)m * t / T), (int)((int64_t)m * (t + 1) / T));
+                rcs[(size_t)t] = rc;
+            }
+            if (rcs[(size_t)t]) errs[(size_t)t] = last_error();
+        });
+    for (auto &th : pool) th.join();
+    for (int t = 0; t < T; t++)
+        if (rcs[(size_t)t]) return fail(rcs[(size_t)t], "%s", errs[(size_t)t].c_str());
+    return OMR_OK;
+}
+
+// Development aid (make debug, -DOMR_RUNS_DEBUG only; the release library reads no such switch): with
+// OMR_CORRECT_BATCH_TIMES set in the environment, every run of a bucket prints the wall time of its phases (context,
+// upload, device pipeline, canvases to host images) to stderr.
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector<int> &idx)
+{
+#ifdef OMR_RUNS_DEBUG
+    static const bool times = getenv("OMR_CORRECT_BATCH_TIMES") != nullptr;
+#else
+    const bool times = false;
+#endif
+    double t0 = now_ms(), t_ctx = 0, t_up = 0, t_run = 0, t_down = 0;
+    const int m = (int)idx.size();
+    std::shared_ptr<omr_correct_batch> cbp;
+    int rc = cached_context(CtxKey{a.device, rows, cols, cn, a.max_angle, a.step, a.max_w, a.max_h, a.hmin, a.hgap}, &cbp);
+    if (rc == OMR_ERR_ASSERT) {  // the projection size truncates to 0 x n: the per-call function fails on each of these sheets
+        for (int i : idx) a.scan_rc[i] = rc, a.angle[i] = 0.0, a.need_check[i] = 0;
+        clear_error();
+        return OMR_OK;
+    }
+    if (rc) return rc;
+    omr_correct_batch *cb = cbp.get();
+    t_ctx = now_ms() - t0;
+    const int zmax = std::min(m, kChunk);
+    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
+    const int64_t out_step = (int64_t)cb->DC * cn, out_stride = out_step * cb->DR;
+    HStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
+    if ((rc = st.create())) return rc;
+    DevBuf din, dout;
+    OMR_HIP(din.alloc((size_t)zmax * in_stride));
+    if (a.rotated) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
+    std::vector<double> ang((size_t)zmax);
+    std::vector<int32_t> chk((size_t)zmax), src((size_t)zmax), size(2 * (size_t)zmax);
+    for (int j0 = 0; j0 < m; j0 += zmax) {
+        const int z = std::min(zmax, m - j0);
+        double t1 = now_ms();
+        // host memory -> device, from several threads
+        rc = on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {
+            for (int j = lo; j < hi; j++) {
+                const omr_image &im = a.srcs[idx[(size_t)(j0 + j)]];
+                uint8_t *d = din.as<uint8_t>() + (size_t)j * in_stride;
+                if (im.step_bytes == row)
+                    OMR_HIP(hipMemcpyAsync(d, im.data, (size_t)row * rows, hipMemcpyHostToDevice, s));
+                else
+                    OMR_HIP(hipMemcpy2DAsync(d, (size_t)row, im.data, (size_t)im.step_bytes, (size_t)row, (size_t)rows,
+                                             hipMemcpyHostToDevice, s));
+            }
+            OMR_HIP(hipStreamSynchronize(s));
+            return OMR_OK;
+        });
+        if (rc) return rc;
+        double t2 = now_ms();
+        t_up += t2 - t1;
+        if ((rc = omr_correct_batch_run_device(cb, din.as<uint8_t>(), in_stride, row, z, ang.data(), chk.data(), src.data(),
+                                               a.rotated ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data())))
+            return rc;
+        for (int j = 0; j < z; j++) {
+            const int i = idx[(size_t)(j0 + j)];
+            a.angle[i] = ang[(size_t)j];
+            a.need_check[i] = chk[(size_t)j];
+            a.scan_rc[i] = src[(size_t)j];
+        }
+        double t3 = now_ms();
+        t_run += t3 - t2;
+        if (!a.rotated) continue;
+        // canvases -> fresh host images, from several threads: packed on the device, then one staged copy each
+        rc = on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {
+            DevBuf pack;
+            OMR_HIP(pack.alloc((size_t)out_stride));
+            for (int j = lo; j < hi; j++) {
+                if (src[(size_t)j] != OMR_OK) continue;
+                const int r = size[2 * (size_t)j], c = size[2 * (size_t)j + 1];
+                omr_image_owned &o = a.rotated[idx[(size_t)(j0 + j)]];
+                const int64_t ostep = (int64_t)c * cn;
+                uint8_t *data = (uint8_t *)malloc((size_t)r * ostep);
+                if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
+                o = omr_image_owned{data, r, c, cn, ostep};
+                OMR_HIP(hipMemcpy2DAsync(pack.p, (size_t)ostep, dout.as<uint8_t>() + (size_t)j * out_stride, (size_t)out_step,
+                                         (size_t)ostep, (size_t)r, hipMemcpyDeviceToDevice, s));
+                int rc1 = staged_d2h(o.data, pack.p, (size_t)r * ostep, s);
+                if (rc1) return rc1;
+            }
+            return OMR_OK;
+        });
+        if (rc) return rc;
+        t_down += now_ms() - t3;
+    }
+    if (times)
+        fprintf(stderr, "omr_correct_default_batch %d x %dx%dx%d: context %.2f ms, upload %.2f ms, device %.2f ms, canvases %.2f ms\n", m,
+                rows, cols, cn, t_ctx, t_up, t_run, t_down);
+    return OMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int omr_correct_batch_canvas(int32_t rows, int32_t cols, int32_t *max_rows, int32_t *max_cols)
+{
+    clear_error();
+    if (!max_rows || !max_cols || rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "bad arguments");
+    int R, C;
+    canvas_of(rows, cols, &R, &C);
+    *max_rows = R;
+    *max_cols = C;
+    return OMR_OK;
+}
+
+int omr_correct_batch_create(int32_t rows, int32_t cols, int32_t channels, uint16_t projection_max_angle,
+                             double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
+                             double hough_min_line_length, double hough_max_line_gap, int32_t device, int32_t max_scans,
+                             omr_correct_batch **out)
+{
+    clear_error();
+    if (!out) return fail(OMR_ERR_BADARG, "null out");
+    *out = nullptr;
+    if (max_scans < 1 || max_scans > 65535) return fail(OMR_ERR_BADARG, "max_scans must be in 1..65535");
+    if (device < 0) return fail(OMR_ERR_BADARG, "negative device");
+    int rc = check_shape(rows, cols, channels);
+    if (rc) return rc;
+    int N = 0;
+    const int A = candidate_count(projection_max_angle, projection_angle_step, &N);
+    if (A <= 0) return fail(OMR_ERR_BADARG, "empty candidate range");
+    // omr.rs:60-82, :114-126
+    const double ws = projection_max_width <= 0 ? 1.0 : (double)projection_max_width / (double)cols;
+    const double hs = projection_max_height <= 0 ? 1.0 : (double)projection_max_height / (double)rows;
+    const double scale = ws < hs ? ws : hs;
+    const int dc = (int)((double)cols * scale), dr = (int)((double)rows * scale);
+    if (dr <= 0 || dc <= 0) return fail(OMR_ERR_ASSERT, "resize to an empty size");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
+    if (device >= ndev) return fail(OMR_ERR_BADARG, "device %d of %d", device, ndev);
+    OMR_HIP(hipSetDevice(device));
+    NoPoolScope owned;
+    std::unique_ptr<omr_correct_batch> cb(new omr_correct_batch);
+    cb->device = device, cb->rows = rows, cb->cols = cols, cb->cn = channels, cb->max_scans = max_scans;
+    cb->max_angle = projection_max_angle, cb->step = projection_angle_step;
+    cb->hough_min = hough_min_line_length, cb->hough_gap = hough_max_line_gap;
+    cb->N = N, cb->A = A, cb->scale = scale, cb->dr = dr, cb->dc = dc;
+    front_mode(cb.get());
+    canvas_of(rows, cols, &cb->DR, &cb->DC);
+    cb->small_step = (dc + 3) & ~3;
+    cb->small_stride = ((int64_t)dr * cb->small_step + 255) & ~(int64_t)255;
+    OMR_HIP(hipStreamCreateWithFlags(&cb->s, hipStreamNonBlocking));
+    OMR_HIP(hipStreamCreateWithFlags(&cb->sw, hipStreamNonBlocking));
+    OMR_HIP(cb->small.alloc((size_t)max_scans * cb->small_stride));
+    OMR_HIP(cb->best.alloc(sizeof(int32_t) * (size_t)max_scans));
+    OMR_HIP(cb->vsd.alloc(sizeof(double) * (size_t)max_scans * A));
+    OMR_HIP(cb->hsd.alloc(sizeof(double) * (size_t)max_scans * A));
+    OMR_HIP(hipHostMalloc((void **)&cb->h_vsd, sizeof(double) * (size_t)max_scans * A, hipHostMallocDefault));
+    OMR_HIP(hipHostMalloc((void **)&cb->h_hsd, sizeof(double) * (size_t)max_scans * A, hipHostMallocDefault));
+    if (cb->mode != FRONT_AREA_FUSED) cb->er_stride = ((int64_t)rows * cols + 255) & ~(int64_t)255;  // buffer: front_end
+    if (cb->mode == FRONT_AREA_GENERAL) {  // resizeArea_'s tap tables, once per context
+        std::vector<AreaTap> xt, yt;
+        std::vector<int32_t> xo, yo;
+        area_tab(cols, dc, 1, 1. / ((double)dc / cols), &xt, &xo);
+        area_tab(rows, dr, 1, 1. / ((double)dr / rows), &yt, &yo);
+        OMR_HIP(cb->xt.alloc(sizeof(AreaTap) * xt.size()));
+        OMR_HIP(cb->xo.alloc(sizeof(int32_t) * xo.size()));
+        OMR_HIP(cb->yt.alloc(sizeof(AreaTap) * yt.size()));
+        OMR_HIP(cb->yo.alloc(sizeof(int32_t) * yo.size()));
+        OMR_HIP(hipMemcpy(cb->xt.p, xt.data(), sizeof(AreaTap) * xt.size(), hipMemcpyHostToDevice));
+        OMR_HIP(hipMemcpy(cb->xo.p, xo.data(), sizeof(int32_t) * xo.size(), hipMemcpyHostToDevice));
+        OMR_HIP(hipMemcpy(cb->yt.p, yt.data(), sizeof(AreaTap) * yt.size(), hipMemcpyHostToDevice));
+        OMR_HIP(hipMemcpy(cb->yo.p, yo.data(), sizeof(int32_t) * yo.size(), hipMemcpyHostToDevice));
+    }
+    if ((rc = omr_batch_create(dr, dc, projection_max_angle, projection_angle_step, scale, device, 1, &cb->sweep))) return rc;
+    if ((rc = omr_batch_set_group(cb->sweep, std::min(max_scans, 64)))) return rc;
+    *out = cb.release();
+    return OMR_OK;
+}
+
+void omr_correct_batch_destroy(omr_correct_batch *cb) { delete cb; }
+
+int omr_correct_batch_run_device(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride_bytes, int64_t step_bytes,
+                                 int32_t n, double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t *d_out,
+                                 int64_t out_stride_bytes, int64_t out_step_bytes, int32_t *out_size)
+{
+    clear_error();
+    if (!cb || !d_scans || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "null argument");
+    if (n < 1 || n > cb->max_scans) return fail(OMR_ERR_BADARG, "n = %d outside 1..max_scans (%d)", n, cb->max_scans);
+    if (step_bytes < (int64_t)cb->cols * cb->cn) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
+    if (scan_stride_bytes < (int64_t)cb->rows * step_bytes) return fail(OMR_ERR_BADARG, "scan_stride_bytes < rows x step_bytes");
+    if (d_out && (out_step_bytes < (int64_t)cb->DC * cb->cn || out_stride_bytes < (int64_t)cb->DR * out_step_bytes))
+        return fail(OMR_ERR_BADARG, "every output slot must hold %d x %d x %d channels (omr_correct_batch_canvas)", cb->DR, cb->DC,
+                    cb->cn);
+    std::lock_guard<std::mutex> lk(cb->mu);
+    OMR_HIP(hipSetDevice(cb->device));
+    int rc = run_locked(cb, d_scans, scan_stride_bytes, step_bytes, n, rotate_angle, need_check, scan_rc, d_out, out_stride_bytes,
+                        out_step_bytes, out_size);
+    if (rc) {  // nothing of this call may still run when the next one starts
+        (void)hipStreamSynchronize(cb->s);
+        (void)hipStreamSynchronize(cb->sw);
+        (void)omr_batch_sync(cb->sweep);
+    }
+    return rc;
+}
+
+int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
+                              int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
+                              double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
+                              omr_image_owned *rotated)
+{
+    clear_error();
+    if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    std::vector<std::tuple<int, int, int>> shapes;  // in order of first appearance
+    std::vector<std::vector<int>> members;
+    for (int i = 0; i < n; i++) {
+        const omr_image &im = srcs[i];
+        if (!im.data) return fail(OMR_ERR_BADARG, "null image %d", i);
+        int rc = check_shape(im.rows, im.cols, im.channels);
+        if (rc) return rc;
+        if (im.step_bytes < (int64_t)im.cols * im.channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
+        const std::tuple<int, int, int> sh(im.rows, im.cols, im.channels);
+        size_t k = 0;
+        while (k < shapes.size() && shapes[k] != sh) k++;
+        if (k == shapes.size()) {
+            shapes.push_back(sh);
+            members.emplace_back();
+        }
+        members[k].push_back(i);
+    }
+    if (rotated)
+        for (int i = 0; i < n; i++) rotated[i] = omr_image_owned{nullptr, 0, 0, 0, 0};
+    int rc = have_device();
+    if (rc) return rc;
+    int dev = 0;
+    OMR_HIP(hipGetDevice(&dev));
+    const HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                     hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
+    for (size_t k = 0; k < shapes.size() && rc == OMR_OK; k++)
+        rc = host_bucket(a, std::get<0>(shapes[k]), std::get<1>(shapes[k]), std::get<2>(shapes[k]), members[k]);
+    if (rc && rotated)
+        for (int i = 0; i < n; i++) omr_image_free(&rotated[i]);
+    return rc;
+}
+
+}  // extern "C"

@@ -101,6 +101,8 @@ int candidate_count(uint16_t max_angle, double step, int *N_out);  // projection
 void sweep_matrices(int rows, int cols, int N, double step, double scale, double *M_out);
 // rotate_mat's forward matrix and canvas (transfer.rs:459-523; oics_host.cpp)
 int rotate_geometry(int rows, int cols, double angle_deg, double scale, int clip, double M[6], int *drows, int *dcols);
+// OpenCV computeResizeAreaTab for resizeArea_, grouped per destination index (CSR offsets ofs[0..dsize]); oics_host.cpp
+void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs);
 
 // Immutable per-(shape, matrices) state: inverse matrices, fixed-point tables, LDS tiling.
 struct SweepTables {

@@ -171,8 +171,10 @@ inline int cv_ceil(double v)
     return i + (i < v);
 }
 
+}  // namespace
+
 // OpenCV computeResizeAreaTab (resize.cpp), grouped per destination index (CSR offsets).
-void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs)
+void omr::area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs)
 {
     tab->clear();
     ofs->assign((size_t)dsize + 1, 0);
@@ -194,6 +196,8 @@ void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *
     }
     (*ofs)[dsize] = (int32_t)tab->size();
 }
+
+namespace {
 
 // resize(src, dsize, interp) on the device for the two flags the reference passes (transfer.rs:66-91
 // scale_self: INTER_LINEAR when enlarging, INTER_AREA otherwise; transfer.rs:128-145 resize_self and

@@ -1,5 +1,6 @@
 """oics::omr (packages/lib/src/omr.rs) through the C ABI."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -103,6 +104,77 @@ def correct_default(src_mat, projection_max_angle, projection_angle_step, projec
                                     float(hough_max_line_gap), C.byref(ang), C.byref(chk),
                                     C.byref(owned) if want_image else None))
     return ang.value, bool(chk.value), (_take(owned) if want_image else None)
+
+
+def correct_batch_canvas(rows, cols):
+    """Largest CONTAIN canvas any angle gives at rows x cols (cols rounded up to 4) -> (rows, cols); no GPU needed."""
+    r, c = C.c_int32(), C.c_int32()
+    check(lib().omr_correct_batch_canvas(int(rows), int(cols), C.byref(r), C.byref(c)))
+    return r.value, c.value
+
+
+class CorrectBatch:
+    """omr_correct_batch_*: correct_default for repeated batches of device-resident sheets of one shape and one
+    parameter set."""
+
+    def __init__(self, rows, cols, channels, projection_max_angle, projection_angle_step, projection_max_width,
+                 projection_max_height, hough_min_line_length, hough_max_line_gap, device=0, max_scans=256):
+        self.handle = C.c_void_p()
+        check(lib().omr_correct_batch_create(int(rows), int(cols), int(channels), int(projection_max_angle),
+                                             float(projection_angle_step), int(projection_max_width),
+                                             int(projection_max_height), float(hough_min_line_length),
+                                             float(hough_max_line_gap), int(device), int(max_scans), C.byref(self.handle)))
+        self.rows, self.cols, self.channels, self.max_scans = rows, cols, channels, max_scans
+        self.canvas = correct_batch_canvas(rows, cols)
+
+    def close(self):
+        if self.handle:
+            lib().omr_correct_batch_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def run_device(self, d_scans, scan_stride, step, n, d_out=None, out_stride=0, out_step=0):
+        """device pointers in -> (rotate_angle f64[n], need_check bool[n], scan_rc i32[n], out_size i32[n, 2])"""
+        ang = np.zeros(n, np.float64)
+        chk = np.zeros(n, np.int32)
+        rc = np.zeros(n, np.int32)
+        size = np.zeros((n, 2), np.int32)
+        check(lib().omr_correct_batch_run_device(self.handle, d_scans, int(scan_stride), int(step), int(n),
+                                                 ang.ctypes.data_as(f64p), chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p),
+                                                 d_out, int(out_stride), int(out_step), size.ctypes.data_as(i32p)))
+        return ang, chk.astype(bool), rc, size
+
+
+def correct_default_batch(src_mats, projection_max_angle, projection_angle_step, projection_max_width,
+                          projection_max_height, hough_min_line_length, hough_max_line_gap, want_image=True):
+    """omr_correct_default_batch: correct_default of many decoded sheets of any shapes ->
+    [(rotate_angle, need_check, rotated image or None, scan_rc)] in input order (scan_rc != 0: the sheet failed as the
+    per-call function would, and carries no image)"""
+    from .hough import _take
+    from ._lib import OmrImage
+    keep, ims = [], []
+    for m in src_mats:
+        a, im = as_image(_mat(m))
+        keep.append(a)
+        ims.append(im)
+    n = len(ims)
+    arr = (OmrImage * n)(*ims)
+    ang = np.zeros(n, np.float64)
+    chk = np.zeros(n, np.int32)
+    rc = np.zeros(n, np.int32)
+    owned = (OmrImageOwned * n)() if want_image else None
+    check(lib().omr_correct_default_batch(arr, n, int(projection_max_angle), float(projection_angle_step),
+                                          int(projection_max_width), int(projection_max_height),
+                                          float(hough_min_line_length), float(hough_max_line_gap), ang.ctypes.data_as(f64p),
+                                          chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), owned))
+    imgs = [None] * n
+    if want_image:  # one copy per image out of the library's buffer: on threads (numpy's copy releases the GIL)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+            imgs = list(ex.map(lambda i: _take(owned[i]) if owned[i].data else None, range(n)))
+    return [(float(ang[i]), bool(chk[i]), imgs[i], int(rc[i])) for i in range(n)]
 
 
 def get_result_from_fourier_transform(src_mat, canny_threshold_weak, canny_threshold_strong, fourier_min_line_length,
