@@ -470,6 +470,23 @@ int omr_correct_batch_run_device(omr_correct_batch *cb, const uint8_t *d_scans, 
                                  int64_t step_bytes, int32_t n, double *rotate_angle, int32_t *need_check,
                                  int32_t *scan_rc, uint8_t *d_out, int64_t out_stride_bytes,
                                  int64_t out_step_bytes, int32_t *out_size);
+/* How a context's front end (gray + erode x3 + INTER_AREA to the projection size) runs: */
+#define OMR_CORRECT_FRONT_AREA_FUSED 0   /* integer factors <= 64 (1 x 1: no resize), one fused kernel */
+#define OMR_CORRECT_FRONT_AREA_INT 1     /* integer factors, one of them > 64: eroded sheets, then resizeAreaFast_ */
+#define OMR_CORRECT_FRONT_AREA_GENERAL 2 /* fractional shrink: eroded sheets, then resizeArea_ (tap tables) */
+#define OMR_CORRECT_FRONT_LINEAR 3       /* an axis enlarges (quirk B7): eroded sheets, then the bilinear emulation */
+/* For tests and inspection: the projection size (proj_rows x proj_cols), the front-end mode (OMR_CORRECT_FRONT_*) and
+ * the integer shrink factors kx (across) and ky (down), 0 outside the two integer modes.  Pointers may be NULL. */
+int omr_correct_batch_info(omr_correct_batch *cb, int32_t *proj_rows, int32_t *proj_cols, int32_t *front_mode,
+                           int32_t *kx, int32_t *ky);
+/* For tests and inspection: the front end of omr_correct_batch_run_device alone (same dispatch, chunks and stream) on
+ * n sheets laid out as there; sheet i's projection-size image, before the threshold, lands in the top-left of
+ * d_small + i * small_stride_bytes, rows small_step_bytes apart.  Arguments are checked as
+ * omr_correct_batch_run_device does, and small_step_bytes >= proj_cols, small_stride_bytes >= proj_rows x
+ * small_step_bytes.  Synchronous.  Runs do not depend on it. */
+int omr_correct_batch_front_device(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                                   int64_t step_bytes, int32_t n, uint8_t *d_small, int64_t small_stride_bytes,
+                                   int64_t small_step_bytes);
 /* Host images of any shapes, bucketed by (rows, cols, channels) as omr_sweep_batch does, on the current device;
  * results land at the sheets' own positions.  rotated (n owned images, omr_image_free each) may be NULL; a sheet
  * with scan_rc[i] != 0 gets an empty image (data NULL) -- a shape whose projection size truncates to 0 gives every

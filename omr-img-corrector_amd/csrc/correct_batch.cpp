@@ -45,11 +45,12 @@ hipError_t launch_area_general_batch(const uint8_t *d_src, int64_t scan_stride, 
 
 namespace {
 
+// the front-end modes (include/omrdeskew.h, OMR_CORRECT_FRONT_*)
 enum FrontMode {
-    FRONT_AREA_FUSED = 0,  // integer factors <= 64: gray + erode + resizeAreaFast_ in one kernel
-    FRONT_AREA_INT = 1,    // integer factors > 64: eroded sheets, then the per-call resizeAreaFast_ kernel per sheet
-    FRONT_AREA_GENERAL = 2,  // fractional shrink: eroded sheets, then resizeArea_ with the context's tap tables
-    FRONT_LINEAR = 3,        // an axis enlarges (quirk B7): eroded sheets, then the per-call bilinear kernel per sheet
+    FRONT_AREA_FUSED = OMR_CORRECT_FRONT_AREA_FUSED,  // integer factors <= 64: gray + erode + resizeAreaFast_ in one kernel
+    FRONT_AREA_INT = OMR_CORRECT_FRONT_AREA_INT,      // integer factors > 64: eroded sheets, then resizeAreaFast_ per sheet
+    FRONT_AREA_GENERAL = OMR_CORRECT_FRONT_AREA_GENERAL,  // fractional shrink: eroded sheets, then resizeArea_ (tap tables)
+    FRONT_LINEAR = OMR_CORRECT_FRONT_LINEAR,  // an axis enlarges (quirk B7): eroded sheets, then the bilinear kernel per sheet
 };
 const int kChunk = 256;  // sheets per front-end / warp launch when a full-size intermediate is needed
 
@@ -377,6 +378,16 @@ int run_locked(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_strid
     return OMR_OK;
 }
 
+// the sheet arguments of omr_correct_batch_run_device / _front_device
+int check_sheets(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n)
+{
+    if (!cb || !d_scans) return fail(OMR_ERR_BADARG, "null argument");
+    if (n < 1 || n > cb->max_scans) return fail(OMR_ERR_BADARG, "n = %d outside 1..max_scans (%d)", n, cb->max_scans);
+    if (step < (int64_t)cb->cols * cb->cn) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
+    if (scan_stride < (int64_t)cb->rows * step) return fail(OMR_ERR_BADARG, "scan_stride_bytes < rows x step_bytes");
+    return OMR_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -644,22 +655,56 @@ int omr_correct_batch_run_device(omr_correct_batch *cb, const uint8_t *d_scans, 
                                  int64_t out_stride_bytes, int64_t out_step_bytes, int32_t *out_size)
 {
     clear_error();
-    if (!cb || !d_scans || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "null argument");
-    if (n < 1 || n > cb->max_scans) return fail(OMR_ERR_BADARG, "n = %d outside 1..max_scans (%d)", n, cb->max_scans);
-    if (step_bytes < (int64_t)cb->cols * cb->cn) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (scan_stride_bytes < (int64_t)cb->rows * step_bytes) return fail(OMR_ERR_BADARG, "scan_stride_bytes < rows x step_bytes");
+    if (!rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "null argument");
+    int rc = check_sheets(cb, d_scans, scan_stride_bytes, step_bytes, n);
+    if (rc) return rc;
     if (d_out && (out_step_bytes < (int64_t)cb->DC * cb->cn || out_stride_bytes < (int64_t)cb->DR * out_step_bytes))
         return fail(OMR_ERR_BADARG, "every output slot must hold %d x %d x %d channels (omr_correct_batch_canvas)", cb->DR, cb->DC,
                     cb->cn);
     std::lock_guard<std::mutex> lk(cb->mu);
     OMR_HIP(hipSetDevice(cb->device));
-    int rc = run_locked(cb, d_scans, scan_stride_bytes, step_bytes, n, rotate_angle, need_check, scan_rc, d_out, out_stride_bytes,
-                        out_step_bytes, out_size);
+    rc = run_locked(cb, d_scans, scan_stride_bytes, step_bytes, n, rotate_angle, need_check, scan_rc, d_out, out_stride_bytes,
+                    out_step_bytes, out_size);
     if (rc) {  // nothing of this call may still run when the next one starts
         (void)hipStreamSynchronize(cb->s);
         (void)hipStreamSynchronize(cb->sw);
         (void)omr_batch_sync(cb->sweep);
     }
+    return rc;
+}
+
+int omr_correct_batch_info(omr_correct_batch *cb, int32_t *proj_rows, int32_t *proj_cols, int32_t *front_mode, int32_t *kx,
+                           int32_t *ky)
+{
+    clear_error();
+    if (!cb) return fail(OMR_ERR_BADARG, "null context");
+    const bool integer = cb->mode == FRONT_AREA_FUSED || cb->mode == FRONT_AREA_INT;
+    if (proj_rows) *proj_rows = cb->dr;
+    if (proj_cols) *proj_cols = cb->dc;
+    if (front_mode) *front_mode = cb->mode;
+    if (kx) *kx = integer ? cb->kx : 0;
+    if (ky) *ky = integer ? cb->ky : 0;
+    return OMR_OK;
+}
+
+int omr_correct_batch_front_device(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride_bytes, int64_t step_bytes,
+                                   int32_t n, uint8_t *d_small, int64_t small_stride_bytes, int64_t small_step_bytes)
+{
+    clear_error();
+    int rc = check_sheets(cb, d_scans, scan_stride_bytes, step_bytes, n);
+    if (rc) return rc;
+    if (!d_small) return fail(OMR_ERR_BADARG, "null argument");
+    if (small_step_bytes < cb->dc || small_stride_bytes < (int64_t)cb->dr * small_step_bytes)
+        return fail(OMR_ERR_BADARG, "every output slot must hold %d x %d bytes", cb->dr, cb->dc);
+    std::lock_guard<std::mutex> lk(cb->mu);
+    OMR_HIP(hipSetDevice(cb->device));
+    rc = front_end(cb, d_scans, scan_stride_bytes, step_bytes, n);
+    for (int i = 0; rc == OMR_OK && i < n; i++)
+        if (hipMemcpy2DAsync(d_small + (size_t)i * small_stride_bytes, (size_t)small_step_bytes,
+                             cb->small.as<uint8_t>() + (size_t)i * cb->small_stride, (size_t)cb->small_step, (size_t)cb->dc,
+                             (size_t)cb->dr, hipMemcpyDeviceToDevice, cb->s) != hipSuccess)
+            rc = fail(OMR_ERR_GPU, "hipMemcpy2DAsync failed");
+    if (hipStreamSynchronize(cb->s) != hipSuccess && rc == OMR_OK) rc = fail(OMR_ERR_GPU, "hipStreamSynchronize failed");
     return rc;
 }
 

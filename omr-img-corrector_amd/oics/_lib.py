@@ -132,6 +132,9 @@ SYMBOLS = {
     "omr_correct_batch_canvas": (C.c_int, [C.c_int32, C.c_int32, i32p, i32p]),
     "omr_correct_batch_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, f64p, i32p, i32p,
                                                C.c_void_p, C.c_int64, C.c_int64, i32p]),
+    "omr_correct_batch_info": (C.c_int, [C.c_void_p, i32p, i32p, i32p, i32p, i32p]),
+    "omr_correct_batch_front_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                 C.c_int64, C.c_int64]),
     "omr_correct_default_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_int32, C.c_int32,
                                             C.c_double, C.c_double, f64p, i32p, i32p, C.POINTER(OmrImageOwned)]),
     "omr_get_fft_image": (C.c_int, [C.POINTER(OmrImage), C.POINTER(OmrImageOwned), C.POINTER(OmrImageOwned)]),

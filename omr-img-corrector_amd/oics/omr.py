@@ -146,6 +146,22 @@ class CorrectBatch:
                                                  d_out, int(out_stride), int(out_step), size.ctypes.data_as(i32p)))
         return ang, chk.astype(bool), rc, size
 
+    def info(self):
+        """-> (proj_rows, proj_cols, front_mode, kx, ky): the front end's projection size, OMR_CORRECT_FRONT_* mode and
+        integer shrink factors (0 outside the integer modes).  For tests and inspection."""
+        v = [C.c_int32() for _ in range(5)]
+        check(lib().omr_correct_batch_info(self.handle, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def front_device(self, d_scans, scan_stride, step, n, d_small, small_stride, small_step):
+        """the front end alone: n sheets' projection-size images (before the threshold) to d_small.  For tests and
+        inspection."""
+        check(lib().omr_correct_batch_front_device(self.handle, d_scans, int(scan_stride), int(step), int(n), d_small,
+                                                   int(small_stride), int(small_step)))
+
+
+FRONT_AREA_FUSED, FRONT_AREA_INT, FRONT_AREA_GENERAL, FRONT_LINEAR = 0, 1, 2, 3  # OMR_CORRECT_FRONT_*
+
 
 def correct_default_batch(src_mats, projection_max_angle, projection_angle_step, projection_max_width,
                           projection_max_height, hough_min_line_length, hough_max_line_gap, want_image=True):

@@ -3,6 +3,7 @@ include/omrdeskew.h with the agreed parameter lists, exported by the library, bo
 bound against omr_rotate_size; argument errors reported without a GPU."""
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -28,6 +29,13 @@ DECLS = {
         ("int64_t", "step_bytes"), ("int32_t", "n"), ("double *", "rotate_angle"), ("int32_t *", "need_check"),
         ("int32_t *", "scan_rc"), ("uint8_t *", "d_out"), ("int64_t", "out_stride_bytes"), ("int64_t", "out_step_bytes"),
         ("int32_t *", "out_size")]),
+    "omr_correct_batch_info": ("int", [
+        ("omr_correct_batch *", "cb"), ("int32_t *", "proj_rows"), ("int32_t *", "proj_cols"), ("int32_t *", "front_mode"),
+        ("int32_t *", "kx"), ("int32_t *", "ky")]),
+    "omr_correct_batch_front_device": ("int", [
+        ("omr_correct_batch *", "cb"), ("const uint8_t *", "d_scans"), ("int64_t", "scan_stride_bytes"),
+        ("int64_t", "step_bytes"), ("int32_t", "n"), ("uint8_t *", "d_small"), ("int64_t", "small_stride_bytes"),
+        ("int64_t", "small_step_bytes")]),
     "omr_correct_default_batch": ("int", [
         ("const omr_image *", "srcs"), ("int32_t", "n"), ("uint16_t", "projection_max_angle"),
         ("double", "projection_angle_step"), ("int32_t", "projection_max_width"), ("int32_t", "projection_max_height"),
@@ -115,6 +123,24 @@ def test_run_device_rejects_a_null_context():
     assert L.omr_correct_batch_run_device(None, C.c_void_p(256), 1150 * 1240 * 3, 1240 * 3, n, ang, chk, rc, None, 0, 0,
                                           None) == -5
     assert len(L.omr_last_error()) > 0
+
+
+def test_inspection_entry_points_reject_a_null_context():
+    L = oics.lib()
+    v = [C.c_int32(7) for _ in range(5)]
+    assert L.omr_correct_batch_info(None, *[C.byref(x) for x in v]) == -5
+    assert [x.value for x in v] == [7] * 5
+    assert L.omr_correct_batch_info(None, None, None, None, None, None) == -5
+    assert L.omr_correct_batch_front_device(None, C.c_void_p(256), 1150 * 1240 * 3, 1240 * 3, 2, C.c_void_p(512), 230 * 248,
+                                            248) == -5
+    assert len(L.omr_last_error()) > 0
+
+
+def test_front_mode_names_match_the_header():
+    text = open(os.path.join(ROOT, "include", "omrdeskew.h")).read()
+    for name in ("AREA_FUSED", "AREA_INT", "AREA_GENERAL", "LINEAR"):
+        m = re.search(r"#define OMR_CORRECT_FRONT_%s (\d+)" % name, text)
+        assert m and int(m.group(1)) == getattr(omr, "FRONT_" + name), name
 
 
 def test_host_batch_rejects_bad_arguments_without_a_gpu():
