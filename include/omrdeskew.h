@@ -65,6 +65,17 @@ typedef struct {
 #define OMR_INTER_NEAREST 0
 #define OMR_INTER_LINEAR 1
 #define OMR_INTER_AREA 3 /* imgproc::INTER_AREA: resize only */
+/* warpAffine flags and border modes (OpenCV 4.6.0 numbering) for omr_rotate_ex / omr_rotate_device_ex */
+#define OMR_INTER_CUBIC 2
+#define OMR_INTER_LANCZOS4 4
+#define OMR_WARP_FILL_OUTLIERS 8
+#define OMR_WARP_INVERSE_MAP 16
+#define OMR_BORDER_CONSTANT 0
+#define OMR_BORDER_REPLICATE 1
+#define OMR_BORDER_REFLECT 2
+#define OMR_BORDER_WRAP 3
+#define OMR_BORDER_REFLECT_101 4
+#define OMR_BORDER_TRANSPARENT 5
 
 int omr_version(void);
 int omr_device_count(void);
@@ -376,6 +387,25 @@ int omr_rotate_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int3
                       int32_t channels, double angle_deg, double scale, int32_t interp,
                       const uint8_t border_value[4], int32_t clip, uint8_t *d_dst, int64_t dst_step,
                       int32_t dst_rows, int32_t dst_cols, void *stream);
+/* rotate_mat with every flag and border mode warpAffine takes (transfer.rs:459-523 passes both through).
+ * flags & 7 is the interpolation: NEAREST, LINEAR, CUBIC, LANCZOS4; 3 (INTER_AREA) is LINEAR, as in warpAffine;
+ * 5..7 are OMR_ERR_NOTIMPL.  OMR_WARP_INVERSE_MAP uses rotate_mat's matrix as the dst->src map as it is;
+ * OMR_WARP_FILL_OUTLIERS is ignored (warpAffine ignores it); any other bit is OMR_ERR_BADARG.  border_mode is
+ * OMR_BORDER_CONSTANT..OMR_BORDER_TRANSPARENT (anything else, BORDER_ISOLATED included: OMR_ERR_BADARG).  Canvas
+ * and matrix are omr_rotate's; channels 1..4.  Every argument is checked before any device work.  NEAREST and
+ * LINEAR (or AREA) with BORDER_CONSTANT and without OMR_WARP_INVERSE_MAP take omr_rotate's path and give its bytes.
+ * BORDER_TRANSPARENT: the device form leaves the skipped destination pixels as they were; the host form starts
+ * from a zero-filled canvas, so they are 0 there (the reference writes into a fresh Mat: undefined). */
+int omr_rotate_ex(const omr_image *src, double angle_deg, double scale, int32_t flags, int32_t border_mode,
+                  const uint8_t border_value[4], int32_t clip, omr_image_owned *dst);
+int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, int32_t channels,
+                         double angle_deg, double scale, int32_t flags, int32_t border_mode,
+                         const uint8_t border_value[4], int32_t clip, uint8_t *d_dst, int64_t dst_step,
+                         int32_t dst_rows, int32_t dst_cols, void *stream);
+/* The fixed-point weight table the warp uses for OMR_INTER_CUBIC (k = 4) or OMR_INTER_LANCZOS4 (k = 8): OpenCV's
+ * initInterTab2D(method, fixpt = true), 32 * 32 entries of k * k int16, entry fy * 32 + fx, tap row * k + col.
+ * *n_out = 1024 * k * k; out == NULL only reports the size; cap < *n_out is OMR_ERR_BADARG.  Host only. */
+int omr_warp_coeff_table(int32_t interp, int16_t *out, int32_t cap, int32_t *n_out);
 
 /* ---- Hough-line deskew path ---------------------------------------------
  * OpenCV 4.6.0 semantics restated on the GPU: Canny is exact (integer stencils + a set-valued

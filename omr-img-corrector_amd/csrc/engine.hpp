@@ -101,6 +101,10 @@ int candidate_count(uint16_t max_angle, double step, int *N_out);  // projection
 void sweep_matrices(int rows, int cols, int N, double step, double scale, double *M_out);
 // rotate_mat's forward matrix and canvas (transfer.rs:459-523; oics_host.cpp)
 int rotate_geometry(int rows, int cols, double angle_deg, double scale, int clip, double M[6], int *drows, int *dcols);
+// warpAffine's INTER_CUBIC / INTER_LANCZOS4 fixed-point weight tables (initInterTab2D): built once per process,
+// uploaded once per device (oics_rotate.cpp)
+const std::vector<int16_t> &warp_coeff_host(int interp);
+int warp_coeff_device(int interp, const int16_t **d_tab);
 // OpenCV computeResizeAreaTab for resizeArea_, grouped per destination index (CSR offsets ofs[0..dsize]); oics_host.cpp
 void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs);
 

@@ -202,6 +202,12 @@ hipError_t launch_resize_area_int_fast(const uint8_t *d_src, int64_t sstep, int 
 hipError_t launch_warp_fast(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
                             int64_t dstep, int drows, int dcols, const double Minv[6], int interp, uint32_t border_rgba,
                             hipStream_t s);
+// warpAffine with interp 0 / 1 / 2 / 4 (K = 1, 2, 4, 8 taps per axis) under border mode 0..5, 1..4 channels
+// (warp_taps.hip); Minv is a HOST pointer, d_wtab the device weight table for interp 2 / 4 (NULL otherwise).
+// BORDER_TRANSPARENT stores nothing at the pixels it skips.
+hipError_t launch_warp_taps(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
+                            int64_t dstep, int drows, int dcols, const double Minv[6], int interp, int border_mode,
+                            uint32_t border_rgba, const int16_t *d_wtab, hipStream_t s);
 // resize(INTER_LINEAR) (area_mode false) / INTER_AREA's bilinear emulation when an axis enlarges (true)
 hipError_t launch_resize_linear(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
                                 int64_t dstep, int drows, int dcols, bool area_mode, hipStream_t s);

@@ -615,6 +615,102 @@ int omr_rotate(const omr_image *src, double angle_deg, double scale, int32_t int
     return rc;
 }
 
+// warpAffine's flags and border mode as omr_rotate_ex takes them: interpolation 0 / 1 / 2 / 4 (INTER_AREA is LINEAR,
+// imgwarp.cpp), whether the matrix is already dst->src
+static int rotate_ex_args(int flags, int border_mode, int *interp, bool *inverse)
+{
+    if (flags & ~(7 | OMR_WARP_FILL_OUTLIERS | OMR_WARP_INVERSE_MAP)) return fail(OMR_ERR_BADARG, "unknown warp flags 0x%x", flags);
+    int ip = flags & 7;
+    if (ip == OMR_INTER_AREA) ip = OMR_INTER_LINEAR;
+    if (ip > OMR_INTER_LANCZOS4) return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", ip);
+    if (border_mode < OMR_BORDER_CONSTANT || border_mode > OMR_BORDER_TRANSPARENT)
+        return fail(OMR_ERR_BADARG, "unknown border mode %d", border_mode);
+    *interp = ip;
+    *inverse = (flags & OMR_WARP_INVERSE_MAP) != 0;
+    return OMR_OK;
+}
+
+// omr_rotate's launch for the pairs it covers (bit for bit its result), warp_taps.hip for every other
+static int rotate_ex_launch(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, const double M[6], int interp,
+                            bool inverse, int border_mode, const uint8_t border_value[4], uint8_t *d_dst, int64_t dstep,
+                            int drows, int dcols, hipStream_t s, DevBuf *keep)
+{
+    if (!inverse && border_mode == OMR_BORDER_CONSTANT && interp <= OMR_INTER_LINEAR)
+        return rotate_launch(d_src, sstep, rows, cols, cn, M, interp, border_value, d_dst, dstep, drows, dcols, s, keep);
+    double Minv[6];
+    if (inverse) memcpy(Minv, M, sizeof Minv);
+    else invert_affine(M, Minv);
+    const int16_t *tab = nullptr;
+    if (interp >= OMR_INTER_CUBIC) {
+        int rc = warp_coeff_device(interp, &tab);
+        if (rc) return rc;
+    }
+    uint32_t border = (uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16) |
+                      ((uint32_t)border_value[3] << 24);
+    OMR_HIP(launch_warp_taps(d_src, sstep, rows, cols, cn, d_dst, dstep, drows, dcols, Minv, interp, border_mode, border,
+                             tab, s));
+    return OMR_OK;
+}
+
+int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, int32_t channels,
+                         double angle_deg, double scale, int32_t flags, int32_t border_mode,
+                         const uint8_t border_value[4], int32_t clip, uint8_t *d_dst, int64_t dst_step,
+                         int32_t dst_rows, int32_t dst_cols, void *stream)
+{
+    if (!d_src || !d_dst || !border_value) return fail(OMR_ERR_BADARG, "null pointer");
+    if (rows <= 0 || cols <= 0 || rows >= 32767 || cols >= 32767 || channels < 1 || channels > 4)
+        return fail(OMR_ERR_ASSERT, "bad image shape");
+    int interp;
+    bool inverse;
+    int rc = rotate_ex_args(flags, border_mode, &interp, &inverse);
+    if (rc) return rc;
+    double M[6];
+    int dr, dc;
+    if ((rc = rotate_geometry_impl(rows, cols, angle_deg, scale, clip, M, &dr, &dc))) return rc;
+    if (dr != dst_rows || dc != dst_cols) return fail(OMR_ERR_ASSERT, "destination must be %dx%d", dc, dr);
+    if (src_step < (int64_t)cols * channels || dst_step < (int64_t)dc * channels) return fail(OMR_ERR_BADARG, "step too small");
+    DevBuf keep;
+    rc = rotate_ex_launch(d_src, src_step, rows, cols, channels, M, interp, inverse, border_mode, border_value, d_dst,
+                          dst_step, dr, dc, (hipStream_t)stream, &keep);
+    if (!rc && keep.p) OMR_HIP(hipStreamSynchronize((hipStream_t)stream));  // generic path: matrix buffer is freed
+    return rc;
+}
+
+int omr_rotate_ex(const omr_image *src, double angle_deg, double scale, int32_t flags, int32_t border_mode,
+                  const uint8_t border_value[4], int32_t clip, omr_image_owned *dst)
+{
+    int rc = check_image(src, false);
+    if (rc) return rc;
+    if (!dst || !border_value) return fail(OMR_ERR_BADARG, "null output");
+    int interp;
+    bool inverse;
+    if ((rc = rotate_ex_args(flags, border_mode, &interp, &inverse))) return rc;
+    double M[6];
+    int drows, dcols;
+    if ((rc = rotate_geometry_impl(src->rows, src->cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
+    int dev;
+    if ((rc = current_device(&dev))) return rc;
+    Stream st;
+    if ((rc = st.create())) return rc;
+    DevImage in, out;
+    DevBuf keep;
+    if ((rc = in.upload(src, st.s))) return rc;
+    if ((rc = out.alloc(drows, dcols, src->channels))) return rc;
+    if (border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(out.ptr(), 0, (size_t)drows * out.step(), st.s));
+    if ((rc = rotate_ex_launch(in.ptr(), in.step(), in.rows, in.cols, in.cn, M, interp, inverse, border_mode, border_value,
+                               out.ptr(), out.step(), drows, dcols, st.s, &keep)))
+        return rc;
+    dst->rows = drows;
+    dst->cols = dcols;
+    dst->channels = src->channels;
+    dst->step_bytes = (int64_t)dcols * src->channels;
+    dst->data = (uint8_t *)malloc((size_t)drows * dst->step_bytes);
+    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
+    rc = out.download(dst->data, dst->step_bytes, st.s);
+    if (rc) omr_image_free(dst);
+    return rc;
+}
+
 // ---- device-resident stages --------------------------------------------------------------------
 static int check_dev_image(const void *s, const void *d, int rows, int cols, int64_t sstep, int64_t dstep, int scn,
                            int dcn)

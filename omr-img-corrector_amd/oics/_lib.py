@@ -15,6 +15,12 @@ i32p = C.POINTER(C.c_int32)
 u32p = C.POINTER(C.c_uint32)
 f64p = C.POINTER(C.c_double)
 
+# warpAffine flags and border modes of omr_rotate_ex / omr_rotate_device_ex (include/omrdeskew.h)
+OMR_INTER_NEAREST, OMR_INTER_LINEAR, OMR_INTER_CUBIC, OMR_INTER_AREA, OMR_INTER_LANCZOS4 = 0, 1, 2, 3, 4
+OMR_WARP_FILL_OUTLIERS, OMR_WARP_INVERSE_MAP = 8, 16
+OMR_BORDER_CONSTANT, OMR_BORDER_REPLICATE, OMR_BORDER_REFLECT, OMR_BORDER_WRAP = 0, 1, 2, 3
+OMR_BORDER_REFLECT_101, OMR_BORDER_TRANSPARENT = 4, 5
+
 
 class OmrImage(C.Structure):
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("channels", C.c_int32),
@@ -114,6 +120,12 @@ SYMBOLS = {
     "omr_rotate_size": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_int32, i32p, i32p]),
     "omr_rotate_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                     C.c_int32, u8p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "omr_rotate_ex": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_int32, C.c_int32, u8p, C.c_int32,
+                                C.POINTER(OmrImageOwned)]),
+    "omr_rotate_device_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                       C.c_int32, C.c_int32, u8p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                       C.c_void_p]),
+    "omr_warp_coeff_table": (C.c_int, [C.c_int32, C.POINTER(C.c_int16), C.c_int32, i32p]),
     "omr_canny": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_hough_lines_p": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, i32p,
                                     C.c_int32, i32p]),

@@ -13,6 +13,17 @@ from .types import RotateClipStrategy
 
 INTER_NEAREST = 0  # == imgproc::WARP_POLAR_LINEAR's numeric value, what the reference passes
 INTER_LINEAR = 1
+INTER_CUBIC = _lib.OMR_INTER_CUBIC
+INTER_AREA = _lib.OMR_INTER_AREA
+INTER_LANCZOS4 = _lib.OMR_INTER_LANCZOS4
+WARP_FILL_OUTLIERS = _lib.OMR_WARP_FILL_OUTLIERS
+WARP_INVERSE_MAP = _lib.OMR_WARP_INVERSE_MAP
+BORDER_CONSTANT = _lib.OMR_BORDER_CONSTANT
+BORDER_REPLICATE = _lib.OMR_BORDER_REPLICATE
+BORDER_REFLECT = _lib.OMR_BORDER_REFLECT
+BORDER_WRAP = _lib.OMR_BORDER_WRAP
+BORDER_REFLECT_101 = _lib.OMR_BORDER_REFLECT_101
+BORDER_TRANSPARENT = _lib.OMR_BORDER_TRANSPARENT
 
 
 def as_image(a):
@@ -122,14 +133,14 @@ def get_projection_standard_deviations(src):
 
 def rotate_mat(src, angle, scale, flags, border_mode=0, border_value=(255.0, 255.0, 255.0, 0.0),
                clip_strategy=RotateClipStrategy.DEFAULT):
-    """transfer.rs:459-523.  border_mode must be BORDER_CONSTANT (0), the only one the reference uses."""
-    if border_mode != 0:
-        raise _lib.OmrError(-213, "only BORDER_CONSTANT is implemented")
+    """transfer.rs:459-523 through omr_rotate_ex: every warpAffine flag (INTER_NEAREST / LINEAR / CUBIC / AREA /
+    LANCZOS4, WARP_INVERSE_MAP, WARP_FILL_OUTLIERS) and border mode (BORDER_CONSTANT .. BORDER_TRANSPARENT; the pixels
+    TRANSPARENT skips are 0)."""
     a, im = as_image(_mat(src))
     b = np.array([int(v) for v in border_value], np.uint8)
     out = OmrImageOwned()
-    check(lib().omr_rotate(C.byref(im), float(angle), float(scale), int(flags), b.ctypes.data_as(u8p),
-                           int(clip_strategy), C.byref(out)))
+    check(lib().omr_rotate_ex(C.byref(im), float(angle), float(scale), int(flags), int(border_mode),
+                              b.ctypes.data_as(u8p), int(clip_strategy), C.byref(out)))
     try:
         shape = (out.rows, out.cols) if out.channels == 1 else (out.rows, out.cols, out.channels)
         n = out.rows * out.step_bytes

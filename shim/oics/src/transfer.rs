@@ -173,8 +173,9 @@ pub fn transfer_thresh_binary_to_vertical_projection(src: &TransformableMatrix) 
     Ok(TransformableMatrix { matrix: pic })
 }
 
-/// transfer.rs:459-523 -> omr_rotate.  `flags` is the interpolation flag as the reference passes it
-/// (0 = INTER_NEAREST, the numeric value of WARP_POLAR_LINEAR; 1 = INTER_LINEAR); only BORDER_CONSTANT exists.
+/// transfer.rs:459-523 -> omr_rotate_ex.  `flags` and `border_mode` go to warpAffine as the reference passes them:
+/// INTER_NEAREST (0, the numeric value of WARP_POLAR_LINEAR), LINEAR, CUBIC, AREA (= LINEAR) or LANCZOS4, with
+/// WARP_INVERSE_MAP / WARP_FILL_OUTLIERS; BORDER_CONSTANT .. BORDER_TRANSPARENT.  Flags 5..7 are OMR_ERR_NOTIMPL.
 pub fn rotate_mat(
     src: &TransformableMatrix,
     angle: f64,
@@ -184,12 +185,11 @@ pub fn rotate_mat(
     border_value: Scalar,
     clip_strategy: RotateClipStrategy,
 ) -> Result<TransformableMatrix, opencv::Error> {
-    if border_mode != opencv::core::BORDER_CONSTANT {
-        return Err(opencv::Error::new(ffi::OMR_ERR_NOTIMPL, String::from("only BORDER_CONSTANT is implemented")));
-    }
     let border = border_bytes(border_value);
     let mut out = ffi::OmrImageOwned::empty();
-    check(unsafe { ffi::omr_rotate(&view(&src.matrix)?, angle, scale, flags, border.as_ptr(), clip_strategy.to_abi(), &mut out) })?;
+    check(unsafe {
+        ffi::omr_rotate_ex(&view(&src.matrix)?, angle, scale, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), &mut out)
+    })?;
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
