@@ -76,6 +76,12 @@ typedef struct {
 #define OMR_BORDER_WRAP 3
 #define OMR_BORDER_REFLECT_101 4
 #define OMR_BORDER_TRANSPARENT 5
+/* erode / dilate (OpenCV 4.6.0 MorphShapes numbering) for omr_structuring_element / omr_morph* */
+#define OMR_MORPH_RECT 0
+#define OMR_MORPH_CROSS 1
+#define OMR_MORPH_ELLIPSE 2
+#define OMR_MORPH_ERODE 0
+#define OMR_MORPH_DILATE 1
 
 int omr_version(void);
 int omr_device_count(void);
@@ -406,6 +412,37 @@ int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, i
  * initInterTab2D(method, fixpt = true), 32 * 32 entries of k * k int16, entry fy * 32 + fx, tap row * k + col.
  * *n_out = 1024 * k * k; out == NULL only reports the size; cap < *n_out is OMR_ERR_BADARG.  Host only. */
 int omr_warp_coeff_table(int32_t interp, int16_t *out, int32_t cap, int32_t *n_out);
+
+/* ---- erode / dilate with any structuring element (transfer.rs:206-277) -------------------------
+ * TransformableMatrix::erode / dilate call imgproc::erode / dilate with get_structuring_element(shape, size,
+ * anchor), that anchor, `iterations`, BORDER_CONSTANT and morphology_default_border_value():
+ *   dst(y, x) = min (erode) or max (dilate) over the set cells (i, j) of the element of src(y + i - ay, x + j - ax),
+ * each channel on its own; positions outside the image take no part (255 for erode, 0 for dilate).  Dilate uses
+ * the element unmirrored, as OpenCV does.  iterations == 0, or a 1 x 1 element, copies src; iterations < 0 is
+ * OMR_ERR_BADARG; iterations > 1 is that many passes.  kw, kh and iterations have no upper limit (OMR_ERR_NOMEM
+ * when a table or the intermediate image cannot be allocated); the element may be larger than the image.
+ * Channels 1..4.  Every argument is checked before any device work. */
+
+/* getStructuringElement(shape, Size(kw, kh), Point(ax, ay)) -> out[kh * kw], 0 or 1.  Host only.  An anchor
+ * coordinate of -1 is the centre (kw / 2, kh / 2); a 1 x 1 element is RECT; CROSS: row ay full, column ax elsewhere;
+ * ELLIPSE ignores the anchor: r = kh / 2, c = kw / 2, row i spans [max(c - dx, 0), min(c + dx + 1, kw)) with
+ * dx = cvRound(c * sqrt((r * r - (i - r)^2) / (r * r))).  kw < 1, kh < 1, an anchor outside the element or an
+ * unknown shape: OMR_ERR_ASSERT. */
+int omr_structuring_element(int32_t shape, int32_t kw, int32_t kh, int32_t ax, int32_t ay, uint8_t *out);
+/* per call, host memory to host memory; op: OMR_MORPH_ERODE / OMR_MORPH_DILATE */
+int omr_morph(const omr_image *src, int32_t op, int32_t shape, int32_t kw, int32_t kh, int32_t ax, int32_t ay,
+              int32_t iterations, omr_image_owned *dst);
+/* device-resident; d_src == d_dst is OMR_ERR_BADARG.  Synchronises `stream` before returning when the call had
+ * to take an intermediate image (more passes than one launch fuses) or a span table (elements over 31 x 31). */
+int omr_morph_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, int32_t channels,
+                     int32_t op, int32_t shape, int32_t kw, int32_t kh, int32_t ax, int32_t ay, int32_t iterations,
+                     uint8_t *d_dst, int64_t dst_step, void *stream);
+/* n same-size images, image i at d_src + i * src_stride_bytes / d_dst + i * dst_stride_bytes, one launch per
+ * pass (the image index is blockIdx.z); image i's result is byte-identical to omr_morph_device's. */
+int omr_morph_batch_device(const uint8_t *d_src, int32_t n, int64_t src_stride_bytes, int64_t src_step, int32_t rows,
+                           int32_t cols, int32_t channels, int32_t op, int32_t shape, int32_t kw, int32_t kh, int32_t ax,
+                           int32_t ay, int32_t iterations, uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step,
+                           void *stream);
 
 /* ---- Hough-line deskew path ---------------------------------------------
  * OpenCV 4.6.0 semantics restated on the GPU: Canny is exact (integer stencils + a set-valued

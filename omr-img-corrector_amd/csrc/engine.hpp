@@ -105,6 +105,13 @@ int rotate_geometry(int rows, int cols, double angle_deg, double scale, int clip
 // uploaded once per device (oics_rotate.cpp)
 const std::vector<int16_t> &warp_coeff_host(int interp);
 int warp_coeff_device(int interp, const int16_t **d_tab);
+// erode / dilate (oics_morph.cpp): every argument check of the omr_morph* entry points, and the launches on `s`
+// for n images `sstride` / `dstride` bytes apart (arguments already checked; synchronises `s` when it took scratch)
+int morph_check_args(const void *src, const void *dst, int64_t sstep, int64_t dstep, int rows, int cols, int cn, int op,
+                     int shape, int kw, int kh, int ax, int ay, int iterations);
+int morph_device(const uint8_t *d_src, int64_t sstride, int64_t sstep, int n, int rows, int cols, int cn, int op, int shape,
+                 int kw, int kh, int ax, int ay, int iterations, uint8_t *d_dst, int64_t dstride, int64_t dstep,
+                 hipStream_t s);
 // OpenCV computeResizeAreaTab for resizeArea_, grouped per destination index (CSR offsets ofs[0..dsize]); oics_host.cpp
 void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs);
 

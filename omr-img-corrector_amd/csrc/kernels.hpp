@@ -214,4 +214,28 @@ hipError_t launch_resize_linear(const uint8_t *d_src, int64_t sstep, int srows, 
 hipError_t launch_threshold_fast(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
                                  int thresh, int maxval, hipStream_t s);
 
+// ---- erode / dilate with any structuring element (morph.hip; the callers are in oics_morph.cpp) ---------------
+#define MORPH_MAXK 31  // largest element side of the two LDS kernels
+// `n` images of rows x wbytes (= cols * channels) bytes, image i at src + i * sstride / dst + i * dstride (n <= 65535)
+struct MorphImg {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t sstride, sstep, dstride, dstep;
+    int rows, wbytes, cn, n;
+};
+// an element's rows as runs of set cells [j1, j1 + len) (len 0: an empty row), passed by value
+struct MorphSpans {
+    uint8_t j1[MORPH_MAXK], len[MORPH_MAXK];
+};
+// op: 0 erode, 1 dilate.  How many passes of a kw x kh element one launch of the LDS span kernel can fuse (the
+// accumulated halo stays within a tile and the two LDS buffers within 64 KB); 0 when the element is too large for it.
+int morph_spans_lds_max_passes(int kw, int kh, int ax, int cn);
+hipError_t launch_morph_spans_lds(const MorphImg &im, int op, const MorphSpans &sp, int kw, int kh, int ax, int ay,
+                                  int passes, hipStream_t s);
+// a full kw x kh rectangle (both <= MORPH_MAXK), one pass
+hipError_t launch_morph_rect(const MorphImg &im, int op, int kw, int kh, int ax, int ay, hipStream_t s);
+// any element: d_spans holds kh pairs (j1, len) of int32 on the device, one pass
+hipError_t launch_morph_spans_global(const MorphImg &im, int op, const int32_t *d_spans, int kh, int ax, int ay,
+                                     hipStream_t s);
+
 }  // namespace omr

@@ -711,6 +711,29 @@ int omr_rotate_ex(const omr_image *src, double angle_deg, double scale, int32_t 
     return rc;
 }
 
+// transfer.rs:206-277 erode / dilate, host memory to host memory (the device forms are in oics_morph.cpp)
+int omr_morph(const omr_image *src, int32_t op, int32_t shape, int32_t kw, int32_t kh, int32_t ax, int32_t ay,
+              int32_t iterations, omr_image_owned *dst)
+{
+    int rc = check_image(src, false);
+    if (rc) return rc;
+    if (!dst) return fail(OMR_ERR_BADARG, "null output");
+    if ((rc = morph_check_args(src->data, dst, src->step_bytes, src->step_bytes, src->rows, src->cols, src->channels, op,
+                               shape, kw, kh, ax, ay, iterations)))
+        return rc;
+    int dev;
+    if ((rc = current_device(&dev))) return rc;
+    Stream st;
+    if ((rc = st.create())) return rc;
+    DevImage in, out;
+    if ((rc = in.upload(src, st.s))) return rc;
+    if ((rc = out.alloc(src->rows, src->cols, src->channels))) return rc;
+    if ((rc = morph_device(in.ptr(), 0, in.step(), 1, in.rows, in.cols, in.cn, op, shape, kw, kh, ax, ay, iterations,
+                           out.ptr(), 0, out.step(), st.s)))
+        return rc;
+    return give_owned(out, dst, st.s);
+}
+
 // ---- device-resident stages --------------------------------------------------------------------
 static int check_dev_image(const void *s, const void *d, int rows, int cols, int64_t sstep, int64_t dstep, int scn,
                            int dcn)

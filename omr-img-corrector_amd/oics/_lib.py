@@ -20,6 +20,9 @@ OMR_INTER_NEAREST, OMR_INTER_LINEAR, OMR_INTER_CUBIC, OMR_INTER_AREA, OMR_INTER_
 OMR_WARP_FILL_OUTLIERS, OMR_WARP_INVERSE_MAP = 8, 16
 OMR_BORDER_CONSTANT, OMR_BORDER_REPLICATE, OMR_BORDER_REFLECT, OMR_BORDER_WRAP = 0, 1, 2, 3
 OMR_BORDER_REFLECT_101, OMR_BORDER_TRANSPARENT = 4, 5
+# structuring element shapes and operations of omr_structuring_element / omr_morph* (include/omrdeskew.h)
+OMR_MORPH_RECT, OMR_MORPH_CROSS, OMR_MORPH_ELLIPSE = 0, 1, 2
+OMR_MORPH_ERODE, OMR_MORPH_DILATE = 0, 1
 
 
 class OmrImage(C.Structure):
@@ -126,6 +129,14 @@ SYMBOLS = {
                                        C.c_int32, C.c_int32, u8p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                        C.c_void_p]),
     "omr_warp_coeff_table": (C.c_int, [C.c_int32, C.POINTER(C.c_int16), C.c_int32, i32p]),
+    "omr_structuring_element": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, u8p]),
+    "omr_morph": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                            C.POINTER(OmrImageOwned)]),
+    "omr_morph_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "omr_morph_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "omr_canny": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_hough_lines_p": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, i32p,
                                     C.c_int32, i32p]),

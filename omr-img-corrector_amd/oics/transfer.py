@@ -24,6 +24,7 @@ BORDER_REFLECT = _lib.OMR_BORDER_REFLECT
 BORDER_WRAP = _lib.OMR_BORDER_WRAP
 BORDER_REFLECT_101 = _lib.OMR_BORDER_REFLECT_101
 BORDER_TRANSPARENT = _lib.OMR_BORDER_TRANSPARENT
+MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = _lib.OMR_MORPH_RECT, _lib.OMR_MORPH_CROSS, _lib.OMR_MORPH_ELLIPSE
 
 
 def as_image(a):
@@ -69,6 +70,28 @@ class TransformableMatrix:
         """transfer.rs:128-145: INTER_AREA to (width, height)"""
         self.matrix = _owned_call(lib().omr_resize, self.matrix, C.c_int32(int(width)), C.c_int32(int(height)))
         return self
+
+    def dilate(self, kernel_shape, kernel_size, anchor, iterations):
+        """transfer.rs:206-231: dilate with get_structuring_element(kernel_shape, kernel_size = (w, h), anchor = (x, y)),
+        BORDER_CONSTANT and the default border value; returns a new object"""
+        return self._morph(_lib.OMR_MORPH_DILATE, kernel_shape, kernel_size, anchor, iterations)
+
+    def erode(self, kernel_shape, kernel_size, anchor, iterations):
+        """transfer.rs:254-277: erode, same parameters"""
+        return self._morph(_lib.OMR_MORPH_ERODE, kernel_shape, kernel_size, anchor, iterations)
+
+    def _morph(self, op, kernel_shape, kernel_size, anchor, iterations):
+        (kw, kh), (ax, ay) = kernel_size, anchor
+        args = [C.c_int32(int(v)) for v in (op, kernel_shape, kw, kh, ax, ay, iterations)]
+        return TransformableMatrix(_owned_call(lib().omr_morph, self.matrix, *args))
+
+
+def get_structuring_element(shape, size, anchor=(-1, -1)):
+    """imgproc::get_structuring_element(shape, Size(w, h), Point(x, y)) -> (h, w) uint8 mask of 0 / 1 (host only)"""
+    (kw, kh), (ax, ay) = size, anchor
+    out = np.zeros((max(int(kh), 0), max(int(kw), 0)), np.uint8)
+    check(lib().omr_structuring_element(int(shape), int(kw), int(kh), int(ax), int(ay), out.ctypes.data_as(u8p)))
+    return out
 
 
 def _take_owned(out):

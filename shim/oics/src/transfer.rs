@@ -6,7 +6,7 @@ use crate::ffi;
 use crate::types::{ImageFormat, RotateClipStrategy};
 use opencv::core::{Mat, Scalar, Vector};
 use opencv::prelude::*;
-use opencv::{highgui, imgcodecs, imgproc};
+use opencv::{highgui, imgcodecs};
 
 /// Owning wrapper over a `Mat` (transfer.rs:16-18).
 pub struct TransformableMatrix {
@@ -88,21 +88,24 @@ impl TransformableMatrix {
         TransformableMatrix { matrix: self.matrix.clone() }
     }
 
-    /// Visualisation helper outside the corrector's paths (transfer.rs:206-231): host OpenCV.
+    /// transfer.rs:206-231 -> omr_morph (OMR_MORPH_DILATE): getStructuringElement(kernel_shape, kernel_size, anchor),
+    /// `iterations` passes, BORDER_CONSTANT with the default border value, any channel count, on the GPU.
     pub fn dilate(&self, kernel_shape: i32, kernel_size: opencv::core::Size, anchor: opencv::core::Point, iterations: i32) -> opencv::Result<Self> {
-        let kernel = imgproc::get_structuring_element(kernel_shape, kernel_size, anchor)?;
-        let mut dst = Mat::default();
-        imgproc::dilate(&self.matrix, &mut dst, &kernel, anchor, iterations, opencv::core::BORDER_CONSTANT, imgproc::morphology_default_border_value()?)?;
-        Ok(TransformableMatrix { matrix: dst })
+        let mut out = ffi::OmrImageOwned::empty();
+        check(unsafe {
+            ffi::omr_morph(&view(&self.matrix)?, 1, kernel_shape, kernel_size.width, kernel_size.height, anchor.x, anchor.y, iterations, &mut out)
+        })?;
+        Ok(TransformableMatrix { matrix: into_mat(out)? })
     }
 
-    /// Visualisation helper outside the corrector's paths (transfer.rs:254-277): host OpenCV.
+    /// transfer.rs:254-277 -> omr_morph (OMR_MORPH_ERODE).
     /// (The erode that IS on path 2, omr.rs:98-112, runs inside omr_get_result_from_projection.)
     pub fn erode(&self, kernel_shape: i32, kernel_size: opencv::core::Size, anchor: opencv::core::Point, iterations: i32) -> opencv::Result<Self> {
-        let kernel = imgproc::get_structuring_element(kernel_shape, kernel_size, anchor)?;
-        let mut dst = Mat::default();
-        imgproc::erode(&self.matrix, &mut dst, &kernel, anchor, iterations, opencv::core::BORDER_CONSTANT, imgproc::morphology_default_border_value()?)?;
-        Ok(TransformableMatrix { matrix: dst })
+        let mut out = ffi::OmrImageOwned::empty();
+        check(unsafe {
+            ffi::omr_morph(&view(&self.matrix)?, 0, kernel_shape, kernel_size.width, kernel_size.height, anchor.x, anchor.y, iterations, &mut out)
+        })?;
+        Ok(TransformableMatrix { matrix: into_mat(out)? })
     }
 }
 
