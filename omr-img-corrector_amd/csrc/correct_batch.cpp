@@ -265,8 +265,8 @@ int front_end(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride
                 if (cb->mode == FRONT_LINEAR)
                     OMR_HIP(launch_resize_linear(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc, true, s));
                 else
-                    OMR_HIP(launch_resize_area_int_fast(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc,
-                                                        cb->kx, cb->ky, s));
+                    OMR_HIP(launch_resize_area_int(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc,
+                                                   cb->kx, cb->ky, s));
             }
         }
     }

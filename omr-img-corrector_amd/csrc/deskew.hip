@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "warp_fixed.hpp"
 
 namespace omr {
 
@@ -34,30 +35,6 @@ __device__ __forceinline__ int dw_mad24_asm(int a, int b, int c)
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-__device__ __forceinline__ uint8_t dw_sat_u8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
-
-template <bool LINEAR>
-__device__ __forceinline__ int dw_tap_global(const uint8_t *__restrict__ src, int64_t sstep, int srows, int scols, int Xf,
-                                             int Yf, int border)
-{
-    if (!LINEAR) {
-        const int X = max(-32768, min(32767, Xf >> 10)), Y = max(-32768, min(32767, Yf >> 10));
-        return ((unsigned)X < (unsigned)scols && (unsigned)Y < (unsigned)srows) ? src[(int64_t)Y * sstep + X] : border;
-    }
-    const int X = Xf >> 5, Y = Yf >> 5;
-    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
-    const int fx = X & 31, fy = Y & 31;
-    if (sx >= scols || sx + 1 < 0 || sy >= srows || sy + 1 < 0) return border;
-    const bool in_x0 = sx >= 0 && sx < scols, in_x1 = sx + 1 >= 0 && sx + 1 < scols;
-    const bool in_y0 = sy >= 0 && sy < srows, in_y1 = sy + 1 >= 0 && sy + 1 < srows;
-    const int v0 = in_x0 && in_y0 ? src[(int64_t)sy * sstep + sx] : border;
-    const int v1 = in_x1 && in_y0 ? src[(int64_t)sy * sstep + sx + 1] : border;
-    const int v2 = in_x0 && in_y1 ? src[(int64_t)(sy + 1) * sstep + sx] : border;
-    const int v3 = in_x1 && in_y1 ? src[(int64_t)(sy + 1) * sstep + sx + 1] : border;
-    const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-    return dw_sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
-}
-
 // ---- per-tile records (round 5).  The warp kernel used to be a chain of FOUR dependent memory round trips per tile
 // (winner -> canvas size -> table entries of the corners -> box -> taps) with five workgroups per CU to hide them: 30 / 50
 // lane-cycles per pixel for 9 / 25 operations.  Everything that depends only on (scan, tile) -- the winner, the canvas, the
@@ -309,8 +286,8 @@ __global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const D
             if (y >= drows) break;
             uint8_t *D = dst + (int64_t)y * p.dstep + x0;
             for (int j = 0; j < 4 && x0 + j < dcols; j++)
-                D[j] = (uint8_t)dw_tap_global<LINEAR>(src, p.sstep, p.srows, p.scols, rowtab[y - ty0].x + rd + adv[j],
-                                                      rowtab[y - ty0].y + rd + bdv[j], p.border);
+                D[j] = (uint8_t)warp_tap_global<LINEAR>(src, p.sstep, p.srows, p.scols, 1, rowtab[y - ty0].x + rd + adv[j],
+                                                        rowtab[y - ty0].y + rd + bdv[j], p.border);
         }
         return;
     }
@@ -402,16 +379,18 @@ __global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const D
 #define DW3_TH 64
 #define DW3_LDS 24576
 
+// channel c of the colour sample at (Xf, Yf) from global memory: warp_tap_global with cn = 3, but one base address offset
+// four times -- a whole scan takes this path when its pitch, stride or address is not a multiple of 4
 template <bool LINEAR>
 __device__ __forceinline__ int dw3_tap_global(const uint8_t *__restrict__ src, int64_t sstep, int srows, int scols, int Xf, int Yf,
                                               int c, int border)
 {
     if (!LINEAR) {
-        const int X = max(-32768, min(32767, Xf >> 10)), Y = max(-32768, min(32767, Yf >> 10));
+        const int X = sat16(Xf >> 10), Y = sat16(Yf >> 10);
         return ((unsigned)X < (unsigned)scols && (unsigned)Y < (unsigned)srows) ? src[(int64_t)Y * sstep + (int64_t)X * 3 + c] : border;
     }
     const int X = Xf >> 5, Y = Yf >> 5;
-    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
+    const int sx = sat16(X >> 5), sy = sat16(Y >> 5);
     const int fx = X & 31, fy = Y & 31;
     if (sx >= scols || sx + 1 < 0 || sy >= srows || sy + 1 < 0) return border;
     const bool in_x0 = sx >= 0 && sx < scols, in_x1 = sx + 1 >= 0 && sx + 1 < scols;
@@ -422,7 +401,7 @@ __device__ __forceinline__ int dw3_tap_global(const uint8_t *__restrict__ src, i
     const int v2 = in_x0 && in_y1 ? S[sstep] : border;
     const int v3 = in_x1 && in_y1 ? S[sstep + 3] : border;
     const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-    return dw_sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
+    return sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
 }
 
 // one thread per (scan, tile): the DeskewTile record of a colour tile (bb0, bwb in BYTES of a source row, whole dwords)

@@ -9,6 +9,7 @@
 #include <map>
 #include <vector>
 
+#include "../../include/omrdeskew.h"
 #include "kernels.hpp"
 #include "slane.hpp"
 
@@ -101,6 +102,13 @@ int candidate_count(uint16_t max_angle, double step, int *N_out);  // projection
 void sweep_matrices(int rows, int cols, int N, double step, double scale, double *M_out);
 // rotate_mat's forward matrix and canvas (transfer.rs:459-523; oics_host.cpp)
 int rotate_geometry(int rows, int cols, double angle_deg, double scale, int clip, double M[6], int *drows, int *dcols);
+// path 2's projection result (omr.rs:52-229) and rotate_mat (transfer.rs:459-523) on a packed image that is already on
+// the device -- correct_default uploads its sheet once (oics_host.cpp)
+int result_from_projection_device(const uint8_t *d_src, int rows, int cols, int cn, uint16_t max_angle, double step,
+                                  int32_t max_w, int32_t max_h, hipStream_t s, double *angle, int32_t *status,
+                                  double *candidates, int32_t cand_cap, int32_t *cand_len);
+int rotate_device_to_host(const uint8_t *d_src, int rows, int cols, int cn, double angle_deg, double scale, int interp,
+                          const uint8_t border_value[4], int clip, hipStream_t s, omr_image_owned *dst);
 // warpAffine's INTER_CUBIC / INTER_LANCZOS4 fixed-point weight tables (initInterTab2D): built once per process,
 // uploaded once per device (oics_rotate.cpp)
 const std::vector<int16_t> &warp_coeff_host(int interp);

@@ -722,236 +722,4 @@ hipError_t launch_argmax_path1(const double *d_v_sd, const double *d_h_sd, int A
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------
-// Per-image helpers (callers and data formats either side of the sweep).
-
-// transfer.rs:294-301 / omr.rs:129-139: threshold(127, 255, THRESH_BINARY)
-__global__ __launch_bounds__(256) void threshold_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
-                                                        int cols, uint8_t *__restrict__ dst, int64_t dstep,
-                                                        int thresh, int maxval)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x < cols) dst[(int64_t)y * dstep + x] = (int)src[(int64_t)y * sstep + x] > thresh ? (uint8_t)maxval : 0;
-}
-
-hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
-                            int thresh, int maxval, hipStream_t s)
-{
-    hipLaunchKernelGGL(threshold_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d_src, sstep, rows, cols,
-                       d_dst, dstep, thresh, maxval);
-    return hipGetLastError();
-}
-
-// transfer.rs:283-290 / omr.rs:88-92: cvtColor(COLOR_RGB2GRAY) 8U,
-// (c0*9798 + c1*19235 + c2*3735 + 16384) >> 15 in memory order (quirk B8 kept).
-__global__ __launch_bounds__(256) void rgb2gray_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
-                                                       int cols, int cn, uint8_t *__restrict__ dst, int64_t dstep)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x < cols) {
-        const uint8_t *S = src + (int64_t)y * sstep + (int64_t)x * cn;
-        dst[(int64_t)y * dstep + x] = (uint8_t)((S[0] * 9798 + S[1] * 19235 + S[2] * 3735 + (1 << 14)) >> 15);
-    }
-}
-
-hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
-                           int64_t dstep, hipStream_t s)
-{
-    hipLaunchKernelGGL(rgb2gray_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d_src, sstep, rows, cols, cn,
-                       d_dst, dstep);
-    return hipGetLastError();
-}
-
-// omr.rs:98-112: one pass of erode with the 3x3 "ellipse" (= cross) element, border = +inf.
-__global__ __launch_bounds__(256) void erode_cross3_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
-                                                           int cols, uint8_t *__restrict__ dst, int64_t dstep)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= cols) return;
-    const uint8_t *S = src + (int64_t)y * sstep + x;
-    int m = S[0];
-    if (y > 0) m = min(m, (int)S[-sstep]);
-    if (y + 1 < rows) m = min(m, (int)S[sstep]);
-    if (x > 0) m = min(m, (int)S[-1]);
-    if (x + 1 < cols) m = min(m, (int)S[1]);
-    dst[(int64_t)y * dstep + x] = (uint8_t)m;
-}
-
-hipError_t launch_erode_cross3(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
-                               hipStream_t s)
-{
-    hipLaunchKernelGGL(erode_cross3_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d_src, sstep, rows, cols,
-                       d_dst, dstep);
-    return hipGetLastError();
-}
-
-__device__ inline uint8_t sat_u8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
-
-// resize INTER_AREA, integer factors (OpenCV resizeAreaFast_): transfer.rs:66-91, omr.rs:114-126.
-// One thread per destination byte (x runs over dcols*cn).
-__global__ __launch_bounds__(256) void resize_area_int_kernel(const uint8_t *__restrict__ src, int64_t sstep,
-                                                              int srows, int scols, int cn,
-                                                              uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                              int dcols, int kx, int ky)
-{
-    const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    const int dwidth = dcols * cn, swidth = scols * cn;
-    if (dx >= dwidth) return;
-    const int sy0 = dy * ky;
-    uint8_t out;
-    if (sy0 >= srows) {
-        out = 0;
-    } else {
-        const int dwidth1 = (scols / kx) * cn;
-        const int w = sy0 + ky <= srows ? dwidth1 : 0;
-        const int sx0 = kx * (dx / cn) * cn + dx % cn;
-        if (dx < w) {
-            int sum = 0;
-            for (int sy = 0; sy < ky; sy++)
-                for (int sx = 0; sx < kx; sx++) sum += src[(int64_t)(sy0 + sy) * sstep + sx0 + sx * cn];
-            if (kx == 2 && ky == 2) out = (uint8_t)((sum + 2) >> 2);
-            else out = sat_u8((int)rintf((float)sum * (1.f / (float)(kx * ky))));
-        } else {
-            int sum = 0, count = 0;
-            for (int sy = 0; sy < ky; sy++) {
-                if (sy0 + sy >= srows) break;
-                for (int sx = 0; sx < kx * cn; sx += cn) {
-                    if (sx0 + sx >= swidth) break;
-                    sum += src[(int64_t)(sy0 + sy) * sstep + sx0 + sx];
-                    count++;
-                }
-            }
-            out = count ? sat_u8((int)rintf((float)sum / (float)count)) : 0;
-        }
-    }
-    dst[(int64_t)dy * dstep + dx] = out;
-}
-
-hipError_t launch_resize_area_int(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                                  int64_t dstep, int drows, int dcols, int kx, int ky, hipStream_t s)
-{
-    hipLaunchKernelGGL(resize_area_int_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src, sstep,
-                       srows, scols, cn, d_dst, dstep, drows, dcols, kx, ky);
-    return hipGetLastError();
-}
-
-// resize INTER_AREA, general shrink (OpenCV resizeArea_<uchar,float>): per destination byte the
-// same float accumulation order as ResizeArea_Invoker: for each source row tap (ascending) the
-// row sum buf = sum_k S*alpha_k (ascending k), then sum (+)= beta*buf.  xofs/yofs: CSR offsets
-// of the taps of every destination column / row.
-__global__ __launch_bounds__(256) void resize_area_general_kernel(const uint8_t *__restrict__ src, int64_t sstep,
-                                                                  int cn, uint8_t *__restrict__ dst, int64_t dstep,
-                                                                  int drows, int dcols,
-                                                                  const AreaTap *__restrict__ xtab,
-                                                                  const int32_t *__restrict__ xofs,
-                                                                  const AreaTap *__restrict__ ytab,
-                                                                  const int32_t *__restrict__ yofs)
-{
-    const int dxb = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    if (dxb >= dcols * cn) return;
-    const int dx = dxb / cn, c = dxb % cn;
-    float sum = 0.f;
-    bool first = true;
-    for (int j = yofs[dy]; j < yofs[dy + 1]; j++) {
-        const float beta = ytab[j].alpha;
-        const uint8_t *S = src + (int64_t)ytab[j].si * sstep + c;
-        float buf = 0.f;
-        for (int k = xofs[dx]; k < xofs[dx + 1]; k++) buf += (float)S[xtab[k].si] * xtab[k].alpha;
-        if (first) {
-            sum = beta * buf;  // ResizeArea_Invoker assigns on the first tap of a destination row
-            first = false;
-        } else {
-            sum += beta * buf;
-        }
-    }
-    dst[(int64_t)dy * dstep + dxb] = sat_u8((int)rintf(sum));
-}
-
-hipError_t launch_resize_area_general(const uint8_t *d_src, int64_t sstep, int cn, uint8_t *d_dst, int64_t dstep,
-                                      int drows, int dcols, const AreaTap *d_xtab, const int32_t *d_xofs,
-                                      const AreaTap *d_ytab, const int32_t *d_yofs, hipStream_t s)
-{
-    hipLaunchKernelGGL(resize_area_general_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src,
-                       sstep, cn, d_dst, dstep, drows, dcols, d_xtab, d_xofs, d_ytab, d_yofs);
-    return hipGetLastError();
-}
-
-// warpAffine INTER_NEAREST on a cn-channel u8 image (transfer.rs:477-485, omr.rs:435-443): the
-// final deskew of correct_default and rotate_mat's materialising form.  Tables are evaluated
-// in place (same f64 expressions, no contraction).
-__global__ __launch_bounds__(256) void warp_nn_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
-                                                      int scols, int cn, uint8_t *__restrict__ dst, int64_t dstep,
-                                                      int drows, int dcols, const double *__restrict__ M,
-                                                      uint32_t border)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= dcols) return;
-    const int adelta = (int)rint(M[0] * (double)x * 1024.0);
-    const int bdelta = (int)rint(M[3] * (double)x * 1024.0);
-    const int X0 = (int)rint((M[1] * (double)y + M[2]) * 1024.0) + 512;
-    const int Y0 = (int)rint((M[4] * (double)y + M[5]) * 1024.0) + 512;
-    int X = (X0 + adelta) >> 10, Y = (Y0 + bdelta) >> 10;
-    X = max(-32768, min(32767, X));
-    Y = max(-32768, min(32767, Y));
-    uint8_t *D = dst + (int64_t)y * dstep + (int64_t)x * cn;
-    if ((unsigned)X < (unsigned)scols && (unsigned)Y < (unsigned)srows) {
-        const uint8_t *S = src + (int64_t)Y * sstep + (int64_t)X * cn;
-        for (int k = 0; k < cn; k++) D[k] = S[k];
-    } else {
-        for (int k = 0; k < cn; k++) D[k] = (uint8_t)(border >> (8 * k));
-    }
-}
-
-hipError_t launch_warp_nn(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                          int64_t dstep, int drows, int dcols, const double *d_Minv, uint32_t border_rgba,
-                          hipStream_t s)
-{
-    hipLaunchKernelGGL(warp_nn_kernel, dim3((dcols + 255) / 256, drows), dim3(256), 0, s, d_src, sstep, srows, scols,
-                       cn, d_dst, dstep, drows, dcols, d_Minv, border_rgba);
-    return hipGetLastError();
-}
-
-// warpAffine INTER_LINEAR (core/src/main.rs:72-81, app test.rs:322-331 through rotate_mat
-// CONTAIN): 5 fractional bits, 15-bit weights (32-fy)(32-fx)*32 ..., (v + 16384) >> 15.
-__global__ __launch_bounds__(256) void warp_linear_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
-                                                          int scols, int cn, uint8_t *__restrict__ dst,
-                                                          int64_t dstep, int drows, int dcols,
-                                                          const double *__restrict__ M, uint32_t border)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= dcols) return;
-    const int adelta = (int)rint(M[0] * (double)x * 1024.0);
-    const int bdelta = (int)rint(M[3] * (double)x * 1024.0);
-    const int X0 = (int)rint((M[1] * (double)y + M[2]) * 1024.0) + 16;
-    const int Y0 = (int)rint((M[4] * (double)y + M[5]) * 1024.0) + 16;
-    const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
-    const int fx = X & 31, fy = Y & 31;
-    const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-    uint8_t *D = dst + (int64_t)y * dstep + (int64_t)x * cn;
-    if (sx >= scols || sx + 1 < 0 || sy >= srows || sy + 1 < 0) {
-        for (int k = 0; k < cn; k++) D[k] = (uint8_t)(border >> (8 * k));
-        return;
-    }
-    const bool in_x0 = sx >= 0 && sx < scols, in_x1 = sx + 1 >= 0 && sx + 1 < scols;
-    const bool in_y0 = sy >= 0 && sy < srows, in_y1 = sy + 1 >= 0 && sy + 1 < srows;
-    for (int k = 0; k < cn; k++) {
-        const int b = (int)((border >> (8 * k)) & 255u);
-        const int v0 = in_x0 && in_y0 ? src[(int64_t)sy * sstep + (int64_t)sx * cn + k] : b;
-        const int v1 = in_x1 && in_y0 ? src[(int64_t)sy * sstep + (int64_t)(sx + 1) * cn + k] : b;
-        const int v2 = in_x0 && in_y1 ? src[(int64_t)(sy + 1) * sstep + (int64_t)sx * cn + k] : b;
-        const int v3 = in_x1 && in_y1 ? src[(int64_t)(sy + 1) * sstep + (int64_t)(sx + 1) * cn + k] : b;
-        D[k] = sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
-    }
-}
-
-hipError_t launch_warp_linear(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                              int64_t dstep, int drows, int dcols, const double *d_Minv, uint32_t border_rgba,
-                              hipStream_t s)
-{
-    hipLaunchKernelGGL(warp_linear_kernel, dim3((dcols + 255) / 256, drows), dim3(256), 0, s, d_src, sstep, srows,
-                       scols, cn, d_dst, dstep, drows, dcols, d_Minv, border_rgba);
-    return hipGetLastError();
-}
-
 }  // namespace omr

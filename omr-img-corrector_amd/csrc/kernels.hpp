@@ -1,4 +1,5 @@
-// kernels.hpp -- launch wrappers of the gfx950 kernels (kernels.hip). Host-callable, no torch types.
+// kernels.hpp -- launch wrappers of the gfx950 kernels: the sweep (kernels.hip, runs.hip) first, then the per-image
+// stages, the warps and the morphology.  Host-callable, no torch types.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -140,31 +141,6 @@ hipError_t launch_stddev(const uint32_t *d_vproj, const uint32_t *d_hproj, Sweep
 hipError_t launch_argmax_path1(const double *d_v_sd, const double *d_h_sd, int A, int32_t *d_best,
                                hipStream_t s, int scans = 1);
 
-// ---- per-image helpers -------------------------------------------------------------------
-hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst,
-                            int64_t dstep, int thresh, int maxval, hipStream_t s);
-hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn,
-                           uint8_t *d_dst, int64_t dstep, hipStream_t s);
-hipError_t launch_erode_cross3(const uint8_t *d_src, int64_t sstep, int rows, int cols,
-                               uint8_t *d_dst, int64_t dstep, hipStream_t s);
-hipError_t launch_resize_area_int(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                                  uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
-                                  hipStream_t s);
-struct AreaTap {
-    int32_t si, di;
-    float alpha;
-};
-hipError_t launch_resize_area_general(const uint8_t *d_src, int64_t sstep, int cn, uint8_t *d_dst,
-                                      int64_t dstep, int drows, int dcols, const AreaTap *d_xtab,
-                                      const int32_t *d_xofs, const AreaTap *d_ytab,
-                                      const int32_t *d_yofs, hipStream_t s);
-hipError_t launch_warp_nn(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                          uint8_t *d_dst, int64_t dstep, int drows, int dcols, const double *d_Minv,
-                          uint32_t border_rgba, hipStream_t s);
-hipError_t launch_warp_linear(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                              uint8_t *d_dst, int64_t dstep, int drows, int dcols,
-                              const double *d_Minv, uint32_t border_rgba, hipStream_t s);
-
 // ---- batched final deskew (deskew.hip): scan z is rotated by the candidate best[z]'s angle, CONTAIN geometry
 struct DeskewPass {
     const uint8_t *src;       // scans, cn channels: scan_stride bytes apart, sstep bytes per row
@@ -187,32 +163,37 @@ struct DeskewPass {
 size_t deskew_tile_bytes(const DeskewPass &p, int scans);
 hipError_t launch_deskew_warp(const DeskewPass &p, int scans, int interp, void *d_tiles, hipStream_t s);
 
-// ---- tuned single-channel stage kernels (stages.hip); each falls back to the generic form -------
-hipError_t launch_rgb2gray_fast(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
-                                int64_t dstep, hipStream_t s);
+// ---- per-image stages either side of the sweep (stages.hip): each launcher picks the tuned kernel where the
+// layout and alignment allow and the generic one (any channel count, one thread per byte) otherwise
+hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
+                            int thresh, int maxval, hipStream_t s);
+hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
+                           int64_t dstep, hipStream_t s);
 // erode(3x3 cross) x 3 iterations fused (omr.rs:98-112)
 hipError_t launch_erode3x_cross(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
                                 hipStream_t s);
-hipError_t launch_resize_area_int_fast(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                                       uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
-                                       hipStream_t s);
-// 1- / 3-channel warpAffine (NEAREST, LINEAR) with the source box of a 64x16 tile staged in LDS; Minv is a
-// HOST pointer (passed by value to the kernel).  Returns hipErrorInvalidValue for other channel counts (use the
-// generic kernel).
-hipError_t launch_warp_fast(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                            int64_t dstep, int drows, int dcols, const double Minv[6], int interp, uint32_t border_rgba,
-                            hipStream_t s);
-// warpAffine with interp 0 / 1 / 2 / 4 (K = 1, 2, 4, 8 taps per axis) under border mode 0..5, 1..4 channels
-// (warp_taps.hip); Minv is a HOST pointer, d_wtab the device weight table for interp 2 / 4 (NULL otherwise).
-// BORDER_TRANSPARENT stores nothing at the pixels it skips.
-hipError_t launch_warp_taps(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                            int64_t dstep, int drows, int dcols, const double Minv[6], int interp, int border_mode,
-                            uint32_t border_rgba, const int16_t *d_wtab, hipStream_t s);
+hipError_t launch_resize_area_int(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
+                                  uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
+                                  hipStream_t s);
+struct AreaTap {
+    int32_t si, di;
+    float alpha;
+};
+hipError_t launch_resize_area_general(const uint8_t *d_src, int64_t sstep, int cn, uint8_t *d_dst,
+                                      int64_t dstep, int drows, int dcols, const AreaTap *d_xtab,
+                                      const int32_t *d_xofs, const AreaTap *d_ytab,
+                                      const int32_t *d_yofs, hipStream_t s);
 // resize(INTER_LINEAR) (area_mode false) / INTER_AREA's bilinear emulation when an axis enlarges (true)
 hipError_t launch_resize_linear(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
                                 int64_t dstep, int drows, int dcols, bool area_mode, hipStream_t s);
-hipError_t launch_threshold_fast(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
-                                 int thresh, int maxval, hipStream_t s);
+
+// ---- warpAffine (warp_affine.hip): interp 0 / 1 / 2 / 4 (NEAREST, LINEAR, CUBIC, LANCZOS4) under border mode 0..5,
+// 1..4 channels.  Minv (dst -> src) is a HOST pointer, passed to the kernel by value; d_wtab is the device weight
+// table for interp 2 / 4 (NULL otherwise).  BORDER_TRANSPARENT stores nothing at the pixels it skips.  The only
+// dispatch rule: 1 / 3 channels, NEAREST / LINEAR, BORDER_CONSTANT take warp_lds_kernel, all else warp_taps_kernel.
+hipError_t launch_warp_affine(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
+                              int64_t dstep, int drows, int dcols, const double Minv[6], int interp, int border_mode,
+                              uint32_t border_rgba, const int16_t *d_wtab, hipStream_t s);
 
 // ---- erode / dilate with any structuring element (morph.hip; the callers are in oics_morph.cpp) ---------------
 #define MORPH_MAXK 31  // largest element side of the two LDS kernels

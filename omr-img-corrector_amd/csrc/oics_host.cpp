@@ -228,8 +228,8 @@ int resize_ptr(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn
         return OMR_OK;
     }
     if (is_area_fast) {
-        OMR_HIP(launch_resize_area_int_fast(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, iscale_x,
-                                            iscale_y, s));
+        OMR_HIP(launch_resize_area_int(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, iscale_x,
+                                       iscale_y, s));
         return OMR_OK;
     }
     std::vector<AreaTap> xt, yt;
@@ -283,18 +283,25 @@ int give_owned(const DevImage &img, omr_image_owned *dst, hipStream_t s)
     return rc;
 }
 
+// cvtColor(COLOR_RGB2GRAY) on device pointers.  A 1-channel source is copied: the reference's cvtColor would raise on
+// a 1-channel Mat; accepted here as a convenience (its callers hold packed images: one linear copy).
+int gray_ptr(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst, int64_t dstep, hipStream_t s)
+{
+    if (cn == 1) {
+        if (sstep != cols || dstep != cols) return fail(OMR_ERR_BADARG, "1-channel gray copy needs packed rows");
+        OMR_HIP(hipMemcpyAsync(d_dst, d_src, (size_t)rows * cols, hipMemcpyDeviceToDevice, s));
+        return OMR_OK;
+    }
+    if (cn != 3 && cn != 4) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels, got %d", cn);
+    OMR_HIP(launch_rgb2gray(d_src, sstep, rows, cols, cn, d_dst, dstep, s));
+    return OMR_OK;
+}
+
 int to_gray(const DevImage &src, DevImage *gray, hipStream_t s)
 {
     int rc = gray->alloc(src.rows, src.cols, 1);
     if (rc) return rc;
-    if (src.cn == 1) {
-        // the reference's cvtColor would raise on a 1-channel Mat; accepted here as a convenience
-        OMR_HIP(hipMemcpyAsync(gray->buf.p, src.buf.p, (size_t)src.rows * src.cols, hipMemcpyDeviceToDevice, s));
-        return OMR_OK;
-    }
-    if (src.cn != 3 && src.cn != 4) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels, got %d", src.cn);
-    OMR_HIP(launch_rgb2gray_fast(src.ptr(), src.step(), src.rows, src.cols, src.cn, gray->ptr(), gray->step(), s));
-    return OMR_OK;
+    return gray_ptr(src.ptr(), src.step(), src.rows, src.cols, src.cn, gray->ptr(), gray->step(), s);
 }
 
 // projection.rs:125-190 on the host copy of the scores (lowest index on exact ties, quirk B5).
@@ -321,10 +328,28 @@ int argmax_path1(const double *v, const double *h, int n)
 
 }  // namespace
 
-namespace omr {
-int result_from_projection_device(const uint8_t *d_src, int rows, int cols, int cn, uint16_t max_angle, double step,
-                                  int32_t max_w, int32_t max_h, hipStream_t s, double *angle, int32_t *status,
-                                  double *candidates, int32_t cand_cap, int32_t *cand_len);
+// transfer.rs:459-523: forward matrix and canvas of rotate_mat
+int omr::rotate_geometry(int rows, int cols, double angle_deg, double scale, int clip, double M[6], int *drows, int *dcols)
+{
+    if (clip == OMR_CLIP_DEFAULT) {  // :472-486
+        *drows = rows;
+        *dcols = cols;
+        rotation_matrix_2d((float)cols / 2.0f, (float)rows / 2.0f, angle_deg, scale, M);
+    } else if (clip == OMR_CLIP_CONTAIN) {  // :487-519
+        const double CV_PI_ = 3.1415926535897932384626433832795;
+        double sn = fabs(sin(angle_deg * CV_PI_ / 180.0)), cs = fabs(cos(angle_deg * CV_PI_ / 180.0));
+        double rotated_width = ceil((double)rows * sn + (double)cols * cs);
+        double rotated_height = ceil((double)cols * sn + (double)rows * cs);
+        *dcols = (int)rotated_width;
+        *drows = (int)rotated_height;
+        rotation_matrix_2d((float)ceil(rotated_width / 2.0), (float)ceil(rotated_height / 2.0), angle_deg, scale, M);
+        M[2] += ceil((rotated_width - (double)cols) / 2.0);
+        M[5] += ceil((rotated_height - (double)rows) / 2.0);
+    } else {
+        return fail(OMR_ERR_BADARG, "unknown clip strategy %d", clip);
+    }
+    if (*drows <= 0 || *dcols <= 0 || *drows >= 32767 || *dcols >= 32767) return fail(OMR_ERR_ASSERT, "bad canvas size");
+    return OMR_OK;
 }
 
 extern "C" {
@@ -479,7 +504,7 @@ int omr_threshold_binary(const omr_image *gray, uint8_t *dst, int64_t dst_step)
     DevImage in, out;
     if ((rc = in.upload(gray, st.s))) return rc;
     if ((rc = out.alloc(in.rows, in.cols, 1))) return rc;
-    OMR_HIP(launch_threshold_fast(in.ptr(), in.step(), in.rows, in.cols, out.ptr(), out.step(), 127, 255, st.s));
+    OMR_HIP(launch_threshold(in.ptr(), in.step(), in.rows, in.cols, out.ptr(), out.step(), 127, 255, st.s));
     return out.download(dst, dst_step, st.s);
 }
 
@@ -499,125 +524,25 @@ int omr_rgb_to_gray(const omr_image *src, uint8_t *dst, int64_t dst_step)
     return out.download(dst, dst_step, st.s);
 }
 
-// transfer.rs:459-523: forward matrix and canvas of rotate_mat
-static int rotate_geometry_impl(int rows, int cols, double angle_deg, double scale, int clip, double M[6], int *drows,
-                           int *dcols)
-{
-    if (clip == OMR_CLIP_DEFAULT) {  // :472-486
-        *drows = rows;
-        *dcols = cols;
-        rotation_matrix_2d((float)cols / 2.0f, (float)rows / 2.0f, angle_deg, scale, M);
-    } else if (clip == OMR_CLIP_CONTAIN) {  // :487-519
-        const double CV_PI_ = 3.1415926535897932384626433832795;
-        double sn = fabs(sin(angle_deg * CV_PI_ / 180.0)), cs = fabs(cos(angle_deg * CV_PI_ / 180.0));
-        double rotated_width = ceil((double)rows * sn + (double)cols * cs);
-        double rotated_height = ceil((double)cols * sn + (double)rows * cs);
-        *dcols = (int)rotated_width;
-        *drows = (int)rotated_height;
-        rotation_matrix_2d((float)ceil(rotated_width / 2.0), (float)ceil(rotated_height / 2.0), angle_deg, scale, M);
-        M[2] += ceil((rotated_width - (double)cols) / 2.0);
-        M[5] += ceil((rotated_height - (double)rows) / 2.0);
-    } else {
-        return fail(OMR_ERR_BADARG, "unknown clip strategy %d", clip);
-    }
-    if (*drows <= 0 || *dcols <= 0 || *drows >= 32767 || *dcols >= 32767) return fail(OMR_ERR_ASSERT, "bad canvas size");
-    return OMR_OK;
-}
+// how a rotate entry point asks warpAffine to sample: interpolation 0 / 1 / 2 / 4, whether the matrix is already
+// dst -> src (WARP_INVERSE_MAP), border mode
+struct WarpMode {
+    int interp;
+    bool inverse;
+    int border_mode;
+};
 
-// launch the warp of rotate_mat on device buffers (1 / 3 channels: LDS-staged tiles; otherwise generic)
-static int rotate_launch(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, const double M[6], int interp,
-                         const uint8_t border_value[4], uint8_t *d_dst, int64_t dstep, int drows, int dcols,
-                         hipStream_t s, DevBuf *keep)
+// omr_rotate / omr_rotate_device: NEAREST or LINEAR, forward matrix, BORDER_CONSTANT
+static int rotate_args(int interp, WarpMode *m)
 {
-    double Minv[6];
-    invert_affine(M, Minv);
-    uint32_t border = (uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16) |
-                      ((uint32_t)border_value[3] << 24);
-    if (cn == 1 || cn == 3) {
-        hipError_t e = launch_warp_fast(d_src, sstep, rows, cols, cn, d_dst, dstep, drows, dcols, Minv, interp, border, s);
-        if (e == hipSuccess) return OMR_OK;
-        return fail_gpu("launch_warp_fast", e);
-    }
-    OMR_HIP(keep->alloc(sizeof Minv));
-    OMR_HIP(hipMemcpyAsync(keep->p, Minv, sizeof Minv, hipMemcpyHostToDevice, s));
-    OMR_HIP(hipStreamSynchronize(s));  // Minv is a stack buffer
-    if (interp == OMR_INTER_NEAREST)
-        OMR_HIP(launch_warp_nn(d_src, sstep, rows, cols, cn, d_dst, dstep, drows, dcols, keep->as<double>(), border, s));
-    else
-        OMR_HIP(launch_warp_linear(d_src, sstep, rows, cols, cn, d_dst, dstep, drows, dcols, keep->as<double>(), border, s));
-    return OMR_OK;
-}
-
-int omr_rotate_size(int32_t rows, int32_t cols, double angle_deg, int32_t clip, int32_t *dst_rows, int32_t *dst_cols)
-{
-    if (!dst_rows || !dst_cols || rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "bad arguments");
-    double M[6];
-    int dr, dc;
-    int rc = rotate_geometry_impl(rows, cols, angle_deg, 1.0, clip, M, &dr, &dc);
-    if (rc) return rc;
-    *dst_rows = dr;
-    *dst_cols = dc;
-    return OMR_OK;
-}
-
-int omr_rotate_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, int32_t channels,
-                      double angle_deg, double scale, int32_t interp, const uint8_t border_value[4], int32_t clip,
-                      uint8_t *d_dst, int64_t dst_step, int32_t dst_rows, int32_t dst_cols, void *stream)
-{
-    if (!d_src || !d_dst || !border_value) return fail(OMR_ERR_BADARG, "null pointer");
-    if (rows <= 0 || cols <= 0 || rows >= 32767 || cols >= 32767 || channels < 1 || channels > 4)
-        return fail(OMR_ERR_ASSERT, "bad image shape");
     if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
         return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
-    double M[6];
-    int dr, dc;
-    int rc = rotate_geometry_impl(rows, cols, angle_deg, scale, clip, M, &dr, &dc);
-    if (rc) return rc;
-    if (dr != dst_rows || dc != dst_cols) return fail(OMR_ERR_ASSERT, "destination must be %dx%d", dc, dr);
-    if (src_step < (int64_t)cols * channels || dst_step < (int64_t)dc * channels) return fail(OMR_ERR_BADARG, "step too small");
-    DevBuf keep;
-    rc = rotate_launch(d_src, src_step, rows, cols, channels, M, interp, border_value, d_dst, dst_step, dr, dc,
-                       (hipStream_t)stream, &keep);
-    if (!rc && keep.p) OMR_HIP(hipStreamSynchronize((hipStream_t)stream));  // generic path: matrix buffer is freed
-    return rc;
+    *m = WarpMode{interp, false, OMR_BORDER_CONSTANT};
+    return OMR_OK;
 }
 
-int omr_rotate(const omr_image *src, double angle_deg, double scale, int32_t interp, const uint8_t border_value[4],
-               int32_t clip, omr_image_owned *dst)
-{
-    int rc = check_image(src, false);
-    if (rc) return rc;
-    if (!dst || !border_value) return fail(OMR_ERR_BADARG, "null output");
-    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
-        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
-    double M[6];
-    int drows, dcols;
-    if ((rc = rotate_geometry_impl(src->rows, src->cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
-    int dev;
-    if ((rc = current_device(&dev))) return rc;
-    Stream st;
-    if ((rc = st.create())) return rc;
-    DevImage in, out;
-    DevBuf keep;
-    if ((rc = in.upload(src, st.s))) return rc;
-    if ((rc = out.alloc(drows, dcols, src->channels))) return rc;
-    if ((rc = rotate_launch(in.ptr(), in.step(), in.rows, in.cols, in.cn, M, interp, border_value, out.ptr(), out.step(),
-                            drows, dcols, st.s, &keep)))
-        return rc;
-    dst->rows = drows;
-    dst->cols = dcols;
-    dst->channels = src->channels;
-    dst->step_bytes = (int64_t)dcols * src->channels;
-    dst->data = (uint8_t *)malloc((size_t)drows * dst->step_bytes);
-    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    rc = out.download(dst->data, dst->step_bytes, st.s);
-    if (rc) omr_image_free(dst);
-    return rc;
-}
-
-// warpAffine's flags and border mode as omr_rotate_ex takes them: interpolation 0 / 1 / 2 / 4 (INTER_AREA is LINEAR,
-// imgwarp.cpp), whether the matrix is already dst->src
-static int rotate_ex_args(int flags, int border_mode, int *interp, bool *inverse)
+// warpAffine's flags and border mode as omr_rotate_ex takes them (INTER_AREA is LINEAR, imgwarp.cpp)
+static int rotate_ex_args(int flags, int border_mode, WarpMode *m)
 {
     if (flags & ~(7 | OMR_WARP_FILL_OUTLIERS | OMR_WARP_INVERSE_MAP)) return fail(OMR_ERR_BADARG, "unknown warp flags 0x%x", flags);
     int ip = flags & 7;
@@ -625,31 +550,85 @@ static int rotate_ex_args(int flags, int border_mode, int *interp, bool *inverse
     if (ip > OMR_INTER_LANCZOS4) return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", ip);
     if (border_mode < OMR_BORDER_CONSTANT || border_mode > OMR_BORDER_TRANSPARENT)
         return fail(OMR_ERR_BADARG, "unknown border mode %d", border_mode);
-    *interp = ip;
-    *inverse = (flags & OMR_WARP_INVERSE_MAP) != 0;
+    *m = WarpMode{ip, (flags & OMR_WARP_INVERSE_MAP) != 0, border_mode};
     return OMR_OK;
 }
 
-// omr_rotate's launch for the pairs it covers (bit for bit its result), warp_taps.hip for every other
-static int rotate_ex_launch(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, const double M[6], int interp,
-                            bool inverse, int border_mode, const uint8_t border_value[4], uint8_t *d_dst, int64_t dstep,
-                            int drows, int dcols, hipStream_t s, DevBuf *keep)
+// the warp of rotate_mat on device buffers, asynchronous on s: M is rotate_geometry's matrix (the kernels take it by
+// value, inverted here unless it already is dst -> src); launch_warp_affine picks the kernel
+static int warp_launch(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, const double M[6], const WarpMode &m,
+                       const uint8_t border_value[4], uint8_t *d_dst, int64_t dstep, int drows, int dcols, hipStream_t s)
 {
-    if (!inverse && border_mode == OMR_BORDER_CONSTANT && interp <= OMR_INTER_LINEAR)
-        return rotate_launch(d_src, sstep, rows, cols, cn, M, interp, border_value, d_dst, dstep, drows, dcols, s, keep);
     double Minv[6];
-    if (inverse) memcpy(Minv, M, sizeof Minv);
+    if (m.inverse) memcpy(Minv, M, sizeof Minv);
     else invert_affine(M, Minv);
     const int16_t *tab = nullptr;
-    if (interp >= OMR_INTER_CUBIC) {
-        int rc = warp_coeff_device(interp, &tab);
+    if (m.interp >= OMR_INTER_CUBIC) {
+        int rc = warp_coeff_device(m.interp, &tab);
         if (rc) return rc;
     }
-    uint32_t border = (uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16) |
-                      ((uint32_t)border_value[3] << 24);
-    OMR_HIP(launch_warp_taps(d_src, sstep, rows, cols, cn, d_dst, dstep, drows, dcols, Minv, interp, border_mode, border,
-                             tab, s));
+    const uint32_t border = (uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16) |
+                            ((uint32_t)border_value[3] << 24);
+    OMR_HIP(launch_warp_affine(d_src, sstep, rows, cols, cn, d_dst, dstep, drows, dcols, Minv, m.interp, m.border_mode, border,
+                               tab, s));
     return OMR_OK;
+}
+
+// a packed device-resident image warped into a new host image (the pixels BORDER_TRANSPARENT skips are 0)
+static int warp_to_host(const uint8_t *d_src, int rows, int cols, int cn, const double M[6], int drows, int dcols,
+                        const WarpMode &m, const uint8_t border_value[4], hipStream_t s, omr_image_owned *dst)
+{
+    DevImage out;
+    int rc = out.alloc(drows, dcols, cn);
+    if (rc) return rc;
+    if (m.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(out.ptr(), 0, (size_t)drows * out.step(), s));
+    if ((rc = warp_launch(d_src, (int64_t)cols * cn, rows, cols, cn, M, m, border_value, out.ptr(), out.step(), drows, dcols, s)))
+        return rc;
+    return give_owned(out, dst, s);
+}
+
+int omr_rotate_size(int32_t rows, int32_t cols, double angle_deg, int32_t clip, int32_t *dst_rows, int32_t *dst_cols)
+{
+    if (!dst_rows || !dst_cols || rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "bad arguments");
+    double M[6];
+    int dr, dc;
+    int rc = rotate_geometry(rows, cols, angle_deg, 1.0, clip, M, &dr, &dc);
+    if (rc) return rc;
+    *dst_rows = dr;
+    *dst_cols = dc;
+    return OMR_OK;
+}
+
+// omr_rotate_device and omr_rotate_device_ex: the checks that come before the flags', and the rest after them
+static int rotate_device_check(const void *d_src, const void *d_dst, const uint8_t *border_value, int rows, int cols, int channels)
+{
+    if (!d_src || !d_dst || !border_value) return fail(OMR_ERR_BADARG, "null pointer");
+    if (rows <= 0 || cols <= 0 || rows >= 32767 || cols >= 32767 || channels < 1 || channels > 4)
+        return fail(OMR_ERR_ASSERT, "bad image shape");
+    return OMR_OK;
+}
+static int rotate_device(const uint8_t *d_src, int64_t src_step, int rows, int cols, int channels, double angle_deg, double scale,
+                         const WarpMode &m, const uint8_t border_value[4], int clip, uint8_t *d_dst, int64_t dst_step,
+                         int dst_rows, int dst_cols, hipStream_t s)
+{
+    double M[6];
+    int dr, dc;
+    int rc = rotate_geometry(rows, cols, angle_deg, scale, clip, M, &dr, &dc);
+    if (rc) return rc;
+    if (dr != dst_rows || dc != dst_cols) return fail(OMR_ERR_ASSERT, "destination must be %dx%d", dc, dr);
+    if (src_step < (int64_t)cols * channels || dst_step < (int64_t)dc * channels) return fail(OMR_ERR_BADARG, "step too small");
+    return warp_launch(d_src, src_step, rows, cols, channels, M, m, border_value, d_dst, dst_step, dr, dc, s);
+}
+
+int omr_rotate_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, int32_t channels,
+                      double angle_deg, double scale, int32_t interp, const uint8_t border_value[4], int32_t clip,
+                      uint8_t *d_dst, int64_t dst_step, int32_t dst_rows, int32_t dst_cols, void *stream)
+{
+    WarpMode m;
+    int rc = rotate_device_check(d_src, d_dst, border_value, rows, cols, channels);
+    if (rc || (rc = rotate_args(interp, &m))) return rc;
+    return rotate_device(d_src, src_step, rows, cols, channels, angle_deg, scale, m, border_value, clip, d_dst, dst_step,
+                         dst_rows, dst_cols, (hipStream_t)stream);
 }
 
 int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, int32_t channels,
@@ -657,58 +636,51 @@ int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, i
                          const uint8_t border_value[4], int32_t clip, uint8_t *d_dst, int64_t dst_step,
                          int32_t dst_rows, int32_t dst_cols, void *stream)
 {
-    if (!d_src || !d_dst || !border_value) return fail(OMR_ERR_BADARG, "null pointer");
-    if (rows <= 0 || cols <= 0 || rows >= 32767 || cols >= 32767 || channels < 1 || channels > 4)
-        return fail(OMR_ERR_ASSERT, "bad image shape");
-    int interp;
-    bool inverse;
-    int rc = rotate_ex_args(flags, border_mode, &interp, &inverse);
+    WarpMode m;
+    int rc = rotate_device_check(d_src, d_dst, border_value, rows, cols, channels);
+    if (rc || (rc = rotate_ex_args(flags, border_mode, &m))) return rc;
+    return rotate_device(d_src, src_step, rows, cols, channels, angle_deg, scale, m, border_value, clip, d_dst, dst_step,
+                         dst_rows, dst_cols, (hipStream_t)stream);
+}
+
+// omr_rotate and omr_rotate_ex likewise
+static int rotate_host_check(const omr_image *src, const uint8_t *border_value, const omr_image_owned *dst)
+{
+    int rc = check_image(src, false);
     if (rc) return rc;
+    if (!dst || !border_value) return fail(OMR_ERR_BADARG, "null output");
+    return OMR_OK;
+}
+static int rotate_host(const omr_image *src, double angle_deg, double scale, const WarpMode &m, const uint8_t border_value[4],
+                       int clip, omr_image_owned *dst)
+{
     double M[6];
-    int dr, dc;
-    if ((rc = rotate_geometry_impl(rows, cols, angle_deg, scale, clip, M, &dr, &dc))) return rc;
-    if (dr != dst_rows || dc != dst_cols) return fail(OMR_ERR_ASSERT, "destination must be %dx%d", dc, dr);
-    if (src_step < (int64_t)cols * channels || dst_step < (int64_t)dc * channels) return fail(OMR_ERR_BADARG, "step too small");
-    DevBuf keep;
-    rc = rotate_ex_launch(d_src, src_step, rows, cols, channels, M, interp, inverse, border_mode, border_value, d_dst,
-                          dst_step, dr, dc, (hipStream_t)stream, &keep);
-    if (!rc && keep.p) OMR_HIP(hipStreamSynchronize((hipStream_t)stream));  // generic path: matrix buffer is freed
-    return rc;
+    int drows, dcols, rc, dev;
+    if ((rc = rotate_geometry(src->rows, src->cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
+    if ((rc = current_device(&dev))) return rc;
+    Stream st;
+    if ((rc = st.create())) return rc;
+    DevImage in;
+    if ((rc = in.upload(src, st.s))) return rc;
+    return warp_to_host(in.ptr(), in.rows, in.cols, in.cn, M, drows, dcols, m, border_value, st.s, dst);
+}
+
+int omr_rotate(const omr_image *src, double angle_deg, double scale, int32_t interp, const uint8_t border_value[4],
+               int32_t clip, omr_image_owned *dst)
+{
+    WarpMode m;
+    int rc = rotate_host_check(src, border_value, dst);
+    if (rc || (rc = rotate_args(interp, &m))) return rc;
+    return rotate_host(src, angle_deg, scale, m, border_value, clip, dst);
 }
 
 int omr_rotate_ex(const omr_image *src, double angle_deg, double scale, int32_t flags, int32_t border_mode,
                   const uint8_t border_value[4], int32_t clip, omr_image_owned *dst)
 {
-    int rc = check_image(src, false);
-    if (rc) return rc;
-    if (!dst || !border_value) return fail(OMR_ERR_BADARG, "null output");
-    int interp;
-    bool inverse;
-    if ((rc = rotate_ex_args(flags, border_mode, &interp, &inverse))) return rc;
-    double M[6];
-    int drows, dcols;
-    if ((rc = rotate_geometry_impl(src->rows, src->cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
-    int dev;
-    if ((rc = current_device(&dev))) return rc;
-    Stream st;
-    if ((rc = st.create())) return rc;
-    DevImage in, out;
-    DevBuf keep;
-    if ((rc = in.upload(src, st.s))) return rc;
-    if ((rc = out.alloc(drows, dcols, src->channels))) return rc;
-    if (border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(out.ptr(), 0, (size_t)drows * out.step(), st.s));
-    if ((rc = rotate_ex_launch(in.ptr(), in.step(), in.rows, in.cols, in.cn, M, interp, inverse, border_mode, border_value,
-                               out.ptr(), out.step(), drows, dcols, st.s, &keep)))
-        return rc;
-    dst->rows = drows;
-    dst->cols = dcols;
-    dst->channels = src->channels;
-    dst->step_bytes = (int64_t)dcols * src->channels;
-    dst->data = (uint8_t *)malloc((size_t)drows * dst->step_bytes);
-    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    rc = out.download(dst->data, dst->step_bytes, st.s);
-    if (rc) omr_image_free(dst);
-    return rc;
+    WarpMode m;
+    int rc = rotate_host_check(src, border_value, dst);
+    if (rc || (rc = rotate_ex_args(flags, border_mode, &m))) return rc;
+    return rotate_host(src, angle_deg, scale, m, border_value, clip, dst);
 }
 
 // transfer.rs:206-277 erode / dilate, host memory to host memory (the device forms are in oics_morph.cpp)
@@ -750,8 +722,7 @@ int omr_rgb_to_gray_device(const uint8_t *d_src, int64_t src_step, int32_t rows,
     if (channels != 3 && channels != 4) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
     int rc = check_dev_image(d_src, d_dst, rows, cols, src_step, dst_step, channels, 1);
     if (rc) return rc;
-    OMR_HIP(launch_rgb2gray_fast(d_src, src_step, rows, cols, channels, d_dst, dst_step, (hipStream_t)stream));
-    return OMR_OK;
+    return gray_ptr(d_src, src_step, rows, cols, channels, d_dst, dst_step, (hipStream_t)stream);
 }
 
 int omr_erode3_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, uint8_t *d_dst,
@@ -825,7 +796,7 @@ int omr_threshold_binary_device(const uint8_t *d_src, int64_t src_step, int32_t 
 {
     int rc = check_dev_image(d_src, d_dst, rows, cols, src_step, dst_step, 1, 1);
     if (rc) return rc;
-    OMR_HIP(launch_threshold_fast(d_src, src_step, rows, cols, d_dst, dst_step, 127, 255, (hipStream_t)stream));
+    OMR_HIP(launch_threshold(d_src, src_step, rows, cols, d_dst, dst_step, 127, 255, (hipStream_t)stream));
     return OMR_OK;
 }
 
@@ -982,13 +953,7 @@ int result_from_projection_device(const uint8_t *d_src, int rows, int cols, int 
     if ((rc = current_device(&dev))) return rc;
     DevImage gray, e1, scaled;
     if ((rc = gray.alloc(rows, cols, 1))) return rc;
-    if (cn == 1) {  // the reference's cvtColor would raise on a 1-channel Mat; accepted here as a convenience
-        OMR_HIP(hipMemcpyAsync(gray.buf.p, d_src, (size_t)rows * cols, hipMemcpyDeviceToDevice, s));
-    } else if (cn == 3 || cn == 4) {
-        OMR_HIP(launch_rgb2gray_fast(d_src, (int64_t)cols * cn, rows, cols, cn, gray.ptr(), gray.step(), s));  // :88-92
-    } else {
-        return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels, got %d", cn);
-    }
+    if ((rc = gray_ptr(d_src, (int64_t)cols * cn, rows, cols, cn, gray.ptr(), gray.step(), s))) return rc;  // :88-92
     // :98-112 erode(3x3 cross, iterations = 3)
     if ((rc = e1.alloc(rows, cols, 1))) return rc;
     OMR_HIP(launch_erode3x_cross(gray.ptr(), gray.step(), rows, cols, e1.ptr(), e1.step(), s));
@@ -1009,17 +974,7 @@ int rotate_device_to_host(const uint8_t *d_src, int rows, int cols, int cn, doub
 {
     double M[6];
     int drows, dcols, rc;
-    if ((rc = rotate_geometry_impl(rows, cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
-    DevImage out;
-    DevBuf keep;
-    if ((rc = out.alloc(drows, dcols, cn))) return rc;
-    if ((rc = rotate_launch(d_src, (int64_t)cols * cn, rows, cols, cn, M, interp, border_value, out.ptr(), out.step(), drows,
-                            dcols, s, &keep)))
-        return rc;
-    return give_owned(out, dst, s);
-}
-int rotate_geometry(int rows, int cols, double angle_deg, double scale, int clip, double M[6], int *drows, int *dcols)
-{
-    return rotate_geometry_impl(rows, cols, angle_deg, scale, clip, M, drows, dcols);
+    if ((rc = rotate_geometry(rows, cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
+    return warp_to_host(d_src, rows, cols, cn, M, drows, dcols, WarpMode{interp, false, OMR_BORDER_CONSTANT}, border_value, s, dst);
 }
 }  // namespace omr

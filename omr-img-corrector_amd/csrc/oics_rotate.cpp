@@ -1,7 +1,7 @@
 // oics_rotate.cpp -- the fixed-point weight tables of warpAffine's INTER_CUBIC and INTER_LANCZOS4 (OpenCV 4.6.0
 // imgwarp.cpp initInterTab1D / initInterTab2D(method, fixpt = true)), built once per process on the host with the
 // C library's sin / cos (the file is built -ffp-contract=off: every float and double operation rounds as OpenCV's
-// scalar code does) and uploaded once per device.  warp_taps.hip reads them; omr_warp_coeff_table exports them.
+// scalar code does) and uploaded once per device.  warp_affine.hip reads them; omr_warp_coeff_table exports them.
 #include <float.h>
 #include <math.h>
 #include <string.h>

@@ -1,15 +1,15 @@
-// stages.hip -- tuned single-channel stage kernels either side of the sweep:
-// the front end of omr.rs:87-139 (gray, erode x3, INTER_AREA shrink) and the final deskew warp of
-// transfer.rs:459-523 / omr.rs:408-445.  All are HBM-bound byte work: the fast forms move 4 pixels
-// per lane (dword loads / stores), stage reuse through LDS and keep OpenCV 4.6.0's integer
-// arithmetic bit for bit (kernels.hip holds the generic any-channel-count forms).
+// stages.hip -- the per-image stage kernels either side of the sweep: the front end
+// of omr.rs:87-139 (gray, erode x3, INTER_AREA shrink), threshold and resize; the final deskew warp is
+// warp_affine.hip.  All are HBM-bound byte work: the tuned forms move 4 or 16 pixels per lane (dword loads /
+// stores), stage reuse through LDS and keep OpenCV 4.6.0's integer arithmetic bit for bit.  One launcher per
+// stage picks the tuned kernel where layout and alignment allow and otherwise the generic form (any channel
+// count, one thread per destination byte) that sits next to it.
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "warp_fixed.hpp"
 
 namespace omr {
-
-__device__ __forceinline__ uint8_t st_sat_u8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 
 // ------------------------------------------------------------------------------------------
 // cvtColor(COLOR_RGB2GRAY), 3 channels, 4 pixels per lane: three dword loads, one dword store.
@@ -35,15 +35,29 @@ __global__ __launch_bounds__(256) void rgb2gray3_x4_kernel(const uint8_t *__rest
     }
 }
 
-hipError_t launch_rgb2gray_fast(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
-                                int64_t dstep, hipStream_t s)
+// transfer.rs:283-290 / omr.rs:88-92: cvtColor(COLOR_RGB2GRAY) 8U,
+// (c0*9798 + c1*19235 + c2*3735 + 16384) >> 15 in memory order (quirk B8 kept).
+__global__ __launch_bounds__(256) void rgb2gray_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
+                                                       int cols, int cn, uint8_t *__restrict__ dst, int64_t dstep)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x < cols) {
+        const uint8_t *S = src + (int64_t)y * sstep + (int64_t)x * cn;
+        dst[(int64_t)y * dstep + x] = (uint8_t)((S[0] * 9798 + S[1] * 19235 + S[2] * 3735 + (1 << 14)) >> 15);
+    }
+}
+
+hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
+                           int64_t dstep, hipStream_t s)
 {
     if (cn == 3 && (sstep & 3) == 0 && (dstep & 3) == 0 && ((uintptr_t)d_src & 3) == 0 && ((uintptr_t)d_dst & 3) == 0) {
         hipLaunchKernelGGL(rgb2gray3_x4_kernel, dim3((cols + 1023) / 1024, rows), dim3(256), 0, s, d_src, sstep, rows,
                            cols, d_dst, dstep);
         return hipGetLastError();
     }
-    return launch_rgb2gray(d_src, sstep, rows, cols, cn, d_dst, dstep, s);
+    hipLaunchKernelGGL(rgb2gray_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d_src, sstep, rows, cols, cn,
+                       d_dst, dstep);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -229,7 +243,7 @@ __global__ __launch_bounds__(256) void resize_area_int_c1_kernel(const uint8_t *
             for (int xx = 0; xx < k; xx++) sum += tile[ly * k + yy][lx * k + xx];
         uint8_t out;
         if (k == 2) out = (uint8_t)((sum + 2) >> 2);
-        else out = st_sat_u8((int)rintf((float)sum * (1.f / (float)(k * k))));
+        else out = sat_u8((int)rintf((float)sum * (1.f / (float)(k * k))));
         dst[(int64_t)oy * dstep + ox] = out;
     }
 }
@@ -274,14 +288,54 @@ __global__ __launch_bounds__(256) void resize_area_int_colsum_kernel(const uint8
         for (int xx = 0; xx < k; xx++) sum += colsum[ly][lx * k + xx];
         uint8_t out;
         if (k == 2) out = (uint8_t)((sum + 2) >> 2);
-        else out = st_sat_u8((int)rintf((float)sum * (1.f / (float)(k * k))));
+        else out = sat_u8((int)rintf((float)sum * (1.f / (float)(k * k))));
         dst[(int64_t)(oy0 + ly) * dstep + ox0 + lx] = out;
     }
 }
 
-hipError_t launch_resize_area_int_fast(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                                       uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
-                                       hipStream_t s)
+// resize INTER_AREA, integer factors (OpenCV resizeAreaFast_): transfer.rs:66-91, omr.rs:114-126.
+// One thread per destination byte (x runs over dcols*cn).
+__global__ __launch_bounds__(256) void resize_area_int_kernel(const uint8_t *__restrict__ src, int64_t sstep,
+                                                              int srows, int scols, int cn,
+                                                              uint8_t *__restrict__ dst, int64_t dstep, int drows,
+                                                              int dcols, int kx, int ky)
+{
+    const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
+    const int dwidth = dcols * cn, swidth = scols * cn;
+    if (dx >= dwidth) return;
+    const int sy0 = dy * ky;
+    uint8_t out;
+    if (sy0 >= srows) {
+        out = 0;
+    } else {
+        const int dwidth1 = (scols / kx) * cn;
+        const int w = sy0 + ky <= srows ? dwidth1 : 0;
+        const int sx0 = kx * (dx / cn) * cn + dx % cn;
+        if (dx < w) {
+            int sum = 0;
+            for (int sy = 0; sy < ky; sy++)
+                for (int sx = 0; sx < kx; sx++) sum += src[(int64_t)(sy0 + sy) * sstep + sx0 + sx * cn];
+            if (kx == 2 && ky == 2) out = (uint8_t)((sum + 2) >> 2);
+            else out = sat_u8((int)rintf((float)sum * (1.f / (float)(kx * ky))));
+        } else {
+            int sum = 0, count = 0;
+            for (int sy = 0; sy < ky; sy++) {
+                if (sy0 + sy >= srows) break;
+                for (int sx = 0; sx < kx * cn; sx += cn) {
+                    if (sx0 + sx >= swidth) break;
+                    sum += src[(int64_t)(sy0 + sy) * sstep + sx0 + sx];
+                    count++;
+                }
+            }
+            out = count ? sat_u8((int)rintf((float)sum / (float)count)) : 0;
+        }
+    }
+    dst[(int64_t)dy * dstep + dx] = out;
+}
+
+hipError_t launch_resize_area_int(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
+                                  uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
+                                  hipStream_t s)
 {
     const bool full = cn == 1 && kx == ky && kx >= 2 && drows * ky == srows && dcols * kx == scols;
     // the dword loads of the last column may run up to 3 bytes past the last source pixel of a row: the row pitch
@@ -296,211 +350,63 @@ hipError_t launch_resize_area_int_fast(const uint8_t *d_src, int64_t sstep, int 
                            dim3(256), 0, s, d_src, sstep, d_dst, dstep, drows, dcols, kx);
         return hipGetLastError();
     }
-    return launch_resize_area_int(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, kx, ky, s);
-}
-
-// ------------------------------------------------------------------------------------------
-// warpAffine on a 1-channel image, 4 destination pixels per lane (one dword store).  The fixed-
-// point tables are evaluated in place with the same f64 expressions (file built -ffp-contract=off).
-struct WarpM {
-    double m[6];
-};
-
-template <bool LINEAR>
-__global__ __launch_bounds__(256) void warp_c1_x4_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
-                                                         int scols, uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                         int dcols, const WarpM W, int border)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    const int x0 = q * 4;
-    if (x0 >= dcols) return;
-    const double *M = W.m;
-    const int rd = LINEAR ? 16 : 512;
-    const int X0 = (int)rint((M[1] * (double)y + M[2]) * 1024.0) + rd;
-    const int Y0 = (int)rint((M[4] * (double)y + M[5]) * 1024.0) + rd;
-    uint32_t out = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int x = x0 + j;
-        const int adelta = (int)rint(M[0] * (double)x * 1024.0);
-        const int bdelta = (int)rint(M[3] * (double)x * 1024.0);
-        int v;
-        if (!LINEAR) {
-            int X = (X0 + adelta) >> 10, Y = (Y0 + bdelta) >> 10;
-            X = max(-32768, min(32767, X));
-            Y = max(-32768, min(32767, Y));
-            v = ((unsigned)X < (unsigned)scols && (unsigned)Y < (unsigned)srows) ? src[(int64_t)Y * sstep + X] : border;
-        } else {
-            const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-            const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
-            const int fx = X & 31, fy = Y & 31;
-            if (sx >= scols || sx + 1 < 0 || sy >= srows || sy + 1 < 0) {
-                v = border;
-            } else {
-                const bool in_x0 = sx >= 0 && sx < scols, in_x1 = sx + 1 >= 0 && sx + 1 < scols;
-                const bool in_y0 = sy >= 0 && sy < srows, in_y1 = sy + 1 >= 0 && sy + 1 < srows;
-                const int v0 = in_x0 && in_y0 ? src[(int64_t)sy * sstep + sx] : border;
-                const int v1 = in_x1 && in_y0 ? src[(int64_t)sy * sstep + sx + 1] : border;
-                const int v2 = in_x0 && in_y1 ? src[(int64_t)(sy + 1) * sstep + sx] : border;
-                const int v3 = in_x1 && in_y1 ? src[(int64_t)(sy + 1) * sstep + sx + 1] : border;
-                const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32,
-                          w3 = fy * fx * 32;
-                v = st_sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
-            }
-        }
-        out |= (uint32_t)v << (8 * j);
-    }
-    uint8_t *D = dst + (int64_t)y * dstep + x0;
-    if (x0 + 4 <= dcols) {
-        *(uint32_t *)D = out;
-    } else {
-        for (int j = 0; x0 + j < dcols; j++) D[j] = (uint8_t)(out >> (8 * j));
-    }
-}
-
-// The same warp with the source staged in LDS.  A workgroup owns a 64 x 16 destination tile; the affine map
-// takes it to a parallelogram whose bounding box (found from the four corner samples, one pixel of slack for
-// the rounding of the fixed-point tables, one more for the bilinear taps) is copied to LDS with row-contiguous
-// dword loads, border value outside the image -- so a tap is one LDS byte read with no bounds test, instead of
-// a byte gather through L1 along a slanted line (about 45 cache lines per wave).  A tile whose box does not
-// fit (strong magnification) takes its taps from global memory as before.
-#define WL_TW 64
-#define WL_TH 16
-#define WL_LDS 16384
-
-template <bool LINEAR>
-__device__ __forceinline__ int warp_tap_global(const uint8_t *__restrict__ src, int64_t sstep, int srows, int scols,
-                                               int cn, int Xf, int Yf, int border)
-{
-    if (!LINEAR) {
-        const int X = max(-32768, min(32767, Xf >> 10)), Y = max(-32768, min(32767, Yf >> 10));
-        return ((unsigned)X < (unsigned)scols && (unsigned)Y < (unsigned)srows) ? src[(int64_t)Y * sstep + (int64_t)X * cn] : border;
-    }
-    const int X = Xf >> 5, Y = Yf >> 5;
-    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
-    const int fx = X & 31, fy = Y & 31;
-    if (sx >= scols || sx + 1 < 0 || sy >= srows || sy + 1 < 0) return border;
-    const bool in_x0 = sx >= 0 && sx < scols, in_x1 = sx + 1 >= 0 && sx + 1 < scols;
-    const bool in_y0 = sy >= 0 && sy < srows, in_y1 = sy + 1 >= 0 && sy + 1 < srows;
-    const int v0 = in_x0 && in_y0 ? src[(int64_t)sy * sstep + (int64_t)sx * cn] : border;
-    const int v1 = in_x1 && in_y0 ? src[(int64_t)sy * sstep + (int64_t)(sx + 1) * cn] : border;
-    const int v2 = in_x0 && in_y1 ? src[(int64_t)(sy + 1) * sstep + (int64_t)sx * cn] : border;
-    const int v3 = in_x1 && in_y1 ? src[(int64_t)(sy + 1) * sstep + (int64_t)(sx + 1) * cn] : border;
-    const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-    return st_sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
-}
-
-template <int CN, bool LINEAR>
-__global__ __launch_bounds__(256) void warp_lds_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
-                                                       int scols, uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                       int dcols, const WarpM W, uint32_t border_rgba)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t box[WL_LDS];
-    const double *M = W.m;
-    const int rd = LINEAR ? 16 : 512;
-    const int tx0 = blockIdx.x * WL_TW, ty0 = blockIdx.y * WL_TH;
-    const int tx1 = min(dcols, tx0 + WL_TW) - 1, ty1 = min(drows, ty0 + WL_TH) - 1;
-    // fixed-point source coordinates (OpenCV's tables) of the tile's corner samples: wave-uniform.  X0(y) and
-    // adelta(x) are both monotone, so the four corners bound every sample of the tile.
-    auto FX = [&](int x, int y) { return (int)rint((M[1] * (double)y + M[2]) * 1024.0) + rd + (int)rint(M[0] * (double)x * 1024.0); };
-    auto FY = [&](int x, int y) { return (int)rint((M[4] * (double)y + M[5]) * 1024.0) + rd + (int)rint(M[3] * (double)x * 1024.0); };
-    const int cx[4] = {FX(tx0, ty0) >> 10, FX(tx1, ty0) >> 10, FX(tx0, ty1) >> 10, FX(tx1, ty1) >> 10};
-    const int cy[4] = {FY(tx0, ty0) >> 10, FY(tx1, ty0) >> 10, FY(tx0, ty1) >> 10, FY(tx1, ty1) >> 10};
-    const int bx0 = min(min(cx[0], cx[1]), min(cx[2], cx[3])) - 1;
-    const int bx1 = max(max(cx[0], cx[1]), max(cx[2], cx[3])) + 1 + (LINEAR ? 1 : 0);
-    const int by0 = min(min(cy[0], cy[1]), min(cy[2], cy[3])) - 1;
-    const int by1 = max(max(cy[0], cy[1]), max(cy[2], cy[3])) + 1 + (LINEAR ? 1 : 0);
-    // the box in BYTES of a source row, widened to whole dwords of the row
-    const int bb0 = (bx0 * CN) & ~3, bb1 = ((bx1 + 1) * CN + 3) & ~3;  // [bb0, bb1)
-    const int bwb = bb1 - bb0, bh = by1 - by0 + 1;
-    const bool staged = bwb > 0 && bh > 0 && (int64_t)bwb * bh <= WL_LDS && bx0 > -30000 && bx1 < 30000 &&
-                        by0 > -30000 && by1 < 30000;
-    const int rowb = scols * CN;  // bytes of a source row that hold pixels
-    if (staged) {
-        const int bq = bwb >> 2;
-        const bool aligned = ((sstep | (int64_t)(uintptr_t)src) & 3) == 0;
-        for (int i = threadIdx.x; i < bq * bh; i += 256) {
-            const int ly = i / bq, lq = i - ly * bq;
-            const int gy = by0 + ly, gb = bb0 + lq * 4;
-            uint32_t v;
-            if (aligned && (unsigned)gy < (unsigned)srows && gb >= 0 && gb + 4 <= rowb) {
-                v = *(const uint32_t *)(src + (int64_t)gy * sstep + gb);
-            } else {
-                v = 0;
-                for (int j = 0; j < 4; j++) {
-                    const int b = gb + j;  // byte b of row gy: pixel b / CN, channel b % CN (floor semantics for b < 0)
-                    const int ch = ((b % CN) + CN) % CN;
-                    uint32_t px = (border_rgba >> (8 * ch)) & 255u;
-                    if ((unsigned)gy < (unsigned)srows && b >= 0 && b < rowb) px = src[(int64_t)gy * sstep + b];
-                    v |= px << (8 * j);
-                }
-            }
-            *(uint32_t *)&box[ly * bwb + lq * 4] = v;
-        }
-    }
-    __syncthreads();
-    const int lx = (threadIdx.x & 15) * 4, ly = threadIdx.x >> 4;
-    const int x0 = tx0 + lx, y = ty0 + ly;
-    if (x0 >= dcols || y >= drows) return;
-    const int X0 = (int)rint((M[1] * (double)y + M[2]) * 1024.0) + rd;
-    const int Y0 = (int)rint((M[4] * (double)y + M[5]) * 1024.0) + rd;
-    uint8_t o[4 * CN];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int x = x0 + j;
-        const int Xf = X0 + (int)rint(M[0] * (double)x * 1024.0), Yf = Y0 + (int)rint(M[3] * (double)x * 1024.0);
-        if (!staged) {
-#pragma unroll
-            for (int c = 0; c < CN; c++)
-                o[j * CN + c] = (uint8_t)warp_tap_global<LINEAR>(src + c, sstep, srows, scols, CN, Xf, Yf, (border_rgba >> (8 * c)) & 255);
-        } else if (!LINEAR) {
-            const uint8_t *B = &box[((Yf >> 10) - by0) * bwb + (Xf >> 10) * CN - bb0];
-#pragma unroll
-            for (int c = 0; c < CN; c++) o[j * CN + c] = B[c];
-        } else {
-            const int X = Xf >> 5, Y = Yf >> 5;
-            const int fx = X & 31, fy = Y & 31;
-            const uint8_t *B = &box[((Y >> 5) - by0) * bwb + (X >> 5) * CN - bb0];
-            const int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-#pragma unroll
-            for (int c = 0; c < CN; c++)
-                o[j * CN + c] = st_sat_u8((B[c] * w0 + B[CN + c] * w1 + B[bwb + c] * w2 + B[bwb + CN + c] * w3 + (1 << 14)) >> 15);
-        }
-    }
-    uint8_t *D = dst + (int64_t)y * dstep + (int64_t)x0 * CN;
-    if (x0 + 4 <= dcols && ((uintptr_t)D & 3) == 0) {  // packed CONTAIN canvases have odd widths: rows start anywhere
-#pragma unroll
-        for (int q = 0; q < CN; q++)
-            ((uint32_t *)D)[q] = (uint32_t)o[4 * q] | ((uint32_t)o[4 * q + 1] << 8) | ((uint32_t)o[4 * q + 2] << 16) |
-                                 ((uint32_t)o[4 * q + 3] << 24);
-    } else {
-        for (int j = 0; j < 4 * CN && x0 * CN + j < dcols * CN; j++) D[j] = o[j];
-    }
-}
-
-// 1- and 3-channel warpAffine (NEAREST / LINEAR) through the LDS-staged kernel: the gray helpers and the final
-// deskew of the colour scan (omr.rs:408-445, core/src/main.rs:72-81).  Returns hipErrorInvalidValue for other
-// channel counts (the caller uses the generic kernel).
-hipError_t launch_warp_fast(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                            int64_t dstep, int drows, int dcols, const double Minv[6], int interp, uint32_t border_rgba,
-                            hipStream_t s)
-{
-    if (cn != 1 && cn != 3) return hipErrorInvalidValue;
-    WarpM W;
-    for (int i = 0; i < 6; i++) W.m[i] = Minv[i];
-    dim3 grid((dcols + WL_TW - 1) / WL_TW, (drows + WL_TH - 1) / WL_TH);
-#define WARP_LAUNCH(CN_, LIN_)                                                                                         \
-    hipLaunchKernelGGL((warp_lds_kernel<CN_, LIN_>), grid, dim3(256), 0, s, d_src, sstep, srows, scols, d_dst, dstep, \
-                       drows, dcols, W, border_rgba)
-    if (cn == 1 && interp == 0) WARP_LAUNCH(1, false);
-    else if (cn == 1) WARP_LAUNCH(1, true);
-    else if (interp == 0) WARP_LAUNCH(3, false);
-    else WARP_LAUNCH(3, true);
-#undef WARP_LAUNCH
+    hipLaunchKernelGGL(resize_area_int_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src, sstep,
+                       srows, scols, cn, d_dst, dstep, drows, dcols, kx, ky);
     return hipGetLastError();
 }
 
-// threshold(thresh, maxval, BINARY), 16 pixels per lane
+// resize INTER_AREA, general shrink (OpenCV resizeArea_<uchar,float>): per destination byte the
+// same float accumulation order as ResizeArea_Invoker: for each source row tap (ascending) the
+// row sum buf = sum_k S*alpha_k (ascending k), then sum (+)= beta*buf.  xofs/yofs: CSR offsets
+// of the taps of every destination column / row.
+__global__ __launch_bounds__(256) void resize_area_general_kernel(const uint8_t *__restrict__ src, int64_t sstep,
+                                                                  int cn, uint8_t *__restrict__ dst, int64_t dstep,
+                                                                  int drows, int dcols,
+                                                                  const AreaTap *__restrict__ xtab,
+                                                                  const int32_t *__restrict__ xofs,
+                                                                  const AreaTap *__restrict__ ytab,
+                                                                  const int32_t *__restrict__ yofs)
+{
+    const int dxb = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
+    if (dxb >= dcols * cn) return;
+    const int dx = dxb / cn, c = dxb % cn;
+    float sum = 0.f;
+    bool first = true;
+    for (int j = yofs[dy]; j < yofs[dy + 1]; j++) {
+        const float beta = ytab[j].alpha;
+        const uint8_t *S = src + (int64_t)ytab[j].si * sstep + c;
+        float buf = 0.f;
+        for (int k = xofs[dx]; k < xofs[dx + 1]; k++) buf += (float)S[xtab[k].si] * xtab[k].alpha;
+        if (first) {
+            sum = beta * buf;  // ResizeArea_Invoker assigns on the first tap of a destination row
+            first = false;
+        } else {
+            sum += beta * buf;
+        }
+    }
+    dst[(int64_t)dy * dstep + dxb] = sat_u8((int)rintf(sum));
+}
+
+hipError_t launch_resize_area_general(const uint8_t *d_src, int64_t sstep, int cn, uint8_t *d_dst, int64_t dstep,
+                                      int drows, int dcols, const AreaTap *d_xtab, const int32_t *d_xofs,
+                                      const AreaTap *d_ytab, const int32_t *d_yofs, hipStream_t s)
+{
+    hipLaunchKernelGGL(resize_area_general_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src,
+                       sstep, cn, d_dst, dstep, drows, dcols, d_xtab, d_xofs, d_ytab, d_yofs);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// transfer.rs:294-301 / omr.rs:129-139: threshold(127, 255, THRESH_BINARY), one pixel per lane
+__global__ __launch_bounds__(256) void threshold_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
+                                                        int cols, uint8_t *__restrict__ dst, int64_t dstep,
+                                                        int thresh, int maxval)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x < cols) dst[(int64_t)y * dstep + x] = (int)src[(int64_t)y * sstep + x] > thresh ? (uint8_t)maxval : 0;
+}
+
+// the same, 16 pixels per lane
 __global__ __launch_bounds__(256) void threshold_x16_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
                                                             int cols, uint8_t *__restrict__ dst, int64_t dstep,
                                                             int thresh, int maxval)
@@ -527,15 +433,17 @@ __global__ __launch_bounds__(256) void threshold_x16_kernel(const uint8_t *__res
     }
 }
 
-hipError_t launch_threshold_fast(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
-                                 int thresh, int maxval, hipStream_t s)
+hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
+                            int thresh, int maxval, hipStream_t s)
 {
     if ((sstep & 15) == 0 && (dstep & 15) == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0) {
         hipLaunchKernelGGL(threshold_x16_kernel, dim3((cols + 4095) / 4096, rows), dim3(256), 0, s, d_src, sstep, rows,
                            cols, d_dst, dstep, thresh, maxval);
         return hipGetLastError();
     }
-    return launch_threshold(d_src, sstep, rows, cols, d_dst, dstep, thresh, maxval, s);
+    hipLaunchKernelGGL(threshold_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d_src, sstep, rows, cols,
+                       d_dst, dstep, thresh, maxval);
+    return hipGetLastError();
 }
 
 // resize(INTER_LINEAR) and INTER_AREA's bilinear emulation when an axis enlarges (OpenCV resizeGeneric_ with

@@ -171,6 +171,27 @@ def test_old_pairs_are_omr_rotate_bit_for_bit():
                 assert (got == exp).all(), (rows, cols, cn, flags)
 
 
+def test_constant_border_pairs_at_sheet_size():
+    """NEAREST / LINEAR with BORDER_CONSTANT on the 301 x 437 content, both clips, at scales that stage a tile's source
+    box in LDS (1.0, 2.5) and one whose boxes do not fit (0.37: taps from global memory).  2 and 4 channels: the device
+    form at odd addresses and pitches against warp_ref, and omr_rotate against the same warp_ref image.  1 and 3
+    channels with WARP_INVERSE_MAP: the kernel choice does not look at the flag."""
+    rng = np.random.default_rng(21)
+    for cn in (2, 4):
+        a = _content(rng, 301, 437, cn)
+        for interp in (0, 1):
+            for clip in (0, 1):
+                for scale in SCALES:
+                    exp = _check(a, 7.3, scale, interp, wr.CONSTANT, clip)  # == warp_ref's image, every byte (no skips)
+                    assert (_old(a, 7.3, scale, interp, clip) == exp).all(), (cn, interp, clip, scale)
+    for cn in (1, 3):
+        a = _content(rng, 301, 437, cn)
+        for interp in (0, 1):
+            for clip in (0, 1):
+                for scale in SCALES:
+                    _check(a, -41.0, scale, interp | 16, wr.CONSTANT, clip)
+
+
 def test_python_rotate_mat_every_flag_and_border():
     rng = np.random.default_rng(4)
     a = _content(rng, 40, 57, 3)

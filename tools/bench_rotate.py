@@ -1,9 +1,9 @@
-"""rotate_mat with every interpolation on the device (omr_rotate_device_ex) on an A4 sheet (2480 x 3508, 1 and 3
-channels, angle 3.3, CONTAIN), BORDER_CONSTANT and BORDER_REPLICATE, with today's omr_rotate_device (NEAREST / LINEAR,
-CONSTANT) on the same geometry as the anchor.  Device-resident buffers, HIP events around `--iters` calls after a
-warm-up.  Per case: ms per call, GB/s of the compulsory bytes (source read once + canvas written once), their share of
-8 TB/s, and tap multiply-adds per second (canvas pixels x channels x K^2).
-Usage: python tools/bench_rotate.py [--iters N] [--json PATH]"""
+"""rotate_mat with every interpolation on the device (omr_rotate_device_ex) on an A4 sheet (2480 x 3508, angle 3.3,
+CONTAIN; 1 and 3 channels unless --channels says otherwise), BORDER_CONSTANT and BORDER_REPLICATE, with omr_rotate_device
+(NEAREST / LINEAR, CONSTANT) on the same geometry as the anchor.  Device-resident buffers, HIP events around `--iters`
+calls after a warm-up.  Per case: ms per call, GB/s of the compulsory bytes (source read once + canvas written once),
+their share of 8 TB/s, and tap multiply-adds per second (canvas pixels x channels x K^2).
+Usage: python tools/bench_rotate.py [--iters N] [--channels 1,3] [--json PATH]"""
 import argparse
 import ctypes as C
 import json
@@ -23,6 +23,7 @@ TAPS = {0: 1, 1: 4, 2: 16, 4: 64}
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--channels", default="1,3", help="comma-separated channel counts, each 1..4")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     lib = _lib.lib()
@@ -34,7 +35,7 @@ def main():
     bp = C.cast(b, _lib.u8p)
     g = torch.Generator().manual_seed(1)
     out = []
-    for cn in (1, 3):
+    for cn in [int(c) for c in args.channels.split(",")]:
         src = torch.randint(0, 256, (rows, cols * cn), dtype=torch.uint8, generator=g).cuda()
         dst = torch.empty((dr, dc * cn), dtype=torch.uint8, device="cuda")
         cases = [("omr_rotate_device", i, 0) for i in (0, 1)]
