@@ -408,6 +408,38 @@ int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, i
                          double angle_deg, double scale, int32_t flags, int32_t border_mode,
                          const uint8_t border_value[4], int32_t clip, uint8_t *d_dst, int64_t dst_step,
                          int32_t dst_rows, int32_t dst_cols, void *stream);
+/* rotate_mat for a batch, an angle per image; scale, flags, border mode, border value and clip are the batch's.
+ * Flags, border modes, channels and error codes are omr_rotate_device_ex's, and image i's canvas is byte for byte what
+ * omr_rotate_device_ex writes for the same image, angle and parameters: the matrices come from the host's libm as
+ * they do there, travel in one upload, and the same kernels run once with the image index in blockIdx.z.
+ *
+ * omr_rotate_batch_canvas (host only, no device needed): image i's canvas is omr_rotate_size(rows, cols, angles[i],
+ * clip); *max_rows and *max_cols are the largest rows and the largest cols over the batch, each on its own, so every
+ * canvas fits a max_rows x max_cols slot (DEFAULT: rows x cols).  out_size, when given: (rows, cols) of canvas i at
+ * [2i], [2i + 1].
+ *
+ * omr_rotate_batch_device_ex: n same-shape images, image i at d_src + i * src_stride_bytes (any stride >= 0: 0
+ * rotates one image by n angles), rows src_step apart.  Canvas i fills the top left of the slot d_dst +
+ * i * dst_stride_bytes, rows dst_step apart; the slot's bytes outside the canvas are not written (nor are the pixels
+ * BORDER_TRANSPARENT skips).  Its (rows, cols) land in the HOST array out_size when given.  OMR_ERR_BADARG besides
+ * omr_rotate_device_ex's own: n <= 0, a null angle array, an angle that is not finite, a slot smaller than
+ * omr_rotate_batch_canvas's answer, dst_step < channels * slot_cols, dst_stride_bytes < slot_rows * dst_step,
+ * src_stride_bytes < 0, source and destination ranges that overlap.  Every argument is checked before any device
+ * work.  The launches are enqueued on `stream`.  Batches of more than 3 images upload a per-call table of matrices and
+ * SYNCHRONISE `stream` before the call returns, because the table is given back on return; smaller ones only enqueue.
+ *
+ * omr_rotate_batch_ex: host images of any mix of shapes and channel counts in, owned images out (dsts[i] belongs to
+ * srcs[i]; free each with omr_image_free).  Same-shape images go through omr_rotate_batch_device_ex's path together.
+ * On an error no image is returned.  BORDER_TRANSPARENT starts from zero-filled canvases, as omr_rotate_ex does. */
+int omr_rotate_batch_canvas(int32_t rows, int32_t cols, const double *angles_deg, int32_t n, int32_t clip,
+                            int32_t *max_rows, int32_t *max_cols, int32_t *out_size);
+int omr_rotate_batch_device_ex(const uint8_t *d_src, int32_t n, int64_t src_stride_bytes, int64_t src_step,
+                               int32_t rows, int32_t cols, int32_t channels, const double *angles_deg, double scale,
+                               int32_t flags, int32_t border_mode, const uint8_t border_value[4], int32_t clip,
+                               uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step, int32_t slot_rows,
+                               int32_t slot_cols, int32_t *out_size, void *stream);
+int omr_rotate_batch_ex(const omr_image *srcs, int32_t n, const double *angles_deg, double scale, int32_t flags,
+                        int32_t border_mode, const uint8_t border_value[4], int32_t clip, omr_image_owned *dsts);
 /* The fixed-point weight table the warp uses for OMR_INTER_CUBIC (k = 4) or OMR_INTER_LANCZOS4 (k = 8): OpenCV's
  * initInterTab2D(method, fixpt = true), 32 * 32 entries of k * k int16, entry fy * 32 + fx, tap row * k + col.
  * *n_out = 1024 * k * k; out == NULL only reports the size; cap < *n_out is OMR_ERR_BADARG.  Host only. */

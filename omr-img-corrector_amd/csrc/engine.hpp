@@ -113,6 +113,24 @@ int rotate_device_to_host(const uint8_t *d_src, int rows, int cols, int cn, doub
 // uploaded once per device (oics_rotate.cpp)
 const std::vector<int16_t> &warp_coeff_host(int interp);
 int warp_coeff_device(int interp, const int16_t **d_tab);
+// how a rotate entry point asks warpAffine to sample: interpolation 0 / 1 / 2 / 4, whether the matrix is already
+// dst -> src (WARP_INVERSE_MAP), border mode; rotate_ex_args checks omr_rotate_ex's flags and border mode (oics_host.cpp)
+struct WarpMode {
+    int interp;
+    bool inverse;
+    int border_mode;
+};
+int rotate_ex_args(int flags, int border_mode, WarpMode *m);
+// rotate_mat of n same-shape images by an angle each (oics_rotate.cpp).  rotate_batch_plan: per image the dst -> src
+// matrix and the canvas, and the largest rows / cols over the batch, on the host; OMR_ERR_BADARG for a non-finite angle.
+// rotate_batch_launch: one table upload and one launch per 65535 images on `s` (arguments already checked; image i at
+// d_src + i * sstride, its canvas at the top left of d_dst + i * dstride); synchronises `s` to give the table back.
+// Up to 3 images go an image per launch instead, without table or wait.
+int rotate_batch_plan(int rows, int cols, const double *angles_deg, int n, double scale, int clip, bool inverse,
+                      std::vector<WarpImg> *per, int *max_rows, int *max_cols);
+int rotate_batch_launch(const uint8_t *d_src, int64_t sstride, int64_t sstep, int rows, int cols, int cn,
+                        const std::vector<WarpImg> &per, int max_rows, int max_cols, const WarpMode &m,
+                        const uint8_t border_value[4], uint8_t *d_dst, int64_t dstride, int64_t dstep, hipStream_t s);
 // erode / dilate (oics_morph.cpp): every argument check of the omr_morph* entry points, and the launches on `s`
 // for n images `sstride` / `dstride` bytes apart (arguments already checked; synchronises `s` when it took scratch)
 int morph_check_args(const void *src, const void *dst, int64_t sstep, int64_t dstep, int rows, int cols, int cn, int op,

@@ -194,6 +194,21 @@ hipError_t launch_resize_linear(const uint8_t *d_src, int64_t sstep, int srows, 
 hipError_t launch_warp_affine(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
                               int64_t dstep, int drows, int dcols, const double Minv[6], int interp, int border_mode,
                               uint32_t border_rgba, const int16_t *d_wtab, hipStream_t s);
+// The same for a batch of n <= 65535 same-shape images in one launch (image index = blockIdx.z): image i at
+// d_src + i * sstride, its dst -> src matrix and canvas in d_per[i] (DEVICE memory), the canvas at the top left of the
+// slot d_dst + i * dstride; max_drows x max_dcols, the largest canvas, sizes the grid.  Same kernels, same bytes.
+struct WarpImg {
+    double minv[6];
+    int32_t rows, cols;
+};
+struct WarpBatch {  // a kernel argument; per == NULL: one image, described by the kernel's own arguments
+    const WarpImg *per;
+    int64_t sstride, dstride;
+};
+hipError_t launch_warp_affine_batch(const uint8_t *d_src, int64_t sstride, int64_t sstep, int srows, int scols, int cn,
+                                    uint8_t *d_dst, int64_t dstride, int64_t dstep, int max_drows, int max_dcols,
+                                    const WarpImg *d_per, int n, int interp, int border_mode, uint32_t border_rgba,
+                                    const int16_t *d_wtab, hipStream_t s);
 
 // ---- erode / dilate with any structuring element (morph.hip; the callers are in oics_morph.cpp) ---------------
 #define MORPH_MAXK 31  // largest element side of the two LDS kernels

@@ -352,6 +352,19 @@ int omr::rotate_geometry(int rows, int cols, double angle_deg, double scale, int
     return OMR_OK;
 }
 
+// warpAffine's flags and border mode as omr_rotate_ex takes them (INTER_AREA is LINEAR, imgwarp.cpp)
+int omr::rotate_ex_args(int flags, int border_mode, WarpMode *m)
+{
+    if (flags & ~(7 | OMR_WARP_FILL_OUTLIERS | OMR_WARP_INVERSE_MAP)) return fail(OMR_ERR_BADARG, "unknown warp flags 0x%x", flags);
+    int ip = flags & 7;
+    if (ip == OMR_INTER_AREA) ip = OMR_INTER_LINEAR;
+    if (ip > OMR_INTER_LANCZOS4) return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", ip);
+    if (border_mode < OMR_BORDER_CONSTANT || border_mode > OMR_BORDER_TRANSPARENT)
+        return fail(OMR_ERR_BADARG, "unknown border mode %d", border_mode);
+    *m = WarpMode{ip, (flags & OMR_WARP_INVERSE_MAP) != 0, border_mode};
+    return OMR_OK;
+}
+
 extern "C" {
 
 void omr_image_free(omr_image_owned *img)
@@ -524,33 +537,12 @@ int omr_rgb_to_gray(const omr_image *src, uint8_t *dst, int64_t dst_step)
     return out.download(dst, dst_step, st.s);
 }
 
-// how a rotate entry point asks warpAffine to sample: interpolation 0 / 1 / 2 / 4, whether the matrix is already
-// dst -> src (WARP_INVERSE_MAP), border mode
-struct WarpMode {
-    int interp;
-    bool inverse;
-    int border_mode;
-};
-
 // omr_rotate / omr_rotate_device: NEAREST or LINEAR, forward matrix, BORDER_CONSTANT
 static int rotate_args(int interp, WarpMode *m)
 {
     if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
         return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
     *m = WarpMode{interp, false, OMR_BORDER_CONSTANT};
-    return OMR_OK;
-}
-
-// warpAffine's flags and border mode as omr_rotate_ex takes them (INTER_AREA is LINEAR, imgwarp.cpp)
-static int rotate_ex_args(int flags, int border_mode, WarpMode *m)
-{
-    if (flags & ~(7 | OMR_WARP_FILL_OUTLIERS | OMR_WARP_INVERSE_MAP)) return fail(OMR_ERR_BADARG, "unknown warp flags 0x%x", flags);
-    int ip = flags & 7;
-    if (ip == OMR_INTER_AREA) ip = OMR_INTER_LINEAR;
-    if (ip > OMR_INTER_LANCZOS4) return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", ip);
-    if (border_mode < OMR_BORDER_CONSTANT || border_mode > OMR_BORDER_TRANSPARENT)
-        return fail(OMR_ERR_BADARG, "unknown border mode %d", border_mode);
-    *m = WarpMode{ip, (flags & OMR_WARP_INVERSE_MAP) != 0, border_mode};
     return OMR_OK;
 }
 
@@ -681,6 +673,100 @@ int omr_rotate_ex(const omr_image *src, double angle_deg, double scale, int32_t 
     int rc = rotate_host_check(src, border_value, dst);
     if (rc || (rc = rotate_ex_args(flags, border_mode, &m))) return rc;
     return rotate_host(src, angle_deg, scale, m, border_value, clip, dst);
+}
+
+// rotate_mat of n host images by an angle each.  The images are bucketed by (rows, cols, channels) as omr_sweep_batch
+// buckets its scans; a bucket travels in pieces of at most 1 GiB of device memory, each piece one upload per image, one
+// launch (rotate_batch_launch) and one download per image, and the results land at the images' own positions.
+int omr_rotate_batch_ex(const omr_image *srcs, int32_t n, const double *angles_deg, double scale, int32_t flags,
+                        int32_t border_mode, const uint8_t border_value[4], int32_t clip, omr_image_owned *dsts)
+{
+    if (!srcs || !dsts || !border_value || !angles_deg) return fail(OMR_ERR_BADARG, "null pointer");
+    if (n <= 0) return fail(OMR_ERR_BADARG, "batch of %d images", n);
+    WarpMode m;
+    int rc;
+    std::vector<std::tuple<int, int, int>> shapes;  // in order of first appearance
+    std::vector<std::vector<int>> members;
+    for (int i = 0; i < n; i++) {
+        if ((rc = check_image(&srcs[i], false))) return rc;
+        const std::tuple<int, int, int> sh(srcs[i].rows, srcs[i].cols, srcs[i].channels);
+        size_t k = 0;
+        while (k < shapes.size() && shapes[k] != sh) k++;
+        if (k == shapes.size()) {
+            shapes.push_back(sh);
+            members.emplace_back();
+        }
+        members[k].push_back(i);
+    }
+    if ((rc = rotate_ex_args(flags, border_mode, &m))) return rc;
+    std::vector<std::vector<WarpImg>> plans(shapes.size());
+    std::vector<std::pair<int, int>> slots(shapes.size());
+    for (size_t k = 0; k < shapes.size(); k++) {
+        std::vector<double> ang;
+        for (int i : members[k]) ang.push_back(angles_deg[i]);
+        if ((rc = rotate_batch_plan(std::get<0>(shapes[k]), std::get<1>(shapes[k]), ang.data(), (int)ang.size(), scale, clip,
+                                    m.inverse, &plans[k], &slots[k].first, &slots[k].second)))
+            return rc;
+    }
+    int dev;
+    if ((rc = current_device(&dev))) return rc;
+    for (int i = 0; i < n; i++) dsts[i] = omr_image_owned{};
+    auto run = [&]() -> int {
+        Stream st;
+        int rc = st.create();
+        if (rc) return rc;
+        for (size_t k = 0; k < shapes.size(); k++) {
+            const int rows = std::get<0>(shapes[k]), cols = std::get<1>(shapes[k]), cn = std::get<2>(shapes[k]);
+            const int64_t sstep = (int64_t)cols * cn, sstride = (sstep * rows + 3) & ~(int64_t)3;
+            const int64_t dstep = ((int64_t)slots[k].second * cn + 3) & ~(int64_t)3, dstride = dstep * slots[k].first;
+            const int total = (int)members[k].size();
+            const int piece = (int)std::max<int64_t>(1, std::min<int64_t>(total, ((int64_t)1 << 30) / (sstride + dstride)));
+            for (int j0 = 0; j0 < total; j0 += piece) {
+                const int cnt = std::min(piece, total - j0);
+                DevBuf in, out;
+                if (in.alloc((size_t)sstride * cnt) != hipSuccess || out.alloc((size_t)dstride * cnt) != hipSuccess)
+                    return fail(OMR_ERR_NOMEM, "out of device memory for %d images of %d x %d", cnt, cols, rows);
+                for (int j = 0; j < cnt; j++) {
+                    const omr_image &im = srcs[members[k][(size_t)(j0 + j)]];
+                    uint8_t *d = in.as<uint8_t>() + j * sstride;
+                    if (im.step_bytes == sstep) OMR_HIP(hipMemcpyAsync(d, im.data, (size_t)sstep * rows, hipMemcpyHostToDevice, st.s));
+                    else
+                        OMR_HIP(hipMemcpy2DAsync(d, (size_t)sstep, im.data, (size_t)im.step_bytes, (size_t)sstep, (size_t)rows,
+                                                 hipMemcpyHostToDevice, st.s));
+                }
+                if (m.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(out.p, 0, (size_t)dstride * cnt, st.s));
+                const std::vector<WarpImg> per(plans[k].begin() + j0, plans[k].begin() + j0 + cnt);
+                if ((rc = rotate_batch_launch(in.as<uint8_t>(), sstride, sstep, rows, cols, cn, per, slots[k].first, slots[k].second, m,
+                                              border_value, out.as<uint8_t>(), dstride, dstep, st.s)))
+                    return rc;
+                // a slot comes down through the pinned staging block (staged_d2h), then its canvas rows are packed
+                std::vector<uint8_t> slot;
+                for (int j = 0; j < cnt; j++) {
+                    omr_image_owned *o = &dsts[members[k][(size_t)(j0 + j)]];
+                    o->rows = per[(size_t)j].rows, o->cols = per[(size_t)j].cols, o->channels = cn;
+                    o->step_bytes = (int64_t)o->cols * cn;
+                    o->data = (uint8_t *)malloc((size_t)o->rows * o->step_bytes);
+                    if (!o->data) return fail(OMR_ERR_NOMEM, "out of host memory");
+                    if (o->step_bytes == dstep) {
+                        if ((rc = staged_d2h(o->data, out.as<uint8_t>() + j * dstride, (size_t)dstep * o->rows, st.s))) return rc;
+                        continue;
+                    }
+                    try {
+                        slot.resize((size_t)dstride);
+                    } catch (const std::bad_alloc &) {
+                        return fail(OMR_ERR_NOMEM, "out of host memory");
+                    }
+                    if ((rc = staged_d2h(slot.data(), out.as<uint8_t>() + j * dstride, (size_t)dstep * o->rows, st.s))) return rc;
+                    for (int y = 0; y < o->rows; y++) memcpy(o->data + y * o->step_bytes, slot.data() + y * dstep, (size_t)o->step_bytes);
+                }
+            }
+        }
+        return OMR_OK;
+    };
+    rc = run();
+    if (rc)
+        for (int i = 0; i < n; i++) omr_image_free(&dsts[i]);
+    return rc;
 }
 
 // transfer.rs:206-277 erode / dilate, host memory to host memory (the device forms are in oics_morph.cpp)

@@ -1,5 +1,6 @@
 // warp_affine.hip -- warpAffine of rotate_mat (transfer.rs:459-523) and of the final deskew of a single sheet
-// (omr.rs:408-445, core/src/main.rs:72-81): one launcher, two kernels.  OpenCV 4.6.0 imgwarp.cpp: WarpAffineInvoker's
+// (omr.rs:408-445, core/src/main.rs:72-81), for one image or for a batch of same-shape images with a matrix and a
+// canvas each (image index = blockIdx.z): one dispatch rule, two kernels.  OpenCV 4.6.0 imgwarp.cpp: WarpAffineInvoker's
 // fixed-point coordinates (AB_BITS = 10, round delta 512 for NEAREST and 16 otherwise, saturate_cast<short>), then
 // remapNearest / remapBilinear / remapBicubic / remapLanczos4 with FixedPtCast<int, uchar, 15> (warp_fixed.hpp).
 //
@@ -23,17 +24,34 @@ namespace omr {
 #define WL_TH 16
 #define WL_LDS 16384
 
+// One image per call (B.per == NULL: the matrix and the canvas are the kernel's arguments) or a batch of same-shape
+// images with a matrix and a canvas each: image blockIdx.z reads its record, moves src / dst to its own image and
+// slot, and leaves at once when the tile lies outside its canvas (the grid covers the largest one).  Everything here
+// is uniform over the workgroup; from here on both cases run the same code.
+#define WARP_PICK_IMAGE(tx0_, ty0_)                                                  \
+    if (B.per) {                                                                     \
+        const WarpImg &I = B.per[blockIdx.z];                                        \
+        for (int i = 0; i < 6; i++) M[i] = I.minv[i];                                \
+        drows = I.rows, dcols = I.cols;                                              \
+        if ((tx0_) >= dcols || (ty0_) >= drows) return;                              \
+        src += (int64_t)blockIdx.z * B.sstride, dst += (int64_t)blockIdx.z * B.dstride; \
+    } else {                                                                         \
+        for (int i = 0; i < 6; i++) M[i] = W.m[i];                                   \
+    }
+
 // The box has one pixel of slack for the rounding of the fixed-point tables and one more for the bilinear taps; pixels
 // outside the image are staged as the border value.
 template <int CN, bool LINEAR>
 __global__ __launch_bounds__(256) void warp_lds_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
                                                        int scols, uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                       int dcols, const WarpM W, uint32_t border_rgba)
+                                                       int dcols, const WarpM W, uint32_t border_rgba,
+                                                       const WarpBatch B)
 {
     __shared__ __attribute__((aligned(16))) uint8_t box[WL_LDS];
-    const double *M = W.m;
     const int rd = LINEAR ? 16 : 512;
     const int tx0 = blockIdx.x * WL_TW, ty0 = blockIdx.y * WL_TH;
+    double M[6];
+    WARP_PICK_IMAGE(tx0, ty0);
     const int tx1 = min(dcols, tx0 + WL_TW) - 1, ty1 = min(drows, ty0 + WL_TH) - 1;
     // fixed-point source coordinates (OpenCV's tables) of the tile's corner samples: wave-uniform.  X0(y) and
     // adelta(x) are both monotone, so the four corners bound every sample of the tile.  (The two kernels write the box
@@ -149,13 +167,14 @@ template <int CN, int K, int BORDER>
 __global__ __launch_bounds__(256) void warp_taps_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
                                                         int scols, uint8_t *__restrict__ dst, int64_t dstep, int drows,
                                                         int dcols, const WarpM W, uint32_t border_rgba,
-                                                        const int16_t *__restrict__ wtab)
+                                                        const int16_t *__restrict__ wtab, const WarpBatch B)
 {
     constexpr int O = K == 1 ? 0 : K / 2 - 1;  // first tap = sx - O
     __shared__ __attribute__((aligned(16))) uint8_t box[WT_LDS];
-    const double *M = W.m;
     const int rd = K == 1 ? 512 : 16;
     const int tx0 = blockIdx.x * WT_TW, ty0 = blockIdx.y * WT_TH;
+    double M[6];
+    WARP_PICK_IMAGE(tx0, ty0);
     const int tx1 = min(dcols, tx0 + WT_TW) - 1, ty1 = min(drows, ty0 + WT_TH) - 1;
     // the corner samples, as in warp_lds_kernel; saturate_cast<short>(X >> 5 >> 5) == sat16(Xf >> 10) for every K
     auto FX = [&](int x, int y) { return warp_row_x(M, y, rd) + warp_col_x(M, x); };
@@ -306,11 +325,11 @@ __global__ __launch_bounds__(256) void warp_taps_kernel(const uint8_t *__restric
 template <int CN, int K>
 static void launch_taps_border(dim3 grid, hipStream_t s, int border_mode, const uint8_t *d_src, int64_t sstep,
                                int srows, int scols, uint8_t *d_dst, int64_t dstep, int drows, int dcols,
-                               const WarpM &W, uint32_t border_rgba, const int16_t *d_wtab)
+                               const WarpM &W, uint32_t border_rgba, const int16_t *d_wtab, const WarpBatch &B)
 {
 #define WT_LAUNCH(B_)                                                                                                  \
     hipLaunchKernelGGL((warp_taps_kernel<CN, K, B_>), grid, dim3(256), 0, s, d_src, sstep, srows, scols, d_dst, dstep, \
-                       drows, dcols, W, border_rgba, d_wtab)
+                       drows, dcols, W, border_rgba, d_wtab, B)
     switch (border_mode) {
     case 0: WT_LAUNCH(0); break;
     case 1: WT_LAUNCH(1); break;
@@ -325,40 +344,59 @@ static void launch_taps_border(dim3 grid, hipStream_t s, int border_mode, const 
 template <int CN>
 static void launch_taps_k(int K, dim3 grid, hipStream_t s, int border_mode, const uint8_t *d_src, int64_t sstep,
                           int srows, int scols, uint8_t *d_dst, int64_t dstep, int drows, int dcols, const WarpM &W,
-                          uint32_t border_rgba, const int16_t *d_wtab)
+                          uint32_t border_rgba, const int16_t *d_wtab, const WarpBatch &B)
 {
-    if (K == 1) launch_taps_border<CN, 1>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    else if (K == 2) launch_taps_border<CN, 2>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    else if (K == 4) launch_taps_border<CN, 4>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    else launch_taps_border<CN, 8>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
+    if (K == 1) launch_taps_border<CN, 1>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    else if (K == 2) launch_taps_border<CN, 2>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    else if (K == 4) launch_taps_border<CN, 4>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    else launch_taps_border<CN, 8>(grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+}
+
+// the one dispatch rule: channels, interpolation and border mode.  The grid covers drows x dcols: the canvas of the one
+// image, or the largest canvas of a batch (grid.z images, their records at B.per)
+static hipError_t launch_warp(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
+                              int64_t dstep, int drows, int dcols, const WarpM &W, const WarpBatch &B, int nz, int interp,
+                              int border_mode, uint32_t border_rgba, const int16_t *d_wtab, hipStream_t s)
+{
+    if (cn < 1 || cn > 4 || border_mode < 0 || border_mode > 5 || nz < 1 || nz > 65535) return hipErrorInvalidValue;
+    const int K = interp == 0 ? 1 : interp == 1 ? 2 : interp == 2 ? 4 : interp == 4 ? 8 : 0;
+    if (!K || (K >= 4 && !d_wtab)) return hipErrorInvalidValue;
+    static_assert(WL_TW == WT_TW && WL_TH == WT_TH, "one grid for both kernels");
+    dim3 grid((dcols + WT_TW - 1) / WT_TW, (drows + WT_TH - 1) / WT_TH, nz);
+    if ((cn == 1 || cn == 3) && K <= 2 && border_mode == 0) {
+#define WL_LAUNCH(CN_, LIN_)                                                                                           \
+    hipLaunchKernelGGL((warp_lds_kernel<CN_, LIN_>), grid, dim3(256), 0, s, d_src, sstep, srows, scols, d_dst, dstep, \
+                       drows, dcols, W, border_rgba, B)
+        if (cn == 1 && K == 1) WL_LAUNCH(1, false);
+        else if (cn == 1) WL_LAUNCH(1, true);
+        else if (K == 1) WL_LAUNCH(3, false);
+        else WL_LAUNCH(3, true);
+#undef WL_LAUNCH
+    } else if (cn == 1) launch_taps_k<1>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    else if (cn == 2) launch_taps_k<2>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    else if (cn == 3) launch_taps_k<3>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    else launch_taps_k<4>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab, B);
+    return hipGetLastError();
 }
 
 hipError_t launch_warp_affine(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
                               int64_t dstep, int drows, int dcols, const double Minv[6], int interp, int border_mode,
                               uint32_t border_rgba, const int16_t *d_wtab, hipStream_t s)
 {
-    if (cn < 1 || cn > 4 || border_mode < 0 || border_mode > 5) return hipErrorInvalidValue;
-    const int K = interp == 0 ? 1 : interp == 1 ? 2 : interp == 2 ? 4 : interp == 4 ? 8 : 0;
-    if (!K || (K >= 4 && !d_wtab)) return hipErrorInvalidValue;
     WarpM W;
     for (int i = 0; i < 6; i++) W.m[i] = Minv[i];
-    static_assert(WL_TW == WT_TW && WL_TH == WT_TH, "one grid for both kernels");
-    dim3 grid((dcols + WT_TW - 1) / WT_TW, (drows + WT_TH - 1) / WT_TH);
-    // the one dispatch rule: channels, interpolation and border mode
-    if ((cn == 1 || cn == 3) && K <= 2 && border_mode == 0) {
-#define WL_LAUNCH(CN_, LIN_)                                                                                           \
-    hipLaunchKernelGGL((warp_lds_kernel<CN_, LIN_>), grid, dim3(256), 0, s, d_src, sstep, srows, scols, d_dst, dstep, \
-                       drows, dcols, W, border_rgba)
-        if (cn == 1 && K == 1) WL_LAUNCH(1, false);
-        else if (cn == 1) WL_LAUNCH(1, true);
-        else if (K == 1) WL_LAUNCH(3, false);
-        else WL_LAUNCH(3, true);
-#undef WL_LAUNCH
-    } else if (cn == 1) launch_taps_k<1>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    else if (cn == 2) launch_taps_k<2>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    else if (cn == 3) launch_taps_k<3>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    else launch_taps_k<4>(K, grid, s, border_mode, d_src, sstep, srows, scols, d_dst, dstep, drows, dcols, W, border_rgba, d_wtab);
-    return hipGetLastError();
+    return launch_warp(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, W, WarpBatch{nullptr, 0, 0}, 1, interp,
+                       border_mode, border_rgba, d_wtab, s);
+}
+
+hipError_t launch_warp_affine_batch(const uint8_t *d_src, int64_t sstride, int64_t sstep, int srows, int scols, int cn,
+                                    uint8_t *d_dst, int64_t dstride, int64_t dstep, int max_drows, int max_dcols,
+                                    const WarpImg *d_per, int n, int interp, int border_mode, uint32_t border_rgba,
+                                    const int16_t *d_wtab, hipStream_t s)
+{
+    if (!d_per) return hipErrorInvalidValue;
+    return launch_warp(d_src, sstep, srows, scols, cn, d_dst, dstep, max_drows, max_dcols, WarpM{}, WarpBatch{d_per, sstride, dstride},
+                       n, interp, border_mode, border_rgba, d_wtab, s);
 }
 
 }  // namespace omr

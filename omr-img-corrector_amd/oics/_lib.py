@@ -128,6 +128,12 @@ SYMBOLS = {
     "omr_rotate_device_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                        C.c_int32, C.c_int32, u8p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                        C.c_void_p]),
+    "omr_rotate_batch_canvas": (C.c_int, [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, i32p, i32p, i32p]),
+    "omr_rotate_batch_device_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                             f64p, C.c_double, C.c_int32, C.c_int32, u8p, C.c_int32, C.c_void_p, C.c_int64,
+                                             C.c_int64, C.c_int32, C.c_int32, i32p, C.c_void_p]),
+    "omr_rotate_batch_ex": (C.c_int, [C.POINTER(OmrImage), C.c_int32, f64p, C.c_double, C.c_int32, C.c_int32, u8p,
+                                      C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_warp_coeff_table": (C.c_int, [C.c_int32, C.POINTER(C.c_int16), C.c_int32, i32p]),
     "omr_structuring_element": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, u8p]),
     "omr_morph": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

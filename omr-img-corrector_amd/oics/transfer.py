@@ -171,3 +171,54 @@ def rotate_mat(src, angle, scale, flags, border_mode=0, border_value=(255.0, 255
     finally:
         lib().omr_image_free(C.byref(out))
     return TransformableMatrix(arr)
+
+
+def _angles(angles):
+    a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+    return a, (a.ctypes.data_as(f64p) if a.size else None)
+
+
+def rotate_batch_canvas(rows, cols, angles, clip_strategy=RotateClipStrategy.DEFAULT):
+    """omr_rotate_batch_canvas (host only): -> (max_rows, max_cols, sizes), sizes[i] = (rows, cols) of the canvas
+    rotate_mat gives a rows x cols image at angles[i]; every canvas fits a max_rows x max_cols slot."""
+    a, ap = _angles(angles)
+    mr, mc = C.c_int32(), C.c_int32()
+    sizes = np.zeros((a.size, 2), np.int32)
+    check(lib().omr_rotate_batch_canvas(int(rows), int(cols), ap, a.size, int(clip_strategy), C.byref(mr), C.byref(mc),
+                                        sizes.ctypes.data_as(_lib.i32p) if a.size else None))
+    return mr.value, mc.value, sizes
+
+
+def rotate_batch_device_ex(d_src, n, src_stride_bytes, src_step, rows, cols, channels, angles, scale, flags, border_mode,
+                           border_value, clip_strategy, d_dst, dst_stride_bytes, dst_step, slot_rows, slot_cols, stream=None):
+    """omr_rotate_batch_device_ex: n same-shape device-resident images (d_src, d_dst: device addresses as ints), image i
+    rotated by angles[i] into the top left of its slot; -> sizes[n, 2], the canvases' (rows, cols).  Image i's canvas is
+    byte for byte omr_rotate_device_ex's.  Synchronises `stream` before returning when n > 3."""
+    a, ap = _angles(angles)
+    if a.size != int(n):
+        raise ValueError("%d angles for %d images" % (a.size, int(n)))
+    b = np.array([int(v) for v in border_value], np.uint8)
+    sizes = np.zeros((a.size, 2), np.int32)
+    check(lib().omr_rotate_batch_device_ex(C.c_void_p(int(d_src)), int(n), int(src_stride_bytes), int(src_step), int(rows),
+                                           int(cols), int(channels), ap, float(scale), int(flags), int(border_mode),
+                                           b.ctypes.data_as(u8p), int(clip_strategy), C.c_void_p(int(d_dst)),
+                                           int(dst_stride_bytes), int(dst_step), int(slot_rows), int(slot_cols),
+                                           sizes.ctypes.data_as(_lib.i32p) if a.size else None,
+                                           C.c_void_p(int(stream)) if stream else None))
+    return sizes
+
+
+def rotate_batch_ex(srcs, angles, scale, flags, border_mode=0, border_value=(255.0, 255.0, 255.0, 0.0),
+                    clip_strategy=RotateClipStrategy.DEFAULT):
+    """omr_rotate_batch_ex: rotate_mat of every image of `srcs` (any mix of shapes and channel counts) by its own angle
+    in one call -> a list of TransformableMatrix at the inputs' positions, each what rotate_mat gives."""
+    views = [as_image(_mat(s)) for s in srcs]
+    a, ap = _angles(angles)
+    if a.size != len(views):
+        raise ValueError("%d angles for %d images" % (a.size, len(views)))
+    ims = (OmrImage * max(len(views), 1))(*[v[1] for v in views])
+    outs = (OmrImageOwned * max(len(views), 1))()
+    b = np.array([int(v) for v in border_value], np.uint8)
+    check(lib().omr_rotate_batch_ex(ims, len(views), ap, float(scale), int(flags), int(border_mode), b.ctypes.data_as(u8p),
+                                    int(clip_strategy), outs))
+    return [TransformableMatrix(_take_owned(outs[i])) for i in range(len(views))]

@@ -196,6 +196,35 @@ pub fn rotate_mat(
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
+/// `rotate_mat` for a slice of images with an angle each -> omr_rotate_batch_ex: one call for the whole slice (images of
+/// one shape share an upload of their matrices and a launch), the results in the order of `srcs`, each what
+/// `rotate_mat(&srcs[i], angles[i], ..)` returns.  Scale, flags, border and clip strategy are the batch's.
+pub fn rotate_mats(
+    srcs: &[TransformableMatrix],
+    angles: &[f64],
+    scale: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+) -> Result<Vec<TransformableMatrix>, opencv::Error> {
+    if srcs.len() != angles.len() {
+        return Err(opencv::Error::new(ffi::OMR_ERR_BADARG, String::from("rotate_mats: one angle per image")));
+    }
+    let border = border_bytes(border_value);
+    let mut views = Vec::with_capacity(srcs.len());
+    for s in srcs {
+        views.push(view(&s.matrix)?);
+    }
+    let mut outs: Vec<ffi::OmrImageOwned> = (0..srcs.len()).map(|_| ffi::OmrImageOwned::empty()).collect();
+    check(unsafe {
+        ffi::omr_rotate_batch_ex(views.as_ptr(), srcs.len() as i32, angles.as_ptr(), scale, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), outs.as_mut_ptr())
+    })?;
+    // every image is taken over before the first error is reported, so none of the library's buffers is lost
+    let mats: Vec<opencv::Result<Mat>> = outs.into_iter().map(into_mat).collect();
+    mats.into_iter().map(|m| Ok(TransformableMatrix { matrix: m? })).collect()
+}
+
 /// transfer.rs:527-536 -> (std-dev of the vertical projection, std-dev of the horizontal projection).
 pub fn get_projection_standard_deviations(src: &TransformableMatrix) -> Result<(f64, f64), opencv::Error> {
     let (mut v_sd, mut h_sd) = (0.0f64, 0.0f64);
