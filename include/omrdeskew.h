@@ -601,6 +601,67 @@ int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t project
                               double hough_max_line_gap, double *rotate_angle, int32_t *need_check,
                               int32_t *scan_rc, omr_image_owned *rotated);
 
+/* ---- get_angle_with_projections with its resize_scale for batches of scans ---------------
+ * A context for repeated batches of one shape (rows x cols x channels) and one parameter set of
+ * omr_get_angle_with_projections.  The reference's order (projection.rs:24-32): scale_self(resize_scale) on the COLOUR
+ * scan (transfer.rs:66-91: size truncated with `as i32`, INTER_AREA when the scale is <= 1, INTER_LINEAR above), then
+ * RGB2GRAY, threshold(127), the sweep.  Here the whole batch is resized in one launch into a working buffer the
+ * context owns (max_scans x wrows x wcols x channels); gray and threshold stay fused in the sweep's loads, so no
+ * full-size intermediate is written and every scan byte is read from memory once.  For every scan that
+ * omr_get_angle_with_projections accepts, the batch gives its angle as the same f64 bits.
+ * channels: 3 (BGR, as imread(IMREAD_COLOR) gives it) or 1 (the gray convenience the per-call function also accepts);
+ * 4 is OMR_ERR_NOTIMPL, 2 is OMR_ERR_ASSERT as per call.  max_scans = the largest n a run may carry (1..65535).
+ * A working size that truncates to 0 on an axis is OMR_ERR_ASSERT, as per call; an empty candidate range, a
+ * resize_scale that is <= 0 or not finite: OMR_ERR_BADARG.  The resize tap tables of a fractional shrink are built
+ * when the context is created and stay on the device: a run uploads no table and allocates nothing (the first run
+ * that asks for scores sizes their device buffer). */
+typedef struct omr_projection_batch omr_projection_batch;
+/* How a context's front end (scale_self on the colour scans) runs; the dispatch is resize()'s in OpenCV 4.6.0: */
+#define OMR_PROJECTION_FRONT_NONE 0         /* resize_scale == 1.0 (or the size does not change): the scans are swept as they are */
+#define OMR_PROJECTION_FRONT_AREA_INT 1     /* both shrink factors are integers: resizeAreaFast_ */
+#define OMR_PROJECTION_FRONT_AREA_GENERAL 2 /* any other shrink: resizeArea_ (tap tables) */
+#define OMR_PROJECTION_FRONT_LINEAR 3       /* resize_scale > 1: the bilinear kernel */
+/* scale_self's size for rows x cols and the mode above.  A pure function: no device needed. */
+int omr_projection_batch_working_size(int32_t rows, int32_t cols, double resize_scale, int32_t *wrows, int32_t *wcols,
+                                      int32_t *front_mode);
+int omr_projection_batch_create(int32_t rows, int32_t cols, int32_t channels, uint16_t max_angle, double step,
+                                double resize_scale, int32_t device, int32_t max_scans, omr_projection_batch **out);
+void omr_projection_batch_destroy(omr_projection_batch *pb);
+/* For tests and inspection: the working size, the front-end mode (OMR_PROJECTION_FRONT_*) and the number of
+ * candidates A.  Pointers may be NULL. */
+int omr_projection_batch_info(omr_projection_batch *pb, int32_t *wrows, int32_t *wcols, int32_t *front_mode,
+                              int32_t *candidates);
+/* For tests and inspection: the front end of omr_projection_batch_run_device alone (same dispatch, kernels and
+ * stream) on n scans laid out as there; scan i's working image (channels interleaved, before gray and threshold)
+ * lands in the top-left of d_small + i * small_stride_bytes, rows small_step_bytes apart: byte for byte what omr_scale
+ * returns for the scan.  Arguments are checked as omr_projection_batch_run_device does, and small_step_bytes >=
+ * wcols x channels, small_stride_bytes >= wrows x small_step_bytes.  Synchronous.  Runs do not depend on it. */
+int omr_projection_batch_front_device(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                                      int64_t step_bytes, int32_t n, uint8_t *d_small, int64_t small_stride_bytes,
+                                      int64_t small_step_bytes);
+/* n device-resident scans (scan i at d_scans + i * scan_stride_bytes, rows step_bytes apart; any stride >= 0) -> host
+ * arrays: angle[i] = (best_idx[i] - N) * step (projection.rs:189-190), best_idx (n, may be NULL), v_sd / h_sd (n x A
+ * scores, may be NULL).  OMR_ERR_BADARG: a null context, scan or angle pointer, n <= 0 or n > max_scans, step_bytes <
+ * channels x cols, a negative stride; every argument is checked before any device work.  Synchronous.
+ * Performance note: the resize kernel stages its source rows with dword loads, which needs d_scans, scan_stride_bytes
+ * and step_bytes to be multiples of 4; otherwise (e.g. a 453-column colour scan, tightly packed) it stages them byte
+ * by byte -- same result, slower. */
+int omr_projection_batch_run_device(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                                    int64_t step_bytes, int32_t n, double *angle, int32_t *best_idx, double *v_sd,
+                                    double *h_sd);
+/* Host images of any mix of shapes, bucketed by (rows, cols, channels) as omr_correct_default_batch does, on the
+ * current device; angles[i] (and best_idx[i], which may be NULL) belong to srcs[i].  Every image is checked as
+ * omr_get_angle_with_projections checks it before any device work, and an invalid one fails the whole call: nothing is
+ * written to the outputs.  Runs of up to 256 scans per shape go through a context the library keeps for later calls
+ * with the same device, shape and parameters (the last 4 are kept); uploads run on up to 16 host threads.  A bucket a
+ * batch context does not take -- 4 channels, a sweep it cannot plan -- goes through omr_get_angle_with_projections
+ * image by image, so every image that function accepts is accepted here, with the same answer.
+ * Whether this form beats omr_get_angle_with_projections from 16 host threads has NOT been measured yet
+ * (profiles/r08_projection_batch.md): like omr_correct_default_batch it pays for uploading every full-size scan, so
+ * expect the device-resident omr_projection_batch_run_device to be the fast path. */
+int omr_get_angles_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t max_angle, double step,
+                                          double resize_scale, double *angles, int32_t *best_idx);
+
 /* ---- FFT deskew path ------------------------------------------------------
  * The 2-D DFT is float32 like the reference's (dft on CV_32F); it is a different factorisation than
  * OpenCV's (radix-2 Stockham / Bluestein chirp-z in LDS), so the 8-bit spectrum pictures agree with

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "resize_linear.hpp"
 #include "warp_fixed.hpp"
 
 namespace omr {
@@ -453,34 +454,6 @@ hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int c
 // saturate_cast<short>(c * 2048) with round-half-even; the file is built -ffp-contract=off): 11-bit
 // horizontal taps on the two source rows, then (((b0*(h0>>4))>>16) + ((b1*(h1>>4))>>16) + 2) >> 2.
 // sx is monotone in dx, so "dx >= xmax" (the columns that copy S[sx] * 2048) is just sx + 1 >= scols.
-__device__ __forceinline__ void linear_coef(int d, double scale, double inv_scale, int ssize, bool area_mode, int &s0,
-                                            int &c0, int &c1, bool &edge)
-{
-    float f;
-    int sx;
-    if (!area_mode) {
-        f = (float)(((double)d + 0.5) * scale - 0.5);
-        sx = (int)floorf(f);
-        f -= (float)sx;
-    } else {
-        sx = (int)floor((double)d * scale);
-        f = (float)((double)(d + 1) - (double)(sx + 1) * inv_scale);
-        f = f <= 0.f ? 0.f : f - floorf(f);
-    }
-    s0 = sx;
-    edge = false;
-    if (ssize > 0) {  // horizontal axis only: the vertical axis keeps sy and clips the ROWS instead
-        if (sx < 0) f = 0.f, sx = 0;
-        if (sx + 1 >= ssize) {
-            edge = true;
-            if (sx >= ssize - 1) f = 0.f, sx = ssize - 1;
-        }
-        s0 = sx;
-    }
-    c0 = max(-32768, min(32767, (int)rintf((1.f - f) * 2048.f)));
-    c1 = max(-32768, min(32767, (int)rintf(f * 2048.f)));
-}
-
 __global__ __launch_bounds__(256) void resize_linear_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
                                                             int scols, int cn, uint8_t *__restrict__ dst, int64_t dstep,
                                                             int drows, int dcols, double scale_x, double inv_scale_x,

@@ -23,6 +23,9 @@ OMR_BORDER_REFLECT_101, OMR_BORDER_TRANSPARENT = 4, 5
 # structuring element shapes and operations of omr_structuring_element / omr_morph* (include/omrdeskew.h)
 OMR_MORPH_RECT, OMR_MORPH_CROSS, OMR_MORPH_ELLIPSE = 0, 1, 2
 OMR_MORPH_ERODE, OMR_MORPH_DILATE = 0, 1
+# front-end modes of omr_projection_batch_* (include/omrdeskew.h)
+OMR_PROJECTION_FRONT_NONE, OMR_PROJECTION_FRONT_AREA_INT = 0, 1
+OMR_PROJECTION_FRONT_AREA_GENERAL, OMR_PROJECTION_FRONT_LINEAR = 2, 3
 
 
 class OmrImage(C.Structure):
@@ -166,6 +169,17 @@ SYMBOLS = {
                                                  C.c_int64, C.c_int64]),
     "omr_correct_default_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_int32, C.c_int32,
                                             C.c_double, C.c_double, f64p, i32p, i32p, C.POINTER(OmrImageOwned)]),
+    "omr_projection_batch_working_size": (C.c_int, [C.c_int32, C.c_int32, C.c_double, i32p, i32p, i32p]),
+    "omr_projection_batch_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint16, C.c_double, C.c_double, C.c_int32,
+                                              C.c_int32, C.POINTER(C.c_void_p)]),
+    "omr_projection_batch_destroy": (None, [C.c_void_p]),
+    "omr_projection_batch_info": (C.c_int, [C.c_void_p, i32p, i32p, i32p, i32p]),
+    "omr_projection_batch_front_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                    C.c_int64, C.c_int64]),
+    "omr_projection_batch_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, f64p, i32p, f64p,
+                                                  f64p]),
+    "omr_get_angles_with_projections_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_double,
+                                                        f64p, i32p]),
     "omr_get_fft_image": (C.c_int, [C.POINTER(OmrImage), C.POINTER(OmrImageOwned), C.POINTER(OmrImageOwned)]),
     "omr_fft_image_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                              C.c_void_p, C.c_void_p]),

@@ -16,6 +16,73 @@ def get_angle_with_projections(src_img, max_angle, step, resize_scale, threads):
     return out.value
 
 
+def get_angles_with_projections(srcs, max_angle, step, resize_scale, want_idx=False):
+    """get_angle_with_projections for a batch (omr_get_angles_with_projections_batch): host images of any mix of shapes,
+    angles[i] belongs to srcs[i] and is the per-call function's answer, same f64 bits.  want_idx: (angles, best_idx)."""
+    from ._lib import OmrImage
+    keep, arr = [], (OmrImage * max(len(srcs), 1))()
+    for i, s in enumerate(srcs):
+        a, im = as_image(_mat(s))
+        keep.append(a)
+        arr[i] = im
+    n = len(srcs)
+    ang = np.zeros(max(n, 1), np.float64)
+    idx = np.zeros(max(n, 1), np.int32)
+    check(lib().omr_get_angles_with_projections_batch(arr, n, int(max_angle), float(step), float(resize_scale),
+                                                      ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p) if want_idx else None))
+    return (ang[:n], idx[:n]) if want_idx else ang[:n]
+
+
+def projection_batch_working_size(rows, cols, resize_scale):
+    """(wrows, wcols, front mode): scale_self's size (transfer.rs:66-91) and how the batch front end gets there"""
+    r, c, m = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().omr_projection_batch_working_size(rows, cols, float(resize_scale), C.byref(r), C.byref(c), C.byref(m)))
+    return r.value, c.value, m.value
+
+
+class ProjectionBatch:
+    """omr_projection_batch_*: get_angle_with_projections with its resize_scale for n device-resident scans of one shape."""
+
+    def __init__(self, rows, cols, channels, max_angle, step, resize_scale, max_scans, device=0):
+        self.handle = C.c_void_p()
+        check(lib().omr_projection_batch_create(rows, cols, channels, int(max_angle), float(step), float(resize_scale), device,
+                                                int(max_scans), C.byref(self.handle)))
+        self.rows, self.cols, self.channels = rows, cols, channels
+        self.wrows, self.wcols, self.front_mode, self.A = self.info()
+
+    def info(self):
+        """(working rows, working cols, front mode OMR_PROJECTION_FRONT_*, candidates)"""
+        r, c, m, a = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().omr_projection_batch_info(self.handle, C.byref(r), C.byref(c), C.byref(m), C.byref(a)))
+        return r.value, c.value, m.value, a.value
+
+    def front_device(self, d_scans, scan_stride, step_bytes, n, d_small, small_stride, small_step):
+        """the front end alone: scan i's working image to d_small + i * small_stride (tests, inspection)"""
+        check(lib().omr_projection_batch_front_device(self.handle, d_scans, scan_stride, step_bytes, n, d_small, small_stride,
+                                                      small_step))
+
+    def run_device(self, d_scans, scan_stride, step_bytes, n, want_sd=False):
+        """(angles, best_idx, v_sd, h_sd) of n scans at d_scans + i * scan_stride; the scores only when asked for"""
+        ang, idx = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        vs = np.zeros((n, self.A)) if want_sd else None
+        hs = np.zeros((n, self.A)) if want_sd else None
+        check(lib().omr_projection_batch_run_device(self.handle, d_scans, scan_stride, step_bytes, n, ang.ctypes.data_as(f64p),
+                                                    idx.ctypes.data_as(i32p), vs.ctypes.data_as(f64p) if want_sd else None,
+                                                    hs.ctypes.data_as(f64p) if want_sd else None))
+        return ang, idx, vs, hs
+
+    def close(self):
+        if self.handle:
+            lib().omr_projection_batch_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:  # at interpreter shutdown the module globals may already be gone
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def find_target_angle(max_angle, step, thresh, threads):
     """app/src-tauri/src/test.rs:83-178"""
     a, im = as_image(_mat(thresh))
