@@ -18,13 +18,11 @@
 #include <string.h>
 
 #include <chrono>
-#include <list>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
-#include <tuple>
 #include <vector>
 
 #include "../../include/omrdeskew.h"
@@ -89,7 +87,8 @@ struct omr_correct_batch {
     int DR = 0, DC = 0;  // largest canvas
     omr_batch_ctx *sweep = nullptr;
     hipStream_t s = nullptr, sw = nullptr;  // front end / sweep hand-off / Hough, and the warp
-    DevBuf small, eroded, best, vsd, hsd, gather, xt, xo, yt, yo;
+    DevBuf small, eroded, best, vsd, hsd, gather;
+    AreaTables area;  // FRONT_AREA_GENERAL
     double *h_vsd = nullptr, *h_hsd = nullptr;  // pinned
     WarpSet warp[2];                            // [0] Believed sheets, [1] the rest
     std::mutex mu;
@@ -107,51 +106,26 @@ struct omr_correct_batch {
 
 namespace {
 
-int check_shape(int rows, int cols, int cn)
-{
-    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_ASSERT, "empty image");
-    if (rows >= 32767 || cols >= 32767) return fail(OMR_ERR_ASSERT, "image dimension >= SHRT_MAX");
-    if (cn == 4) return fail(OMR_ERR_NOTIMPL, "4-channel batches are not implemented (1 or 3 channels)");
-    if (cn == 2) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
-    if (cn != 1 && cn != 3) return fail(OMR_ERR_ASSERT, "Canny / HoughLinesP take 1, 3 or 4 channels, got %d", cn);
-    return OMR_OK;
-}
-
-// resize_ptr's dispatch (oics_host.cpp) for INTER_AREA from rows x cols to dr x dc
+// resize()'s dispatch for INTER_AREA from rows x cols to dr x dc, as front-end modes
 void front_mode(omr_correct_batch *cb)
 {
-    const double scale_x = 1. / ((double)cb->dc / cb->cols), scale_y = 1. / ((double)cb->dr / cb->rows);
-    const int iscale_x = (int)lrint(scale_x), iscale_y = (int)lrint(scale_y);
-    const bool fast = fabs(scale_x - iscale_x) < 2.220446049250313e-16 && fabs(scale_y - iscale_y) < 2.220446049250313e-16;
-    if (cb->dr == cb->rows && cb->dc == cb->cols) {  // a copy: resizeAreaFast_ with factor 1 is the identity
-        cb->mode = FRONT_AREA_FUSED, cb->kx = cb->ky = 1;
-    } else if (!(scale_x >= 1 && scale_y >= 1)) {
-        cb->mode = FRONT_LINEAR;
-    } else if (fast) {
-        cb->kx = iscale_x, cb->ky = iscale_y;
+    const ResizeDispatch d = resize_dispatch(cb->rows, cb->cols, cb->dr, cb->dc, OMR_INTER_AREA);
+    switch (d.kind) {
+    case ResizeDispatch::COPY:  // resizeAreaFast_ with factor 1 is the identity
+    case ResizeDispatch::AREA_INT:
+        cb->kx = d.kx, cb->ky = d.ky;
         cb->mode = cb->kx <= 64 && cb->ky <= 64 ? FRONT_AREA_FUSED : FRONT_AREA_INT;
-    } else {
-        cb->mode = FRONT_AREA_GENERAL;
+        break;
+    case ResizeDispatch::LINEAR: cb->mode = FRONT_LINEAR; break;
+    case ResizeDispatch::AREA_GENERAL: cb->mode = FRONT_AREA_GENERAL; break;
     }
 }
 
 int upload_vec(DevBuf *b, const void *p, size_t bytes, hipStream_t s)
 {
-    if (b->bytes < bytes) {
-        NoPoolScope owned;
-        b->release();
-        OMR_HIP(b->alloc(bytes));
-    }
+    int rc = grow(b, bytes);
+    if (rc) return rc;
     OMR_HIP(hipMemcpyAsync(b->p, p, bytes, hipMemcpyHostToDevice, s));
-    return OMR_OK;
-}
-
-int grow(DevBuf *b, size_t bytes)
-{
-    if (b->bytes >= bytes) return OMR_OK;
-    NoPoolScope owned;
-    b->release();
-    OMR_HIP(b->alloc(bytes));
     return OMR_OK;
 }
 
@@ -257,8 +231,8 @@ int front_end(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride
                              cb->cols, 0, 0, s));
         if (cb->mode == FRONT_AREA_GENERAL) {
             OMR_HIP(launch_area_general_batch(er, cb->er_stride, cb->cols, z, sm, cb->small_stride, cb->small_step, cb->dr, cb->dc,
-                                              cb->xt.as<AreaTap>(), cb->xo.as<int32_t>(), cb->yt.as<AreaTap>(), cb->yo.as<int32_t>(),
-                                              s));
+                                              cb->area.xt.as<AreaTap>(), cb->area.xo.as<int32_t>(), cb->area.yt.as<AreaTap>(),
+                                              cb->area.yo.as<int32_t>(), s));
         } else {
             for (int j = 0; j < z; j++) {
                 const uint8_t *e = er + (size_t)j * cb->er_stride;
@@ -418,32 +392,18 @@ struct CtxKey {
                step == o.step && max_w == o.max_w && max_h == o.max_h && hmin == o.hmin && hgap == o.hgap;
     }
 };
-std::mutex g_ctx_mu;
-std::list<std::pair<CtxKey, std::shared_ptr<omr_correct_batch>>> g_ctx;  // most recent first, at most kCachedContexts
-const size_t kCachedContexts = 4;
+ContextCache<CtxKey, omr_correct_batch> g_ctx(4);
 
-// a context of kChunk sheets for this key: from the cache, or made and cached (the app calls with one parameter set)
+// a context of kChunk sheets for this key: from the cache, or made and cached
 int cached_context(const CtxKey &k, std::shared_ptr<omr_correct_batch> *out)
 {
-    {
-        std::lock_guard<std::mutex> lk(g_ctx_mu);
-        for (auto it = g_ctx.begin(); it != g_ctx.end(); ++it)
-            if (it->first == k) {
-                *out = it->second;
-                g_ctx.splice(g_ctx.begin(), g_ctx, it);
-                return OMR_OK;
-            }
-    }
-    omr_correct_batch *raw = nullptr;
-    int rc = omr_correct_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.max_w, k.max_h, k.hmin, k.hgap, k.device, kChunk,
-                                      &raw);
-    if (rc) return rc;
-    std::shared_ptr<omr_correct_batch> sp(raw, omr_correct_batch_destroy);
-    std::lock_guard<std::mutex> lk(g_ctx_mu);
-    g_ctx.emplace_front(k, sp);
-    while (g_ctx.size() > kCachedContexts) g_ctx.pop_back();
-    *out = sp;
-    return OMR_OK;
+    return g_ctx.get(k, [&](std::shared_ptr<omr_correct_batch> *sp) -> int {
+        omr_correct_batch *raw = nullptr;
+        int rc = omr_correct_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.max_w, k.max_h, k.hmin, k.hgap, k.device,
+                                          kChunk, &raw);
+        if (rc == OMR_OK) sp->reset(raw, omr_correct_batch_destroy);
+        return rc;
+    }, out);
 }
 
 // Development aid (make debug, -DOMR_RUNS_DEBUG only; the release library reads no such switch): with
@@ -473,7 +433,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     const int zmax = std::min(m, kChunk);
     const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
     const int64_t out_step = (int64_t)cb->DC * cn, out_stride = out_step * cb->DR;
-    HStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
+    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
     if ((rc = st.create())) return rc;
     DevBuf din, dout;
     OMR_HIP(din.alloc((size_t)zmax * in_stride));
@@ -484,20 +444,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         const int z = std::min(zmax, m - j0);
         double t1 = now_ms();
         // host memory -> device, from several threads
-        rc = on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {
-            for (int j = lo; j < hi; j++) {
-                const omr_image &im = a.srcs[idx[(size_t)(j0 + j)]];
-                uint8_t *d = din.as<uint8_t>() + (size_t)j * in_stride;
-                if (im.step_bytes == row)
-                    OMR_HIP(hipMemcpyAsync(d, im.data, (size_t)row * rows, hipMemcpyHostToDevice, s));
-                else
-                    OMR_HIP(hipMemcpy2DAsync(d, (size_t)row, im.data, (size_t)im.step_bytes, (size_t)row, (size_t)rows,
-                                             hipMemcpyHostToDevice, s));
-            }
-            OMR_HIP(hipStreamSynchronize(s));
-            return OMR_OK;
-        });
-        if (rc) return rc;
+        if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
         double t2 = now_ms();
         t_up += t2 - t1;
         if ((rc = omr_correct_batch_run_device(cb, din.as<uint8_t>(), in_stride, row, z, ang.data(), chk.data(), src.data(),
@@ -565,22 +512,16 @@ int omr_correct_batch_create(int32_t rows, int32_t cols, int32_t channels, uint1
     *out = nullptr;
     if (max_scans < 1 || max_scans > 65535) return fail(OMR_ERR_BADARG, "max_scans must be in 1..65535");
     if (device < 0) return fail(OMR_ERR_BADARG, "negative device");
-    int rc = check_shape(rows, cols, channels);
-    if (rc) return rc;
+    int rc = check_image_shape(rows, cols);
+    if (rc || (rc = cn_correct_batch(channels))) return rc;
     int N = 0;
     const int A = candidate_count(projection_max_angle, projection_angle_step, &N);
     if (A <= 0) return fail(OMR_ERR_BADARG, "empty candidate range");
     // omr.rs:60-82, :114-126
-    const double ws = projection_max_width <= 0 ? 1.0 : (double)projection_max_width / (double)cols;
-    const double hs = projection_max_height <= 0 ? 1.0 : (double)projection_max_height / (double)rows;
-    const double scale = ws < hs ? ws : hs;
+    const double scale = shrink_scale(cols, rows, projection_max_width, projection_max_height);
     const int dc = (int)((double)cols * scale), dr = (int)((double)rows * scale);
     if (dr <= 0 || dc <= 0) return fail(OMR_ERR_ASSERT, "resize to an empty size");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
-    if (device >= ndev) return fail(OMR_ERR_BADARG, "device %d of %d", device, ndev);
-    OMR_HIP(hipSetDevice(device));
+    if ((rc = select_device(device))) return rc;
     NoPoolScope owned;
     std::unique_ptr<omr_correct_batch> cb(new omr_correct_batch);
     cb->device = device, cb->rows = rows, cb->cols = cols, cb->cn = channels, cb->max_scans = max_scans;
@@ -600,20 +541,8 @@ int omr_correct_batch_create(int32_t rows, int32_t cols, int32_t channels, uint1
     OMR_HIP(hipHostMalloc((void **)&cb->h_vsd, sizeof(double) * (size_t)max_scans * A, hipHostMallocDefault));
     OMR_HIP(hipHostMalloc((void **)&cb->h_hsd, sizeof(double) * (size_t)max_scans * A, hipHostMallocDefault));
     if (cb->mode != FRONT_AREA_FUSED) cb->er_stride = ((int64_t)rows * cols + 255) & ~(int64_t)255;  // buffer: front_end
-    if (cb->mode == FRONT_AREA_GENERAL) {  // resizeArea_'s tap tables, once per context
-        std::vector<AreaTap> xt, yt;
-        std::vector<int32_t> xo, yo;
-        area_tab(cols, dc, 1, 1. / ((double)dc / cols), &xt, &xo);
-        area_tab(rows, dr, 1, 1. / ((double)dr / rows), &yt, &yo);
-        OMR_HIP(cb->xt.alloc(sizeof(AreaTap) * xt.size()));
-        OMR_HIP(cb->xo.alloc(sizeof(int32_t) * xo.size()));
-        OMR_HIP(cb->yt.alloc(sizeof(AreaTap) * yt.size()));
-        OMR_HIP(cb->yo.alloc(sizeof(int32_t) * yo.size()));
-        OMR_HIP(hipMemcpy(cb->xt.p, xt.data(), sizeof(AreaTap) * xt.size(), hipMemcpyHostToDevice));
-        OMR_HIP(hipMemcpy(cb->xo.p, xo.data(), sizeof(int32_t) * xo.size(), hipMemcpyHostToDevice));
-        OMR_HIP(hipMemcpy(cb->yt.p, yt.data(), sizeof(AreaTap) * yt.size(), hipMemcpyHostToDevice));
-        OMR_HIP(hipMemcpy(cb->yo.p, yo.data(), sizeof(int32_t) * yo.size(), hipMemcpyHostToDevice));
-    }
+    // resizeArea_'s tap tables, once per context
+    if (cb->mode == FRONT_AREA_GENERAL && (rc = cb->area.build(cols, dc, rows, dr, 1, nullptr))) return rc;
     if ((rc = omr_batch_create(dr, dc, projection_max_angle, projection_angle_step, scale, device, 1, &cb->sweep))) return rc;
     if ((rc = omr_batch_set_group(cb->sweep, std::min(max_scans, 64)))) return rc;
     *out = cb.release();
@@ -687,33 +616,18 @@ int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t project
 {
     clear_error();
     if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    std::vector<std::tuple<int, int, int>> shapes;  // in order of first appearance
-    std::vector<std::vector<int>> members;
-    for (int i = 0; i < n; i++) {
-        const omr_image &im = srcs[i];
-        if (!im.data) return fail(OMR_ERR_BADARG, "null image %d", i);
-        int rc = check_shape(im.rows, im.cols, im.channels);
-        if (rc) return rc;
-        if (im.step_bytes < (int64_t)im.cols * im.channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
-        const std::tuple<int, int, int> sh(im.rows, im.cols, im.channels);
-        size_t k = 0;
-        while (k < shapes.size() && shapes[k] != sh) k++;
-        if (k == shapes.size()) {
-            shapes.push_back(sh);
-            members.emplace_back();
-        }
-        members[k].push_back(i);
-    }
+    ShapeBuckets b;
+    int rc = bucket_by_shape(srcs, n, [](const omr_image &im) { return check_image(&im, cn_correct_batch); }, &b);
+    if (rc) return rc;
     if (rotated)
         for (int i = 0; i < n; i++) rotated[i] = omr_image_owned{nullptr, 0, 0, 0, 0};
-    int rc = have_device();
-    if (rc) return rc;
+    if ((rc = have_device())) return rc;
     int dev = 0;
     OMR_HIP(hipGetDevice(&dev));
     const HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                      hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
-    for (size_t k = 0; k < shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, std::get<0>(shapes[k]), std::get<1>(shapes[k]), std::get<2>(shapes[k]), members[k]);
+    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
+        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
     if (rc && rotated)
         for (int i = 0; i < n; i++) omr_image_free(&rotated[i]);
     return rc;

@@ -194,20 +194,16 @@ void call_slot_stats(int dev, int *live, int *idle, size_t *idle_pinned)
 namespace {
 struct SlotLease {
     CallSlot *c = nullptr;
-    bool mine = false;
+    LeasedStream own;  // used only when the calling thread's lease is not on `s`
     int take(hipStream_t s)
     {
         if (t_slot && t_slot->stream == s) {
             c = t_slot;
             return 0;
         }
-        int rc = lease_call_slot(&c);
-        mine = rc == 0;
+        int rc = own.create();
+        c = own.slot;
         return rc;
-    }
-    ~SlotLease()
-    {
-        if (mine) return_call_slot(c);
     }
 };
 }  // namespace
@@ -250,6 +246,64 @@ int staged_d2h_2d(void *dst, size_t dst_step, const void *d_src, size_t row_byte
         for (size_t r = 0; r < nr; r++) memcpy((char *)dst + (r0 + r) * dst_step, (const char *)L.c->pinned + r * row_bytes, row_bytes);
     }
     return 0;
+}
+
+int LeasedStream::create()
+{
+    int rc = lease_call_slot(&slot);
+    if (rc) return rc;
+    s = slot->stream;
+    pool_.reset(new PoolScope(s));
+    return OMR_OK;
+}
+LeasedStream::~LeasedStream()
+{
+    pool_.reset();
+    return_call_slot(slot);
+}
+
+int have_device(int *count)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
+    if (count) *count = n;
+    return OMR_OK;
+}
+
+int select_device(int device)
+{
+    int ndev = 0;
+    if (int rc = have_device(&ndev)) return rc;
+    if (device >= ndev) return fail(OMR_ERR_BADARG, "device %d of %d", device, ndev);
+    OMR_HIP(hipSetDevice(device));
+    return OMR_OK;
+}
+
+int upload_rows(void *d_dst, size_t dst_step, const void *src, size_t src_step, size_t row_bytes, size_t rows, hipStream_t s)
+{
+    if (src_step == row_bytes && dst_step == row_bytes)
+        OMR_HIP(hipMemcpyAsync(d_dst, src, row_bytes * rows, hipMemcpyHostToDevice, s));
+    else
+        OMR_HIP(hipMemcpy2DAsync(d_dst, dst_step, src, src_step, row_bytes, rows, hipMemcpyHostToDevice, s));
+    return OMR_OK;
+}
+
+int grow(DevBuf *b, size_t bytes)
+{
+    if (b->bytes >= bytes) return OMR_OK;
+    NoPoolScope owned;
+    b->release();
+    OMR_HIP(b->alloc(bytes));
+    return OMR_OK;
+}
+
+int upload_table(DevBuf *b, const void *p, size_t bytes, hipStream_t s)
+{
+    OMR_HIP(b->alloc(bytes));
+    if (s) OMR_HIP(hipMemcpyAsync(b->p, p, bytes, hipMemcpyHostToDevice, s));
+    else OMR_HIP(hipMemcpy(b->p, p, bytes, hipMemcpyHostToDevice));
+    return OMR_OK;
 }
 
 PoolScope::PoolScope(hipStream_t stream) : prev_(t_pool_stream), prev_on_(t_pool_on)
@@ -809,22 +863,16 @@ int omr_sweep_plan_run(omr_sweep_plan *plan, const omr_image *img, int32_t black
     if (img->step_bytes < img->cols) return fail(OMR_ERR_BADARG, "step_bytes < cols");
     std::lock_guard<std::mutex> lk(plan->mu);
     OMR_HIP(hipSetDevice(plan->tables.device));
-    const size_t need = (size_t)d.rows * d.cols;
-    if (plan->img.bytes < need) {
-        NoPoolScope plan_owned;  // the staging buffer stays with the plan
-        OMR_HIP(plan->img.alloc(need));
-    }
+    int rc = grow(&plan->img, (size_t)d.rows * d.cols);  // the staging buffer stays with the plan
+    if (rc) return rc;
     hipStream_t s = plan->stream;
-    if (img->step_bytes == d.cols)  // packed: one linear copy (the 2-D path is row-by-row DMA for odd widths)
-        OMR_HIP(hipMemcpyAsync(plan->img.p, img->data, need, hipMemcpyHostToDevice, s));
-    else
-        OMR_HIP(hipMemcpy2DAsync(plan->img.p, (size_t)d.cols, img->data, (size_t)img->step_bytes, (size_t)d.cols,
-                                 (size_t)d.rows, hipMemcpyHostToDevice, s));
+    if ((rc = upload_rows(plan->img.p, (size_t)d.cols, img->data, (size_t)img->step_bytes, (size_t)d.cols, (size_t)d.rows, s)))
+        return rc;
     plan->timed = plan->timing;
-    int rc = enqueue_sweep(plan->tables, plan->scratch, plan->kernel_sel, plan->img.as<uint8_t>(), d.cols, black_max, s,
-                           nullptr, nullptr, nullptr, nullptr, plan->scratch.best.as<int32_t>(),
-                           plan->timing ? plan->ev0 : nullptr, plan->timing ? plan->ev1 : nullptr,
-                           vproj != nullptr || hproj != nullptr);
+    rc = enqueue_sweep(plan->tables, plan->scratch, plan->kernel_sel, plan->img.as<uint8_t>(), d.cols, black_max, s,
+                       nullptr, nullptr, nullptr, nullptr, plan->scratch.best.as<int32_t>(),
+                       plan->timing ? plan->ev0 : nullptr, plan->timing ? plan->ev1 : nullptr,
+                       vproj != nullptr || hproj != nullptr);
     if (rc) return rc;
     if (vproj)
         OMR_HIP(hipMemcpyAsync(vproj, plan->scratch.vproj.p, sizeof(uint32_t) * (size_t)d.A * d.cols,
@@ -1059,7 +1107,8 @@ int build_deskew_tables(omr_batch_ctx *ctx)
 }
 
 int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, int64_t step_bytes, int32_t n,
-              int32_t black_max, int32_t *d_best_idx, double *d_v_sd, double *d_h_sd, const DeskewOut *dk, int cn)
+              int32_t black_max, int32_t *d_best_idx, double *d_v_sd, double *d_h_sd, const DeskewOut *dk, int cn,
+              bool packed = false)  // packed: 1-bit scans (batch_run_device_bits), scan-lane contexts only
 {
     const int S = (int)ctx->streams.size();
     const int A = ctx->tables.dims.A;
@@ -1090,7 +1139,7 @@ int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, i
         int rc;
         if (lanes)
             rc = slane_enqueue(ctx->slane, *ctx->slane_scratch[set], d_scans + (size_t)i * scan_stride, scan_stride, step_bytes, z,
-                               black_max, ctx->streams[k], ctx->post_streams[k], ctx->ev_mid[set],
+                               black_max, packed, ctx->streams[k], ctx->post_streams[k], ctx->ev_mid[set],
                                d_v_sd ? d_v_sd + (size_t)i * A : nullptr, d_h_sd ? d_h_sd + (size_t)i * A : nullptr, best, e0, e1, cn);
         else
             rc = enqueue_sweep(ctx->tables, *ctx->scratch[set], KERNEL_AUTO, d_scans + (size_t)i * scan_stride,
@@ -1161,7 +1210,7 @@ int omr::batch_run_device_bits(omr_batch_ctx *ctx, const uint32_t *d_bits, int64
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->lanes <= 0) return fail(OMR_ERR_BADARG, "packed scans need a context in scan-lane mode");
     OMR_HIP(hipSetDevice(ctx->tables.device));
-    return batch_run(ctx, (const uint8_t *)d_bits, scan_stride_bytes, 0, n, /*black_max: packed*/ -1, d_best_idx, d_v_sd, d_h_sd, nullptr, 1);
+    return batch_run(ctx, (const uint8_t *)d_bits, scan_stride_bytes, 0, n, 0, d_best_idx, d_v_sd, d_h_sd, nullptr, 1, /*packed*/ true);
 }
 
 extern "C" {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
+#include "host_image.hpp"
 #include "kernels.hpp"
 #include "slane.hpp"
 
@@ -86,6 +87,33 @@ int lease_call_slot(CallSlot **out);  // on the current device; fails for device
 void return_call_slot(CallSlot *c);   // the caller has drained c->stream (or only queued work that owns nothing)
 void call_slot_stats(int dev, int *live, int *idle, size_t *idle_pinned);
 
+// A call's lease as an object: the slot's stream, and a PoolScope on it, so that the call's device buffers come from the
+// block cache and return to it when the call ends.  The one way an entry point (or one of its host threads) gets a stream.
+struct LeasedStream {
+    hipStream_t s = nullptr;
+    CallSlot *slot = nullptr;
+    ~LeasedStream();
+    int create();
+
+  private:
+    std::unique_ptr<PoolScope> pool_;
+};
+
+// "is there a device" of every entry point (no CPU fallback: OMR_ERR_GPU), and the preamble of a *_create: the same,
+// then OMR_ERR_BADARG for a `device` at or above the count, then hipSetDevice
+int have_device(int *count = nullptr);
+int select_device(int device);
+
+// `rows` rows of `row_bytes` from host memory (`src_step` apart) to the device (`dst_step` apart), asynchronous on `s`.
+// Packed rows travel as one linear copy: the 2-D path degrades to row-by-row DMA for widths that are not a multiple of
+// 4 bytes (26 ms instead of 2 ms for a 2677-wide CONTAIN canvas).
+int upload_rows(void *d_dst, size_t dst_step, const void *src, size_t src_step, size_t row_bytes, size_t rows, hipStream_t s);
+// a long-lived owner's buffer made at least `bytes` large (contents lost when it grows; never pooled)
+int grow(DevBuf *b, size_t bytes);
+// a fresh allocation of `bytes` (pooled or not as the calling thread's scope says) filled from host memory: with a
+// synchronous copy when `s` is null, else asynchronously on `s` (the caller keeps `p` alive until `s` has drained)
+int upload_table(DevBuf *b, const void *p, size_t bytes, hipStream_t s = nullptr);
+
 // Device -> pageable host memory through the pinned staging block of the call's slot (the calling thread's
 // innermost lease when it owns `s`, a temporary lease otherwise).  A direct hipMemcpy into a freshly
 // malloc'ed result image makes the runtime pin the destination pages on the fly: 13 ms for the 5 MB rotated sheet
@@ -140,6 +168,14 @@ int morph_device(const uint8_t *d_src, int64_t sstride, int64_t sstep, int n, in
                  hipStream_t s);
 // OpenCV computeResizeAreaTab for resizeArea_, grouped per destination index (CSR offsets ofs[0..dsize]); oics_host.cpp
 void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs);
+// resizeArea_'s four tap tables for scols x srows -> dcols x drows on the device, with the host copies they were made from
+// (projection_front's tiling reads those).  build uploads like upload_table: synchronously when `s` is null.
+struct AreaTables {
+    DevBuf xt, xo, yt, yo;
+    std::vector<AreaTap> h_xt, h_yt;
+    std::vector<int32_t> h_xo, h_yo;
+    int build(int scols, int dcols, int srows, int drows, int cn, hipStream_t s);
+};
 
 // Immutable per-(shape, matrices) state: inverse matrices, fixed-point tables, LDS tiling.
 struct SweepTables {
@@ -228,8 +264,9 @@ struct SlaneScratch {
     DevBuf bits, hrows, vproj, planes, descs[3], vsd, hsd, best, guard;  // descs[lg]: workgroups of (16 >> lg) strips x (1 << lg) scan groups
     int create(const SlanePlan &p, int groups);
 };
+// packed: d_img holds scans already packed to 1 bit per pixel (black_max unused)
 int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int64_t scan_stride, int64_t step, int nscans,
-                  int black_max, hipStream_t stream, hipStream_t post_stream, hipEvent_t ev_mid, double *d_v_sd, double *d_h_sd,
+                  int black_max, bool packed, hipStream_t stream, hipStream_t post_stream, hipEvent_t ev_mid, double *d_v_sd, double *d_h_sd,
                   int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1, int cn = 1);  // cn: as enqueue_sweep
 
 }  // namespace omr

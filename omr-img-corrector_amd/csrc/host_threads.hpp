@@ -1,18 +1,22 @@
-// host_threads.hpp -- the host-thread fan-out of the batch entry points that start in host memory
-// (correct_batch.cpp, projection_batch.cpp).
+// host_threads.hpp -- what the entry points that start in host memory share above the engine: the host-thread fan-out
+// and chunk upload of the batch forms (correct_batch.cpp, projection_batch.cpp) and the keyed cache of shared contexts
+// (those two, and the per-call drivers' sweep plans in oics_host.cpp).
 #pragma once
 #include <algorithm>
+#include <list>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
-#include "hough_host.hpp"
+#include "engine.hpp"
 
 namespace omr {
-namespace hh {
 
-// fn(t, lo, hi) on T host threads over [0, m) in contiguous slices; the first error wins.  Every thread leases its own stream
-// and pinned staging block (HStream), so pageable copies and the page faults of fresh result images run side by side.
+// fn(stream, lo, hi) on T host threads over [0, m) in contiguous slices; the first error wins.  Every thread leases its own
+// stream and pinned staging block (LeasedStream), so pageable copies and the page faults of fresh result images run side by side.
 template <class F>
 int on_threads(int m, F fn)
 {
@@ -27,7 +31,7 @@ int on_threads(int m, F fn)
             if (hipSetDevice(dev) != hipSuccess) {
                 rcs[(size_t)t] = fail(OMR_ERR_GPU, "hipSetDevice failed");
             } else {
-                HStream st;
+                LeasedStream st;
                 int rc = st.create();
                 if (!rc) rc = fn(st.s, (int)((int64_t)m * t / T), (int)((int64_t)m * (t + 1) / T));
                 rcs[(size_t)t] = rc;
@@ -40,5 +44,56 @@ int on_threads(int m, F fn)
     return OMR_OK;
 }
 
-}  // namespace hh
+// Images srcs[idx[j0 .. j0 + z)], each `rows` rows of `row_bytes`, from host memory to slots 0 .. z of d_in (in_stride
+// bytes apart, rows packed), from several threads; complete on return.
+inline int upload_chunk(const omr_image *srcs, const std::vector<int> &idx, int j0, int z, int rows, int64_t row_bytes,
+                        uint8_t *d_in, int64_t in_stride)
+{
+    return on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {
+        for (int j = lo; j < hi; j++) {
+            const omr_image &im = srcs[idx[(size_t)(j0 + j)]];
+            int rc = upload_rows(d_in + (size_t)j * in_stride, (size_t)row_bytes, im.data, (size_t)im.step_bytes, (size_t)row_bytes,
+                                 (size_t)rows, s);
+            if (rc) return rc;
+        }
+        OMR_HIP(hipStreamSynchronize(s));
+        return OMR_OK;
+    });
+}
+
+// Shared contexts by key, most recently used first, at most `capacity` of them: the app calls with one parameter set over
+// and over.  A context that falls out lives on until its last user lets go.
+template <class Key, class Ctx>
+class ContextCache {
+  public:
+    explicit ContextCache(size_t capacity) : capacity_(capacity) {}
+    // the context of `key`: the cached one, or what make(&ctx) creates (outside the lock: it takes device time)
+    template <class Make>
+    int get(const Key &key, Make make, std::shared_ptr<Ctx> *out)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            for (auto it = entries_.begin(); it != entries_.end(); ++it)
+                if (it->first == key) {
+                    *out = it->second;
+                    entries_.splice(entries_.begin(), entries_, it);
+                    return OMR_OK;
+                }
+        }
+        std::shared_ptr<Ctx> sp;
+        int rc = make(&sp);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(mu_);
+        entries_.emplace_front(key, sp);
+        while (entries_.size() > capacity_) entries_.pop_back();
+        *out = sp;
+        return OMR_OK;
+    }
+
+  private:
+    std::mutex mu_;
+    std::list<std::pair<Key, std::shared_ptr<Ctx>>> entries_;
+    const size_t capacity_;
+};
+
 }  // namespace omr

@@ -12,14 +12,6 @@
 namespace omr {
 namespace hh {
 
-struct HStream {
-    hipStream_t s = nullptr;
-    CallSlot *slot = nullptr;         // leased for the call: stream + pinned staging (engine.cpp)
-    std::unique_ptr<PoolScope> pool;  // the call's device buffers come from / return to the block cache
-    ~HStream();
-    int create();
-};
-
 struct HoughParams {
     double low = 50.0, high = 150.0;  // hough.rs:27, omr.rs:239
     double rho = 1.0, theta = 3.14159265358979323846 / 180.0;
@@ -27,8 +19,7 @@ struct HoughParams {
     double min_line_length = 0, max_line_gap = 0;
 };
 
-int have_device();
-int check_img(const omr_image *im);
+// a host image into a fresh packed device buffer
 int upload(const omr_image *im, DevBuf *buf, hipStream_t s);
 // Canny on n device-resident scans of one shape -> d_map holds the edges (0 / 255), packed;
 // d_rowcnt (n x rows) receives the edge pixels per row (what ppht_device starts from)

@@ -423,7 +423,7 @@ struct FftWork {
 
 int check_gray(const omr_image *im)
 {
-    int rc = check_img(im);
+    int rc = check_image(im, cn_canny);
     if (rc) return rc;
     if (im->channels != 1) return fail(OMR_ERR_ASSERT, "the FFT path takes an 8-bit single-channel image");
     return OMR_OK;
@@ -453,7 +453,7 @@ int omr_get_fft_image(const omr_image *gray, omr_image_owned *magnitude_image, o
     if (rc) return rc;
     if (!magnitude_image && !magnitude_log_image) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevBuf in, m8, l8;
     if ((rc = upload(gray, &in, st.s))) return rc;
@@ -508,7 +508,7 @@ int omr_get_angle_with_fft(const omr_image *gray, double canny_threshold_1, doub
     if (rc) return rc;
     if (!angle_out) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     const int rows = gray->rows, cols = gray->cols;
     DevBuf in, m8, l8;
@@ -557,13 +557,13 @@ int omr_get_result_from_fourier_transform(const omr_image *src, double canny_thr
                                           double *candidates, int32_t cand_cap, int32_t *cand_len)
 {
     clear_error();
-    int rc = check_img(src);
+    int rc = check_image(src, cn_canny);
     if (rc) return rc;
     if (src->channels != 3 && src->channels != 4)
         return fail(OMR_ERR_ASSERT, "cvtColor(RGB2GRAY) needs 3 or 4 channels (omr.rs:314)");
     if (!angle) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     const int rows = src->rows, cols = src->cols;
     DevBuf in, gray, m8, l8, edges, flag, rowcnt;

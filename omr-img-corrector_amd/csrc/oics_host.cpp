@@ -11,18 +11,16 @@
 // Every image operation runs on the GPU; the host only sequences launches, builds the 2x3
 // matrices / resize tap tables (a few hundred doubles) and applies the arg-max policy to the A
 // scores.  No CPU fallback exists: without a HIP device every entry point returns -217.
-#include <float.h>
 #include <math.h>
 #include <string.h>
 
-#include <list>
 #include <memory>
 #include <thread>
-#include <tuple>
 #include <vector>
 
 #include "../../include/omrdeskew.h"
 #include "engine.hpp"
+#include "host_threads.hpp"
 
 using namespace omr;
 
@@ -30,21 +28,9 @@ namespace {
 
 int current_device(int *dev)
 {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
+    int rc = have_device();
+    if (rc) return rc;
     OMR_HIP(hipGetDevice(dev));
-    return OMR_OK;
-}
-
-int check_image(const omr_image *im, bool need_c1)
-{
-    if (!im || !im->data) return fail(OMR_ERR_BADARG, "null image");
-    if (im->rows <= 0 || im->cols <= 0) return fail(OMR_ERR_ASSERT, "empty image");
-    if (im->rows >= 32767 || im->cols >= 32767) return fail(OMR_ERR_ASSERT, "image dimension >= SHRT_MAX");
-    if (im->channels < 1 || im->channels > 4) return fail(OMR_ERR_ASSERT, "unsupported channel count %d", im->channels);
-    if (need_c1 && im->channels != 1) return fail(OMR_ERR_ASSERT, "expected a 1-channel image, got %d", im->channels);
-    if (im->step_bytes < (int64_t)im->cols * im->channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
     return OMR_OK;
 }
 
@@ -66,39 +52,13 @@ struct DevImage {
     {
         int rc = alloc(im->rows, im->cols, im->channels);
         if (rc) return rc;
-        // packed rows travel as one linear copy: the 2-D path degrades to row-by-row DMA for widths
-        // that are not a multiple of 4 bytes (26 ms instead of 2 ms for a 2677-wide CONTAIN canvas)
-        if (im->step_bytes == step())
-            OMR_HIP(hipMemcpyAsync(buf.p, im->data, (size_t)step() * rows, hipMemcpyHostToDevice, s));
-        else
-            OMR_HIP(hipMemcpy2DAsync(buf.p, (size_t)step(), im->data, (size_t)im->step_bytes, (size_t)step(),
-                                     (size_t)rows, hipMemcpyHostToDevice, s));
-        return OMR_OK;
+        return upload_rows(buf.p, (size_t)step(), im->data, (size_t)im->step_bytes, (size_t)step(), (size_t)rows, s);
     }
     int download(uint8_t *dst, int64_t dstep, hipStream_t s) const
     {
         // through the calling thread's pinned staging buffer (engine.cpp: a direct copy into pageable memory is
         // an order of magnitude slower for image-sized results)
         return staged_d2h_2d(dst, (size_t)dstep, buf.p, (size_t)step(), (size_t)rows, s);
-    }
-};
-
-struct Stream {
-    hipStream_t s = nullptr;
-    CallSlot *slot = nullptr;         // leased for the call: stream + pinned staging (engine.cpp)
-    std::unique_ptr<PoolScope> pool;  // the call's device buffers come from / return to the block cache
-    ~Stream()
-    {
-        pool.reset();  // drains the stream for the buffers it returns
-        return_call_slot(slot);
-    }
-    int create()
-    {
-        int rc = lease_call_slot(&slot);
-        if (rc) return rc;
-        s = slot->stream;
-        pool.reset(new PoolScope(s));
-        return OMR_OK;
     }
 };
 
@@ -113,29 +73,16 @@ struct PlanKey {
                scale == o.scale;
     }
 };
-std::mutex g_cache_mu;
-std::list<std::pair<PlanKey, std::shared_ptr<omr_sweep_plan>>> g_cache;
+ContextCache<PlanKey, omr_sweep_plan> g_plans(8);
 
 int get_plan(const PlanKey &k, std::shared_ptr<omr_sweep_plan> *out)
 {
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        for (auto it = g_cache.begin(); it != g_cache.end(); ++it)
-            if (it->first == k) {
-                *out = it->second;
-                g_cache.splice(g_cache.begin(), g_cache, it);
-                return OMR_OK;
-            }
-    }
-    omr_sweep_plan *raw = nullptr;
-    int rc = omr_sweep_plan_create_angles(k.rows, k.cols, k.max_angle, k.step, k.scale, k.device, &raw);
-    if (rc) return rc;
-    std::shared_ptr<omr_sweep_plan> sp(raw);
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    g_cache.emplace_front(k, sp);
-    while (g_cache.size() > 8) g_cache.pop_back();
-    *out = sp;
-    return OMR_OK;
+    return g_plans.get(k, [&](std::shared_ptr<omr_sweep_plan> *sp) -> int {
+        omr_sweep_plan *raw = nullptr;
+        int rc = omr_sweep_plan_create_angles(k.rows, k.cols, k.max_angle, k.step, k.scale, k.device, &raw);
+        if (rc == OMR_OK) sp->reset(raw);
+        return rc;
+    }, out);
 }
 
 // Sweep a device-resident 1-channel image and fetch the A scores.
@@ -197,57 +144,50 @@ void omr::area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaT
     (*ofs)[dsize] = (int32_t)tab->size();
 }
 
+int omr::AreaTables::build(int scols, int dcols, int srows, int drows, int cn, hipStream_t s)
+{
+    area_tab(scols, dcols, cn, 1. / ((double)dcols / scols), &h_xt, &h_xo);
+    area_tab(srows, drows, 1, 1. / ((double)drows / srows), &h_yt, &h_yo);
+    int rc = upload_table(&xt, h_xt.data(), sizeof(AreaTap) * h_xt.size(), s);
+    if (!rc) rc = upload_table(&xo, h_xo.data(), sizeof(int32_t) * h_xo.size(), s);
+    if (!rc) rc = upload_table(&yt, h_yt.data(), sizeof(AreaTap) * h_yt.size(), s);
+    if (!rc) rc = upload_table(&yo, h_yo.data(), sizeof(int32_t) * h_yo.size(), s);
+    return rc;
+}
+
 namespace {
 
 // resize(src, dsize, interp) on the device for the two flags the reference passes (transfer.rs:66-91
 // scale_self: INTER_LINEAR when enlarging, INTER_AREA otherwise; transfer.rs:128-145 resize_self and
-// omr.rs:114-126: INTER_AREA whatever the direction).  OpenCV 4.6.0 resize.cpp dispatch:
-//   same size                         -> copy
-//   INTER_AREA, both axes shrink      -> resizeAreaFast_ (integer factors) / resizeArea_ (tap tables)
-//   INTER_AREA, an axis enlarges      -> the bilinear kernel with area-mode coefficients (quirk B7)
-//   INTER_LINEAR                      -> the bilinear kernel (exact 2x shrink is re-routed to INTER_AREA)
+// omr.rs:114-126: INTER_AREA whatever the direction), by OpenCV's dispatch (resize_dispatch, host_image.hpp)
 int resize_ptr(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst, int64_t dstep,
                int drows, int dcols, int interp, hipStream_t s)
 {
     if (drows <= 0 || dcols <= 0) return fail(OMR_ERR_ASSERT, "resize to an empty size");
     if (interp != OMR_INTER_AREA && interp != OMR_INTER_LINEAR)
         return fail(OMR_ERR_NOTIMPL, "resize interpolation flag %d is not implemented", interp);
-    if (drows == srows && dcols == scols) {
+    const ResizeDispatch d = resize_dispatch(srows, scols, drows, dcols, interp);
+    switch (d.kind) {
+    case ResizeDispatch::COPY:
         OMR_HIP(hipMemcpy2DAsync(d_dst, (size_t)dstep, d_src, (size_t)sstep, (size_t)scols * cn, (size_t)srows,
                                  hipMemcpyDeviceToDevice, s));
-        return OMR_OK;
+        break;
+    case ResizeDispatch::LINEAR:
+        OMR_HIP(launch_resize_linear(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, d.area_mode, s));
+        break;
+    case ResizeDispatch::AREA_INT:
+        OMR_HIP(launch_resize_area_int(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, d.kx, d.ky, s));
+        break;
+    case ResizeDispatch::AREA_GENERAL: {
+        AreaTables t;
+        int rc = t.build(scols, dcols, srows, drows, cn, s);
+        if (rc) return rc;
+        OMR_HIP(launch_resize_area_general(d_src, sstep, cn, d_dst, dstep, drows, dcols, t.xt.as<AreaTap>(), t.xo.as<int32_t>(),
+                                           t.yt.as<AreaTap>(), t.yo.as<int32_t>(), s));
+        OMR_HIP(hipStreamSynchronize(s));  // the tap tables are freed on return
+        break;
     }
-    double inv_scale_x = (double)dcols / scols, inv_scale_y = (double)drows / srows;
-    double scale_x = 1. / inv_scale_x, scale_y = 1. / inv_scale_y;
-    int iscale_x = (int)lrint(scale_x), iscale_y = (int)lrint(scale_y);
-    bool is_area_fast = fabs(scale_x - iscale_x) < DBL_EPSILON && fabs(scale_y - iscale_y) < DBL_EPSILON;
-    if (interp == OMR_INTER_LINEAR && is_area_fast && iscale_x == 2 && iscale_y == 2) interp = OMR_INTER_AREA;
-    if (!(interp == OMR_INTER_AREA && scale_x >= 1 && scale_y >= 1)) {
-        OMR_HIP(launch_resize_linear(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols,
-                                     interp == OMR_INTER_AREA, s));
-        return OMR_OK;
     }
-    if (is_area_fast) {
-        OMR_HIP(launch_resize_area_int(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, iscale_x,
-                                       iscale_y, s));
-        return OMR_OK;
-    }
-    std::vector<AreaTap> xt, yt;
-    std::vector<int32_t> xo, yo;
-    area_tab(scols, dcols, cn, scale_x, &xt, &xo);
-    area_tab(srows, drows, 1, scale_y, &yt, &yo);
-    DevBuf dxt, dxo, dyt, dyo;
-    OMR_HIP(dxt.alloc(sizeof(AreaTap) * xt.size()));
-    OMR_HIP(dxo.alloc(sizeof(int32_t) * xo.size()));
-    OMR_HIP(dyt.alloc(sizeof(AreaTap) * yt.size()));
-    OMR_HIP(dyo.alloc(sizeof(int32_t) * yo.size()));
-    OMR_HIP(hipMemcpyAsync(dxt.p, xt.data(), sizeof(AreaTap) * xt.size(), hipMemcpyHostToDevice, s));
-    OMR_HIP(hipMemcpyAsync(dxo.p, xo.data(), sizeof(int32_t) * xo.size(), hipMemcpyHostToDevice, s));
-    OMR_HIP(hipMemcpyAsync(dyt.p, yt.data(), sizeof(AreaTap) * yt.size(), hipMemcpyHostToDevice, s));
-    OMR_HIP(hipMemcpyAsync(dyo.p, yo.data(), sizeof(int32_t) * yo.size(), hipMemcpyHostToDevice, s));
-    OMR_HIP(launch_resize_area_general(d_src, sstep, cn, d_dst, dstep, drows, dcols, dxt.as<AreaTap>(),
-                                       dxo.as<int32_t>(), dyt.as<AreaTap>(), dyo.as<int32_t>(), s));
-    OMR_HIP(hipStreamSynchronize(s));  // the tap tables are freed on return
     return OMR_OK;
 }
 
@@ -437,7 +377,7 @@ int omr_get_angle_with_projections(const omr_image *src, uint16_t max_angle, dou
                                    size_t threads_hint, double *angle_out)
 {
     (void)threads_hint;  // projection.rs:69-122 is buggy (:94) and unused by every caller
-    int rc = check_image(src, false);
+    int rc = check_image(src, cn_any);
     if (rc) return rc;
     if (!angle_out) return fail(OMR_ERR_BADARG, "null angle_out");
     if (src->channels == 2) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
@@ -445,7 +385,7 @@ int omr_get_angle_with_projections(const omr_image *src, uint16_t max_angle, dou
     if (A <= 0) return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
     int dev;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in, scaled, gray;
     if ((rc = in.upload(src, st.s))) return rc;
@@ -468,14 +408,14 @@ int omr_find_target_angle(uint16_t max_angle, double step, const omr_image *thre
                           double *angle_out)
 {
     (void)threads_hint;
-    int rc = check_image(thresh, true);
+    int rc = check_image(thresh, cn_one);
     if (rc) return rc;
     if (!angle_out) return fail(OMR_ERR_BADARG, "null angle_out");
     int N, A = candidate_count(max_angle, step, &N);
     if (A <= 0) return fail(OMR_ERR_BADARG, "empty candidate range");
     int dev;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in;
     if ((rc = in.upload(thresh, st.s))) return rc;
@@ -491,11 +431,11 @@ int omr_get_result_from_projection(const omr_image *src, uint16_t max_angle, dou
                                    int32_t max_h, double *angle, int32_t *status, double *candidates,
                                    int32_t cand_cap, int32_t *cand_len)
 {
-    int rc = check_image(src, false);
+    int rc = check_image(src, cn_any);
     if (rc) return rc;
     if (!angle || !status) return fail(OMR_ERR_BADARG, "null output");
     if (src->channels == 2) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in;
     if ((rc = in.upload(src, st.s))) return rc;
@@ -507,12 +447,12 @@ int omr_get_result_from_projection(const omr_image *src, uint16_t max_angle, dou
 
 int omr_threshold_binary(const omr_image *gray, uint8_t *dst, int64_t dst_step)
 {
-    int rc = check_image(gray, true);
+    int rc = check_image(gray, cn_one);
     if (rc) return rc;
     if (!dst || dst_step < gray->cols) return fail(OMR_ERR_BADARG, "bad destination");
     int dev;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in, out;
     if ((rc = in.upload(gray, st.s))) return rc;
@@ -523,13 +463,13 @@ int omr_threshold_binary(const omr_image *gray, uint8_t *dst, int64_t dst_step)
 
 int omr_rgb_to_gray(const omr_image *src, uint8_t *dst, int64_t dst_step)
 {
-    int rc = check_image(src, false);
+    int rc = check_image(src, cn_any);
     if (rc) return rc;
     if (src->channels != 3 && src->channels != 4) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
     if (!dst || dst_step < src->cols) return fail(OMR_ERR_BADARG, "bad destination");
     int dev;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in, out;
     if ((rc = in.upload(src, st.s))) return rc;
@@ -638,7 +578,7 @@ int omr_rotate_device_ex(const uint8_t *d_src, int64_t src_step, int32_t rows, i
 // omr_rotate and omr_rotate_ex likewise
 static int rotate_host_check(const omr_image *src, const uint8_t *border_value, const omr_image_owned *dst)
 {
-    int rc = check_image(src, false);
+    int rc = check_image(src, cn_any);
     if (rc) return rc;
     if (!dst || !border_value) return fail(OMR_ERR_BADARG, "null output");
     return OMR_OK;
@@ -650,7 +590,7 @@ static int rotate_host(const omr_image *src, double angle_deg, double scale, con
     int drows, dcols, rc, dev;
     if ((rc = rotate_geometry(src->rows, src->cols, angle_deg, scale, clip, M, &drows, &dcols))) return rc;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in;
     if ((rc = in.upload(src, st.s))) return rc;
@@ -685,26 +625,17 @@ int omr_rotate_batch_ex(const omr_image *srcs, int32_t n, const double *angles_d
     if (n <= 0) return fail(OMR_ERR_BADARG, "batch of %d images", n);
     WarpMode m;
     int rc;
-    std::vector<std::tuple<int, int, int>> shapes;  // in order of first appearance
-    std::vector<std::vector<int>> members;
-    for (int i = 0; i < n; i++) {
-        if ((rc = check_image(&srcs[i], false))) return rc;
-        const std::tuple<int, int, int> sh(srcs[i].rows, srcs[i].cols, srcs[i].channels);
-        size_t k = 0;
-        while (k < shapes.size() && shapes[k] != sh) k++;
-        if (k == shapes.size()) {
-            shapes.push_back(sh);
-            members.emplace_back();
-        }
-        members[k].push_back(i);
-    }
+    ShapeBuckets b;
+    if ((rc = bucket_by_shape(srcs, n, [](const omr_image &im) { return check_image(&im, cn_any); }, &b))) return rc;
+    const std::vector<ImageShape> &shapes = b.shapes;
+    const std::vector<std::vector<int>> &members = b.members;
     if ((rc = rotate_ex_args(flags, border_mode, &m))) return rc;
     std::vector<std::vector<WarpImg>> plans(shapes.size());
     std::vector<std::pair<int, int>> slots(shapes.size());
     for (size_t k = 0; k < shapes.size(); k++) {
         std::vector<double> ang;
         for (int i : members[k]) ang.push_back(angles_deg[i]);
-        if ((rc = rotate_batch_plan(std::get<0>(shapes[k]), std::get<1>(shapes[k]), ang.data(), (int)ang.size(), scale, clip,
+        if ((rc = rotate_batch_plan(shapes[k].rows, shapes[k].cols, ang.data(), (int)ang.size(), scale, clip,
                                     m.inverse, &plans[k], &slots[k].first, &slots[k].second)))
             return rc;
     }
@@ -712,11 +643,11 @@ int omr_rotate_batch_ex(const omr_image *srcs, int32_t n, const double *angles_d
     if ((rc = current_device(&dev))) return rc;
     for (int i = 0; i < n; i++) dsts[i] = omr_image_owned{};
     auto run = [&]() -> int {
-        Stream st;
+        LeasedStream st;
         int rc = st.create();
         if (rc) return rc;
         for (size_t k = 0; k < shapes.size(); k++) {
-            const int rows = std::get<0>(shapes[k]), cols = std::get<1>(shapes[k]), cn = std::get<2>(shapes[k]);
+            const int rows = shapes[k].rows, cols = shapes[k].cols, cn = shapes[k].cn;
             const int64_t sstep = (int64_t)cols * cn, sstride = (sstep * rows + 3) & ~(int64_t)3;
             const int64_t dstep = ((int64_t)slots[k].second * cn + 3) & ~(int64_t)3, dstride = dstep * slots[k].first;
             const int total = (int)members[k].size();
@@ -728,11 +659,9 @@ int omr_rotate_batch_ex(const omr_image *srcs, int32_t n, const double *angles_d
                     return fail(OMR_ERR_NOMEM, "out of device memory for %d images of %d x %d", cnt, cols, rows);
                 for (int j = 0; j < cnt; j++) {
                     const omr_image &im = srcs[members[k][(size_t)(j0 + j)]];
-                    uint8_t *d = in.as<uint8_t>() + j * sstride;
-                    if (im.step_bytes == sstep) OMR_HIP(hipMemcpyAsync(d, im.data, (size_t)sstep * rows, hipMemcpyHostToDevice, st.s));
-                    else
-                        OMR_HIP(hipMemcpy2DAsync(d, (size_t)sstep, im.data, (size_t)im.step_bytes, (size_t)sstep, (size_t)rows,
-                                                 hipMemcpyHostToDevice, st.s));
+                    if ((rc = upload_rows(in.as<uint8_t>() + j * sstride, (size_t)sstep, im.data, (size_t)im.step_bytes, (size_t)sstep,
+                                          (size_t)rows, st.s)))
+                        return rc;
                 }
                 if (m.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(out.p, 0, (size_t)dstride * cnt, st.s));
                 const std::vector<WarpImg> per(plans[k].begin() + j0, plans[k].begin() + j0 + cnt);
@@ -773,7 +702,7 @@ int omr_rotate_batch_ex(const omr_image *srcs, int32_t n, const double *angles_d
 int omr_morph(const omr_image *src, int32_t op, int32_t shape, int32_t kw, int32_t kh, int32_t ax, int32_t ay,
               int32_t iterations, omr_image_owned *dst)
 {
-    int rc = check_image(src, false);
+    int rc = check_image(src, cn_any);
     if (rc) return rc;
     if (!dst) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = morph_check_args(src->data, dst, src->step_bytes, src->step_bytes, src->rows, src->cols, src->channels, op,
@@ -781,7 +710,7 @@ int omr_morph(const omr_image *src, int32_t op, int32_t shape, int32_t kw, int32
         return rc;
     int dev;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in, out;
     if ((rc = in.upload(src, st.s))) return rc;
@@ -837,14 +766,14 @@ int omr_resize_area_device(const uint8_t *d_src, int64_t src_step, int32_t src_r
 // ---- transfer.rs:66-145 on host images: scale_self / shrink_to / resize_self ------------------------
 static int resize_host(const omr_image *src, int drows, int dcols, int interp, omr_image_owned *dst)
 {
-    int rc = check_image(src, false);
+    int rc = check_image(src, cn_any);
     if (rc) return rc;
     if (!dst) return fail(OMR_ERR_BADARG, "null output");
     if (drows <= 0 || dcols <= 0) return fail(OMR_ERR_ASSERT, "resize to an empty size (the reference's resize raises)");
     if (drows >= 32767 || dcols >= 32767) return fail(OMR_ERR_ASSERT, "image dimension >= SHRT_MAX");
     int dev;
     if ((rc = current_device(&dev))) return rc;
-    Stream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevImage in, out;
     if ((rc = in.upload(src, st.s))) return rc;
@@ -866,9 +795,7 @@ int omr_shrink_to(const omr_image *src, int32_t max_width, int32_t max_height, o
 {
     if (!src) return fail(OMR_ERR_BADARG, "null image");
     if (src->cols <= 0 || src->rows <= 0) return fail(OMR_ERR_ASSERT, "empty image");
-    const double ws = max_width <= 0 ? 1.0 : (double)max_width / (double)src->cols;   // transfer.rs:105-114
-    const double hs = max_height <= 0 ? 1.0 : (double)max_height / (double)src->rows;
-    const double t = ws < hs ? ws : hs;
+    const double t = shrink_scale(src->cols, src->rows, max_width, max_height);  // transfer.rs:105-114
     return omr_scale(src, t >= 1.0 ? 1.0 : t, dst);  // :121-125: never enlarges
 }
 
@@ -890,7 +817,7 @@ int omr_threshold_binary_device(const uint8_t *d_src, int64_t src_step, int32_t 
 static int identity_projections(const omr_image *bin, std::vector<uint32_t> *vp, std::vector<uint32_t> *hp, double *v_sd,
                                 double *h_sd)
 {
-    int rc = check_image(bin, true);
+    int rc = check_image(bin, cn_one);
     if (rc) return rc;
     const double I[6] = {1, 0, 0, 0, 1, 0};
     vp->assign((size_t)bin->cols, 0);
@@ -978,26 +905,14 @@ int omr_sweep_batch(const omr_image *scans, int32_t n, uint16_t max_angle, doubl
     int N = 0;
     const int A = candidate_count(max_angle, step, &N);
     if (A <= 0) return fail(OMR_ERR_BADARG, "empty candidate range");
-    std::vector<std::pair<int, int>> shapes;  // in order of first appearance
-    std::vector<std::vector<int>> members;
-    for (int i = 0; i < n; i++) {
-        int rc = check_image(&scans[i], true);
-        if (rc) return rc;
-        const std::pair<int, int> sh(scans[i].rows, scans[i].cols);
-        size_t k = 0;
-        while (k < shapes.size() && shapes[k] != sh) k++;
-        if (k == shapes.size()) {
-            shapes.push_back(sh);
-            members.emplace_back();
-        }
-        members[k].push_back(i);
-    }
-    const bool one = shapes.size() == 1;
-    for (size_t k = 0; k < shapes.size(); k++) {
-        const std::vector<int> &idx = members[k];
+    ShapeBuckets b;  // 1-channel scans only: grouped by (rows, cols)
+    if (int rc = bucket_by_shape(scans, n, [](const omr_image &im) { return check_image(&im, cn_one); }, &b)) return rc;
+    const bool one = b.shapes.size() == 1;
+    for (size_t k = 0; k < b.shapes.size(); k++) {
+        const std::vector<int> &idx = b.members[k];
         const int m = (int)idx.size();
         omr_host_batch *hb = nullptr;
-        int rc = omr_host_batch_create(shapes[k].first, shapes[k].second, max_angle, step, n_devices, m, &hb);
+        int rc = omr_host_batch_create(b.shapes[k].rows, b.shapes[k].cols, max_angle, step, n_devices, m, &hb);
         if (rc) return rc;
         if (one) {
             rc = omr_host_batch_run(hb, scans, n, OMR_HOST_PACKED, best_idx, best_angle, v_sd_opt, h_sd_opt);
@@ -1032,9 +947,7 @@ int result_from_projection_device(const uint8_t *d_src, int rows, int cols, int 
                                   double *candidates, int32_t cand_cap, int32_t *cand_len)
 {
     // :60-82
-    const double width_scale = max_w <= 0 ? 1.0 : (double)max_w / (double)cols;
-    const double height_scale = max_h <= 0 ? 1.0 : (double)max_h / (double)rows;
-    const double scale = width_scale < height_scale ? width_scale : height_scale;
+    const double scale = shrink_scale(cols, rows, max_w, max_h);
     int dev, rc;
     if ((rc = current_device(&dev))) return rc;
     DevImage gray, e1, scaled;

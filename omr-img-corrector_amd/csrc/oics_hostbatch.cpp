@@ -346,11 +346,9 @@ int omr_host_batch_run(omr_host_batch *hb, const omr_image *scans, int32_t n, in
                     if (pinned_src) {  // the caller's memory is page-locked: DMA straight out of it
                         for (int z = 0; z < cg; z++) {
                             const omr_image &im = scans[mine[(size_t)(j0 + c0 + z)]];
-                            if (im.step_bytes == cols)
-                                OMR_HIP(hipMemcpyAsync(dst + (size_t)z * img, im.data, img, hipMemcpyHostToDevice, d.copy));
-                            else
-                                OMR_HIP(hipMemcpy2DAsync(dst + (size_t)z * img, (size_t)cols, im.data, (size_t)im.step_bytes, (size_t)cols,
-                                                         (size_t)rows, hipMemcpyHostToDevice, d.copy));
+                            int rc = upload_rows(dst + (size_t)z * img, (size_t)cols, im.data, (size_t)im.step_bytes, (size_t)cols,
+                                                 (size_t)rows, d.copy);
+                            if (rc) return rc;
                         }
                         continue;
                     }

@@ -30,39 +30,6 @@ using namespace omr::hh;
 namespace omr {
 namespace hh {
 
-int HStream::create()
-{
-    int rc = lease_call_slot(&slot);  // a pooled stream, returned when the call ends
-    if (rc) return rc;
-    s = slot->stream;
-    pool.reset(new PoolScope(s));
-    return OMR_OK;
-}
-HStream::~HStream()
-{
-    pool.reset();
-    return_call_slot(slot);
-}
-
-int have_device()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
-    return OMR_OK;
-}
-
-int check_img(const omr_image *im)
-{
-    if (!im || !im->data) return fail(OMR_ERR_BADARG, "null image");
-    if (im->rows <= 0 || im->cols <= 0) return fail(OMR_ERR_ASSERT, "empty image");
-    if (im->rows >= 32767 || im->cols >= 32767) return fail(OMR_ERR_ASSERT, "image dimension >= SHRT_MAX");
-    if (im->channels != 1 && im->channels != 3 && im->channels != 4)
-        return fail(OMR_ERR_ASSERT, "Canny / HoughLinesP take 1, 3 or 4 channels, got %d", im->channels);
-    if (im->step_bytes < (int64_t)im->cols * im->channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
-    return OMR_OK;
-}
-
 // omr_hough_set_scans_in_flight(): 0 = the default (see ppht_device)
 std::atomic<int> g_scans_in_flight{0};
 
@@ -291,11 +258,7 @@ int upload(const omr_image *im, DevBuf *buf, hipStream_t s)
 {
     const size_t row = (size_t)im->cols * im->channels;
     OMR_HIP(buf->alloc(row * (size_t)im->rows));
-    if ((size_t)im->step_bytes == row)  // packed: one linear copy (the 2-D path is slow for odd widths)
-        OMR_HIP(hipMemcpyAsync(buf->p, im->data, row * (size_t)im->rows, hipMemcpyHostToDevice, s));
-    else
-        OMR_HIP(hipMemcpy2DAsync(buf->p, row, im->data, (size_t)im->step_bytes, row, (size_t)im->rows, hipMemcpyHostToDevice, s));
-    return OMR_OK;
+    return upload_rows(buf->p, row, im->data, (size_t)im->step_bytes, row, (size_t)im->rows, s);
 }
 
 // Canny + HoughLinesP of n device-resident scans -> per-scan segments
@@ -325,11 +288,11 @@ int32_t omr_hough_set_scans_in_flight(int32_t scans)
 int omr_canny(const omr_image *src, double low_thresh, double high_thresh, omr_image_owned *edges)
 {
     clear_error();
-    int rc = check_img(src);
+    int rc = check_image(src, cn_canny);
     if (rc) return rc;
     if (!edges) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevBuf in, map, flag, rowcnt;
     if ((rc = upload(src, &in, st.s))) return rc;
@@ -354,12 +317,12 @@ int omr_hough_lines_p(const omr_image *edges, double rho, double theta, int32_t 
                       double max_line_gap, int32_t *lines, int32_t cap, int32_t *n_lines)
 {
     clear_error();
-    int rc = check_img(edges);
+    int rc = check_image(edges, cn_canny);
     if (rc) return rc;
     if (edges->channels != 1) return fail(OMR_ERR_ASSERT, "HoughLinesP takes an 8-bit single-channel image");
     if (!n_lines || (cap > 0 && !lines)) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevBuf img, rowcnt;
     if ((rc = upload(edges, &img, st.s))) return rc;
@@ -382,11 +345,11 @@ int omr_hough_lines_p(const omr_image *edges, double rho, double theta, int32_t 
 int omr_get_angle_with_hough(const omr_image *gray, double min_line_length, double max_line_gap, double *angle_out)
 {
     clear_error();
-    int rc = check_img(gray);
+    int rc = check_image(gray, cn_canny);
     if (rc) return rc;
     if (!angle_out) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevBuf in;
     if ((rc = upload(gray, &in, st.s))) return rc;
@@ -409,11 +372,11 @@ int omr_get_result_from_edges_detection(const omr_image *src, double edges_min_l
                                         int32_t *cand_len)
 {
     clear_error();
-    int rc = check_img(src);
+    int rc = check_image(src, cn_canny);
     if (rc) return rc;
     if (!angle) return fail(OMR_ERR_BADARG, "null output");
     if ((rc = have_device())) return rc;
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevBuf in;
     if ((rc = upload(src, &in, st.s))) return rc;
@@ -525,7 +488,7 @@ int omr_correct_default(const omr_image *src, uint16_t projection_max_angle, dou
 {
     clear_error();
     if (!rotate_angle || !need_check) return fail(OMR_ERR_BADARG, "null output");
-    int rc = check_img(src);
+    int rc = check_image(src, cn_canny);
     if (rc) return rc;
     double pa = 0;
     int32_t pst = 0, pn = 0;
@@ -536,7 +499,7 @@ int omr_correct_default(const omr_image *src, uint16_t projection_max_angle, dou
     if (src->channels == 2) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
     if ((rc = have_device())) return rc;
     // the sheet goes to the device once; projection, the Hough fallback and the final warp all read that copy
-    HStream st;
+    LeasedStream st;
     if ((rc = st.create())) return rc;
     DevBuf in;
     if ((rc = upload(src, &in, st.s))) return rc;

@@ -173,8 +173,7 @@ int rotate_batch_launch(const uint8_t *d_src, int64_t sstride, int64_t sstep, in
     }
     const uint32_t border = (uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16) |
                             ((uint32_t)border_value[3] << 24);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
+    if (int rc = have_device()) return rc;
     if (n <= 3) {
         // the table's upload and the wait that gives it back cost about 20 us per call (profiles/r07_rotate_batch.md),
         // more than the launches they save: the same kernels, an image per launch, the matrix by value, no wait

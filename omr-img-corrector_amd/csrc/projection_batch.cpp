@@ -2,20 +2,17 @@
 // (DESIGN.md section 4.12):
 //
 //   front end   scale_self on the colour scans (transfer.rs:66-91), one launch over the batch (projection_front.hip),
-//               into the context's working buffer.  The dispatch is resize_ptr's (oics_host.cpp); the tap tables of a
-//               fractional shrink are built by area_tab when the context is created and stay on the device.
+//               into the context's working buffer.  The dispatch is resize()'s (resize_dispatch, host_image.hpp); the tap
+//               tables of a fractional shrink are built when the context is created and stay on the device.
 //   sweep       the context's omr_batch_ctx for the working shape: gray (quirk B8) and threshold(127) fused into its
 //               bit-packing loads, arg-max on the device.
 //
 // Scan i's angle is omr_get_angle_with_projections' for the same scan, as f64 bits.
-#include <float.h>
 #include <math.h>
 #include <string.h>
 
-#include <list>
 #include <memory>
 #include <mutex>
-#include <tuple>
 #include <vector>
 
 #include "../../include/omrdeskew.h"
@@ -31,22 +28,15 @@ namespace {
 
 const int kChunk = 256;  // scans per run of the host form's contexts
 
-// scale_self's size and resize_ptr's dispatch for it, on the host
+// scale_self's size and resize()'s dispatch for it, on the host
 struct Working {
     int wr = 0, wc = 0, mode = OMR_PROJECTION_FRONT_NONE, kx = 0, ky = 0;
     bool area_mode = false;  // LINEAR only: INTER_AREA's bilinear emulation (never reached by scale_self)
 };
 
-int check_shape(int rows, int cols)
-{
-    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_ASSERT, "empty image");
-    if (rows >= 32767 || cols >= 32767) return fail(OMR_ERR_ASSERT, "image dimension >= SHRT_MAX");
-    return OMR_OK;
-}
-
 int working_size(int rows, int cols, double scale, Working *w)
 {
-    int rc = check_shape(rows, cols);
+    int rc = check_image_shape(rows, cols);
     if (rc) return rc;
     if (!isfinite(scale) || scale <= 0.0) return fail(OMR_ERR_BADARG, "resize_scale must be finite and positive");
     if (scale == 1.0) {  // projection.rs:24: no scale_self
@@ -58,45 +48,19 @@ int working_size(int rows, int cols, double scale, Working *w)
     const int dc = (int)fc, dr = (int)fr;  // transfer.rs:70-71 `as i32`
     if (dr <= 0 || dc <= 0) return fail(OMR_ERR_ASSERT, "resize to an empty size");
     w->wr = dr, w->wc = dc;
-    if (dr == rows && dc == cols) return OMR_OK;  // resize() copies
-    int interp = scale > 1.0 ? OMR_INTER_LINEAR : OMR_INTER_AREA;
-    const double inv_scale_x = (double)dc / cols, inv_scale_y = (double)dr / rows;
-    const double scale_x = 1. / inv_scale_x, scale_y = 1. / inv_scale_y;
-    const int iscale_x = (int)lrint(scale_x), iscale_y = (int)lrint(scale_y);
-    const bool fast = fabs(scale_x - iscale_x) < DBL_EPSILON && fabs(scale_y - iscale_y) < DBL_EPSILON;
-    if (interp == OMR_INTER_LINEAR && fast && iscale_x == 2 && iscale_y == 2) interp = OMR_INTER_AREA;
-    if (!(interp == OMR_INTER_AREA && scale_x >= 1 && scale_y >= 1)) {
+    const ResizeDispatch d = resize_dispatch(rows, cols, dr, dc, scale > 1.0 ? OMR_INTER_LINEAR : OMR_INTER_AREA);
+    switch (d.kind) {
+    case ResizeDispatch::COPY: break;  // the working images are the scans
+    case ResizeDispatch::LINEAR:
         w->mode = OMR_PROJECTION_FRONT_LINEAR;
-        w->area_mode = interp == OMR_INTER_AREA;
-    } else if (fast) {
+        w->area_mode = d.area_mode;
+        break;
+    case ResizeDispatch::AREA_INT:
         w->mode = OMR_PROJECTION_FRONT_AREA_INT;
-        w->kx = iscale_x, w->ky = iscale_y;
-    } else {
-        w->mode = OMR_PROJECTION_FRONT_AREA_GENERAL;
+        w->kx = d.kx, w->ky = d.ky;
+        break;
+    case ResizeDispatch::AREA_GENERAL: w->mode = OMR_PROJECTION_FRONT_AREA_GENERAL; break;
     }
-    return OMR_OK;
-}
-
-int check_channels(int cn)
-{
-    if (cn == 4) return fail(OMR_ERR_NOTIMPL, "4-channel batches are not implemented (1 or 3 channels)");
-    if (cn != 1 && cn != 3) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels, got %d", cn);
-    return OMR_OK;
-}
-
-int grow(DevBuf *b, size_t bytes)
-{
-    if (b->bytes >= bytes) return OMR_OK;
-    NoPoolScope owned;
-    b->release();
-    OMR_HIP(b->alloc(bytes));
-    return OMR_OK;
-}
-
-int upload_table(DevBuf *b, const void *p, size_t bytes)
-{
-    OMR_HIP(b->alloc(bytes));
-    OMR_HIP(hipMemcpy(b->p, p, bytes, hipMemcpyHostToDevice));
     return OMR_OK;
 }
 
@@ -111,7 +75,8 @@ struct omr_projection_batch {
     int64_t wstep = 0, wstride = 0;  // the working buffer's row pitch and image stride
     omr_batch_ctx *sweep = nullptr;
     hipStream_t s = nullptr;  // front end and result copies
-    DevBuf work, best, vsd, hsd, xt, xo, yt, yo;
+    DevBuf work, best, vsd, hsd;
+    AreaTables area;  // OMR_PROJECTION_FRONT_AREA_GENERAL
     std::vector<int32_t> h_best;
     std::mutex mu;
     ~omr_projection_batch()
@@ -147,7 +112,8 @@ int front_end(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_str
     p.src = d_scans, p.scan_stride = scan_stride, p.sstep = step;
     p.dst = pb->work.as<uint8_t>(), p.out_stride = pb->wstride, p.dstep = pb->wstep;
     p.cn = pb->cn, p.scols = pb->cols, p.drows = w.wr, p.dcols = w.wc, p.kx = w.kx, p.ky = w.ky;
-    p.xtab = pb->xt.as<AreaTap>(), p.xofs = pb->xo.as<int32_t>(), p.ytab = pb->yt.as<AreaTap>(), p.yofs = pb->yo.as<int32_t>();
+    const AreaTables &t = pb->area;
+    p.xtab = t.xt.as<AreaTap>(), p.xofs = t.xo.as<int32_t>(), p.ytab = t.yt.as<AreaTap>(), p.yofs = t.yo.as<int32_t>();
     OMR_HIP(launch_pf_area(p, pb->tiling, n, pb->s));
     return OMR_OK;
 }
@@ -194,30 +160,16 @@ struct CtxKey {
                step == o.step && scale == o.scale;
     }
 };
-std::mutex g_ctx_mu;
-std::list<std::pair<CtxKey, std::shared_ptr<omr_projection_batch>>> g_ctx;  // most recent first, at most kCachedContexts
-const size_t kCachedContexts = 4;
+ContextCache<CtxKey, omr_projection_batch> g_ctx(4);
 
 int cached_context(const CtxKey &k, std::shared_ptr<omr_projection_batch> *out)
 {
-    {
-        std::lock_guard<std::mutex> lk(g_ctx_mu);
-        for (auto it = g_ctx.begin(); it != g_ctx.end(); ++it)
-            if (it->first == k) {
-                *out = it->second;
-                g_ctx.splice(g_ctx.begin(), g_ctx, it);
-                return OMR_OK;
-            }
-    }
-    omr_projection_batch *raw = nullptr;
-    int rc = omr_projection_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.scale, k.device, kChunk, &raw);
-    if (rc) return rc;
-    std::shared_ptr<omr_projection_batch> sp(raw, omr_projection_batch_destroy);
-    std::lock_guard<std::mutex> lk(g_ctx_mu);
-    g_ctx.emplace_front(k, sp);
-    while (g_ctx.size() > kCachedContexts) g_ctx.pop_back();
-    *out = sp;
-    return OMR_OK;
+    return g_ctx.get(k, [&](std::shared_ptr<omr_projection_batch> *sp) -> int {
+        omr_projection_batch *raw = nullptr;
+        int rc = omr_projection_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.scale, k.device, kChunk, &raw);
+        if (rc == OMR_OK) sp->reset(raw, omr_projection_batch_destroy);
+        return rc;
+    }, out);
 }
 
 struct HostArgs {
@@ -254,7 +206,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     omr_projection_batch *pb = pbp.get();
     const int m = (int)idx.size(), zmax = std::min(m, kChunk);
     const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    HStream st;  // the batch's device buffer comes from the block cache and returns to it when the call ends
+    LeasedStream st;  // the batch's device buffer comes from the block cache and returns to it when the call ends
     if ((rc = st.create())) return rc;
     DevBuf din;
     OMR_HIP(din.alloc((size_t)zmax * in_stride));
@@ -262,20 +214,8 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     std::vector<int32_t> best((size_t)zmax);
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
-        rc = on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {  // host memory -> device, from several threads
-            for (int j = lo; j < hi; j++) {
-                const omr_image &im = a.srcs[idx[(size_t)(j0 + j)]];
-                uint8_t *d = din.as<uint8_t>() + (size_t)j * in_stride;
-                if (im.step_bytes == row)
-                    OMR_HIP(hipMemcpyAsync(d, im.data, (size_t)row * rows, hipMemcpyHostToDevice, s));
-                else
-                    OMR_HIP(hipMemcpy2DAsync(d, (size_t)row, im.data, (size_t)im.step_bytes, (size_t)row, (size_t)rows,
-                                             hipMemcpyHostToDevice, s));
-            }
-            OMR_HIP(hipStreamSynchronize(s));
-            return OMR_OK;
-        });
-        if (rc) return rc;
+        // host memory -> device, from several threads
+        if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
         if ((rc = omr_projection_batch_run_device(pb, din.as<uint8_t>(), in_stride, row, z, ang.data(), best.data(), nullptr, nullptr)))
             return rc;
         for (int j = 0; j < z; j++) {
@@ -311,19 +251,14 @@ int omr_projection_batch_create(int32_t rows, int32_t cols, int32_t channels, ui
     *out = nullptr;
     if (max_scans < 1 || max_scans > 65535) return fail(OMR_ERR_BADARG, "max_scans must be in 1..65535");
     if (device < 0) return fail(OMR_ERR_BADARG, "negative device");
-    int rc = check_shape(rows, cols);
-    if (rc) return rc;
-    if ((rc = check_channels(channels))) return rc;
+    int rc = check_image_shape(rows, cols);
+    if (rc || (rc = cn_projection_batch(channels))) return rc;
     int N = 0;
     const int A = candidate_count(max_angle, step, &N);
     if (A <= 0) return fail(OMR_ERR_BADARG, "empty candidate range");
     Working w;
     if ((rc = working_size(rows, cols, resize_scale, &w))) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(OMR_ERR_GPU, "no usable HIP device (there is no CPU fallback)");
-    if (device >= ndev) return fail(OMR_ERR_BADARG, "device %d of %d", device, ndev);
-    OMR_HIP(hipSetDevice(device));
+    if ((rc = select_device(device))) return rc;
     NoPoolScope owned;
     std::unique_ptr<omr_projection_batch> pb(new omr_projection_batch);
     pb->device = device, pb->rows = rows, pb->cols = cols, pb->cn = channels, pb->max_scans = max_scans;
@@ -337,15 +272,8 @@ int omr_projection_batch_create(int32_t rows, int32_t cols, int32_t channels, ui
         OMR_HIP(pb->work.alloc((size_t)max_scans * pb->wstride));
     }
     if (w.mode == OMR_PROJECTION_FRONT_AREA_GENERAL) {  // resizeArea_'s tap tables, once per context
-        std::vector<AreaTap> xt, yt;
-        std::vector<int32_t> xo, yo;
-        area_tab(cols, w.wc, channels, 1. / ((double)w.wc / cols), &xt, &xo);
-        area_tab(rows, w.wr, 1, 1. / ((double)w.wr / rows), &yt, &yo);
-        pb->tiling = pf_area_tiling(channels, w.wc, 0, &xt, &xo, &yt);
-        if ((rc = upload_table(&pb->xt, xt.data(), sizeof(AreaTap) * xt.size()))) return rc;
-        if ((rc = upload_table(&pb->xo, xo.data(), sizeof(int32_t) * xo.size()))) return rc;
-        if ((rc = upload_table(&pb->yt, yt.data(), sizeof(AreaTap) * yt.size()))) return rc;
-        if ((rc = upload_table(&pb->yo, yo.data(), sizeof(int32_t) * yo.size()))) return rc;
+        if ((rc = pb->area.build(cols, w.wc, rows, w.wr, channels, nullptr))) return rc;
+        pb->tiling = pf_area_tiling(channels, w.wc, 0, &pb->area.h_xt, &pb->area.h_xo, &pb->area.h_yt);
     } else if (w.mode == OMR_PROJECTION_FRONT_AREA_INT) {
         pb->tiling = pf_area_tiling(channels, w.wc, w.kx, nullptr, nullptr, nullptr);
     }
@@ -420,37 +348,22 @@ int omr_get_angles_with_projections_batch(const omr_image *srcs, int32_t n, uint
     int N = 0;
     if (candidate_count(max_angle, step, &N) <= 0)
         return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
-    std::vector<std::tuple<int, int, int>> shapes;  // in order of first appearance
-    std::vector<std::vector<int>> members;
-    for (int i = 0; i < n; i++) {  // omr_get_angle_with_projections' checks, for every image before any device work
-        const omr_image &im = srcs[i];
-        if (!im.data) return fail(OMR_ERR_BADARG, "null image %d", i);
-        int rc = check_shape(im.rows, im.cols);
-        if (rc) return rc;
-        if (im.channels < 1 || im.channels > 4) return fail(OMR_ERR_ASSERT, "unsupported channel count %d", im.channels);
-        if (im.channels == 2) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels");
-        if (im.step_bytes < (int64_t)im.cols * im.channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
+    ShapeBuckets b;
+    // omr_get_angle_with_projections' checks, for every image before any device work
+    int rc = bucket_by_shape(srcs, n, [&](const omr_image &im) -> int {
         Working w;
-        if ((rc = working_size(im.rows, im.cols, resize_scale, &w))) return rc;
-        const std::tuple<int, int, int> sh(im.rows, im.cols, im.channels);
-        size_t k = 0;
-        while (k < shapes.size() && shapes[k] != sh) k++;
-        if (k == shapes.size()) {
-            shapes.push_back(sh);
-            members.emplace_back();
-        }
-        members[k].push_back(i);
-    }
-    int rc = have_device();
-    if (rc) return rc;
+        int rc = check_image(&im, cn_gray_source);
+        return rc ? rc : working_size(im.rows, im.cols, resize_scale, &w);
+    }, &b);
+    if (rc || (rc = have_device())) return rc;
     int dev = 0;
     OMR_HIP(hipGetDevice(&dev));
     // results go to the caller's arrays only when the whole call has succeeded
     std::vector<double> ang((size_t)n);
     std::vector<int32_t> best((size_t)n);
     const HostArgs a{srcs, max_angle, step, resize_scale, N, ang.data(), best.data(), dev};
-    for (size_t k = 0; k < shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, std::get<0>(shapes[k]), std::get<1>(shapes[k]), std::get<2>(shapes[k]), members[k]);
+    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
+        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
     if (rc) return rc;
     memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
     if (best_idx) memcpy(best_idx, best.data(), sizeof(int32_t) * (size_t)n);

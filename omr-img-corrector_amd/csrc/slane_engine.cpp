@@ -298,12 +298,11 @@ int SlaneScratch::create(const SlanePlan &p, int groups)
 }
 
 // pack -> sweep -> column counts -> std-dev -> arg-max for `nscans` device-resident scans (at most nsg * 64)
-// (black_max < 0: d_img holds scans ALREADY packed to 1 bit per pixel, [rows][NW] dwords each, scan_stride bytes apart)
+// (packed: d_img holds scans ALREADY packed to 1 bit per pixel, [rows][NW] dwords each, scan_stride bytes apart)
 int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int64_t scan_stride, int64_t step, int nscans,
-                  int black_max, hipStream_t stream, hipStream_t post_stream, hipEvent_t ev_mid, double *d_v_sd, double *d_h_sd,
-                  int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1, int cn)
+                  int black_max, bool packed, hipStream_t stream, hipStream_t post_stream, hipEvent_t ev_mid, double *d_v_sd,
+                  double *d_h_sd, int32_t *d_best, hipEvent_t ev0, hipEvent_t ev1, int cn)
 {
-    const bool packed = black_max < 0;
     if (!d_img || nscans < 1 || nscans > s.nsg * SL_LANES) return fail(OMR_ERR_BADARG, "scan-lane launch: %d scans, scratch holds %d", nscans, s.nsg * SL_LANES);
     if (!packed && step < (int64_t)p.g.cols * cn)
         return fail(OMR_ERR_BADARG, "step_bytes %lld < cols %d x %d channels", (long long)step, p.g.cols, cn);

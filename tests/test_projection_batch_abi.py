@@ -101,6 +101,38 @@ def test_working_size_is_scale_selfs_shape_and_resizes_dispatch(oracle):
     assert _ws(1, 9, 0.5)[0] == -215 and _ws(9, 1, 0.9)[0] == -215
 
 
+def _resize_rule(srows, scols, drows, dcols, linear):
+    """OpenCV 4.6.0 resize.cpp, the order of its tests kept: (path, kx, ky) for INTER_LINEAR or INTER_AREA"""
+    if (drows, dcols) == (srows, scols):
+        return "COPY", 0, 0
+    sx, sy = 1.0 / (dcols / scols), 1.0 / (drows / srows)
+    kx, ky = round(sx), round(sy)  # both round half to even, as lrint
+    eps = sys.float_info.epsilon
+    fast = abs(sx - kx) < eps and abs(sy - ky) < eps
+    if linear and fast and kx == 2 and ky == 2:
+        linear = False  # an exact 2x shrink is INTER_AREA
+    if linear or not (sx >= 1 and sy >= 1):
+        return "LINEAR", 0, 0
+    return ("AREA_INT", kx, ky) if fast else ("AREA_GENERAL", 0, 0)
+
+
+@pytest.mark.parametrize("rows,cols,scale,path,k", [
+    (453, 641, 1.0, "COPY", 0),        # identity: no scale_self at all
+    (3, 4, 1.2, "COPY", 0),            # 3.6 x 4.8 truncates to the same 3 x 4
+    (452, 640, 0.5, "AREA_INT", 2),    # integer 2x shrink
+    (40, 50, 0.3, "AREA_GENERAL", 0),  # 12 x 15: 3.33.. on both axes
+    (40, 50, 1.5, "LINEAR", 0),
+    (6, 10, 0.499, "AREA_GENERAL", 0),  # 2 x 4: exactly 3 down, 2.5 across -- one integer axis is not enough
+])
+def test_every_branch_of_the_resize_dispatch(rows, cols, scale, path, k):
+    """one case per branch of the rule that resize_ptr, the correct batch and the projection batch share"""
+    dr, dc = (rows, cols) if scale == 1.0 else (int(rows * scale), int(cols * scale))  # transfer.rs:70-71 `as i32`
+    got = _resize_rule(rows, cols, dr, dc, linear=scale > 1.0)
+    assert got == (path, k, k)  # the case is the branch its comment says
+    mode = {"COPY": NONE, "AREA_INT": AREA_INT, "AREA_GENERAL": AREA_GENERAL, "LINEAR": LINEAR}[path]
+    assert _ws(rows, cols, scale) == (0, dr, dc, mode)
+
+
 def test_working_size_argument_errors():
     L = _lib.lib()
     r, c, m = C.c_int32(), C.c_int32(), C.c_int32()
