@@ -11,6 +11,11 @@
 
 namespace omr {
 
+__device__ __forceinline__ uint32_t bgr_gray(uint32_t b0, uint32_t b1, uint32_t b2)
+{
+    return (b0 * 9798u + b1 * 19235u + b2 * 3735u + 16384u) >> 15;
+}
+
 __device__ __forceinline__ uint32_t bgr_black(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t lim)
 {
     return b0 * 9798u + b1 * 19235u + b2 * 3735u + 16384u < lim ? 1u : 0u;

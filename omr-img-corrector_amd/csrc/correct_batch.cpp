@@ -1,8 +1,8 @@
 // correct_batch.cpp -- correct_default (omr.rs:339-448) for batches of sheets on the device:
 //
-//   front end   one launch per stage over the batch (correct_front.hip): gray + erode x3 (+ integer INTER_AREA shrink)
-//               fused; fractional shrinks through the context's resizeArea_ tap tables; enlargement (quirk B7) through
-//               the per-call stage kernel, sheet by sheet
+//   front end   one launch per stage over the batch: gray + erode x3 (+ integer INTER_AREA shrink) fused
+//               (correct_front.hip); every other resize() path on the eroded sheets, a launch per chunk (resize.hip) --
+//               fractional shrinks with the context's resizeArea_ tap tables, enlargement (quirk B7) bilinear
 //   sweep       the context's omr_batch_ctx at the resize scale (quirk B4), black_max 127 (omr.rs:129-139); the scores
 //               go to the host, where omr_select_projection_result decides every sheet (omr.rs:147-221)
 //   Hough       only the sheets that are not Believed: one batched Canny + HoughLinesP pass on a gather of their
@@ -33,23 +33,14 @@
 using namespace omr;
 using namespace omr::hh;
 
-namespace omr {
-// correct_front.hip
-hipError_t launch_front(const uint8_t *d_src, int64_t scan_stride, int64_t sstep, int cn, int rows, int cols, int n,
-                        uint8_t *d_dst, int64_t out_stride, int64_t dstep, int kx, int ky, hipStream_t s);
-hipError_t launch_area_general_batch(const uint8_t *d_src, int64_t scan_stride, int64_t sstep, int n, uint8_t *d_dst,
-                                     int64_t out_stride, int64_t dstep, int drows, int dcols, const AreaTap *d_xtab,
-                                     const int32_t *d_xofs, const AreaTap *d_ytab, const int32_t *d_yofs, hipStream_t s);
-}  // namespace omr
-
 namespace {
 
 // the front-end modes (include/omrdeskew.h, OMR_CORRECT_FRONT_*)
 enum FrontMode {
     FRONT_AREA_FUSED = OMR_CORRECT_FRONT_AREA_FUSED,  // integer factors <= 64: gray + erode + resizeAreaFast_ in one kernel
-    FRONT_AREA_INT = OMR_CORRECT_FRONT_AREA_INT,      // integer factors > 64: eroded sheets, then resizeAreaFast_ per sheet
+    FRONT_AREA_INT = OMR_CORRECT_FRONT_AREA_INT,      // integer factors > 64: eroded sheets, then resizeAreaFast_
     FRONT_AREA_GENERAL = OMR_CORRECT_FRONT_AREA_GENERAL,  // fractional shrink: eroded sheets, then resizeArea_ (tap tables)
-    FRONT_LINEAR = OMR_CORRECT_FRONT_LINEAR,  // an axis enlarges (quirk B7): eroded sheets, then the bilinear kernel per sheet
+    FRONT_LINEAR = OMR_CORRECT_FRONT_LINEAR,  // an axis enlarges (quirk B7): eroded sheets, then the bilinear kernel
 };
 const int kChunk = 256;  // sheets per front-end / warp launch when a full-size intermediate is needed
 
@@ -82,7 +73,8 @@ struct omr_correct_batch {
     int N = 0, A = 0;
     double scale = 1;
     int dr = 0, dc = 0;  // projection-size image
-    int mode = FRONT_AREA_FUSED, kx = 1, ky = 1;
+    ResizeDispatch rd{ResizeDispatch::COPY, false, 1, 1};  // resize()'s path from rows x cols to dr x dc
+    int mode = FRONT_AREA_FUSED;                           // the same as omr_correct_batch_info reports it
     int64_t small_step = 0, small_stride = 0, er_stride = 0;
     int DR = 0, DC = 0;  // largest canvas
     omr_batch_ctx *sweep = nullptr;
@@ -106,15 +98,14 @@ struct omr_correct_batch {
 
 namespace {
 
-// resize()'s dispatch for INTER_AREA from rows x cols to dr x dc, as front-end modes
+// resize()'s dispatch for INTER_AREA from rows x cols to dr x dc, and the front-end mode it means
 void front_mode(omr_correct_batch *cb)
 {
-    const ResizeDispatch d = resize_dispatch(cb->rows, cb->cols, cb->dr, cb->dc, OMR_INTER_AREA);
+    const ResizeDispatch d = cb->rd = resize_dispatch(cb->rows, cb->cols, cb->dr, cb->dc, OMR_INTER_AREA);
     switch (d.kind) {
     case ResizeDispatch::COPY:  // resizeAreaFast_ with factor 1 is the identity
     case ResizeDispatch::AREA_INT:
-        cb->kx = d.kx, cb->ky = d.ky;
-        cb->mode = cb->kx <= 64 && cb->ky <= 64 ? FRONT_AREA_FUSED : FRONT_AREA_INT;
+        cb->mode = d.kx <= 64 && d.ky <= 64 ? FRONT_AREA_FUSED : FRONT_AREA_INT;
         break;
     case ResizeDispatch::LINEAR: cb->mode = FRONT_LINEAR; break;
     case ResizeDispatch::AREA_GENERAL: cb->mode = FRONT_AREA_GENERAL; break;
@@ -218,7 +209,7 @@ int front_end(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride
     hipStream_t s = cb->s;
     if (cb->mode == FRONT_AREA_FUSED) {
         OMR_HIP(launch_front(d_scans, scan_stride, step, cb->cn, cb->rows, cb->cols, n, cb->small.as<uint8_t>(), cb->small_stride,
-                             cb->small_step, cb->kx, cb->ky, s));
+                             cb->small_step, cb->rd.kx, cb->rd.ky, s));
         return OMR_OK;
     }
     for (int i0 = 0; i0 < n; i0 += kChunk) {
@@ -229,21 +220,11 @@ int front_end(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_stride
         uint8_t *sm = cb->small.as<uint8_t>() + (size_t)i0 * cb->small_stride;
         OMR_HIP(launch_front(d_scans + (size_t)i0 * scan_stride, scan_stride, step, cb->cn, cb->rows, cb->cols, z, er, cb->er_stride,
                              cb->cols, 0, 0, s));
-        if (cb->mode == FRONT_AREA_GENERAL) {
-            OMR_HIP(launch_area_general_batch(er, cb->er_stride, cb->cols, z, sm, cb->small_stride, cb->small_step, cb->dr, cb->dc,
-                                              cb->area.xt.as<AreaTap>(), cb->area.xo.as<int32_t>(), cb->area.yt.as<AreaTap>(),
-                                              cb->area.yo.as<int32_t>(), s));
-        } else {
-            for (int j = 0; j < z; j++) {
-                const uint8_t *e = er + (size_t)j * cb->er_stride;
-                uint8_t *d = sm + (size_t)j * cb->small_stride;
-                if (cb->mode == FRONT_LINEAR)
-                    OMR_HIP(launch_resize_linear(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc, true, s));
-                else
-                    OMR_HIP(launch_resize_area_int(e, cb->cols, cb->rows, cb->cols, 1, d, cb->small_step, cb->dr, cb->dc,
-                                                   cb->kx, cb->ky, s));
-            }
-        }
+        ResizeImgs im{};
+        im.src = er, im.scan_stride = cb->er_stride, im.sstep = cb->cols;
+        im.dst = sm, im.out_stride = cb->small_stride, im.dstep = cb->small_step;
+        im.cn = 1, im.srows = cb->rows, im.scols = cb->cols, im.drows = cb->dr, im.dcols = cb->dc;
+        OMR_HIP(launch_resize(cb->rd, im, z, s, cb->area.taps()));
     }
     return OMR_OK;
 }
@@ -579,12 +560,11 @@ int omr_correct_batch_info(omr_correct_batch *cb, int32_t *proj_rows, int32_t *p
 {
     clear_error();
     if (!cb) return fail(OMR_ERR_BADARG, "null context");
-    const bool integer = cb->mode == FRONT_AREA_FUSED || cb->mode == FRONT_AREA_INT;
     if (proj_rows) *proj_rows = cb->dr;
     if (proj_cols) *proj_cols = cb->dc;
     if (front_mode) *front_mode = cb->mode;
-    if (kx) *kx = integer ? cb->kx : 0;
-    if (ky) *ky = integer ? cb->ky : 0;
+    if (kx) *kx = cb->rd.kx;  // 0 unless the factors are integers
+    if (ky) *ky = cb->rd.ky;
     return OMR_OK;
 }
 

@@ -3,19 +3,19 @@
 //
 //   front_kernel      gray (cvtColor(COLOR_RGB2GRAY) on BGR bytes, quirk B8, bgr.hpp's arithmetic) + erode(3x3 cross,
 //                     iterations = 3) + -- when the shrink is an integer factor -- INTER_AREA's resizeAreaFast_, fused:
-//                     every sheet is read once and only its projection-size image is written.  Other shrinks: the
-//                     eroded gray sheets are written and area_general_kernel takes over.
-//   area_general_kernel  resizeArea_ (fractional shrink) over the batch with the context's tap tables.
+//                     every sheet is read once and only its projection-size image is written.  Other resizes: the
+//                     eroded gray sheets are written and resize.hip takes over, one launch per chunk.
 //
-// Arithmetic is the per-call stage kernels' (stages.hip, kernels.hip) operation for operation, so the images are the
+// Arithmetic is the per-call stage kernels' (stages.hip, resize.hip) operation for operation, so the images are the
 // per-call path's bit for bit.
 #include <hip/hip_runtime.h>
 
+#include "bgr.hpp"
 #include "kernels.hpp"
+#include "warp_fixed.hpp"
 
 namespace omr {
 
-__device__ __forceinline__ uint8_t cb_sat_u8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 __device__ __forceinline__ uint32_t cb_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 // One workgroup = one tile of one sheet (blockIdx.z).  The tile is EW x EH eroded pixels (EW <= 256: one column per lane);
@@ -43,8 +43,7 @@ __global__ __launch_bounds__(256) void front_kernel(const uint8_t *__restrict__ 
         uint32_t v = 255;
         if ((unsigned)gy < (unsigned)rows && (unsigned)gx < (unsigned)cols) {
             const uint8_t *P = S + (int64_t)gy * sstep + (int64_t)gx * cn;
-            v = cn == 1 ? (uint32_t)P[0]
-                        : ((uint32_t)P[0] * 9798u + (uint32_t)P[1] * 19235u + (uint32_t)P[2] * 3735u + 16384u) >> 15;
+            v = cn == 1 ? (uint32_t)P[0] : bgr_gray(P[0], P[1], P[2]);
         }
         gt[i] = (uint8_t)v;
     }
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(256) void front_kernel(const uint8_t *__restrict__ 
         for (int j = 0; j < kx; j++) sum += (int)colsum[ly * EW + lx * kx + j];
         uint8_t out;
         if (kx == 2 && ky == 2) out = (uint8_t)((sum + 2) >> 2);
-        else out = cb_sat_u8((int)rintf((float)sum * (1.f / (float)(kx * ky))));
+        else out = sat_u8((int)rintf((float)sum * (1.f / (float)(kx * ky))));
         D[(int64_t)oy * dstep + ox] = out;
     }
 }
@@ -138,43 +137,6 @@ hipError_t launch_front(const uint8_t *d_src, int64_t scan_stride, int64_t sstep
     else grid = dim3((cols + EW - 1) / EW, (rows + EH - 1) / EH, n);
     hipLaunchKernelGGL(front_kernel, grid, dim3(256), lds, s, d_src, scan_stride, sstep, cn, rows, cols, d_dst, out_stride, dstep,
                        kx, ky, TWo, THo, EW, EH);
-    return hipGetLastError();
-}
-
-// resizeArea_ of n 1-channel images (resize_area_general_kernel's float accumulation order, image blockIdx.z).
-__global__ __launch_bounds__(256) void area_general_kernel(const uint8_t *__restrict__ src, int64_t scan_stride, int64_t sstep,
-                                                           uint8_t *__restrict__ dst, int64_t out_stride, int64_t dstep,
-                                                           int drows, int dcols, const AreaTap *__restrict__ xtab,
-                                                           const int32_t *__restrict__ xofs, const AreaTap *__restrict__ ytab,
-                                                           const int32_t *__restrict__ yofs)
-{
-    const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    if (dx >= dcols) return;
-    const uint8_t *Sz = src + (int64_t)blockIdx.z * scan_stride;
-    float sum = 0.f;
-    bool first = true;
-    for (int j = yofs[dy]; j < yofs[dy + 1]; j++) {
-        const float beta = ytab[j].alpha;
-        const uint8_t *S = Sz + (int64_t)ytab[j].si * sstep;
-        float buf = 0.f;
-        for (int k = xofs[dx]; k < xofs[dx + 1]; k++) buf += (float)S[xtab[k].si] * xtab[k].alpha;
-        if (first) {
-            sum = beta * buf;
-            first = false;
-        } else {
-            sum += beta * buf;
-        }
-    }
-    dst[(int64_t)blockIdx.z * out_stride + (int64_t)dy * dstep + dx] = cb_sat_u8((int)rintf(sum));
-}
-
-hipError_t launch_area_general_batch(const uint8_t *d_src, int64_t scan_stride, int64_t sstep, int n, uint8_t *d_dst,
-                                     int64_t out_stride, int64_t dstep, int drows, int dcols, const AreaTap *d_xtab,
-                                     const int32_t *d_xofs, const AreaTap *d_ytab, const int32_t *d_yofs, hipStream_t s)
-{
-    if (n <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(area_general_kernel, dim3((dcols + 255) / 256, drows, n), dim3(256), 0, s, d_src, scan_stride, sstep, d_dst,
-                       out_stride, dstep, drows, dcols, d_xtab, d_xofs, d_ytab, d_yofs);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/omrdeskew.h"
 #include "host_image.hpp"
 #include "kernels.hpp"
+#include "resize.hpp"
 #include "slane.hpp"
 
 namespace omr {
@@ -169,12 +170,13 @@ int morph_device(const uint8_t *d_src, int64_t sstride, int64_t sstep, int n, in
 // OpenCV computeResizeAreaTab for resizeArea_, grouped per destination index (CSR offsets ofs[0..dsize]); oics_host.cpp
 void area_tab(int ssize, int dsize, int cn, double scale, std::vector<AreaTap> *tab, std::vector<int32_t> *ofs);
 // resizeArea_'s four tap tables for scols x srows -> dcols x drows on the device, with the host copies they were made from
-// (projection_front's tiling reads those).  build uploads like upload_table: synchronously when `s` is null.
+// (pf_area_tiling reads those).  build uploads like upload_table: synchronously when `s` is null.
 struct AreaTables {
     DevBuf xt, xo, yt, yo;
     std::vector<AreaTap> h_xt, h_yt;
     std::vector<int32_t> h_xo, h_yo;
     int build(int scols, int dcols, int srows, int drows, int cn, hipStream_t s);
+    AreaTaps taps() const { return AreaTaps{xt.as<AreaTap>(), yt.as<AreaTap>(), xo.as<int32_t>(), yo.as<int32_t>()}; }
 };
 
 // Immutable per-(shape, matrices) state: inverse matrices, fixed-point tables, LDS tiling.

@@ -163,8 +163,8 @@ struct DeskewPass {
 size_t deskew_tile_bytes(const DeskewPass &p, int scans);
 hipError_t launch_deskew_warp(const DeskewPass &p, int scans, int interp, void *d_tiles, hipStream_t s);
 
-// ---- per-image stages either side of the sweep (stages.hip): each launcher picks the tuned kernel where the
-// layout and alignment allow and the generic one (any channel count, one thread per byte) otherwise
+// ---- per-image stages either side of the sweep (stages.hip; the resizes are resize.hpp): each launcher picks the tuned
+// kernel where the layout and alignment allow and the generic one (one thread per byte) otherwise
 hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
                             int thresh, int maxval, hipStream_t s);
 hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
@@ -172,20 +172,12 @@ hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int co
 // erode(3x3 cross) x 3 iterations fused (omr.rs:98-112)
 hipError_t launch_erode3x_cross(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
                                 hipStream_t s);
-hipError_t launch_resize_area_int(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                                  uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
-                                  hipStream_t s);
-struct AreaTap {
-    int32_t si, di;
-    float alpha;
-};
-hipError_t launch_resize_area_general(const uint8_t *d_src, int64_t sstep, int cn, uint8_t *d_dst,
-                                      int64_t dstep, int drows, int dcols, const AreaTap *d_xtab,
-                                      const int32_t *d_xofs, const AreaTap *d_ytab,
-                                      const int32_t *d_yofs, hipStream_t s);
-// resize(INTER_LINEAR) (area_mode false) / INTER_AREA's bilinear emulation when an axis enlarges (true)
-hipError_t launch_resize_linear(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                                int64_t dstep, int drows, int dcols, bool area_mode, hipStream_t s);
+
+// ---- the front end of correct_default over a batch (correct_front.hip): gray + erode(3x3 cross) x 3 of n same-shape
+// sheets of cn = 1 or 3 channels, sheet i at d_src + i * scan_stride, and -- kx, ky in 1..64 -- resizeAreaFast_ by those
+// factors fused in; kx = 0 writes the eroded gray sheets at full size
+hipError_t launch_front(const uint8_t *d_src, int64_t scan_stride, int64_t sstep, int cn, int rows, int cols, int n,
+                        uint8_t *d_dst, int64_t out_stride, int64_t dstep, int kx, int ky, hipStream_t s);
 
 // ---- warpAffine (warp_affine.hip): interp 0 / 1 / 2 / 4 (NEAREST, LINEAR, CUBIC, LANCZOS4) under border mode 0..5,
 // 1..4 channels.  Minv (dst -> src) is a HOST pointer, passed to the kernel by value; d_wtab is the device weight

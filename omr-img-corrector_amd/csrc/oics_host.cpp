@@ -167,27 +167,21 @@ int resize_ptr(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn
     if (interp != OMR_INTER_AREA && interp != OMR_INTER_LINEAR)
         return fail(OMR_ERR_NOTIMPL, "resize interpolation flag %d is not implemented", interp);
     const ResizeDispatch d = resize_dispatch(srows, scols, drows, dcols, interp);
-    switch (d.kind) {
-    case ResizeDispatch::COPY:
+    if (d.kind == ResizeDispatch::COPY) {
         OMR_HIP(hipMemcpy2DAsync(d_dst, (size_t)dstep, d_src, (size_t)sstep, (size_t)scols * cn, (size_t)srows,
                                  hipMemcpyDeviceToDevice, s));
-        break;
-    case ResizeDispatch::LINEAR:
-        OMR_HIP(launch_resize_linear(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, d.area_mode, s));
-        break;
-    case ResizeDispatch::AREA_INT:
-        OMR_HIP(launch_resize_area_int(d_src, sstep, srows, scols, cn, d_dst, dstep, drows, dcols, d.kx, d.ky, s));
-        break;
-    case ResizeDispatch::AREA_GENERAL: {
-        AreaTables t;
+        return OMR_OK;
+    }
+    ResizeImgs im{};
+    im.src = d_src, im.sstep = sstep, im.dst = d_dst, im.dstep = dstep;
+    im.cn = cn, im.srows = srows, im.scols = scols, im.drows = drows, im.dcols = dcols;
+    AreaTables t;
+    if (d.kind == ResizeDispatch::AREA_GENERAL) {
         int rc = t.build(scols, dcols, srows, drows, cn, s);
         if (rc) return rc;
-        OMR_HIP(launch_resize_area_general(d_src, sstep, cn, d_dst, dstep, drows, dcols, t.xt.as<AreaTap>(), t.xo.as<int32_t>(),
-                                           t.yt.as<AreaTap>(), t.yo.as<int32_t>(), s));
-        OMR_HIP(hipStreamSynchronize(s));  // the tap tables are freed on return
-        break;
     }
-    }
+    OMR_HIP(launch_resize(d, im, 1, s, t.taps()));
+    if (d.kind == ResizeDispatch::AREA_GENERAL) OMR_HIP(hipStreamSynchronize(s));  // the tap tables are freed on return
     return OMR_OK;
 }
 
@@ -755,7 +749,8 @@ int omr_resize_area_device(const uint8_t *d_src, int64_t src_step, int32_t src_r
                            void *stream)
 {
     if (!d_src || !d_dst) return fail(OMR_ERR_BADARG, "null device pointer");
-    if (src_rows <= 0 || src_cols <= 0 || dst_rows <= 0 || dst_cols <= 0 || channels < 1 || channels > 4)
+    if (src_rows <= 0 || src_cols <= 0 || dst_rows <= 0 || dst_cols <= 0 || channels < 1 || channels > 4 || src_rows >= 32767 ||
+        src_cols >= 32767 || dst_rows >= 32767 || dst_cols >= 32767)
         return fail(OMR_ERR_ASSERT, "bad image shape");
     if (src_step < (int64_t)src_cols * channels || dst_step < (int64_t)dst_cols * channels)
         return fail(OMR_ERR_BADARG, "step too small");

@@ -1,7 +1,7 @@
 // projection_batch.cpp -- get_angle_with_projections (projection.rs:17-194) with its resize_scale for batches of scans
 // (DESIGN.md section 4.12):
 //
-//   front end   scale_self on the colour scans (transfer.rs:66-91), one launch over the batch (projection_front.hip),
+//   front end   scale_self on the colour scans (transfer.rs:66-91), one launch over the batch (resize.hip),
 //               into the context's working buffer.  The dispatch is resize()'s (resize_dispatch, host_image.hpp); the tap
 //               tables of a fractional shrink are built when the context is created and stay on the device.
 //   sweep       the context's omr_batch_ctx for the working shape: gray (quirk B8) and threshold(127) fused into its
@@ -19,7 +19,6 @@
 #include "engine.hpp"
 #include "host_threads.hpp"
 #include "hough_host.hpp"
-#include "projection_front.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -28,10 +27,19 @@ namespace {
 
 const int kChunk = 256;  // scans per run of the host form's contexts
 
-// scale_self's size and resize()'s dispatch for it, on the host
+// scale_self's size and resize()'s dispatch for it, on the host (COPY: the working images are the scans)
 struct Working {
-    int wr = 0, wc = 0, mode = OMR_PROJECTION_FRONT_NONE, kx = 0, ky = 0;
-    bool area_mode = false;  // LINEAR only: INTER_AREA's bilinear emulation (never reached by scale_self)
+    int wr = 0, wc = 0;
+    ResizeDispatch d{ResizeDispatch::COPY, false, 1, 1};
+    int front_mode() const  // as omr_projection_batch_working_size and _info report it
+    {
+        switch (d.kind) {
+        case ResizeDispatch::LINEAR: return OMR_PROJECTION_FRONT_LINEAR;
+        case ResizeDispatch::AREA_INT: return OMR_PROJECTION_FRONT_AREA_INT;
+        case ResizeDispatch::AREA_GENERAL: return OMR_PROJECTION_FRONT_AREA_GENERAL;
+        default: return OMR_PROJECTION_FRONT_NONE;
+        }
+    }
 };
 
 int working_size(int rows, int cols, double scale, Working *w)
@@ -48,19 +56,7 @@ int working_size(int rows, int cols, double scale, Working *w)
     const int dc = (int)fc, dr = (int)fr;  // transfer.rs:70-71 `as i32`
     if (dr <= 0 || dc <= 0) return fail(OMR_ERR_ASSERT, "resize to an empty size");
     w->wr = dr, w->wc = dc;
-    const ResizeDispatch d = resize_dispatch(rows, cols, dr, dc, scale > 1.0 ? OMR_INTER_LINEAR : OMR_INTER_AREA);
-    switch (d.kind) {
-    case ResizeDispatch::COPY: break;  // the working images are the scans
-    case ResizeDispatch::LINEAR:
-        w->mode = OMR_PROJECTION_FRONT_LINEAR;
-        w->area_mode = d.area_mode;
-        break;
-    case ResizeDispatch::AREA_INT:
-        w->mode = OMR_PROJECTION_FRONT_AREA_INT;
-        w->kx = d.kx, w->ky = d.ky;
-        break;
-    case ResizeDispatch::AREA_GENERAL: w->mode = OMR_PROJECTION_FRONT_AREA_GENERAL; break;
-    }
+    w->d = resize_dispatch(rows, cols, dr, dc, scale > 1.0 ? OMR_INTER_LINEAR : OMR_INTER_AREA);
     return OMR_OK;
 }
 
@@ -76,7 +72,7 @@ struct omr_projection_batch {
     omr_batch_ctx *sweep = nullptr;
     hipStream_t s = nullptr;  // front end and result copies
     DevBuf work, best, vsd, hsd;
-    AreaTables area;  // OMR_PROJECTION_FRONT_AREA_GENERAL
+    AreaTables area;  // AREA_GENERAL
     std::vector<int32_t> h_best;
     std::mutex mu;
     ~omr_projection_batch()
@@ -98,23 +94,18 @@ int check_scans(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_s
     return OMR_OK;
 }
 
-// scale_self of n scans -> pb->work, on pb->s (nothing to do, and nothing written, in mode NONE)
+// scale_self of n scans -> pb->work, on pb->s (nothing to do, and nothing written, when the dispatch is COPY)
 int front_end(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n)
 {
     const Working &w = pb->w;
-    if (w.mode == OMR_PROJECTION_FRONT_NONE) return OMR_OK;
-    if (w.mode == OMR_PROJECTION_FRONT_LINEAR) {
-        OMR_HIP(launch_pf_linear(d_scans, scan_stride, step, pb->rows, pb->cols, pb->cn, n, pb->work.as<uint8_t>(), pb->wstride,
-                                 pb->wstep, w.wr, w.wc, w.area_mode, pb->s));
-        return OMR_OK;
-    }
-    PfArea p{};
-    p.src = d_scans, p.scan_stride = scan_stride, p.sstep = step;
-    p.dst = pb->work.as<uint8_t>(), p.out_stride = pb->wstride, p.dstep = pb->wstep;
-    p.cn = pb->cn, p.scols = pb->cols, p.drows = w.wr, p.dcols = w.wc, p.kx = w.kx, p.ky = w.ky;
-    const AreaTables &t = pb->area;
-    p.xtab = t.xt.as<AreaTap>(), p.xofs = t.xo.as<int32_t>(), p.ytab = t.yt.as<AreaTap>(), p.yofs = t.yo.as<int32_t>();
-    OMR_HIP(launch_pf_area(p, pb->tiling, n, pb->s));
+    if (w.d.kind == ResizeDispatch::COPY) return OMR_OK;
+    ResizeImgs im{};
+    im.src = d_scans, im.scan_stride = scan_stride, im.sstep = step;
+    im.dst = pb->work.as<uint8_t>(), im.out_stride = pb->wstride, im.dstep = pb->wstep;
+    im.cn = pb->cn, im.srows = pb->rows, im.scols = pb->cols, im.drows = w.wr, im.dcols = w.wc;
+    // INTER_AREA goes through the tile kernel: on a colour scan the per-byte gather is the whole cost
+    const bool area = w.d.kind != ResizeDispatch::LINEAR;
+    OMR_HIP(launch_resize(w.d, im, n, pb->s, pb->area.taps(), area ? &pb->tiling : nullptr));
     return OMR_OK;
 }
 
@@ -129,7 +120,7 @@ int run_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_st
         if ((rc = grow(&pb->hsd, sizeof(double) * (size_t)n * A))) return rc;
     }
     if ((rc = front_end(pb, d_scans, scan_stride, step, n))) return rc;
-    const bool resized = pb->w.mode != OMR_PROJECTION_FRONT_NONE;
+    const bool resized = pb->w.d.kind != ResizeDispatch::COPY;
     if (resized) OMR_HIP(hipStreamSynchronize(pb->s));  // the sweep runs on the batch context's own streams
     // projection.rs:29-32: RGB2GRAY and threshold(127) are fused into the sweep's loads
     if ((rc = omr_batch_run_device_cn(pb->sweep, resized ? pb->work.as<uint8_t>() : d_scans, resized ? pb->wstride : scan_stride,
@@ -239,7 +230,7 @@ int omr_projection_batch_working_size(int32_t rows, int32_t cols, double resize_
     Working w;
     int rc = working_size(rows, cols, resize_scale, &w);
     if (rc) return rc;
-    *wrows = w.wr, *wcols = w.wc, *front_mode = w.mode;
+    *wrows = w.wr, *wcols = w.wc, *front_mode = w.front_mode();
     return OMR_OK;
 }
 
@@ -266,16 +257,16 @@ int omr_projection_batch_create(int32_t rows, int32_t cols, int32_t channels, ui
     pb->h_best.assign((size_t)max_scans, 0);
     OMR_HIP(hipStreamCreateWithFlags(&pb->s, hipStreamNonBlocking));
     OMR_HIP(pb->best.alloc(sizeof(int32_t) * (size_t)max_scans));
-    if (w.mode != OMR_PROJECTION_FRONT_NONE) {
+    if (w.d.kind != ResizeDispatch::COPY) {
         pb->wstep = ((int64_t)w.wc * channels + 3) & ~(int64_t)3;
         pb->wstride = ((int64_t)w.wr * pb->wstep + 255) & ~(int64_t)255;
         OMR_HIP(pb->work.alloc((size_t)max_scans * pb->wstride));
     }
-    if (w.mode == OMR_PROJECTION_FRONT_AREA_GENERAL) {  // resizeArea_'s tap tables, once per context
+    if (w.d.kind == ResizeDispatch::AREA_GENERAL) {  // resizeArea_'s tap tables, once per context
         if ((rc = pb->area.build(cols, w.wc, rows, w.wr, channels, nullptr))) return rc;
         pb->tiling = pf_area_tiling(channels, w.wc, 0, &pb->area.h_xt, &pb->area.h_xo, &pb->area.h_yt);
-    } else if (w.mode == OMR_PROJECTION_FRONT_AREA_INT) {
-        pb->tiling = pf_area_tiling(channels, w.wc, w.kx, nullptr, nullptr, nullptr);
+    } else if (w.d.kind == ResizeDispatch::AREA_INT) {
+        pb->tiling = pf_area_tiling(channels, w.wc, w.d.kx, nullptr, nullptr, nullptr);
     }
     // the sweep of the working shape at unit scale (projection.rs:47-65), whatever kernels the context picks for it
     if ((rc = omr_batch_create(w.wr, w.wc, max_angle, step, 1.0, device, 1, &pb->sweep))) return rc;
@@ -292,7 +283,7 @@ int omr_projection_batch_info(omr_projection_batch *pb, int32_t *wrows, int32_t 
     if (!pb) return fail(OMR_ERR_BADARG, "null context");
     if (wrows) *wrows = pb->w.wr;
     if (wcols) *wcols = pb->w.wc;
-    if (front_mode) *front_mode = pb->w.mode;
+    if (front_mode) *front_mode = pb->w.front_mode();
     if (candidates) *candidates = pb->A;
     return OMR_OK;
 }
@@ -311,7 +302,7 @@ int omr_projection_batch_front_device(omr_projection_batch *pb, const uint8_t *d
     std::lock_guard<std::mutex> lk(pb->mu);
     OMR_HIP(hipSetDevice(pb->device));
     rc = front_end(pb, d_scans, scan_stride_bytes, step_bytes, n);
-    const bool resized = pb->w.mode != OMR_PROJECTION_FRONT_NONE;  // NONE: the working images are the scans
+    const bool resized = pb->w.d.kind != ResizeDispatch::COPY;  // NONE: the working images are the scans
     for (int i = 0; rc == OMR_OK && i < n; i++) {
         const uint8_t *from = resized ? pb->work.as<uint8_t>() + (size_t)i * pb->wstride : d_scans + (size_t)i * scan_stride_bytes;
         if (hipMemcpy2DAsync(d_small + (size_t)i * small_stride_bytes, (size_t)small_step_bytes, from,

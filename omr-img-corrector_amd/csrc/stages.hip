@@ -1,14 +1,13 @@
 // stages.hip -- the per-image stage kernels either side of the sweep: the front end
-// of omr.rs:87-139 (gray, erode x3, INTER_AREA shrink), threshold and resize; the final deskew warp is
-// warp_affine.hip.  All are HBM-bound byte work: the tuned forms move 4 or 16 pixels per lane (dword loads /
-// stores), stage reuse through LDS and keep OpenCV 4.6.0's integer arithmetic bit for bit.  One launcher per
-// stage picks the tuned kernel where layout and alignment allow and otherwise the generic form (any channel
-// count, one thread per destination byte) that sits next to it.
+// of omr.rs:87-139 (gray, erode x3) and threshold; the INTER_AREA shrink and every other resize are resize.hip, the
+// final deskew warp is warp_affine.hip.  All are HBM-bound byte work: the tuned forms move 4 or 16 pixels per lane
+// (dword loads / stores), stage reuse through LDS and keep OpenCV 4.6.0's integer arithmetic bit for bit.  One
+// launcher per stage picks the tuned kernel where layout and alignment allow and otherwise the generic form (one
+// thread per destination byte) that sits next to it.
 #include <hip/hip_runtime.h>
 
+#include "bgr.hpp"
 #include "kernels.hpp"
-#include "resize_linear.hpp"
-#include "warp_fixed.hpp"
 
 namespace omr {
 
@@ -32,7 +31,7 @@ __global__ __launch_bounds__(256) void rgb2gray3_x4_kernel(const uint8_t *__rest
         *(uint32_t *)D = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
     } else {
         for (int j = 0; x + j < cols; j++)
-            D[j] = (uint8_t)((S[3 * j] * 9798 + S[3 * j + 1] * 19235 + S[3 * j + 2] * 3735 + (1 << 14)) >> 15);
+            D[j] = (uint8_t)bgr_gray(S[3 * j], S[3 * j + 1], S[3 * j + 2]);
     }
 }
 
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(256) void rgb2gray_kernel(const uint8_t *__restrict
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x < cols) {
         const uint8_t *S = src + (int64_t)y * sstep + (int64_t)x * cn;
-        dst[(int64_t)y * dstep + x] = (uint8_t)((S[0] * 9798 + S[1] * 19235 + S[2] * 3735 + (1 << 14)) >> 15);
+        dst[(int64_t)y * dstep + x] = (uint8_t)bgr_gray(S[0], S[1], S[2]);
     }
 }
 
@@ -205,199 +204,6 @@ hipError_t launch_erode3x_cross(const uint8_t *d_src, int64_t sstep, int rows, i
 }
 
 // ------------------------------------------------------------------------------------------
-// resize INTER_AREA, integer factor k (OpenCV resizeAreaFast_), 1 channel, full blocks only
-// (k divides both sizes): coalesced row loads, k*k sum per output pixel from LDS.
-#define RA_OW 64
-#define RA_OH 4
-#define RA_MAXK 8
-
-__global__ __launch_bounds__(256) void resize_area_int_c1_kernel(const uint8_t *__restrict__ src, int64_t sstep,
-                                                                 uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                                 int dcols, int k)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t tile[RA_OH * RA_MAXK][RA_OW * RA_MAXK + 4];
-    const int ox0 = blockIdx.x * RA_OW, oy0 = blockIdx.y * RA_OH;
-    const int iw = min(RA_OW, dcols - ox0) * k, ih = min(RA_OH, drows - oy0) * k;
-    const uint8_t *S = src + (int64_t)oy0 * k * sstep + (int64_t)ox0 * k;
-    if ((((uintptr_t)S | (uintptr_t)sstep) & 3) == 0) {  // dword loads: a quarter of the load instructions
-        const int iw4 = iw >> 2;
-        for (int i = threadIdx.x; i < iw4 * ih; i += 256) {
-            const int ly = i / iw4, lq = i - ly * iw4;
-            *(uint32_t *)&tile[ly][lq * 4] = *(const uint32_t *)(S + (int64_t)ly * sstep + lq * 4);
-        }
-        for (int i = threadIdx.x; i < (iw & 3) * ih; i += 256) {  // last, partial block of a row
-            const int ly = i / (iw & 3), lx = (iw & ~3) + i % (iw & 3);
-            tile[ly][lx] = S[(int64_t)ly * sstep + lx];
-        }
-    } else {
-        for (int i = threadIdx.x; i < iw * ih; i += 256) {
-            const int ly = i / iw, lx = i - ly * iw;
-            tile[ly][lx] = S[(int64_t)ly * sstep + lx];
-        }
-    }
-    __syncthreads();
-    const int lx = threadIdx.x & (RA_OW - 1), ly = threadIdx.x / RA_OW;
-    const int ox = ox0 + lx, oy = oy0 + ly;
-    if (ox < dcols && oy < drows) {
-        int sum = 0;
-        for (int yy = 0; yy < k; yy++)
-            for (int xx = 0; xx < k; xx++) sum += tile[ly * k + yy][lx * k + xx];
-        uint8_t out;
-        if (k == 2) out = (uint8_t)((sum + 2) >> 2);
-        else out = sat_u8((int)rintf((float)sum * (1.f / (float)(k * k))));
-        dst[(int64_t)oy * dstep + ox] = out;
-    }
-}
-
-// The same reduction with the column sums taken first: a lane adds the k source rows of one dword column
-// straight from global memory (k coalesced dword loads in flight, 4 pixels each, byte pairs widened to
-// u16 with two masks and added with v_pk_add_u16), parks four u16 column sums in LDS, and after the
-// barrier a lane per output pixel adds k neighbouring column sums -- 2k LDS accesses per output pixel
-// instead of k*k byte reads, and no staging of the raw tile.
-#define RB_OW 64
-#define RB_OH 4
-#define RB_MAXK 16
-
-__global__ __launch_bounds__(256) void resize_area_int_colsum_kernel(const uint8_t *__restrict__ src, int64_t sstep,
-                                                                     uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                                     int dcols, int k)
-{
-    __shared__ uint16_t colsum[RB_OH][RB_OW * RB_MAXK + 8];
-    const int ox0 = blockIdx.x * RB_OW, oy0 = blockIdx.y * RB_OH;
-    const int ow = min(RB_OW, dcols - ox0), oh = min(RB_OH, drows - oy0);
-    const int iw = ow * k, nq = (iw + 3) >> 2;  // source pixels / dword columns of the tile (iw may end inside a dword)
-    const uint8_t *S = src + (int64_t)oy0 * k * sstep + (int64_t)ox0 * k;  // 4-byte aligned: ox0 * k is a multiple of 64
-    for (int i = threadIdx.x; i < nq * oh; i += 256) {
-        const int ly = i / nq, q = i - ly * nq;
-        const uint8_t *P = S + (int64_t)ly * k * sstep + q * 4;
-        uint32_t e = 0, o = 0;  // (px0, px2) and (px1, px3) as u16 pairs
-        for (int yy = 0; yy < k; yy++) {
-            const uint32_t v = *(const uint32_t *)(P + (int64_t)yy * sstep);  // may read past iw inside the row pitch: unused
-            e += v & 0x00ff00ffu;
-            o += (v >> 8) & 0x00ff00ffu;
-        }
-        uint16_t *C = &colsum[ly][q * 4];
-        C[0] = (uint16_t)e;
-        C[1] = (uint16_t)o;
-        C[2] = (uint16_t)(e >> 16);
-        C[3] = (uint16_t)(o >> 16);
-    }
-    __syncthreads();
-    const int lx = threadIdx.x & (RB_OW - 1), ly = threadIdx.x / RB_OW;
-    if (lx < ow && ly < oh) {
-        int sum = 0;
-        for (int xx = 0; xx < k; xx++) sum += colsum[ly][lx * k + xx];
-        uint8_t out;
-        if (k == 2) out = (uint8_t)((sum + 2) >> 2);
-        else out = sat_u8((int)rintf((float)sum * (1.f / (float)(k * k))));
-        dst[(int64_t)(oy0 + ly) * dstep + ox0 + lx] = out;
-    }
-}
-
-// resize INTER_AREA, integer factors (OpenCV resizeAreaFast_): transfer.rs:66-91, omr.rs:114-126.
-// One thread per destination byte (x runs over dcols*cn).
-__global__ __launch_bounds__(256) void resize_area_int_kernel(const uint8_t *__restrict__ src, int64_t sstep,
-                                                              int srows, int scols, int cn,
-                                                              uint8_t *__restrict__ dst, int64_t dstep, int drows,
-                                                              int dcols, int kx, int ky)
-{
-    const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    const int dwidth = dcols * cn, swidth = scols * cn;
-    if (dx >= dwidth) return;
-    const int sy0 = dy * ky;
-    uint8_t out;
-    if (sy0 >= srows) {
-        out = 0;
-    } else {
-        const int dwidth1 = (scols / kx) * cn;
-        const int w = sy0 + ky <= srows ? dwidth1 : 0;
-        const int sx0 = kx * (dx / cn) * cn + dx % cn;
-        if (dx < w) {
-            int sum = 0;
-            for (int sy = 0; sy < ky; sy++)
-                for (int sx = 0; sx < kx; sx++) sum += src[(int64_t)(sy0 + sy) * sstep + sx0 + sx * cn];
-            if (kx == 2 && ky == 2) out = (uint8_t)((sum + 2) >> 2);
-            else out = sat_u8((int)rintf((float)sum * (1.f / (float)(kx * ky))));
-        } else {
-            int sum = 0, count = 0;
-            for (int sy = 0; sy < ky; sy++) {
-                if (sy0 + sy >= srows) break;
-                for (int sx = 0; sx < kx * cn; sx += cn) {
-                    if (sx0 + sx >= swidth) break;
-                    sum += src[(int64_t)(sy0 + sy) * sstep + sx0 + sx];
-                    count++;
-                }
-            }
-            out = count ? sat_u8((int)rintf((float)sum / (float)count)) : 0;
-        }
-    }
-    dst[(int64_t)dy * dstep + dx] = out;
-}
-
-hipError_t launch_resize_area_int(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn,
-                                  uint8_t *d_dst, int64_t dstep, int drows, int dcols, int kx, int ky,
-                                  hipStream_t s)
-{
-    const bool full = cn == 1 && kx == ky && kx >= 2 && drows * ky == srows && dcols * kx == scols;
-    // the dword loads of the last column may run up to 3 bytes past the last source pixel of a row: the row pitch
-    // must cover them (always true for a pitch that is a multiple of 4)
-    if (full && kx <= RB_MAXK && (sstep & 3) == 0 && ((uintptr_t)d_src & 3) == 0) {
-        hipLaunchKernelGGL(resize_area_int_colsum_kernel, dim3((dcols + RB_OW - 1) / RB_OW, (drows + RB_OH - 1) / RB_OH),
-                           dim3(256), 0, s, d_src, sstep, d_dst, dstep, drows, dcols, kx);
-        return hipGetLastError();
-    }
-    if (full && kx <= RA_MAXK) {
-        hipLaunchKernelGGL(resize_area_int_c1_kernel, dim3((dcols + RA_OW - 1) / RA_OW, (drows + RA_OH - 1) / RA_OH),
-                           dim3(256), 0, s, d_src, sstep, d_dst, dstep, drows, dcols, kx);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(resize_area_int_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src, sstep,
-                       srows, scols, cn, d_dst, dstep, drows, dcols, kx, ky);
-    return hipGetLastError();
-}
-
-// resize INTER_AREA, general shrink (OpenCV resizeArea_<uchar,float>): per destination byte the
-// same float accumulation order as ResizeArea_Invoker: for each source row tap (ascending) the
-// row sum buf = sum_k S*alpha_k (ascending k), then sum (+)= beta*buf.  xofs/yofs: CSR offsets
-// of the taps of every destination column / row.
-__global__ __launch_bounds__(256) void resize_area_general_kernel(const uint8_t *__restrict__ src, int64_t sstep,
-                                                                  int cn, uint8_t *__restrict__ dst, int64_t dstep,
-                                                                  int drows, int dcols,
-                                                                  const AreaTap *__restrict__ xtab,
-                                                                  const int32_t *__restrict__ xofs,
-                                                                  const AreaTap *__restrict__ ytab,
-                                                                  const int32_t *__restrict__ yofs)
-{
-    const int dxb = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    if (dxb >= dcols * cn) return;
-    const int dx = dxb / cn, c = dxb % cn;
-    float sum = 0.f;
-    bool first = true;
-    for (int j = yofs[dy]; j < yofs[dy + 1]; j++) {
-        const float beta = ytab[j].alpha;
-        const uint8_t *S = src + (int64_t)ytab[j].si * sstep + c;
-        float buf = 0.f;
-        for (int k = xofs[dx]; k < xofs[dx + 1]; k++) buf += (float)S[xtab[k].si] * xtab[k].alpha;
-        if (first) {
-            sum = beta * buf;  // ResizeArea_Invoker assigns on the first tap of a destination row
-            first = false;
-        } else {
-            sum += beta * buf;
-        }
-    }
-    dst[(int64_t)dy * dstep + dxb] = sat_u8((int)rintf(sum));
-}
-
-hipError_t launch_resize_area_general(const uint8_t *d_src, int64_t sstep, int cn, uint8_t *d_dst, int64_t dstep,
-                                      int drows, int dcols, const AreaTap *d_xtab, const int32_t *d_xofs,
-                                      const AreaTap *d_ytab, const int32_t *d_yofs, hipStream_t s)
-{
-    hipLaunchKernelGGL(resize_area_general_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src,
-                       sstep, cn, d_dst, dstep, drows, dcols, d_xtab, d_xofs, d_ytab, d_yofs);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------
 // transfer.rs:294-301 / omr.rs:129-139: threshold(127, 255, THRESH_BINARY), one pixel per lane
 __global__ __launch_bounds__(256) void threshold_kernel(const uint8_t *__restrict__ src, int64_t sstep, int rows,
                                                         int cols, uint8_t *__restrict__ dst, int64_t dstep,
@@ -444,50 +250,6 @@ hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int c
     }
     hipLaunchKernelGGL(threshold_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d_src, sstep, rows, cols,
                        d_dst, dstep, thresh, maxval);
-    return hipGetLastError();
-}
-
-// resize(INTER_LINEAR) and INTER_AREA's bilinear emulation when an axis enlarges (OpenCV resizeGeneric_ with
-// HResizeLinear<uchar,int,short,2048> / VResizeLinear<uchar,int,short,FixedPtCast<22>>): scale_self with
-// scale > 1 (transfer.rs:66-91) and path 2's unclamped scale (omr.rs:60-82,114-126, quirk B7).  Every thread
-// rebuilds its two coefficient pairs with the expressions of resize.cpp (double products, float fractions,
-// saturate_cast<short>(c * 2048) with round-half-even; the file is built -ffp-contract=off): 11-bit
-// horizontal taps on the two source rows, then (((b0*(h0>>4))>>16) + ((b1*(h1>>4))>>16) + 2) >> 2.
-// sx is monotone in dx, so "dx >= xmax" (the columns that copy S[sx] * 2048) is just sx + 1 >= scols.
-__global__ __launch_bounds__(256) void resize_linear_kernel(const uint8_t *__restrict__ src, int64_t sstep, int srows,
-                                                            int scols, int cn, uint8_t *__restrict__ dst, int64_t dstep,
-                                                            int drows, int dcols, double scale_x, double inv_scale_x,
-                                                            double scale_y, double inv_scale_y, int area_mode)
-{
-    const int dxb = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    if (dxb >= dcols * cn) return;
-    const int dx = dxb / cn, c = dxb - dx * cn;
-    int sx, a0, a1, sy, b0, b1;
-    bool edge, unused;
-    linear_coef(dx, scale_x, inv_scale_x, scols, area_mode != 0, sx, a0, a1, edge);
-    linear_coef(dy, scale_y, inv_scale_y, 0, area_mode != 0, sy, b0, b1, unused);
-    const int sy0 = max(0, min(srows - 1, sy)), sy1 = max(0, min(srows - 1, sy + 1));
-    const uint8_t *S0 = src + (int64_t)sy0 * sstep + (int64_t)sx * cn + c;
-    const uint8_t *S1 = src + (int64_t)sy1 * sstep + (int64_t)sx * cn + c;
-    int h0, h1;
-    if (!edge) {
-        h0 = (int)S0[0] * a0 + (int)S0[cn] * a1;
-        h1 = (int)S1[0] * a0 + (int)S1[cn] * a1;
-    } else {
-        h0 = (int)S0[0] * 2048;
-        h1 = (int)S1[0] * 2048;
-    }
-    dst[(int64_t)dy * dstep + dxb] = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
-}
-
-hipError_t launch_resize_linear(const uint8_t *d_src, int64_t sstep, int srows, int scols, int cn, uint8_t *d_dst,
-                                int64_t dstep, int drows, int dcols, bool area_mode, hipStream_t s)
-{
-    const double inv_scale_x = (double)dcols / scols, inv_scale_y = (double)drows / srows;
-    const double scale_x = 1. / inv_scale_x, scale_y = 1. / inv_scale_y;
-    hipLaunchKernelGGL(resize_linear_kernel, dim3((dcols * cn + 255) / 256, drows), dim3(256), 0, s, d_src, sstep, srows,
-                       scols, cn, d_dst, dstep, drows, dcols, scale_x, inv_scale_x, scale_y, inv_scale_y,
-                       area_mode ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -673,6 +673,15 @@ def test_resize_area_device_all_branches(oracle):
         torch.cuda.synchronize()
         exp = oracle.resize_area(img, dr, dc)
         assert (out.cpu().numpy() == exp).all(), (dr, dc)
+    # colour, integer factors that differ per axis (ky = 3, kx = 4), a row pitch that is no multiple of 4
+    img3 = rng.integers(0, 256, (12, 20, 3), dtype=np.uint8)
+    buf = np.full((12, 61), 7, np.uint8)
+    buf[:, :60] = img3.reshape(12, 60)
+    d3 = torch.from_numpy(buf).to("cuda:0")
+    out3 = torch.zeros((4, 5, 3), dtype=torch.uint8, device="cuda:0")
+    check(lib().omr_resize_area_device(d3.data_ptr(), 61, 12, 20, 3, out3.data_ptr(), 15, 4, 5, None))
+    torch.cuda.synchronize()
+    assert (out3.cpu().numpy() == oracle.resize_area(img3, 4, 5)).all()
 
 
 def test_fused_erode_fast_path_edges(oracle):

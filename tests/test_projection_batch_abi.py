@@ -133,6 +133,22 @@ def test_every_branch_of_the_resize_dispatch(rows, cols, scale, path, k):
     assert _ws(rows, cols, scale) == (0, dr, dc, mode)
 
 
+def test_integer_area_factors_divide_the_source_exactly():
+    """The integer INTER_AREA kernels carry no partial-block arithmetic and launch_resize refuses d * k != s.  That is
+    sound only if resize()'s test for integer factors, |1 / (d / s) - lrint(.)| < DBL_EPSILON, passes for exact
+    multiples alone at every size an entry point admits (check_image_shape: <= 32766).  Every source size up to
+    2048, the A4 sides and the largest size, against every d below it (the test is per axis, so squares cover it)."""
+    fast = 0
+    for s in list(range(1, 2049)) + [2480, 3508, 32766]:
+        for d in range(1, s):
+            path, kx, ky = _resize_rule(s, s, d, d, linear=False)
+            if path == "AREA_INT":
+                assert kx == ky == s // d and d * kx == s, (s, d, kx)
+                fast += 1
+    assert fast > 2048  # integer factors were met
+    assert _resize_rule(49, 49, 1, 1, linear=False)[0] == "AREA_GENERAL"  # the converse is false, as in OpenCV
+
+
 def test_working_size_argument_errors():
     L = _lib.lib()
     r, c, m = C.c_int32(), C.c_int32(), C.c_int32()
