@@ -476,6 +476,36 @@ int omr_morph_batch_device(const uint8_t *d_src, int32_t n, int64_t src_stride_b
                            int32_t ay, int32_t iterations, uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step,
                            void *stream);
 
+/* ---- the projection pictures (transfer.rs:337-376, :409-455) ---------------------------
+ * The input is 8-bit, one channel, ANY values (OMR_ERR_ASSERT for another channel count, an empty image or a side of
+ * 32767 or more); each picture has the input's size.  What the reference's loops come to:
+ *   horizontal, row r:  k0 = index of the first pixel == 255 (cols when the row has none), K = number of pixels != 255;
+ *                       columns [0, k0) keep the source bytes, [k0, K) are 0, [K, cols) are 255;
+ *   vertical, column c: n = number of pixels <= 127; rows [0, rows - n) are 255, rows [rows - n, rows) are 0.
+ * On a strictly 0 / 255 image the black run of row r is omr_get_horizontal_projection()[r] long and the bar of column c
+ * omr_get_vertical_projection()[c] high (those count == 0); on any other image the three predicates differ.
+ * Either output may be NULL, not both (OMR_ERR_BADARG); a picture is the same whether or not the other is asked for.
+ * OMR_ERR_BADARG besides: a null image or source pointer, n <= 0, a step below cols, a picture stride below rows * step,
+ * a negative source stride (any stride >= 0 is taken: 0 draws one scan n times), d_src == a destination.  Every argument
+ * is checked before any device work.  Source and destinations MUST NOT OVERLAP; only equal pointers are detected.
+ * The bytes of a destination row past `cols` are never written: the caller's pitch padding stays as it was.
+ * The device forms enqueue on `stream` only.  A call that draws the horizontal picture alone returns without
+ * synchronising; one that draws the vertical picture takes a per-call table of column counts (n x cols uint32) and
+ * SYNCHRONISES `stream` before it returns, because the table is given back on return (as omr_rotate_batch_device_ex).
+ * Performance note: rows are read and written as dwords when the image's base, stride and step are multiples of 4;
+ * any other layout takes byte accesses -- same pictures, slower. */
+/* transfer_thresh_binary_to_{horizontal,vertical}_projection; owned images out (omr_image_free each) */
+int omr_projection_pictures(const omr_image *src_u8c1, omr_image_owned *horizontal, omr_image_owned *vertical);
+/* device-resident */
+int omr_projection_pictures_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols,
+                                   uint8_t *d_horizontal, int64_t h_step, uint8_t *d_vertical, int64_t v_step, void *stream);
+/* n scans of one shape, scan i at d_src + i * src_stride_bytes; its pictures at d_horizontal + i * h_stride_bytes and
+ * d_vertical + i * v_stride_bytes, byte for byte the per-call form's.  One set of launches for the batch (per 65535 scans). */
+int omr_projection_pictures_batch_device(const uint8_t *d_src, int32_t n, int64_t src_stride_bytes, int64_t src_step,
+                                         int32_t rows, int32_t cols, uint8_t *d_horizontal, int64_t h_stride_bytes,
+                                         int64_t h_step, uint8_t *d_vertical, int64_t v_stride_bytes, int64_t v_step,
+                                         void *stream);
+
 /* ---- Hough-line deskew path ---------------------------------------------
  * OpenCV 4.6.0 semantics restated on the GPU: Canny is exact (integer stencils + a set-valued
  * hysteresis); HoughLinesP keeps hough.cpp's point order (cv::RNG seed 2^64-1), float32 votes and

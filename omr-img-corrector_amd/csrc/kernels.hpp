@@ -226,4 +226,19 @@ hipError_t launch_morph_rect(const MorphImg &im, int op, int kw, int kh, int ax,
 hipError_t launch_morph_spans_global(const MorphImg &im, int op, const int32_t *d_spans, int kh, int ax, int ay,
                                      hipStream_t s);
 
+// ---- the projection pictures (projpic.hip; the callers are in oics_host.cpp) -----------------------------------
+// `n` one-channel scans of rows x cols, scan i at src + i * sstride, its horizontal picture at hdst + i * hstride, its
+// vertical one at vdst + i * vstride (n <= 65535); a launch only touches the pointers of its own picture
+struct ProjPicImg {
+    const uint8_t *src;
+    uint8_t *hdst, *vdst;
+    int64_t sstride, sstep, hstride, hstep, vstride, vstep;
+    int rows, cols, n;
+};
+// transfer.rs:337-376: every picture row from one read of its source row
+hipError_t launch_projpic_rows(const ProjPicImg &p, hipStream_t s);
+// transfer.rs:409-455: pixels <= 127 per column added onto d_counts (n x cols uint32, zeroed by the caller), then the bars
+hipError_t launch_projpic_col_counts(const ProjPicImg &p, uint32_t *d_counts, hipStream_t s);
+hipError_t launch_projpic_col_bars(const ProjPicImg &p, const uint32_t *d_counts, hipStream_t s);
+
 }  // namespace omr

@@ -14,6 +14,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -713,6 +714,101 @@ int omr_morph(const omr_image *src, int32_t op, int32_t shape, int32_t kw, int32
                            out.ptr(), 0, out.step(), st.s)))
         return rc;
     return give_owned(out, dst, st.s);
+}
+
+// ---- transfer.rs:337-376 / :409-455: the projection pictures (kernels: projpic.hip) -------------------------------
+// the checks of the two device forms (n = 1, strides 0 for the per-call one), in the header's order
+static int projpic_check(const uint8_t *d_src, int n, int64_t sstride, int64_t sstep, int rows, int cols, const uint8_t *d_h,
+                         int64_t hstride, int64_t hstep, const uint8_t *d_v, int64_t vstride, int64_t vstep, bool batch)
+{
+    if (n <= 0) return fail(OMR_ERR_BADARG, "batch of %d scans", n);
+    if (!d_src) return fail(OMR_ERR_BADARG, "null device pointer");
+    if (!d_h && !d_v) return fail(OMR_ERR_BADARG, "no picture asked for: both outputs are null");
+    int rc = check_image_shape(rows, cols);
+    if (rc) return rc;
+    if (sstep < cols || (d_h && hstep < cols) || (d_v && vstep < cols)) return fail(OMR_ERR_BADARG, "step too small");
+    if (batch) {
+        if (sstride < 0) return fail(OMR_ERR_BADARG, "negative source stride");
+        if ((d_h && hstride < rows * hstep) || (d_v && vstride < rows * vstep))
+            return fail(OMR_ERR_BADARG, "picture stride smaller than a picture");
+    }
+    if (d_src == d_h || d_src == d_v || (d_h && d_h == d_v)) return fail(OMR_ERR_BADARG, "the pictures cannot be made in place");
+    return OMR_OK;
+}
+
+// arguments already checked.  The horizontal picture only enqueues; the vertical one takes the table of column counts
+// from the block cache and synchronises `s`, because the table goes back on return
+static int projpic_device(const uint8_t *d_src, int n, int64_t sstride, int64_t sstep, int rows, int cols, uint8_t *d_h,
+                          int64_t hstride, int64_t hstep, uint8_t *d_v, int64_t vstride, int64_t vstep, hipStream_t s)
+{
+    PoolScope scope(s);
+    DevBuf counts;
+    if (d_v) {
+        if (counts.alloc((size_t)n * cols * sizeof(uint32_t)) != hipSuccess)
+            return fail(OMR_ERR_NOMEM, "out of device memory for the column counts of %d scans", n);
+        OMR_HIP(hipMemsetAsync(counts.p, 0, (size_t)n * cols * sizeof(uint32_t), s));
+    }
+    for (int i0 = 0; i0 < n; i0 += 65535) {
+        ProjPicImg p{};
+        p.n = std::min(n - i0, 65535);
+        p.rows = rows, p.cols = cols;
+        p.src = d_src + i0 * sstride, p.sstride = sstride, p.sstep = sstep;
+        if (d_h) {
+            p.hdst = d_h + i0 * hstride, p.hstride = hstride, p.hstep = hstep;
+            OMR_HIP(launch_projpic_rows(p, s));
+        }
+        if (d_v) {
+            p.vdst = d_v + i0 * vstride, p.vstride = vstride, p.vstep = vstep;
+            OMR_HIP(launch_projpic_col_counts(p, counts.as<uint32_t>() + (size_t)i0 * cols, s));
+            OMR_HIP(launch_projpic_col_bars(p, counts.as<uint32_t>() + (size_t)i0 * cols, s));
+        }
+    }
+    if (d_v) OMR_HIP(hipStreamSynchronize(s));
+    return OMR_OK;
+}
+
+int omr_projection_pictures_batch_device(const uint8_t *d_src, int32_t n, int64_t src_stride_bytes, int64_t src_step,
+                                         int32_t rows, int32_t cols, uint8_t *d_horizontal, int64_t h_stride_bytes,
+                                         int64_t h_step, uint8_t *d_vertical, int64_t v_stride_bytes, int64_t v_step,
+                                         void *stream)
+{
+    int rc = projpic_check(d_src, n, src_stride_bytes, src_step, rows, cols, d_horizontal, h_stride_bytes, h_step, d_vertical,
+                           v_stride_bytes, v_step, true);
+    if (rc || (rc = have_device())) return rc;
+    return projpic_device(d_src, n, src_stride_bytes, src_step, rows, cols, d_horizontal, h_stride_bytes, h_step, d_vertical,
+                          v_stride_bytes, v_step, (hipStream_t)stream);
+}
+
+int omr_projection_pictures_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, uint8_t *d_horizontal,
+                                   int64_t h_step, uint8_t *d_vertical, int64_t v_step, void *stream)
+{
+    int rc = projpic_check(d_src, 1, 0, src_step, rows, cols, d_horizontal, 0, h_step, d_vertical, 0, v_step, false);
+    if (rc || (rc = have_device())) return rc;
+    return projpic_device(d_src, 1, 0, src_step, rows, cols, d_horizontal, 0, h_step, d_vertical, 0, v_step,
+                          (hipStream_t)stream);
+}
+
+int omr_projection_pictures(const omr_image *src, omr_image_owned *horizontal, omr_image_owned *vertical)
+{
+    int rc = check_image(src, cn_one);
+    if (rc) return rc;
+    if (!horizontal && !vertical) return fail(OMR_ERR_BADARG, "no picture asked for: both outputs are null");
+    int dev;
+    if ((rc = current_device(&dev))) return rc;
+    LeasedStream st;
+    if ((rc = st.create())) return rc;
+    DevImage in, h, v;
+    if ((rc = in.upload(src, st.s))) return rc;
+    if (horizontal && (rc = h.alloc(in.rows, in.cols, 1))) return rc;
+    if (vertical && (rc = v.alloc(in.rows, in.cols, 1))) return rc;
+    if ((rc = projpic_device(in.ptr(), 1, 0, in.step(), in.rows, in.cols, h.ptr(), 0, h.step(), v.ptr(), 0, v.step(), st.s)))
+        return rc;
+    if (horizontal && (rc = give_owned(h, horizontal, st.s))) return rc;
+    if (vertical && (rc = give_owned(v, vertical, st.s))) {
+        if (horizontal) omr_image_free(horizontal);
+        return rc;
+    }
+    return OMR_OK;
 }
 
 // ---- device-resident stages --------------------------------------------------------------------

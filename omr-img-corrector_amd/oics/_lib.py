@@ -146,6 +146,12 @@ SYMBOLS = {
     "omr_morph_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "omr_projection_pictures": (C.c_int, [C.POINTER(OmrImage), C.POINTER(OmrImageOwned), C.POINTER(OmrImageOwned)]),
+    "omr_projection_pictures_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "omr_projection_pictures_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                       C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                       C.c_void_p]),
     "omr_canny": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_hough_lines_p": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, i32p,
                                     C.c_int32, i32p]),

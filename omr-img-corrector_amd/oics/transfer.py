@@ -154,6 +154,41 @@ def get_projection_standard_deviations(src):
     return v.value, h.value
 
 
+def projection_pictures(src, horizontal=True, vertical=True):
+    """omr_projection_pictures: (horizontal picture, vertical picture) of an 8-bit one-channel image of any values, each
+    a TransformableMatrix of the image's size -- or None for a picture that was not asked for (not both)."""
+    a, im = as_image(_mat(src))
+    h, v = OmrImageOwned(), OmrImageOwned()
+    check(lib().omr_projection_pictures(C.byref(im), C.byref(h) if horizontal else None, C.byref(v) if vertical else None))
+    # both images are taken over before either is wrapped, so neither of the library's buffers is lost
+    mats = [_take_owned(o) if want else None for o, want in ((h, horizontal), (v, vertical))]
+    return tuple(None if m is None else TransformableMatrix(m) for m in mats)
+
+
+def transfer_thresh_binary_to_horizontal_projection(src):
+    """transfer.rs:337-376: per row, the pixels before the first 255 stay, then as many 0 as the row has pixels != 255
+    in all, then 255"""
+    return projection_pictures(src, vertical=False)[0]
+
+
+def transfer_thresh_binary_to_vertical_projection(src):
+    """transfer.rs:409-455: per column, a black bar from the bottom edge as high as the column has pixels <= 127"""
+    return projection_pictures(src, horizontal=False)[1]
+
+
+def projection_pictures_batch_device(d_src, n, src_stride_bytes, src_step, rows, cols, d_horizontal, h_stride_bytes, h_step,
+                                     d_vertical, v_stride_bytes, v_step, stream=None):
+    """omr_projection_pictures_batch_device: n same-shape device-resident one-channel scans (d_src, d_horizontal,
+    d_vertical: device addresses as ints; 0 / None for a picture that is not wanted, not both), scan i's pictures at
+    d_* + i * *_stride_bytes, byte for byte omr_projection_pictures_device's.  Synchronises `stream` before returning
+    when the vertical picture is asked for."""
+    check(lib().omr_projection_pictures_batch_device(
+        C.c_void_p(int(d_src)), int(n), int(src_stride_bytes), int(src_step), int(rows), int(cols),
+        C.c_void_p(int(d_horizontal)) if d_horizontal else None, int(h_stride_bytes), int(h_step),
+        C.c_void_p(int(d_vertical)) if d_vertical else None, int(v_stride_bytes), int(v_step),
+        C.c_void_p(int(stream)) if stream else None))
+
+
 def rotate_mat(src, angle, scale, flags, border_mode=0, border_value=(255.0, 255.0, 255.0, 0.0),
                clip_strategy=RotateClipStrategy.DEFAULT):
     """transfer.rs:459-523 through omr_rotate_ex: every warpAffine flag (INTER_NEAREST / LINEAR / CUBIC / AREA /

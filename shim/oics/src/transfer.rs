@@ -1,6 +1,6 @@
 //! `oics::transfer` (reference: packages/lib/src/transfer.rs) over the C ABI.
 //! File decode / encode / windows stay host-side OpenCV calls; every pixel operation the corrector's
-//! paths use (gray, threshold, resize, rotate, projections) runs on the GPU.
+//! paths use (gray, threshold, resize, rotate, projections, the projection pictures) runs on the GPU.
 use crate::bridge::{border_bytes, check, into_mat, view};
 use crate::ffi;
 use crate::types::{ImageFormat, RotateClipStrategy};
@@ -147,33 +147,20 @@ pub fn get_vertical_projection(src: &TransformableMatrix) -> Result<Vec<f64>, op
     Ok(out)
 }
 
-/// Debug picture (transfer.rs:337-376): row r gets its black count as a bar from the left edge.
+/// transfer.rs:337-376 -> omr_projection_pictures (horizontal).  Any 8-bit values: per row the pixels before the first
+/// `== 255` stay as they are, then come as many 0 as the row has pixels `!= 255` in all, then 255.
 pub fn transfer_thresh_binary_to_horizontal_projection(src: &TransformableMatrix) -> Result<TransformableMatrix, opencv::Error> {
-    let counts = get_horizontal_projection(src)?;
-    let (rows, cols) = (src.matrix.rows(), src.matrix.cols());
-    let mut pic = Mat::new_rows_cols_with_default(rows, cols, opencv::core::CV_8UC1, Scalar::all(255.0))?;
-    for r in 0..rows {
-        let n = (counts[r as usize] as i32).min(cols);
-        let row = pic.at_row_mut::<u8>(r)?;
-        for px in row.iter_mut().take(n as usize) {
-            *px = 0;
-        }
-    }
-    Ok(TransformableMatrix { matrix: pic })
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_projection_pictures(&view(&src.matrix)?, &mut out, std::ptr::null_mut()) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
-/// Debug picture (transfer.rs:409-455): column c gets its black count as a bar from the bottom edge.
+/// transfer.rs:409-455 -> omr_projection_pictures (vertical).  Any 8-bit values: column c gets a black bar from the
+/// bottom edge as high as the column has pixels `<= 127`; the rest is 255.
 pub fn transfer_thresh_binary_to_vertical_projection(src: &TransformableMatrix) -> Result<TransformableMatrix, opencv::Error> {
-    let counts = get_vertical_projection(src)?;
-    let (rows, cols) = (src.matrix.rows(), src.matrix.cols());
-    let mut pic = Mat::new_rows_cols_with_default(rows, cols, opencv::core::CV_8UC1, Scalar::all(255.0))?;
-    for c in 0..cols {
-        let n = (counts[c as usize] as i32).min(rows);
-        for r in (rows - n)..rows {
-            *pic.at_2d_mut::<u8>(r, c)? = 0;
-        }
-    }
-    Ok(TransformableMatrix { matrix: pic })
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_projection_pictures(&view(&src.matrix)?, std::ptr::null_mut(), &mut out) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
 /// transfer.rs:459-523 -> omr_rotate_ex.  `flags` and `border_mode` go to warpAffine as the reference passes them:
