@@ -1380,8 +1380,8 @@ int omr_batch_set_lanes(omr_batch_ctx *ctx, int32_t max_scans_per_launch)
     return OMR_OK;
 }
 
-// Inspection switch: launches leave their row counts in the scratch set (omr_batch_lanes_projections reads them)
-// instead of clearing them behind the std-dev kernel; the next launch on that set then clears them first.
+// Inspection switch: launches leave their row counts in the scratch set (omr_batch_lanes_projections reads them): the
+// std-dev kernel does not clear them behind its read; the next launch on that set then clears them first.
 int omr_batch_lanes_keep(omr_batch_ctx *ctx, int32_t on)
 {
     if (!ctx || ctx->lanes <= 0) return fail(OMR_ERR_BADARG, "the context is not in scan-lane mode");
@@ -1454,11 +1454,24 @@ int omr_batch_lanes_projections(omr_batch_ctx *ctx, int32_t set, int32_t scan, i
     const SlaneScratch &s = *ctx->slane_scratch[(size_t)set];
     const SlanePlan &p = ctx->slane;
     const size_t nscp = (size_t)s.nsg * SL_LANES;
-    if (vproj) {  // column counts are u16 on the device
-        std::vector<uint16_t> c16((size_t)p.g.cols);
-        OMR_HIP(hipMemcpy2D(c16.data(), 2, s.vproj.as<uint16_t>() + (size_t)a * p.g.cols * nscp + scan, nscp * 2, 2, c16.size(),
-                            hipMemcpyDeviceToHost));
-        for (int c = 0; c < p.g.cols; c++) vproj[c] = c16[(size_t)c];
+    if (vproj) {  // from the counter dumps of the candidate's strips, which a launch leaves in place (slane.hip: slane_stddev_kernel)
+        const int NS = p.g.NS, sg = scan / SL_LANES, lane = scan % SL_LANES;
+        int ai = 0;  // the candidate's place in launch order
+        while (ai < p.A && p.tasks[(size_t)ai * NS] / NS != a) ai++;
+        if (ai == p.A) return fail(OMR_ERR_GPU, "candidate %d is not in the plan's launch order", a);
+        std::vector<uint32_t> pl((size_t)SL_K * SL_DUMP);
+        for (int st = 0; st < NS; st++) {
+            const uint32_t *src = s.planes.as<uint32_t>() + (((size_t)ai * NS + st) * s.nsg + sg) * SL_K * SL_DUMP * SL_LANES + lane;
+            OMR_HIP(hipMemcpy2D(pl.data(), 4, src, SL_LANES * 4, 4, pl.size(), hipMemcpyDeviceToHost));
+            for (int k = 0; k < SL_K; k++)
+                for (int b = 0; b < 32; b++) {
+                    const int c = (st * SL_K + k) * 32 - p.g.off + b;
+                    if (c < 0 || c >= p.g.cols) continue;
+                    uint32_t v = 0;
+                    for (int j = 0; j < SL_DUMP; j++) v |= ((pl[(size_t)k * SL_DUMP + j] >> b) & 1u) << j;
+                    vproj[c] = v;
+                }
+        }
     }
     if (hproj) {  // rows travel packed in pairs: record 2 i in the low half of a dword, 2 i + 1 in the high half
         std::vector<uint32_t> pairs((size_t)p.nrec / 2);

@@ -261,8 +261,9 @@ hipError_t launch_slane_pack_bits(const uint32_t *d_packed, int64_t scan_stride_
 hipError_t launch_slane(const SlaneTask *d_descs, int nsgq, int nsgp, int A, int NQ, int sgw_log, int32_t *d_guard,
                         const int32_t *d_unit_tab, int per_xcd, hipStream_t s);
 std::vector<int32_t> slane_deal_units(const std::vector<double> &chunk_weight, const std::vector<int> &chunk_size, int ncq, int *per_xcd);
-hipError_t launch_slane_vproj(const uint32_t *d_planes, const int32_t *d_tasks, int ntasks, int nsg_used, int nsg, int NS,
-                              int cols, int off, int nrec, uint16_t *d_vproj, uint32_t *d_total, hipStream_t s);
-hipError_t launch_slane_stddev(const uint16_t *d_vproj, const uint32_t *d_hproj, const uint32_t *d_total, int A, int cols, int rows, int hpairs_per_cand,
-                               int hrow0, int nsg_used, int nsg, int nscans, double *d_v_sd, double *d_h_sd, hipStream_t s);
+// std-dev of both projections of every scan, read where the sweep left them (d_planes: the waves' counter dumps; d_hproj: the
+// row counts, cleared behind the read when clear_rows).  nsg_run = scan groups the sweep ran (whole workgroups), >= nsg_used
+hipError_t launch_slane_stddev(const uint32_t *d_planes, const int32_t *d_tasks, uint32_t *d_hproj, bool clear_rows, int A, const SlaneGeom &g,
+                               int hpairs_per_cand, int hrow0, int nsg_used, int nsg_run, int nsg, int nscans, double *d_v_sd,
+                               double *d_h_sd, hipStream_t s);
 }  // namespace omr

@@ -1,5 +1,7 @@
 // slane_engine.cpp -- host side of the scan-lane sweep: the plan (every strip's program, generated on the device by
-// slane_build.hip, or on the host's cores by slane_plan.cpp -- the reference implementation -- and uploaded), the per-launch scratch and the enqueue (slane.hpp).
+// slane_build.hip, or on the host's cores by slane_plan.cpp -- the reference implementation -- and uploaded), the per-launch scratch and the enqueue: pack and sweep on the
+// caller's stream, then ONE kernel on the post stream that turns the waves' counter dumps and the row counts into scores and
+// leaves the row counts zero, and the arg-max (slane.hpp).
 #include <stdlib.h>
 #include <string.h>
 
@@ -232,14 +234,12 @@ int SlaneScratch::create(const SlanePlan &p, int groups)
     OMR_HIP(bits.alloc(bits_b));
     OMR_HIP(hipMemset(bits.p, 0, bits_b));  // entry 0 and the guard columns stay zero for good
     bits_base = (uint32_t *)(((uintptr_t)bits.p + gstride - 1) & ~(uintptr_t)(gstride - 1));
-    // row counts, two records per dword, and behind them the black-pixel totals [candidate][scan] (added up by the
-    // column-count kernel): both are accumulated with atomics, so every launch leaves them zero again
-    rows_bytes = sizeof(uint32_t) * ((size_t)p.A * (p.nrec / 2) * nscp + (size_t)p.A * nscp);
+    // row counts, two records per dword: accumulated with atomics, so every launch leaves them zero again
+    rows_bytes = sizeof(uint32_t) * (size_t)p.A * (p.nrec / 2) * nscp;
     OMR_HIP(hrows.alloc(rows_bytes));
     OMR_HIP(hipMemset(hrows.p, 0, rows_bytes));
     OMR_HIP(guard.alloc(sizeof(int32_t)));
     OMR_HIP(hipMemset(guard.p, 0, sizeof(int32_t)));
-    OMR_HIP(vproj.alloc(sizeof(uint16_t) * (size_t)p.A * g.cols * nscp));  // column counts <= rows <= 65535
     OMR_HIP(vsd.alloc(sizeof(double) * nscp * p.A));
     OMR_HIP(hsd.alloc(sizeof(double) * nscp * p.A));
     OMR_HIP(best.alloc(sizeof(int32_t) * nscp));
@@ -297,7 +297,7 @@ int SlaneScratch::create(const SlanePlan &p, int groups)
     return OMR_OK;
 }
 
-// pack -> sweep -> column counts -> std-dev -> arg-max for `nscans` device-resident scans (at most nsg * 64)
+// pack -> sweep -> std-dev (which also clears the row counts) -> arg-max for `nscans` device-resident scans (at most nsg * 64)
 // (packed: d_img holds scans ALREADY packed to 1 bit per pixel, [rows][NW] dwords each, scan_stride bytes apart)
 int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int64_t scan_stride, int64_t step, int nscans,
                   int black_max, bool packed, hipStream_t stream, hipStream_t post_stream, hipEvent_t ev_mid, double *d_v_sd,
@@ -310,7 +310,7 @@ int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int
     if (packed && ((scan_stride & 3) != 0 || scan_stride < (int64_t)p.g.rows * p.g.NW * 4 || ((uintptr_t)d_img & 3) != 0))
         return fail(OMR_ERR_BADARG, "packed scans: rows x %d dwords each, 4-byte aligned", p.g.NW);
     const int used = (nscans + SL_LANES - 1) / SL_LANES;  // scan groups that hold scans; the descriptors are laid out for s.nsg
-    const size_t nscp = (size_t)s.nsg * SL_LANES;
+    int nsg_run = used;  // scan groups the sweep adds row counts for: whole workgroups, as far as the scratch holds them
     if (s.rows_dirty) {  // the previous launch was asked to keep its row counts (omr_batch_lanes_keep)
         OMR_HIP(hipMemsetAsync(s.hrows.p, 0, s.rows_bytes, stream));
         s.rows_dirty = false;
@@ -328,6 +328,7 @@ int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int
         OMR_HIP(launch_slane(s.descs[lg].as<SlaneTask>(), nsgq, ((s.nsg + sgw - 1) / sgw) * sgw, p.A, NQ, lg, s.guard.as<int32_t>(),
                              d_tab, per_xcd, stream));
         s.guard_pending = true;
+        nsg_run = std::min(nsgq * sgw, s.nsg);
     }
     if (ev1) OMR_HIP(hipEventRecord(ev1, stream));
     if (post_stream && ev_mid) {
@@ -335,17 +336,13 @@ int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int
         OMR_HIP(hipStreamWaitEvent(post_stream, ev_mid, 0));
         stream = post_stream;
     }
-    OMR_HIP(launch_slane_vproj(s.planes.as<uint32_t>(), p.d_tasks.as<int32_t>(), (int)p.tasks.size(), used, s.nsg, p.g.NS, p.g.cols,
-                               p.g.off, p.nrec, s.vproj.as<uint16_t>(), s.hrows.as<uint32_t>() + (size_t)p.A * (p.nrec / 2) * nscp, stream));
     double *vs = d_v_sd ? d_v_sd : s.vsd.as<double>(), *hs = d_h_sd ? d_h_sd : s.hsd.as<double>();
-    OMR_HIP(launch_slane_stddev(s.vproj.as<uint16_t>(), s.hrows.as<uint32_t>(), s.hrows.as<uint32_t>() + (size_t)p.A * (p.nrec / 2) * nscp,
-                                p.A, p.g.cols, p.g.rows, p.nrec / 2, p.hrow0, used, s.nsg,
-                                nscans, vs, hs, stream));
+    // the row counts are accumulated with atomics: their only reader clears them, off the sweep's stream (the caller orders
+    // the next launch on this scratch set behind this stream's work), unless they are to be inspected
+    OMR_HIP(launch_slane_stddev(s.planes.as<uint32_t>(), p.d_tasks.as<int32_t>(), s.hrows.as<uint32_t>(), !s.keep_rows, p.A, p.g, p.nrec / 2,
+                                p.hrow0, used, nsg_run, s.nsg, nscans, vs, hs, stream));
     if (d_best) OMR_HIP(launch_argmax_path1(vs, hs, p.A, d_best, stream, nscans));
-    // the row counts are accumulated with atomics: cleared here, behind their only reader and off the sweep's stream
-    // (the caller orders the next launch on this scratch set behind this stream's work)
     if (s.keep_rows) s.rows_dirty = true;
-    else OMR_HIP(hipMemsetAsync(s.hrows.p, 0, s.rows_bytes, stream));
     return OMR_OK;
 }
 

@@ -273,11 +273,12 @@ class Batch:
         check(lib().omr_batch_lanes_check_programs(self.handle, C.byref(n), C.byref(d)))
         return n.value, d.value
 
-    def lanes_projections(self, scan, a, rows, cols, scratch_set=0):
-        """(vproj, hproj) of one scan / candidate as the last scan-lane launch left them (tests, inspection)."""
-        vp, hp = np.zeros(cols, np.uint32), np.zeros(rows, np.uint32)
+    def lanes_projections(self, scan, a, rows, cols, scratch_set=0, want_rows=True):
+        """(vproj, hproj) of one scan / candidate as the last scan-lane launch left them (tests, inspection).  The row
+        counts need lanes_keep(); want_rows=False asks for the column counts alone (hproj is None)."""
+        vp, hp = np.zeros(cols, np.uint32), np.zeros(rows, np.uint32) if want_rows else None
         check(lib().omr_batch_lanes_projections(self.handle, scratch_set, scan, a, vp.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                hp.ctypes.data_as(C.POINTER(C.c_uint32))))
+                                                hp.ctypes.data_as(C.POINTER(C.c_uint32)) if want_rows else None))
         return vp, hp
 
     def info(self):
