@@ -526,11 +526,47 @@ int omr_hough_lines_p(const omr_image *edges_u8c1, double rho, double theta, int
 
 /* oics::hough::get_angle_with_hough(&TransformableMatrix, min_line_length, max_line_gap, file_name,
  * edge_image_output_dir) -> Result<f64> (hough.rs:17-100; called core/src/main.rs:103-110,
- * app/src-tauri/src/test.rs:383-390).  The debug picture the reference writes with imwrite
- * (hough.rs:46-63, :94-99) is host-side codec work and stays with the caller, hence no file
- * arguments.  No segment found: -215 (the reference panics on angles[0], hough.rs:74). */
+ * app/src-tauri/src/test.rs:383-390).  No file arguments: encoding and writing the debug picture
+ * (imwrite, hough.rs:91-96) is host-side codec work and stays with the caller; the picture itself --
+ * the edge map in colour with every segment drawn on (hough.rs:44-63) -- comes from
+ * omr_get_angle_with_hough_ex below.  No segment found: -215 (the reference panics on angles[0],
+ * hough.rs:74). */
 int omr_get_angle_with_hough(const omr_image *gray, double min_line_length, double max_line_gap,
                              double *angle_out);
+/* The same detector -- Canny and HoughLinesP run once, *angle_out has the same bits -- which also hands
+ * back the reference's picture in colour (186, 88, 255) as an owned 3-channel image (omr_image_free).
+ * lined == NULL: exactly omr_get_angle_with_hough.  No segment found: -215 and no picture (lined->data
+ * is NULL), as the reference panics before its imwrite. */
+int omr_get_angle_with_hough_ex(const omr_image *gray, double min_line_length, double max_line_gap,
+                                double *angle_out, omr_image_owned *lined);
+
+/* ---- the detectors' line picture (hough.rs:44-63, fft.rs:173-213) --------------------
+ * cvtColor(GRAY2BGR) of an 8-bit one-channel edge map (ANY values), then every segment (x0, y0, x1, y1), as
+ * omr_hough_lines_p returns them, drawn on by imgproc::line(.., colour, 1, LINE_AA, 0) -- OpenCV 4.6.0 LineAA restated,
+ * tests/lined_ref.py -- one after another in list order: LINE_AA blends into what is there, so where segments cross
+ * the order shows.  bgr: the colour's three bytes (B, G, R).  n_lines == 0 gives the GRAY2BGR picture.
+ * Every end point must lie inside the picture (HoughLinesP gives no others; clipLine is not restated): OMR_ERR_BADARG
+ * otherwise -- found on the host by omr_lined_picture before any device work, by a first kernel in the device forms,
+ * which then draw nothing.  OMR_ERR_BADARG besides: a null pointer, n <= 0, n_lines < 0, a line_offsets entry below its
+ * predecessor or below 0, a step below cols (edges) or 3 * cols (picture), a picture stride below rows * out_step, a
+ * negative edge-map stride, d_edges == d_out.  OMR_ERR_ASSERT: an empty image, a side of 32767 or more, and for the host
+ * form a channel count other than 1.  All of these are checked before any device work.
+ * The device forms enqueue on `stream` and SYNCHRONISE it before they return (the end-point verdict is read, the
+ * per-call segment records are given back).  Picture bytes past 3 * cols of a row are never written.
+ * Performance note: picture rows leave as dwords when the picture's base, stride and step are multiples of 4. */
+int omr_lined_picture(const omr_image *edges_u8c1, const int32_t *lines, int32_t n_lines, const uint8_t bgr[3],
+                      omr_image_owned *picture);
+/* device-resident edge map and segments; the picture has its own row pitch */
+int omr_lined_picture_device(const uint8_t *d_edges, int64_t edge_step, int32_t rows, int32_t cols,
+                             const int32_t *d_lines, int32_t n_lines, const uint8_t bgr[3], uint8_t *d_out,
+                             int64_t out_step, void *stream);
+/* n edge maps of one shape, map i at d_edges + i * edge_stride_bytes, its picture at d_out + i * out_stride_bytes;
+ * picture i draws the segments line_offsets[i] .. line_offsets[i + 1] of d_lines (line_offsets: HOST array of n + 1).
+ * One drawing launch for the batch (per 65535 maps); every picture is byte for byte the per-call form's. */
+int omr_lined_picture_batch_device(const uint8_t *d_edges, int32_t n, int64_t edge_stride_bytes, int64_t edge_step,
+                                   int32_t rows, int32_t cols, const int32_t *d_lines, const int32_t *line_offsets,
+                                   const uint8_t bgr[3], uint8_t *d_out, int64_t out_stride_bytes, int64_t out_step,
+                                   void *stream);
 
 /* oics::omr::get_result_from_edges_detection(&Mat, f64, f64) -> Result<OmrResult> (omr.rs:231-302). */
 int omr_get_result_from_edges_detection(const omr_image *src, double edges_min_line_length,
@@ -712,10 +748,17 @@ int omr_fft_image_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_s
 
 /* oics::fft::get_angle_with_fft(&TransformableMatrix, canny_threshold_1, canny_threshold_2,
  * min_line_length, max_line_gap, file_name, edge_image_output_dir) -> Result<f64> (fft.rs:145-256;
- * called core/src/main.rs:141-150, app/src-tauri/src/test.rs:450-459).  The debug picture stays with
- * the caller (as for omr_get_angle_with_hough).  Keeps the vote's quirk (fft.rs:231 re-reads line i). */
+ * called core/src/main.rs:141-150, app/src-tauri/src/test.rs:450-459).  Writing the debug picture stays
+ * with the caller (as for omr_get_angle_with_hough); omr_get_angle_with_fft_ex makes it.  Keeps the vote's
+ * quirk (fft.rs:231 re-reads line i). */
 int omr_get_angle_with_fft(const omr_image *gray_u8c1, double canny_threshold_1, double canny_threshold_2,
                            double min_line_length, double max_line_gap, double *angle_out);
+/* The same detector -- the transform, Canny and HoughLinesP run once, *angle_out has the same bits -- which also
+ * hands back the reference's picture (fft.rs:173-213): the edges of the log spectrum in colour with every segment
+ * drawn on in (186, 88, 255), an owned 3-channel image.  lined == NULL: exactly omr_get_angle_with_fft.  No segment
+ * found: angle 0 and the bare GRAY2BGR picture, as the reference gives. */
+int omr_get_angle_with_fft_ex(const omr_image *gray_u8c1, double canny_threshold_1, double canny_threshold_2,
+                              double min_line_length, double max_line_gap, double *angle_out, omr_image_owned *lined);
 
 /* oics::omr::get_result_from_fourier_transform(&Mat, weak, strong, min_line_length, max_line_gap) ->
  * Result<OmrResult> (omr.rs:304-337) on the 3/4-channel scan. */

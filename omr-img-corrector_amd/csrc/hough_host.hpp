@@ -28,8 +28,15 @@ int canny_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int ro
 // HoughLinesP on n device-resident edge images (packed)
 int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, const HoughParams &hp, hipStream_t s,
                 std::vector<std::vector<int32_t>> *lines_out);
+// keep_edges (may be null): receives a copy of the edge maps, which HoughLinesP consumes
 int edges_lines_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int rows, int cols, int cn, int n,
-                       const HoughParams &hp, hipStream_t s, std::vector<std::vector<int32_t>> *lines);
+                       const HoughParams &hp, hipStream_t s, std::vector<std::vector<int32_t>> *lines,
+                       DevBuf *keep_edges = nullptr);
+// the detectors' line picture (lined.hip): GRAY2BGR of a packed device edge map with `n_lines` host segments
+// (x0, y0, x1, y1) drawn on in list order, as a fresh host image; synchronises `s`
+extern const uint8_t kLinedBgr[3];
+int lined_to_host(const uint8_t *d_edges, int rows, int cols, const int32_t *lines, int n_lines, const uint8_t bgr[3],
+                  hipStream_t s, omr_image_owned *picture);
 void line_angles(const std::vector<int32_t> &l, std::vector<float> *ang);
 int vote_counts(const std::vector<float> &ang, bool as_f64, hipStream_t s, std::vector<int32_t> *counts);
 int select_omr_rs(const std::vector<float> &ang, const std::vector<int32_t> &cnt, double *angle, int32_t *status,

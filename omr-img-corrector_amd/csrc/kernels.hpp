@@ -241,4 +241,26 @@ hipError_t launch_projpic_rows(const ProjPicImg &p, hipStream_t s);
 hipError_t launch_projpic_col_counts(const ProjPicImg &p, uint32_t *d_counts, hipStream_t s);
 hipError_t launch_projpic_col_bars(const ProjPicImg &p, const uint32_t *d_counts, hipStream_t s);
 
+// ---- the detectors' line pictures (lined.hip; the callers are in oics_hough.cpp) --------------------------------
+// A segment as LineAA's loop sees it (OpenCV 4.6 drawing.cpp, thickness 1, LINE_AA, shift 0): step k = 0 .. e paints the
+// major coordinate m0 + k at the minor 16.16 value v0 + k * step; slope_x = the slope correction (9 bits) | x-major << 16
+struct LinedSeg {
+    int32_t m0, e, step, slope_x;
+    int64_t v0;
+};
+// `n` one-channel edge maps of rows x cols, map i at src + i * sstride, its 3-channel picture at dst + i * dstride
+// (n <= 65535); picture i draws segs[off[i] .. off[i + 1]) in that order
+struct LinedImg {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t sstride, sstep, dstride, dstep;
+    int rows, cols, n;
+    uint32_t bgr;  // B | G << 8 | R << 16
+};
+// (x0, y0, x1, y1) x count -> segs; *d_bad is OR-ed with 1 when an end point lies outside cols x rows
+hipError_t launch_lined_prepare(const int32_t *d_lines, int64_t count, int rows, int cols, LinedSeg *d_segs, int32_t *d_bad,
+                                hipStream_t s);
+// GRAY2BGR of every map with its segments drawn on, one launch
+hipError_t launch_lined_draw(const LinedImg &p, const LinedSeg *d_segs, const int32_t *d_off, hipStream_t s);
+
 }  // namespace omr

@@ -500,10 +500,12 @@ int omr_fft_image_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_s
     return OMR_OK;
 }
 
-int omr_get_angle_with_fft(const omr_image *gray, double canny_threshold_1, double canny_threshold_2,
-                           double min_line_length, double max_line_gap, double *angle_out)
+// get_angle_with_fft; `lined` (may be null) receives the picture the reference writes (fft.rs:173-213, :248-253)
+static int angle_with_fft(const omr_image *gray, double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                          double max_line_gap, double *angle_out, omr_image_owned *lined)
 {
     clear_error();
+    if (lined) memset(lined, 0, sizeof(*lined));
     int rc = check_gray(gray);
     if (rc) return rc;
     if (!angle_out) return fail(OMR_ERR_BADARG, "null output");
@@ -525,7 +527,9 @@ int omr_get_angle_with_fft(const omr_image *gray, double canny_threshold_1, doub
     hp.min_line_length = min_line_length;
     hp.max_line_gap = max_line_gap;
     std::vector<std::vector<int32_t>> lines;
-    if ((rc = edges_lines_device(l8.as<uint8_t>(), 0, cols, rows, cols, 1, 1, hp, st.s, &lines))) return rc;
+    DevBuf edges;  // the picture's background: the edges of the log spectrum as Canny left them
+    if ((rc = edges_lines_device(l8.as<uint8_t>(), 0, cols, rows, cols, 1, 1, hp, st.s, &lines, lined ? &edges : nullptr)))
+        return rc;
     // fft.rs:197-247: f64 angles folded into [-45, 45]; the inner loop re-reads line i (quirk B10), so
     // line i collects n - 1 votes iff its raw angle is within 0.1 of its folded angle, else none
     const std::vector<int32_t> &l = lines[0];
@@ -548,7 +552,20 @@ int omr_get_angle_with_fft(const omr_image *gray, double canny_threshold_1, doub
         if (max_votes == n - 1 && n > 1) break;  // nothing can beat n - 1 with a strict '>'
     }
     *angle_out = average_angle;
-    return OMR_OK;
+    if (!lined) return OMR_OK;
+    return lined_to_host(edges.as<uint8_t>(), rows, cols, l.data(), n, kLinedBgr, st.s, lined);  // no segment: the bare edges
+}
+
+int omr_get_angle_with_fft(const omr_image *gray, double canny_threshold_1, double canny_threshold_2,
+                           double min_line_length, double max_line_gap, double *angle_out)
+{
+    return angle_with_fft(gray, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, angle_out, nullptr);
+}
+
+int omr_get_angle_with_fft_ex(const omr_image *gray, double canny_threshold_1, double canny_threshold_2,
+                              double min_line_length, double max_line_gap, double *angle_out, omr_image_owned *lined)
+{
+    return angle_with_fft(gray, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, angle_out, lined);
 }
 
 int omr_get_result_from_fourier_transform(const omr_image *src, double canny_threshold_weak,

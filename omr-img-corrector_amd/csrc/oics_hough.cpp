@@ -33,6 +33,8 @@ namespace hh {
 // omr_hough_set_scans_in_flight(): 0 = the default (see ppht_device)
 std::atomic<int> g_scans_in_flight{0};
 
+const uint8_t kLinedBgr[3] = {186, 88, 255};  // Scalar(186, 88, 255, 0): hough.rs:59, fft.rs:209
+
 inline int cv_round(double v) { return (int)lrint(v); }
 inline int cv_round(float v) { return (int)lrintf(v); }
 
@@ -261,9 +263,10 @@ int upload(const omr_image *im, DevBuf *buf, hipStream_t s)
     return upload_rows(buf->p, row, im->data, (size_t)im->step_bytes, row, (size_t)im->rows, s);
 }
 
-// Canny + HoughLinesP of n device-resident scans -> per-scan segments
+// Canny + HoughLinesP of n device-resident scans -> per-scan segments.  keep_edges: receives a copy of the edge maps
+// (packed, n x rows x cols), taken before HoughLinesP, which erases the points it has used from its input
 int edges_lines_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int rows, int cols, int cn, int n,
-                       const HoughParams &hp, hipStream_t s, std::vector<std::vector<int32_t>> *lines)
+                       const HoughParams &hp, hipStream_t s, std::vector<std::vector<int32_t>> *lines, DevBuf *keep_edges)
 {
     DevBuf map, flag, rowcnt;
     OMR_HIP(map.alloc((size_t)n * rows * cols));
@@ -272,7 +275,93 @@ int edges_lines_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, 
     int rc = canny_device(d_src, scan_stride, step, rows, cols, cn, n, hp.low, hp.high, map.as<uint8_t>(), flag.as<int>(), s,
                           rowcnt.as<int32_t>());
     if (rc) return rc;
+    if (keep_edges) {
+        OMR_HIP(keep_edges->alloc(map.bytes));
+        OMR_HIP(hipMemcpyAsync(keep_edges->p, map.p, (size_t)n * rows * cols, hipMemcpyDeviceToDevice, s));
+    }
     return ppht_device(map.as<uint8_t>(), rowcnt.as<int32_t>(), rows, cols, n, hp, s, lines);
+}
+
+// ---- the line picture (lined.hip): every argument rule of the omr_lined_picture* entry points, before any device work
+static int lined_check(const void *d_edges, int n, int64_t estride, int64_t estep, int rows, int cols, const void *d_lines,
+                       const int32_t *off, const uint8_t *bgr, const void *d_out, int64_t ostride, int64_t ostep, bool batch)
+{
+    clear_error();
+    if (!d_edges || !d_out || !off || !bgr) return fail(OMR_ERR_BADARG, "null pointer");
+    if (n <= 0) return fail(OMR_ERR_BADARG, "empty batch");
+    int rc = check_image_shape(rows, cols);
+    if (rc) return rc;
+    if (estep < cols || ostep < 3 * (int64_t)cols) return fail(OMR_ERR_BADARG, "step too small");
+    if (batch) {
+        if (estride < 0) return fail(OMR_ERR_BADARG, "negative edge-map stride");
+        if (ostride < rows * ostep) return fail(OMR_ERR_BADARG, "picture stride smaller than a picture");
+    }
+    if (off[0] < 0) return fail(OMR_ERR_BADARG, "negative segment count or offset");
+    for (int i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) return fail(OMR_ERR_BADARG, "line_offsets must not decrease (picture %d)", i);
+    if (off[n] > off[0] && !d_lines) return fail(OMR_ERR_BADARG, "null segment list");
+    if (d_edges == d_out) return fail(OMR_ERR_BADARG, "the picture cannot be made in place");
+    return OMR_OK;
+}
+
+// arguments already checked.  Synchronises `s`: the end-point verdict is read before anything is drawn, and the segment
+// records go back to the block cache on return
+int lined_device(const uint8_t *d_edges, int n, int64_t estride, int64_t estep, int rows, int cols, const int32_t *d_lines,
+                 const int32_t *off, const uint8_t bgr[3], uint8_t *d_out, int64_t ostride, int64_t ostep, hipStream_t s)
+{
+    PoolScope scope(s);
+    const int64_t total = (int64_t)off[n] - off[0];
+    std::vector<int32_t> rel((size_t)n + 1);
+    for (int i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+    DevBuf segs, doff, bad;
+    OMR_HIP(segs.alloc(sizeof(LinedSeg) * (size_t)std::max<int64_t>(total, 1)));
+    OMR_HIP(doff.alloc(sizeof(int32_t) * rel.size()));
+    OMR_HIP(hipMemcpyAsync(doff.p, rel.data(), sizeof(int32_t) * rel.size(), hipMemcpyHostToDevice, s));
+    if (total > 0) {
+        int32_t verdict = 0;
+        OMR_HIP(bad.alloc(sizeof(int32_t)));
+        OMR_HIP(hipMemsetAsync(bad.p, 0, sizeof(int32_t), s));
+        OMR_HIP(launch_lined_prepare(d_lines + 4 * (int64_t)off[0], total, rows, cols, segs.as<LinedSeg>(), bad.as<int32_t>(), s));
+        OMR_HIP(hipMemcpyAsync(&verdict, bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+        if (verdict) return fail(OMR_ERR_BADARG, "a segment's end point lies outside the %d x %d picture", cols, rows);
+    }
+    for (int i0 = 0; i0 < n; i0 += 65535) {
+        LinedImg p{};
+        p.n = std::min(n - i0, 65535);
+        p.rows = rows, p.cols = cols;
+        p.src = d_edges + i0 * estride, p.sstride = estride, p.sstep = estep;
+        p.dst = d_out + i0 * ostride, p.dstride = ostride, p.dstep = ostep;
+        p.bgr = (uint32_t)bgr[0] | (uint32_t)bgr[1] << 8 | (uint32_t)bgr[2] << 16;
+        OMR_HIP(launch_lined_draw(p, segs.as<LinedSeg>(), doff.as<int32_t>() + i0, s));
+    }
+    OMR_HIP(hipStreamSynchronize(s));
+    return OMR_OK;
+}
+
+// the picture of one packed device edge map with host segments, as a fresh host image
+int lined_to_host(const uint8_t *d_edges, int rows, int cols, const int32_t *lines, int n_lines, const uint8_t bgr[3],
+                  hipStream_t s, omr_image_owned *picture)
+{
+    const int32_t off[2] = {0, n_lines};
+    DevBuf dl, out;
+    if (n_lines > 0) {
+        OMR_HIP(dl.alloc(sizeof(int32_t) * 4 * (size_t)n_lines));
+        OMR_HIP(hipMemcpyAsync(dl.p, lines, sizeof(int32_t) * 4 * (size_t)n_lines, hipMemcpyHostToDevice, s));
+    }
+    const size_t row = (size_t)cols * 3;
+    OMR_HIP(out.alloc(row * rows));
+    int rc = lined_device(d_edges, 1, 0, cols, rows, cols, dl.as<int32_t>(), off, bgr, out.as<uint8_t>(), 0, (int64_t)row, s);
+    if (rc) return rc;
+    picture->rows = rows;
+    picture->cols = cols;
+    picture->channels = 3;
+    picture->step_bytes = (int64_t)row;
+    picture->data = (uint8_t *)malloc(row * rows);
+    if (!picture->data) return fail(OMR_ERR_NOMEM, "out of host memory");
+    rc = staged_d2h(picture->data, out.p, row * rows, s);
+    if (rc) omr_image_free(picture);
+    return rc;
 }
 
 }  // namespace hh
@@ -342,9 +431,12 @@ int omr_hough_lines_p(const omr_image *edges, double rho, double theta, int32_t 
     return OMR_OK;
 }
 
-int omr_get_angle_with_hough(const omr_image *gray, double min_line_length, double max_line_gap, double *angle_out)
+// get_angle_with_hough; `lined` (may be null) receives the picture the reference writes (hough.rs:44-63, :91-96)
+static int angle_with_hough(const omr_image *gray, double min_line_length, double max_line_gap, double *angle_out,
+                            omr_image_owned *lined)
 {
     clear_error();
+    if (lined) memset(lined, 0, sizeof(*lined));
     int rc = check_image(gray, cn_canny);
     if (rc) return rc;
     if (!angle_out) return fail(OMR_ERR_BADARG, "null output");
@@ -357,14 +449,69 @@ int omr_get_angle_with_hough(const omr_image *gray, double min_line_length, doub
     hp.min_line_length = min_line_length;
     hp.max_line_gap = max_line_gap;
     std::vector<std::vector<int32_t>> lines;
+    DevBuf edges;  // the picture's background: the edge map as Canny left it
     if ((rc = edges_lines_device(in.as<uint8_t>(), 0, (int64_t)gray->cols * gray->channels, gray->rows, gray->cols,
-                                 gray->channels, 1, hp, st.s, &lines)))
+                                 gray->channels, 1, hp, st.s, &lines, lined ? &edges : nullptr)))
         return rc;
     std::vector<float> ang;
     std::vector<int32_t> cnt;
     line_angles(lines[0], &ang);
     if ((rc = vote_counts(ang, false, st.s, &cnt))) return rc;
-    return select_hough_rs(ang, cnt, angle_out);
+    if ((rc = select_hough_rs(ang, cnt, angle_out)) || !lined) return rc;  // no segment: the reference panics before its imwrite
+    return lined_to_host(edges.as<uint8_t>(), gray->rows, gray->cols, lines[0].data(), (int)(lines[0].size() / 4), kLinedBgr,
+                         st.s, lined);
+}
+
+int omr_get_angle_with_hough(const omr_image *gray, double min_line_length, double max_line_gap, double *angle_out)
+{
+    return angle_with_hough(gray, min_line_length, max_line_gap, angle_out, nullptr);
+}
+
+int omr_get_angle_with_hough_ex(const omr_image *gray, double min_line_length, double max_line_gap, double *angle_out,
+                                omr_image_owned *lined)
+{
+    return angle_with_hough(gray, min_line_length, max_line_gap, angle_out, lined);
+}
+
+int omr_lined_picture_batch_device(const uint8_t *d_edges, int32_t n, int64_t edge_stride_bytes, int64_t edge_step,
+                                   int32_t rows, int32_t cols, const int32_t *d_lines, const int32_t *line_offsets,
+                                   const uint8_t bgr[3], uint8_t *d_out, int64_t out_stride_bytes, int64_t out_step,
+                                   void *stream)
+{
+    int rc = lined_check(d_edges, n, edge_stride_bytes, edge_step, rows, cols, d_lines, line_offsets, bgr, d_out,
+                         out_stride_bytes, out_step, true);
+    if (rc || (rc = have_device())) return rc;
+    return lined_device(d_edges, n, edge_stride_bytes, edge_step, rows, cols, d_lines, line_offsets, bgr, d_out,
+                        out_stride_bytes, out_step, (hipStream_t)stream);
+}
+
+int omr_lined_picture_device(const uint8_t *d_edges, int64_t edge_step, int32_t rows, int32_t cols, const int32_t *d_lines,
+                             int32_t n_lines, const uint8_t bgr[3], uint8_t *d_out, int64_t out_step, void *stream)
+{
+    const int32_t off[2] = {0, n_lines};
+    int rc = lined_check(d_edges, 1, 0, edge_step, rows, cols, d_lines, off, bgr, d_out, 0, out_step, false);
+    if (rc || (rc = have_device())) return rc;
+    return lined_device(d_edges, 1, 0, edge_step, rows, cols, d_lines, off, bgr, d_out, 0, out_step, (hipStream_t)stream);
+}
+
+int omr_lined_picture(const omr_image *edges, const int32_t *lines, int32_t n_lines, const uint8_t bgr[3],
+                      omr_image_owned *picture)
+{
+    clear_error();
+    int rc = check_image(edges, cn_one);
+    if (rc) return rc;
+    if (!picture || !bgr) return fail(OMR_ERR_BADARG, "null pointer");
+    if (n_lines < 0 || (n_lines > 0 && !lines)) return fail(OMR_ERR_BADARG, "negative segment count or null segment list");
+    for (int64_t i = 0; i < 4 * (int64_t)n_lines; i++)
+        if (lines[i] < 0 || lines[i] >= ((i & 1) ? edges->rows : edges->cols))
+            return fail(OMR_ERR_BADARG, "end point of segment %lld lies outside the %d x %d picture", (long long)(i / 4),
+                        edges->cols, edges->rows);
+    if ((rc = have_device())) return rc;
+    LeasedStream st;
+    if ((rc = st.create())) return rc;
+    DevBuf in;
+    if ((rc = upload(edges, &in, st.s))) return rc;
+    return lined_to_host(in.as<uint8_t>(), edges->rows, edges->cols, lines, n_lines, bgr, st.s, picture);
 }
 
 int omr_get_result_from_edges_detection(const omr_image *src, double edges_min_line_length, double edges_max_line_gap,

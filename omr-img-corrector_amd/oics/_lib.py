@@ -156,6 +156,12 @@ SYMBOLS = {
     "omr_hough_lines_p": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, i32p,
                                     C.c_int32, i32p]),
     "omr_get_angle_with_hough": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, f64p]),
+    "omr_get_angle_with_hough_ex": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, f64p, C.POINTER(OmrImageOwned)]),
+    "omr_lined_picture": (C.c_int, [C.POINTER(OmrImage), i32p, C.c_int32, u8p, C.POINTER(OmrImageOwned)]),
+    "omr_lined_picture_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, u8p,
+                                           C.c_void_p, C.c_int64, C.c_void_p]),
+    "omr_lined_picture_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                 C.c_void_p, i32p, u8p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "omr_get_result_from_edges_detection": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, f64p, i32p, f64p,
                                                       C.c_int32, i32p]),
     "omr_edges_detection_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
@@ -190,6 +196,8 @@ SYMBOLS = {
     "omr_fft_image_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                              C.c_void_p, C.c_void_p]),
     "omr_get_angle_with_fft": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double, C.c_double, f64p]),
+    "omr_get_angle_with_fft_ex": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double, C.c_double, f64p,
+                                            C.POINTER(OmrImageOwned)]),
     "omr_get_result_from_fourier_transform": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double,
                                                         C.c_double, f64p, i32p, f64p, C.c_int32, i32p]),
     "omr_scale": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.POINTER(OmrImageOwned)]),

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import OmrImageOwned, check, i32p, lib
+from ._lib import OmrImageOwned, check, i32p, lib, u8p
 from .transfer import _mat, as_image
 
 
@@ -38,9 +38,50 @@ def hough_lines_p(edges, rho, theta, threshold, min_line_length, max_line_gap):
         cap = n.value
 
 
-def get_angle_with_hough(gray_tm, min_line_length, max_line_gap):
-    """hough.rs:17-100 without the debug picture (file_name / edge_image_output_dir stay host-side)."""
+LINED_COLOR = (186, 88, 255)  # Scalar(186, 88, 255, 0), B G R: hough.rs:59, fft.rs:209
+
+
+def _bgr(color):
+    c = np.asarray(color, np.uint8).reshape(3)
+    return c, c.ctypes.data_as(u8p)
+
+
+def lined_picture(edges, lines, color=LINED_COLOR):
+    """omr_lined_picture: GRAY2BGR of an 8-bit one-channel edge map with the segments `lines` ([n, 4] x0 y0 x1 y1, as
+    hough_lines_p returns them) drawn on in list order by line(.., color, 1, LINE_AA, 0) -- hough.rs:44-63.  Returns
+    [rows, cols, 3] uint8."""
+    a, im = as_image(_mat(edges))
+    l = np.ascontiguousarray(np.asarray(lines, np.int32).reshape(-1, 4))
+    keep, c = _bgr(color)
+    owned = OmrImageOwned()
+    check(lib().omr_lined_picture(C.byref(im), l.ctypes.data_as(i32p) if len(l) else None, len(l), c, C.byref(owned)))
+    return _take(owned)
+
+
+def lined_picture_batch_device(d_edges, n, edge_stride_bytes, edge_step, rows, cols, d_lines, line_offsets, d_out,
+                               out_stride_bytes, out_step, color=LINED_COLOR, stream=None):
+    """omr_lined_picture_batch_device: n same-shape device-resident edge maps (d_edges, d_lines, d_out: device
+    addresses), picture i at d_out + i * out_stride_bytes with the segments line_offsets[i] .. line_offsets[i + 1] of
+    d_lines drawn on; line_offsets is a host sequence of n + 1.  Byte for byte omr_lined_picture_device's pictures.
+    Synchronises `stream` before returning."""
+    off = np.ascontiguousarray(np.asarray(line_offsets, np.int32).reshape(-1))
+    if len(off) != int(n) + 1:
+        raise ValueError("line_offsets holds n + 1 entries")
+    keep, c = _bgr(color)
+    check(lib().omr_lined_picture_batch_device(d_edges, int(n), int(edge_stride_bytes), int(edge_step), int(rows), int(cols),
+                                               d_lines, off.ctypes.data_as(i32p), c, d_out, int(out_stride_bytes),
+                                               int(out_step), stream))
+
+
+def get_angle_with_hough(gray_tm, min_line_length, max_line_gap, want_picture=False):
+    """hough.rs:17-100; file_name / edge_image_output_dir stay host-side.  want_picture=True returns (angle, picture):
+    the picture the reference writes there -- the edge map in colour with every segment drawn on, [rows, cols, 3]."""
     a, im = as_image(_mat(gray_tm))
     out = C.c_double()
-    check(lib().omr_get_angle_with_hough(C.byref(im), float(min_line_length), float(max_line_gap), C.byref(out)))
-    return out.value
+    if not want_picture:
+        check(lib().omr_get_angle_with_hough(C.byref(im), float(min_line_length), float(max_line_gap), C.byref(out)))
+        return out.value
+    owned = OmrImageOwned()
+    check(lib().omr_get_angle_with_hough_ex(C.byref(im), float(min_line_length), float(max_line_gap), C.byref(out),
+                                            C.byref(owned)))
+    return out.value, _take(owned)

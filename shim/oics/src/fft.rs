@@ -1,4 +1,4 @@
-//! `oics::fft` (reference: packages/lib/src/fft.rs) -> omr_get_fft_image / omr_get_angle_with_fft.
+//! `oics::fft` (reference: packages/lib/src/fft.rs) -> omr_get_fft_image / omr_get_angle_with_fft / _ex.
 use crate::bridge::{check, into_mat, view};
 use crate::ffi;
 use crate::transfer::TransformableMatrix;
@@ -24,8 +24,9 @@ pub fn get_fft_image(gray_tm: &TransformableMatrix) -> opencv::Result<(Mat, Mat)
 }
 
 /// fft.rs:145-256: spectrum picture -> Canny(t1, t2) -> HoughLinesP(threshold 100) -> the reference's vote
-/// (including its fft.rs:231 quirk), all on the GPU.  The debug picture (the log spectrum) is written when
-/// `edge_image_output_dir` is not empty, as in the reference.
+/// (including its fft.rs:231 quirk), all on the GPU.  The debug picture (fft.rs:173-213, :248-253: the edges of
+/// the log spectrum in colour with every segment drawn on) comes from omr_get_angle_with_fft_ex in the same pass and
+/// is written when `edge_image_output_dir` is not empty.
 pub fn get_angle_with_fft(
     gray_tm: &TransformableMatrix,
     canny_threshold_1: f64,
@@ -37,12 +38,17 @@ pub fn get_angle_with_fft(
 ) -> Result<f64, opencv::Error> {
     let v = view(gray_tm.get_mat())?;
     let mut angle = 0.0f64;
-    check(unsafe { ffi::omr_get_angle_with_fft(&v, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, &mut angle) })?;
-    if !edge_image_output_dir.is_empty() {
-        let (_, log_pic) = get_fft_image(gray_tm)?;
+    if edge_image_output_dir.is_empty() {
+        check(unsafe { ffi::omr_get_angle_with_fft(&v, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, &mut angle) })?;
+    } else {
+        let mut lined = ffi::OmrImageOwned::empty();
+        check(unsafe {
+            ffi::omr_get_angle_with_fft_ex(&v, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, &mut angle, &mut lined)
+        })?;
+        let pic = into_mat(lined)?;
         let path = Path::new(edge_image_output_dir).join(file_name);
         let params: Vector<i32> = Vector::from_slice(&[imgcodecs::IMWRITE_JPEG_QUALITY, 100]);
-        imgcodecs::imwrite(path.to_str().unwrap_or(file_name), &log_pic, &params)?;
+        imgcodecs::imwrite(path.to_str().unwrap_or(file_name), &pic, &params)?;
     }
     Ok(angle)
 }
