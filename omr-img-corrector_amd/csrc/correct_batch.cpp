@@ -46,9 +46,10 @@ const int kChunk = 256;  // sheets per front-end / warp launch when a full-size 
 
 // the decided angles of one warp phase as a candidate set of the batch warp
 struct WarpSet {
-    DevBuf minv, size, adelta, bdelta, xy0, best, ovf, tiles;
-    std::vector<double> h_minv;
-    std::vector<int32_t> h_size, h_best;
+    DeskewTables tab;
+    DevBuf best, tiles;
+    std::vector<double> angles;  // the distinct ones
+    std::vector<int32_t> h_best;
 };
 
 // Largest CONTAIN canvas over every angle: ceil(rows |sin| + cols |cos|) <= ceil(sqrt(rows^2 + cols^2)) on both axes,
@@ -128,65 +129,36 @@ int warp_phase(omr_correct_batch *cb, WarpSet &w, const std::vector<int> &sheets
 {
     if (sheets.empty()) return OMR_OK;
     std::map<uint64_t, int> index;  // angle bits -> candidate
-    w.h_minv.clear();
-    w.h_size.clear();
+    w.angles.clear();
     w.h_best.assign((size_t)cb->max_scans, 0);
     for (int i : sheets) {
         uint64_t bits;
         memcpy(&bits, &angle[i], sizeof bits);
         auto it = index.find(bits);
         if (it == index.end()) {
-            double M[6], Mi[6];
-            int r, c;
-            int rc = rotate_geometry(cb->rows, cb->cols, angle[i], 1.0, OMR_CLIP_CONTAIN, M, &r, &c);
-            if (rc) return rc;
-            if (r > cb->DR || c > cb->DC) return fail(OMR_ERR_ASSERT, "canvas %d x %d exceeds the context's %d x %d", r, c, cb->DR, cb->DC);
-            invert_affine(M, Mi);
-            w.h_minv.insert(w.h_minv.end(), Mi, Mi + 6);
-            w.h_size.push_back(r);
-            w.h_size.push_back(c);
             it = index.emplace(bits, (int)index.size()).first;
+            w.angles.push_back(angle[i]);
         }
         w.h_best[(size_t)i] = it->second;
-        if (out_size) {
-            out_size[2 * (size_t)i] = w.h_size[2 * (size_t)it->second];
-            out_size[2 * (size_t)i + 1] = w.h_size[2 * (size_t)it->second + 1];
-        }
     }
-    const int A = (int)index.size();
-    int rc;
-    if ((rc = upload_vec(&w.minv, w.h_minv.data(), sizeof(double) * w.h_minv.size(), s))) return rc;
-    if ((rc = upload_vec(&w.size, w.h_size.data(), sizeof(int32_t) * w.h_size.size(), s))) return rc;
+    DeskewTables &t = w.tab;
+    int rc = t.plan(cb->rows, cb->cols, w.angles.data(), (int)w.angles.size());
+    if (rc) return rc;
+    if (t.rows > cb->DR || t.cols > cb->DC)
+        return fail(OMR_ERR_ASSERT, "canvas %d x %d exceeds the context's %d x %d", t.rows, t.cols, cb->DR, cb->DC);
+    if (out_size)
+        for (int i : sheets) memcpy(&out_size[2 * (size_t)i], &t.h_size[2 * (size_t)w.h_best[(size_t)i]], 2 * sizeof(int32_t));
+    t.rows = cb->DR, t.cols = cb->DC;  // tables and tiles of the context's canvas whatever the angles: the buffers grow once
     if ((rc = upload_vec(&w.best, w.h_best.data(), sizeof(int32_t) * w.h_best.size(), s))) return rc;
-    if ((rc = grow(&w.adelta, sizeof(int32_t) * (size_t)A * cb->DC))) return rc;
-    if ((rc = grow(&w.bdelta, sizeof(int32_t) * (size_t)A * cb->DC))) return rc;
-    if ((rc = grow(&w.xy0, sizeof(int2_t) * (size_t)A * cb->DR))) return rc;
-    if ((rc = grow(&w.ovf, sizeof(int32_t)))) return rc;
-    OMR_HIP(hipMemsetAsync(w.ovf.p, 0, sizeof(int32_t), s));
-    SweepDims td{cb->DR, cb->DC, A, 0};
-    OMR_HIP(launch_tables(w.minv.as<double>(), td, 0, w.adelta.as<int32_t>(), w.bdelta.as<int32_t>(), w.xy0.as<int2_t>(),
-                          w.ovf.as<int32_t>(), s));
-    {  // as build_deskew_tables: no canvas is written from tables that left warpAffine's 32-bit fixed-point range
-        int32_t h_ovf = 0;
-        OMR_HIP(hipMemcpyAsync(&h_ovf, w.ovf.p, sizeof h_ovf, hipMemcpyDeviceToHost, s));
-        OMR_HIP(hipStreamSynchronize(s));
-        if (h_ovf) return fail(OMR_ERR_BADARG, "affine map leaves the 32-bit fixed-point range of warpAffine");
-    }
-    DeskewPass p{};
+    if ((rc = t.upload(s))) return rc;
+    DeskewPass p = t.pass();
     p.scan_stride = scan_stride;
     p.sstep = step;
     p.srows = cb->rows;
     p.scols = cb->cols;
     p.out_stride = out_stride;
     p.dstep = out_step;
-    p.wsize = w.size.as<int32_t>();
-    p.adelta = w.adelta.as<int32_t>();
-    p.bdelta = w.bdelta.as<int32_t>();
-    p.xy0 = w.xy0.as<int2_t>();
-    p.DC = cb->DC;
-    p.DR = cb->DR;
     p.border = cb->cn == 1 ? 255 : 0xffffff;  // omr.rs:438: Scalar(255, 255, 255, 0)
-    p.out_size = nullptr;
     p.cn = cb->cn;
     if ((rc = grow(&w.tiles, deskew_tile_bytes(p, kChunk)))) return rc;
     // one launch per run of consecutive sheets (at most kChunk of them)

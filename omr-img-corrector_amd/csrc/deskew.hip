@@ -14,15 +14,20 @@
 
 namespace omr {
 
-#define DW_TW 128  // destination tile: 128 x 32 pixels per 256-thread workgroup, 4 x 4 pixels per thread
-// tile height: 64 rows for NEAREST (the fixed chain of memory round trips per tile is spread over more pixels),
-// 32 for LINEAR (four taps per pixel: at 64 rows the pixels in flight cost 200 VGPRs)
-#ifndef DW_TH_NN
-#define DW_TH_NN 64
-#define DW_TH_LIN 64
-#define DW_LDS 16384
-#endif
-#define DW_TH (LINEAR ? DW_TH_LIN : DW_TH_NN)
+// 1 channel: a destination tile of 128 x 64 pixels per 256-thread workgroup, a thread = 4 adjacent pixels in each of 8 rows
+// 8 apart; 64 rows, so that the fixed chain of memory round trips per tile is spread over more pixels (LINEAR ran 32 rows for
+// a while: with every row of a 64-row tile in flight its four taps per pixel cost 200 VGPRs; the loop over the rows is now
+// rolled, DW_KU below).  The source box of a tile is staged in DW_LDS bytes of LDS.
+constexpr int DW_TW = 128, DW_TH = 64, DW_LDS = 16384;
+// the warp kernels' second launch bound.  (While every row of a tile was in flight, forcing more waves per SIMD was measured
+// and lost: __launch_bounds__(256, 6) spilled, 127 / 126 us per 8 A4 scans against 62 / 104 at the compiler's own 100 / 92
+// VGPRs.  With the rolled loop the kernels fit 64 VGPRs without scratch, and 8 keeps them there.)
+constexpr int DW_MIN_BLOCKS = 8;
+// 3 channels (BGR): 64 x 64 pixels = 192 x 64 bytes, a box of DW3_LDS bytes; the reasons stand with deskew_warp3_kernel
+constexpr int DW3_TW = 64, DW3_TH = 64, DW3_LDS = 24576;
+template <int CN> constexpr int dw_tw = CN == 3 ? DW3_TW : DW_TW;
+template <int CN> constexpr int dw_th = CN == 3 ? DW3_TH : DW_TH;
+template <int CN> constexpr int dw_lds = CN == 3 ? DW3_LDS : DW_LDS;
 
 __device__ __forceinline__ int dw_mad24(int a, int b, int c) { return __mul24(a, b) + c; }  // v_mad_i32_i24
 // The same, spelled out: the compiler turns __mul24 of operands it has folded into other arithmetic back into a plain multiply
@@ -49,9 +54,12 @@ struct DeskewTile {
     int32_t last;     // tx1 | ty1 << 16: the tile's last column and row inside the canvas
 };
 
-template <bool LINEAR>
+// One thread per (scan, tile).  CN = 3: bb0 and bwb are BYTES of a source row as well (three per pixel, widened to whole dwords);
+// a1 / b1 stay 0 (the colour warp repeats the last column's entries itself) and there are no 16-byte pieces.
+template <bool LINEAR, int CN>
 __global__ __launch_bounds__(64) void deskew_tiles_kernel(const DeskewPass p, DeskewTile *__restrict__ tiles, int ntx, int nty)
 {
+    constexpr int TW = dw_tw<CN>, TH = dw_th<CN>, LDS = dw_lds<CN>;
     const int t = blockIdx.x * 64 + threadIdx.x, z = blockIdx.y;
     if (t >= ntx * nty) return;
     const int tyi = t / ntx, txi = t - tyi * ntx;
@@ -63,12 +71,12 @@ __global__ __launch_bounds__(64) void deskew_tiles_kernel(const DeskewPass p, De
     }
     DeskewTile r;
     r.a = -1, r.bb0 = r.by0 = r.bwb = r.bh = r.a1 = r.b1 = r.last = 0;
-    const int tx0 = txi * DW_TW, ty0 = tyi * DW_TH;
+    const int tx0 = txi * TW, ty0 = tyi * TH;
     if (tx0 < dcols && ty0 < drows) {
         const int32_t *__restrict__ AD = p.adelta + (int64_t)a * p.DC, *__restrict__ BD = p.bdelta + (int64_t)a * p.DC;
         const int2_t *__restrict__ XY = p.xy0 + (int64_t)a * p.DR;
         const int rd = LINEAR ? 16 : 512;
-        const int tx1 = min(dcols, tx0 + DW_TW) - 1, ty1 = min(drows, ty0 + DW_TH) - 1;
+        const int tx1 = min(dcols, tx0 + TW) - 1, ty1 = min(drows, ty0 + TH) - 1;
         const int2_t r0 = XY[ty0], r1 = XY[ty1];
         const int a0 = AD[tx0], a1 = AD[tx1], b0 = BD[tx0], b1 = BD[tx1];
         // fixed-point source coordinates of the tile's corner samples.  X0(y) and adelta(x) are both monotone, so the four
@@ -80,36 +88,47 @@ __global__ __launch_bounds__(64) void deskew_tiles_kernel(const DeskewPass p, De
         const int bx1 = max(max(cx[0], cx[1]), max(cx[2], cx[3])) + 1 + (LINEAR ? 1 : 0);
         const int by0 = min(min(cy[0], cy[1]), min(cy[2], cy[3])) - 1;
         const int by1 = max(max(cy[0], cy[1]), max(cy[2], cy[3])) + 1 + (LINEAR ? 1 : 0);
-        const int bb0 = bx0 & ~3, bb1 = (bx1 + 4) & ~3;  // the box in bytes of a source row, widened to whole dwords: [bb0, bb1)
+        const bool sane = bx0 > -30000 && bx1 < 30000 && by0 > -30000 && by1 < 30000;
+        // the box in bytes of a source row, widened to whole dwords: [bb0, bb1)
+        int bb0, bb1;
+        if constexpr (CN == 1) bb0 = bx0 & ~3, bb1 = (bx1 + 4) & ~3;
+        else bb0 = sane ? (bx0 * 3) & ~3 : 0, bb1 = sane ? ((bx1 + 1) * 3 + 3) & ~3 : 0;
         const int bwb = bb1 - bb0, bh = by1 - by0 + 1;
-        // (a scan whose rows are not whole aligned dwords -- width, pitch or address not a multiple of 4 -- takes the
-        // unstaged path: the staging loop then has no partial dwords and no branches)
+        // (a scan whose rows are not whole aligned dwords -- pitch, stride or address not a multiple of 4, nor the width of
+        // a 1-channel scan -- takes the unstaged path: the staging loop then has no partial dwords and no branches)
         // ... nor a scan of 2 GB or more: the staging loads address it by 32-bit byte offsets through a buffer descriptor
-        const bool dwords = ((p.sstep | p.scan_stride | (int64_t)(uintptr_t)p.src | (int64_t)p.scols) & 3) == 0 &&
+        const bool dwords = ((p.sstep | p.scan_stride | (int64_t)(uintptr_t)p.src | (CN == 1 ? (int64_t)p.scols : 0)) & 3) == 0 &&
                             (int64_t)p.srows * p.sstep < (int64_t)0x7fffffff;
-        // ... nor a canvas of 2 GB or more, or with rows of 16 MB: the staged path's stores address the scan's canvas by 32-bit
-        // offsets made with a 24-bit multiply (a 64-bit address per store row cost two full-rate-quarter multiplies, see below)
-        const bool canvas32 = p.dstep < (1 << 24) && (int64_t)p.DR * p.dstep < (int64_t)0x7fffffff;
-        const bool staged = dwords && canvas32 && bwb > 0 && bh > 0 && (int64_t)bwb * bh <= DW_LDS && bx0 > -30000 && bx1 < 30000 &&
-                            by0 > -30000 && by1 < 30000;
+        // ... nor (1 channel) a canvas of 2 GB or more, or with rows of 16 MB: the staged path's stores address the scan's canvas by
+        // 32-bit offsets made with a 24-bit multiply (a 64-bit address per store row cost two quarter-rate multiplies, see below)
+        bool canvas32 = true;
+        if constexpr (CN == 1) canvas32 = p.dstep < (1 << 24) && (int64_t)p.DR * p.dstep < (int64_t)0x7fffffff;
+        const bool staged = dwords && canvas32 && sane && bwb > 0 && bh > 0 && (int64_t)bwb * bh <= LDS;
         // A tile whose box lies wholly outside the scan (the corners of a CONTAIN canvas: up to a fifth of it at 10 degrees)
         // is the border value: every tap of every sample is outside, NEAREST takes it as it is and the bilinear weights of
         // four equal taps sum to 2^15
         const bool all_border = bx1 < 0 || by1 < 0 || bx0 >= p.scols || by0 >= p.srows;
-        // a box that lies wholly inside the image -- all but the tiles on the scan's edges -- is fetched in 16-byte pieces
-        // (rows padded to a multiple of 16 bytes in LDS; the padding stays inside the image row too): a quarter of the
-        // DMA instructions.  Bit 30 of bh says so.
-        const int bwb16 = (bwb + 15) & ~15;
-        const bool x4 = staged && bb0 >= 0 && by0 >= 0 && by0 + bh <= p.srows && bb0 + bwb16 <= p.scols && (int64_t)bwb16 * bh <= DW_LDS;
         r.a = a, r.bb0 = bb0, r.by0 = by0;
-        r.bwb = all_border ? 0 : x4 ? bwb16 : staged ? bwb : -1;  // the box's pitch in LDS; -1: taps from global memory
-        r.bh = bh | (x4 ? 1 << 30 : 0), r.a1 = a1, r.b1 = b1, r.last = tx1 | (ty1 << 16);
+        r.bwb = all_border ? 0 : staged ? bwb : -1;  // the box's pitch in LDS; -1: taps from global memory
+        r.bh = bh, r.last = tx1 | (ty1 << 16);
+        if constexpr (CN == 1) {
+            // a box that lies wholly inside the image -- all but the tiles on the scan's edges -- is fetched in 16-byte pieces
+            // (rows padded to a multiple of 16 bytes in LDS; the padding stays inside the image row too): a quarter of the
+            // DMA instructions.  Bit 30 of bh says so.
+            const int bwb16 = (bwb + 15) & ~15;
+            const bool x4 = staged && bb0 >= 0 && by0 >= 0 && by0 + bh <= p.srows && bb0 + bwb16 <= p.scols && (int64_t)bwb16 * bh <= LDS;
+            if (x4 && !all_border) r.bwb = bwb16;
+            r.bh = bh | (x4 ? 1 << 30 : 0), r.a1 = a1, r.b1 = b1;
+        }
     }
     tiles[(int64_t)z * ntx * nty + t] = r;
 }
 
-// grid = (tiles across the largest canvas, tiles down it, scans of the launch); a tile outside its scan's canvas
-// leaves at once.  (Scans fastest instead -- XCD x warps only scan x, so overlapping boxes meet in one L2 -- halves the
+// grid = 8 * ntx * ceil(nty / 8) * scans workgroups in one dimension (ntx x nty: the tiles of the largest canvas; a tile outside
+// its scan's canvas leaves at once).  Workgroup ids go round-robin to the 8 XCDs, so XCD k warps the tile ROWS k, k + 8, .. of
+// every scan, left to right: the overlapping boxes of a row's neighbouring tiles meet in one L2, and every XCD has the same
+// share of every scan.  (Two 3-D grids came before it.  Tiles fastest: every L2 saw every eighth tile of a row and each box was
+// fetched from memory in full, 2 x the scans' bytes.  Scans fastest -- XCD x warps only scan x, x + 8, .. -- halves the
 // HBM fetch, 71.8 -> 34.3 MB per 8 scans = the scans' own bytes, but is no faster: 65 / 114 us against 66 / 105.  The
 // kernel is not waiting for HBM.  Nor for its chain of round trips alone: a software-pipelined form -- a vertical strip of
 // four 128 x 32 tiles per workgroup, tile i sampled from one LDS box while the box of tile i + 1 is in flight and the
@@ -120,32 +139,15 @@ __global__ __launch_bounds__(64) void deskew_tiles_kernel(const DeskewPass p, De
 // memory round trips (tile record -> {table entries, box} -> taps): everything that depends on (scan, tile) alone was
 // worked out by deskew_tiles_kernel, and the thread's own column and row table entries are requested with the box.
 template <bool LINEAR>
-// (forcing more waves per SIMD was measured and lost: __launch_bounds__(256, 6) spills, 127 / 126 us per 8 A4 scans
-// against 62 / 104 at the compiler's own 100 / 92 VGPRs)
-#ifndef DW_MIN_BLOCKS
-#define DW_MIN_BLOCKS 8
-#endif
-__global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const DeskewPass p, const DeskewTile *__restrict__ tiles)
+__global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const DeskewPass p, const DeskewTile *__restrict__ tiles, int ntx,
+                                                                         int nty)
 {
     __shared__ __attribute__((aligned(16))) uint8_t box[DW_LDS];
-    // grid = (scans, tiles across, tiles down), scans fastest: workgroup ids go round-robin to the 8 XCDs, so XCD x warps the
-    // scans x, x + 8, .. only and the overlapping boxes of a scan's neighbouring tiles meet in ONE L2 (with tiles fastest every
-    // L2 saw every eighth tile of a row and each box was fetched from memory in full: 2 x the scans' bytes)
-    // (p.order = 0: tiles fastest, grid = (tiles across, tiles down, scans); 1: scans fastest; 2: a 1-D grid in which XCD k --
-    // workgroup ids go round-robin to the 8 XCDs -- warps the tile ROWS k, k + 8, .. of every scan, left to right: the
-    // overlapping boxes of a row's neighbouring tiles meet in one L2, and every XCD has the same share of every scan)
-    int z, txi, tyi, ntx, nty;
-    if (p.order == 2) {
-        ntx = p.ntx, nty = p.nty;
-        const int nty8 = (nty + 7) >> 3, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        txi = j % ntx;
-        const int q = j / ntx, r = q % nty8;
-        z = q / nty8, tyi = r * 8 + xcd;
-        if (tyi >= nty) return;
-    } else {
-        z = p.order ? blockIdx.x : blockIdx.z, txi = p.order ? blockIdx.y : blockIdx.x, tyi = p.order ? blockIdx.z : blockIdx.y;
-        ntx = p.order ? gridDim.y : gridDim.x, nty = p.order ? gridDim.z : gridDim.y;
-    }
+    const int nty8 = (nty + 7) >> 3, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    const int txi = jb % ntx;
+    const int q = jb / ntx, rq = q % nty8;
+    const int z = q / nty8, tyi = rq * 8 + xcd;
+    if (tyi >= nty) return;
     // the tile's record: wave-uniform, fetched by the scalar unit
     const DeskewTile *__restrict__ tr = tiles + ((int64_t)z * nty + tyi) * ntx + txi;
     const int a = tr->a;
@@ -187,7 +189,7 @@ __global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const D
     // the tile's row table entries travel through LDS (thread t brings row ty0 + t): one load per thread instead of DW_TH / 8,
     // and no registers hold them while the box is in flight
     __shared__ int2_t rowtab[DW_TH];
-    static_assert(DW_TH_NN <= 256 && DW_TH_LIN <= 256, "one thread per row of the tile brings its table entry");
+    static_assert(DW_TH <= 256, "one thread per row of the tile brings its table entry");
     if (threadIdx.x < DW_TH) rowtab[threadIdx.x] = XY[min(ty0 + (int)threadIdx.x, ty1)];
     if (staged) {
         // the box as dwords, thread t takes dwords t, t + 256, ..: LDS-DMA (`buffer_load_dword ... lds`: the 64 lanes of a
@@ -291,12 +293,11 @@ __global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const D
         }
         return;
     }
-    // box[(sy - by0) * bwb + (sx - bb0)]: the box's origin rides on the row's X0 / Y0 (multiples of 1024: the fraction
-    // bits stay; |coordinates| < 30000 pixels, so nothing overflows).  Straight-line: the 16 / 32 pixels' taps are all requested before the first is blended,
-    // and nothing below is conditional except the last tile column's byte stores -- a row past the tile's last one
-    // recomputes that row's pixels (its table entry was clamped) and stores them there again, the same bytes.
-    // The box's origin rides on the thread's column entries (multiples of 1024: the fraction bits stay; |coordinates| <
-    // 30000 pixels, so nothing overflows): a sample is two additions, two shifts and one multiply-add away from its LDS byte.
+    // box[(sy - by0) * bwb + (sx - bb0)]: the box's origin rides on the thread's column entries (multiples of 1024: the
+    // fraction bits stay; |coordinates| < 30000 pixels, so nothing overflows), so a sample is two additions, two shifts and one
+    // multiply-add away from its LDS byte.  Nothing below is conditional except the last tile column's byte stores -- a row
+    // past the tile's last one recomputes that row's pixels (its table entry was clamped) and stores them there again, the
+    // same bytes.
     const int orgx = rd - (bb0 << 10), orgy = rd - (by0 << 10);
 #pragma unroll
     for (int j = 0; j < 4; j++) adv[j] += orgx, bdv[j] += orgy;
@@ -375,10 +376,6 @@ __global__ __launch_bounds__(256, DW_MIN_BLOCKS) void deskew_warp_kernel(const D
 // tile of an A4 scan up to about +-14 degrees (the gray kernel's 128 x 64 tile would need about 140 x 88 x 3 = 37 KB per box,
 // and twice the staged bytes per stored byte at the edges of a row of tiles is the smaller cost: a box row is 1.2 x the tile's
 // row at 64 pixels against 1.1 x at 128).  p.border holds the border value's three bytes (channel c = byte c).
-#define DW3_TW 64
-#define DW3_TH 64
-#define DW3_LDS 24576
-
 // channel c of the colour sample at (Xf, Yf) from global memory: warp_tap_global with cn = 3, but one base address offset
 // four times -- a whole scan takes this path when its pitch, stride or address is not a multiple of 4
 template <bool LINEAR>
@@ -404,57 +401,13 @@ __device__ __forceinline__ int dw3_tap_global(const uint8_t *__restrict__ src, i
     return sat_u8((v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15);
 }
 
-// one thread per (scan, tile): the DeskewTile record of a colour tile (bb0, bwb in BYTES of a source row, whole dwords)
-template <bool LINEAR>
-__global__ __launch_bounds__(64) void deskew_tiles3_kernel(const DeskewPass p, DeskewTile *__restrict__ tiles, int ntx, int nty)
-{
-    const int t = blockIdx.x * 64 + threadIdx.x, z = blockIdx.y;
-    if (t >= ntx * nty) return;
-    const int tyi = t / ntx, txi = t - tyi * ntx;
-    const int a = p.best[z];
-    const int drows = p.wsize[2 * a], dcols = p.wsize[2 * a + 1];
-    if (t == 0 && p.out_size) {
-        p.out_size[2 * z] = drows;
-        p.out_size[2 * z + 1] = dcols;
-    }
-    DeskewTile r;
-    r.a = -1, r.bb0 = r.by0 = r.bwb = r.bh = r.a1 = r.b1 = r.last = 0;
-    const int tx0 = txi * DW3_TW, ty0 = tyi * DW3_TH;
-    if (tx0 < dcols && ty0 < drows) {
-        const int32_t *__restrict__ AD = p.adelta + (int64_t)a * p.DC, *__restrict__ BD = p.bdelta + (int64_t)a * p.DC;
-        const int2_t *__restrict__ XY = p.xy0 + (int64_t)a * p.DR;
-        const int rd = LINEAR ? 16 : 512;
-        const int tx1 = min(dcols, tx0 + DW3_TW) - 1, ty1 = min(drows, ty0 + DW3_TH) - 1;
-        const int2_t r0 = XY[ty0], r1 = XY[ty1];
-        const int a0 = AD[tx0], a1 = AD[tx1], b0 = BD[tx0], b1 = BD[tx1];
-        const int cx[4] = {(r0.x + rd + a0) >> 10, (r0.x + rd + a1) >> 10, (r1.x + rd + a0) >> 10, (r1.x + rd + a1) >> 10};
-        const int cy[4] = {(r0.y + rd + b0) >> 10, (r0.y + rd + b1) >> 10, (r1.y + rd + b0) >> 10, (r1.y + rd + b1) >> 10};
-        const int bx0 = min(min(cx[0], cx[1]), min(cx[2], cx[3])) - 1;
-        const int bx1 = max(max(cx[0], cx[1]), max(cx[2], cx[3])) + 1 + (LINEAR ? 1 : 0);
-        const int by0 = min(min(cy[0], cy[1]), min(cy[2], cy[3])) - 1;
-        const int by1 = max(max(cy[0], cy[1]), max(cy[2], cy[3])) + 1 + (LINEAR ? 1 : 0);
-        const bool sane = bx0 > -30000 && bx1 < 30000 && by0 > -30000 && by1 < 30000;
-        const int bb0 = sane ? (bx0 * 3) & ~3 : 0, bb1 = sane ? ((bx1 + 1) * 3 + 3) & ~3 : 0;  // [bb0, bb1): bytes of a row
-        const int bwb = bb1 - bb0, bh = by1 - by0 + 1;
-        // rows that are not whole aligned dwords (pitch, scan stride or address not a multiple of 4): the unstaged path
-        const bool dwords = ((p.sstep | p.scan_stride | (int64_t)(uintptr_t)p.src) & 3) == 0 && (int64_t)p.srows * p.sstep < (int64_t)0x7fffffff;
-        const bool staged = dwords && sane && bwb > 0 && bh > 0 && (int64_t)bwb * bh <= DW3_LDS;
-        const bool all_border = bx1 < 0 || by1 < 0 || bx0 >= p.scols || by0 >= p.srows;
-        r.a = a, r.bb0 = bb0, r.by0 = by0;
-        r.bwb = all_border ? 0 : staged ? bwb : -1;
-        r.bh = bh, r.last = tx1 | (ty1 << 16);
-    }
-    tiles[(int64_t)z * ntx * nty + t] = r;
-}
-
-// grid = 8 * ntx * ceil(nty / 8) * scans workgroups, the gray kernel's order 2 (XCD k warps the tile rows k, k + 8, .. of every
+// grid = 8 * ntx * ceil(nty / 8) * scans workgroups, as the 1-channel kernel's (XCD k warps the tile rows k, k + 8, .. of every
 // scan); the box is staged with dword loads (border bytes outside the image, channel = byte offset mod 3), a tap is LDS reads
 // with no bounds test.
 template <bool LINEAR>
-__global__ __launch_bounds__(256) void deskew_warp3_kernel(const DeskewPass p, const DeskewTile *__restrict__ tiles)
+__global__ __launch_bounds__(256) void deskew_warp3_kernel(const DeskewPass p, const DeskewTile *__restrict__ tiles, int ntx, int nty)
 {
     __shared__ __attribute__((aligned(16))) uint8_t box[DW3_LDS];
-    const int ntx = p.ntx, nty = p.nty;
     const int nty8 = (nty + 7) >> 3, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
     const int txi = jb % ntx;
     const int q = jb / ntx, rq = q % nty8;
@@ -574,54 +527,43 @@ __global__ __launch_bounds__(256) void deskew_warp3_kernel(const DeskewPass p, c
     }
 }
 
-size_t deskew_tile_bytes(const DeskewPass &p, int scans)
+namespace {
+// tiles across and down the largest canvas
+template <int CN>
+void deskew_tile_counts(const DeskewPass &p, int *ntx, int *nty)
 {
-    if (p.cn == 3)
-        return sizeof(DeskewTile) * (size_t)((p.DC + DW3_TW - 1) / DW3_TW) * (size_t)((p.DR + DW3_TH - 1) / DW3_TH) * (size_t)scans;
-    // (tiles of the LINEAR kernel: the smaller tile, so the buffer serves both)
-    constexpr int th = DW_TH_LIN < DW_TH_NN ? DW_TH_LIN : DW_TH_NN;
-    return sizeof(DeskewTile) * (size_t)((p.DC + DW_TW - 1) / DW_TW) * (size_t)((p.DR + th - 1) / th) * (size_t)scans;
+    *ntx = (p.DC + dw_tw<CN> - 1) / dw_tw<CN>, *nty = (p.DR + dw_th<CN> - 1) / dw_th<CN>;
 }
 
-hipError_t launch_deskew_warp(const DeskewPass &p0, int scans, int interp, void *d_tiles, hipStream_t s)
+// the records of the launch's tiles, then the warp that starts from them
+template <bool LINEAR, int CN>
+hipError_t deskew_launch(const DeskewPass &p, int scans, DeskewTile *tiles, hipStream_t s)
+{
+    int ntx, nty;
+    deskew_tile_counts<CN>(p, &ntx, &nty);
+    hipLaunchKernelGGL((deskew_tiles_kernel<LINEAR, CN>), dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
+    const dim3 grid(8 * ntx * ((nty + 7) / 8) * scans);
+    if constexpr (CN == 3) hipLaunchKernelGGL(deskew_warp3_kernel<LINEAR>, grid, dim3(256), 0, s, p, tiles, ntx, nty);
+    else hipLaunchKernelGGL(deskew_warp_kernel<LINEAR>, grid, dim3(256), 0, s, p, tiles, ntx, nty);
+    return hipGetLastError();
+}
+}  // namespace
+
+size_t deskew_tile_bytes(const DeskewPass &p, int scans)
+{
+    int ntx, nty;
+    if (p.cn == 3) deskew_tile_counts<3>(p, &ntx, &nty);
+    else deskew_tile_counts<1>(p, &ntx, &nty);
+    return sizeof(DeskewTile) * (size_t)ntx * (size_t)nty * (size_t)scans;
+}
+
+hipError_t launch_deskew_warp(const DeskewPass &p, int scans, int interp, void *d_tiles, hipStream_t s)
 {
     if (scans <= 0) return hipSuccess;
-    DeskewPass p = p0;
-#ifdef DW_ORDER
-    p.order = DW_ORDER;
-#else
-    p.order = 2;
-#endif
-    if ((p.DC & 3) != 0 || !d_tiles) return hipErrorInvalidValue;
+    if ((p.DC & 3) != 0 || !d_tiles || (p.cn != 3 && p.cn > 1)) return hipErrorInvalidValue;  // (cn 0 = 1)
     DeskewTile *tiles = (DeskewTile *)d_tiles;
-    if (p.cn == 3) {  // BGR scans: 64 x 64 tiles, always the order-2 grid
-        const int ntx = (p.DC + DW3_TW - 1) / DW3_TW, nty = (p.DR + DW3_TH - 1) / DW3_TH;
-        p.ntx = ntx, p.nty = nty;
-        const dim3 grid(8 * ntx * ((nty + 7) / 8) * scans);
-        if (interp == 0) {
-            hipLaunchKernelGGL(deskew_tiles3_kernel<false>, dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
-            hipLaunchKernelGGL(deskew_warp3_kernel<false>, grid, dim3(256), 0, s, p, tiles);
-        } else {
-            hipLaunchKernelGGL(deskew_tiles3_kernel<true>, dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
-            hipLaunchKernelGGL(deskew_warp3_kernel<true>, grid, dim3(256), 0, s, p, tiles);
-        }
-        return hipGetLastError();
-    }
-    if (p.cn > 1) return hipErrorInvalidValue;  // (0 = 1)
-    if (interp == 0) {
-        constexpr bool LINEAR = false;
-        const int ntx = (p.DC + DW_TW - 1) / DW_TW, nty = (p.DR + DW_TH - 1) / DW_TH;
-        hipLaunchKernelGGL(deskew_tiles_kernel<false>, dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
-        p.ntx = ntx, p.nty = nty;
-        hipLaunchKernelGGL(deskew_warp_kernel<false>, p.order == 2 ? dim3(8 * ntx * ((nty + 7) / 8) * scans) : p.order ? dim3(scans, ntx, nty) : dim3(ntx, nty, scans), dim3(256), 0, s, p, tiles);
-    } else {
-        constexpr bool LINEAR = true;
-        const int ntx = (p.DC + DW_TW - 1) / DW_TW, nty = (p.DR + DW_TH - 1) / DW_TH;
-        hipLaunchKernelGGL(deskew_tiles_kernel<true>, dim3((ntx * nty + 63) / 64, scans), dim3(64), 0, s, p, tiles, ntx, nty);
-        p.ntx = ntx, p.nty = nty;
-        hipLaunchKernelGGL(deskew_warp_kernel<true>, p.order == 2 ? dim3(8 * ntx * ((nty + 7) / 8) * scans) : p.order ? dim3(scans, ntx, nty) : dim3(ntx, nty, scans), dim3(256), 0, s, p, tiles);
-    }
-    return hipGetLastError();
+    if (p.cn == 3) return interp == 0 ? deskew_launch<false, 3>(p, scans, tiles, s) : deskew_launch<true, 3>(p, scans, tiles, s);
+    return interp == 0 ? deskew_launch<false, 1>(p, scans, tiles, s) : deskew_launch<true, 1>(p, scans, tiles, s);
 }
 
 }  // namespace omr

@@ -306,6 +306,74 @@ int upload_table(DevBuf *b, const void *p, size_t bytes, hipStream_t s)
     return OMR_OK;
 }
 
+int DeskewTables::plan(int srows, int scols, const double *angles_deg, int n)
+{
+    h_minv.assign((size_t)n * 6, 0.0);
+    h_size.assign((size_t)n * 2, 0);
+    rows = cols = 0;
+    on_device = false;
+    for (int i = 0; i < n; i++) {
+        double M[6];
+        int rc = rotate_geometry(srows, scols, angles_deg[i], 1.0, OMR_CLIP_CONTAIN, M, &h_size[2 * (size_t)i], &h_size[2 * (size_t)i + 1]);
+        if (rc) {
+            h_size.clear();
+            return rc;
+        }
+        invert_affine(M, &h_minv[6 * (size_t)i]);
+        rows = std::max(rows, (int)h_size[2 * (size_t)i]);
+        cols = std::max(cols, (int)h_size[2 * (size_t)i + 1]);
+    }
+    cols = (cols + 3) & ~3;
+    return OMR_OK;
+}
+
+int DeskewTables::upload(hipStream_t s)
+{
+    const size_t A = (size_t)count();
+    on_device = false;
+    auto put = [s](DevBuf *b, const void *p, size_t bytes) {
+        int rc = grow(b, bytes);
+        if (rc) return rc;
+        if (s) OMR_HIP(hipMemcpyAsync(b->p, p, bytes, hipMemcpyHostToDevice, s));
+        else OMR_HIP(hipMemcpy(b->p, p, bytes, hipMemcpyHostToDevice));
+        return (int)OMR_OK;
+    };
+    int rc;
+    if ((rc = put(&minv, h_minv.data(), sizeof(double) * h_minv.size()))) return rc;
+    if ((rc = put(&size, h_size.data(), sizeof(int32_t) * h_size.size()))) return rc;
+    if ((rc = grow(&ovf, sizeof(int32_t)))) return rc;
+    if (s) OMR_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int32_t), s));
+    else OMR_HIP(hipMemset(ovf.p, 0, sizeof(int32_t)));
+    if ((rc = grow(&adelta, sizeof(int32_t) * A * (size_t)cols))) return rc;
+    if ((rc = grow(&bdelta, sizeof(int32_t) * A * (size_t)cols))) return rc;
+    if ((rc = grow(&xy0, sizeof(int2_t) * A * (size_t)rows))) return rc;
+    SweepDims td{rows, cols, (int)A, 0};
+    OMR_HIP(launch_tables(minv.as<double>(), td, 0, adelta.as<int32_t>(), bdelta.as<int32_t>(), xy0.as<int2_t>(), ovf.as<int32_t>(), s));
+    // no canvas is written from tables that left the fixed-point range; the answer also says that the tables are complete
+    int32_t h_ovf = 0;
+    if (s) {
+        OMR_HIP(hipMemcpyAsync(&h_ovf, ovf.p, sizeof h_ovf, hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+    } else {
+        OMR_HIP(hipMemcpy(&h_ovf, ovf.p, sizeof h_ovf, hipMemcpyDeviceToHost));
+    }
+    if (h_ovf) return fail(OMR_ERR_BADARG, "affine map leaves the 32-bit fixed-point range of warpAffine");
+    on_device = true;
+    return OMR_OK;
+}
+
+DeskewPass DeskewTables::pass() const
+{
+    DeskewPass p{};
+    p.wsize = size.as<int32_t>();
+    p.adelta = adelta.as<int32_t>();
+    p.bdelta = bdelta.as<int32_t>();
+    p.xy0 = xy0.as<int2_t>();
+    p.DC = cols;
+    p.DR = rows;
+    return p;
+}
+
 PoolScope::PoolScope(hipStream_t stream) : prev_(t_pool_stream), prev_on_(t_pool_on)
 {
     t_pool_stream = stream;
@@ -1062,48 +1130,21 @@ struct DeskewOut {  // omr_batch_deskew_device's extra stage
     int32_t *d_out_size;
 };
 
-// per candidate: CONTAIN canvas + warpAffine's tables of its rotation (transfer.rs:487-519), once per context
-int build_deskew_tables(omr_batch_ctx *ctx)
+// the candidates' canvases, on the host alone: the slot checks of the deskew entry points come before any device work
+int deskew_plan(omr_batch_ctx *ctx)
 {
-    if (ctx->dk_built) return OMR_OK;
-    NoPoolScope ctx_owned;
-    const SweepDims &d = ctx->tables.dims;
-    const int A = d.A;
-    std::vector<double> minv((size_t)A * 6);
-    std::vector<int32_t> size((size_t)A * 2);
-    int DR = 0, DC = 0;
-    for (int i = 0; i < A; i++) {
-        double M[6];
-        int dr, dc;
-        int rc = rotate_geometry(d.rows, d.cols, (double)(i - ctx->N) * ctx->step, 1.0, OMR_CLIP_CONTAIN, M, &dr, &dc);
-        if (rc) return rc;
-        invert_affine(M, &minv[6 * (size_t)i]);
-        size[2 * (size_t)i] = dr;
-        size[2 * (size_t)i + 1] = dc;
-        DR = std::max(DR, dr);
-        DC = std::max(DC, dc);
-    }
-    DC = (DC + 3) & ~3;
-    DevBuf d_minv, ovf;
-    OMR_HIP(d_minv.alloc(sizeof(double) * minv.size()));
-    OMR_HIP(ovf.alloc(sizeof(int32_t)));
-    OMR_HIP(ctx->dk_size.alloc(sizeof(int32_t) * size.size()));
-    OMR_HIP(ctx->dk_adelta.alloc(sizeof(int32_t) * (size_t)A * DC));
-    OMR_HIP(ctx->dk_bdelta.alloc(sizeof(int32_t) * (size_t)A * DC));
-    OMR_HIP(ctx->dk_xy0.alloc(sizeof(int2_t) * (size_t)A * DR));
-    OMR_HIP(hipMemcpy(d_minv.p, minv.data(), sizeof(double) * minv.size(), hipMemcpyHostToDevice));
-    OMR_HIP(hipMemcpy(ctx->dk_size.p, size.data(), sizeof(int32_t) * size.size(), hipMemcpyHostToDevice));
-    OMR_HIP(hipMemset(ovf.p, 0, sizeof(int32_t)));
-    SweepDims td{DR, DC, A, 0};
-    OMR_HIP(launch_tables(d_minv.as<double>(), td, 0, ctx->dk_adelta.as<int32_t>(), ctx->dk_bdelta.as<int32_t>(),
-                          ctx->dk_xy0.as<int2_t>(), ovf.as<int32_t>(), nullptr));
-    int32_t h_ovf = 0;
-    OMR_HIP(hipMemcpy(&h_ovf, ovf.p, sizeof h_ovf, hipMemcpyDeviceToHost));  // also: the tables are complete
-    if (h_ovf) return fail(OMR_ERR_BADARG, "affine map leaves the 32-bit fixed-point range of warpAffine");
-    ctx->dk_rows = DR;
-    ctx->dk_cols = DC;
-    ctx->dk_built = true;
-    return OMR_OK;
+    if (ctx->dk.count()) return OMR_OK;
+    std::vector<double> angles((size_t)ctx->tables.dims.A);
+    for (size_t i = 0; i < angles.size(); i++) angles[i] = (double)((int)i - ctx->N) * ctx->step;
+    return ctx->dk.plan(ctx->tables.dims.rows, ctx->tables.dims.cols, angles.data(), (int)angles.size());
+}
+
+// ... and their tables on the device, once per context
+int deskew_tables(omr_batch_ctx *ctx)
+{
+    if (ctx->dk.on_device) return OMR_OK;
+    int rc = deskew_plan(ctx);
+    return rc ? rc : ctx->dk.upload(nullptr);
 }
 
 int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, int64_t step_bytes, int32_t n,
@@ -1148,7 +1189,7 @@ int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, i
                                e1, false, ctx->post_streams[k], ctx->ev_mid[set], z, scan_stride, cn);
         if (rc) return rc;
         if (dk) {  // after the arg-max, on the post stream: overlaps the next group's sweep
-            DeskewPass p{};
+            DeskewPass p = ctx->dk.pass();
             p.src = d_scans + (size_t)i * scan_stride;
             p.scan_stride = scan_stride;
             p.sstep = step_bytes;
@@ -1158,12 +1199,6 @@ int batch_run(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t scan_stride, i
             p.out_stride = dk->out_stride;
             p.dstep = dk->out_step;
             p.best = best;
-            p.wsize = ctx->dk_size.as<int32_t>();
-            p.adelta = ctx->dk_adelta.as<int32_t>();
-            p.bdelta = ctx->dk_bdelta.as<int32_t>();
-            p.xy0 = ctx->dk_xy0.as<int2_t>();
-            p.DC = ctx->dk_cols;
-            p.DR = ctx->dk_rows;
             p.border = dk->border;
             p.out_size = dk->d_out_size ? dk->d_out_size + 2 * (size_t)i : nullptr;
             p.cn = cn;
@@ -1220,10 +1255,10 @@ int omr_batch_deskew_canvas(omr_batch_ctx *ctx, int32_t *max_rows, int32_t *max_
     if (!ctx) return fail(OMR_ERR_BADARG, "null ctx");
     std::lock_guard<std::mutex> lk(ctx->mu);
     OMR_HIP(hipSetDevice(ctx->tables.device));
-    int rc = build_deskew_tables(ctx);
+    int rc = deskew_tables(ctx);
     if (rc) return rc;
-    if (max_rows) *max_rows = ctx->dk_rows;
-    if (max_cols) *max_cols = ctx->dk_cols;
+    if (max_rows) *max_rows = ctx->dk.rows;
+    if (max_cols) *max_cols = ctx->dk.cols;
     return OMR_OK;
 }
 
@@ -1236,11 +1271,11 @@ int omr_batch_deskew_device(omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t 
         return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
     std::lock_guard<std::mutex> lk(ctx->mu);
     OMR_HIP(hipSetDevice(ctx->tables.device));
-    int rc = build_deskew_tables(ctx);
+    int rc = deskew_tables(ctx);
     if (rc) return rc;
-    if (out_step < ctx->dk_cols || out_stride < (int64_t)ctx->dk_rows * out_step)
+    if (out_step < ctx->dk.cols || out_stride < (int64_t)ctx->dk.rows * out_step)
         return fail(OMR_ERR_BADARG, "every output slot must hold the largest canvas, %d x %d (omr_batch_deskew_canvas)",
-                    ctx->dk_cols, ctx->dk_rows);
+                    ctx->dk.cols, ctx->dk.rows);
     DeskewOut dk{interp, (int)border_value, d_out, out_stride, out_step, d_out_size};
     return batch_run(ctx, d_scans, scan_stride, step_bytes, n, black_max, d_best_idx, nullptr, nullptr, &dk, 1);
 }
@@ -1260,27 +1295,6 @@ int check_batch_cn(const omr_batch_ctx *ctx, const uint8_t *d_scans, int64_t ste
     return OMR_OK;
 }
 
-// the largest CONTAIN canvas of the candidate set, from the context's tables or (before they exist) from the host geometry
-// alone: the slot check of omr_batch_deskew_device_cn comes before any device work
-int deskew_canvas_host(const omr_batch_ctx *ctx, int *DR, int *DC)
-{
-    if (ctx->dk_built) {
-        *DR = ctx->dk_rows, *DC = ctx->dk_cols;
-        return OMR_OK;
-    }
-    const SweepDims &d = ctx->tables.dims;
-    int R = 0, Cc = 0;
-    for (int i = 0; i < d.A; i++) {
-        double M[6];
-        int dr, dc;
-        int rc = rotate_geometry(d.rows, d.cols, (double)(i - ctx->N) * ctx->step, 1.0, OMR_CLIP_CONTAIN, M, &dr, &dc);
-        if (rc) return rc;
-        R = std::max(R, dr);
-        Cc = std::max(Cc, dc);
-    }
-    *DR = R, *DC = (Cc + 3) & ~3;  // as build_deskew_tables
-    return OMR_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -1305,13 +1319,13 @@ int omr_batch_deskew_device_cn(omr_batch_ctx *ctx, const uint8_t *d_scans, int64
     if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
         return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int DR = 0, DC = 0;
-    if ((rc = deskew_canvas_host(ctx, &DR, &DC))) return rc;
+    if ((rc = deskew_plan(ctx))) return rc;
+    const int DR = ctx->dk.rows, DC = ctx->dk.cols;
     if (out_step < (int64_t)DC * channels || out_stride < (int64_t)DR * out_step)
         return fail(OMR_ERR_BADARG, "every output slot must hold the largest canvas, %d x %d x %d channels (omr_batch_deskew_canvas)",
                     DC, DR, channels);
     OMR_HIP(hipSetDevice(ctx->tables.device));
-    if ((rc = build_deskew_tables(ctx))) return rc;
+    if ((rc = deskew_tables(ctx))) return rc;
     // 3 channels: the border's bytes 0..2 packed into DeskewPass::border (channel c = byte c)
     const int border = channels == 1 ? (int)border_value[0]
                                      : (int)((uint32_t)border_value[0] | ((uint32_t)border_value[1] << 8) | ((uint32_t)border_value[2] << 16));

@@ -179,6 +179,25 @@ struct AreaTables {
     AreaTaps taps() const { return AreaTaps{xt.as<AreaTap>(), yt.as<AreaTap>(), xo.as<int32_t>(), yo.as<int32_t>()}; }
 };
 
+// The batch warp's candidate set (deskew.hip): per angle the CONTAIN canvas of rotate_mat (transfer.rs:487-519) and
+// warpAffine's fixed-point tables of its rotation.  plan() is host arithmetic alone -- the canvases, and the largest of them,
+// which is all a check of the caller's output slots needs; upload() puts the set on the device.
+struct DeskewTables {
+    std::vector<double> h_minv;   // [A][6] dst -> src matrices
+    std::vector<int32_t> h_size;  // [A][2] canvas rows, cols
+    int rows = 0, cols = 0;       // pitch of the tables: the largest canvas, cols rounded up to 4 (a caller with a bound of
+                                  // its own may widen them between plan and upload)
+    bool on_device = false;
+    DevBuf minv, size, adelta, bdelta, xy0, ovf;  // grow-only
+    int count() const { return (int)h_size.size() / 2; }
+    int plan(int srows, int scols, const double *angles_deg, int n);
+    // copies and launch_tables on `s` (with a null `s`: synchronous copies, as upload_table), then waits for the verdict:
+    // OMR_ERR_BADARG for tables that left warpAffine's 32-bit fixed-point range.  The host vectors stay as they are until then.
+    int upload(hipStream_t s);
+    // the table fields of a launch; source, destination, best, border, out_size and cn are the caller's
+    DeskewPass pass() const;
+};
+
 // Immutable per-(shape, matrices) state: inverse matrices, fixed-point tables, LDS tiling.
 struct SweepTables {
     int device = 0;
@@ -311,9 +330,7 @@ struct omr_batch_ctx {
     omr::SlanePlan slane;
     std::vector<std::unique_ptr<omr::SlaneScratch>> slane_scratch;  // [2 * n_streams]
     // final deskew (omr_batch_deskew_device): per candidate the CONTAIN canvas and warpAffine's fixed-point tables
-    bool dk_built = false;
-    int dk_rows = 0, dk_cols = 0;  // largest canvas (cols rounded up to 4)
-    omr::DevBuf dk_size, dk_adelta, dk_bdelta, dk_xy0;
+    omr::DeskewTables dk;  // planned and uploaded once per context, when a deskew entry point first needs them
     std::vector<std::unique_ptr<omr::DevBuf>> dk_tiles;  // per post stream: the warp's per-tile records (deskew.hip)
     std::mutex mu;
     std::mutex guard_mu;  // omr_batch_sync is called with and without `mu` held: the guard flags have a lock of their own

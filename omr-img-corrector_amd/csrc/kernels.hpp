@@ -141,7 +141,8 @@ hipError_t launch_stddev(const uint32_t *d_vproj, const uint32_t *d_hproj, Sweep
 hipError_t launch_argmax_path1(const double *d_v_sd, const double *d_h_sd, int A, int32_t *d_best,
                                hipStream_t s, int scans = 1);
 
-// ---- batched final deskew (deskew.hip): scan z is rotated by the candidate best[z]'s angle, CONTAIN geometry
+// ---- batched final deskew (deskew.hip): scan z is rotated by the candidate best[z]'s angle, CONTAIN geometry.  Every field
+// is the caller's: the table fields (wsize .. DR) as DeskewTables::pass() fills them (engine.hpp), the rest per launch.
 struct DeskewPass {
     const uint8_t *src;       // scans, cn channels: scan_stride bytes apart, sstep bytes per row
     int64_t scan_stride, sstep;
@@ -155,9 +156,8 @@ struct DeskewPass {
     int32_t DC, DR;           // largest canvas over the candidates (DC a multiple of 4)
     int32_t border;           // border value (0..255)
     int32_t *out_size;        // [scans][2] canvas rows, cols of every scan (device), or null
-    int32_t order, ntx, nty;  // (set by launch_deskew_warp) the workgroup order and the tiles across / down the largest canvas
-    int32_t cn;               // channels of the scans and canvases: 1, or 3 (BGR; border then holds one byte per channel,
-                              // channel c = byte c).  (Fills the struct's tail padding: the 1-channel kernels' arguments keep their offsets.)
+    int32_t cn;               // channels of the scans and canvases: 1 (or 0), or 3 (BGR; border then holds one byte per channel,
+                              // channel c = byte c)
 };
 // d_tiles: deskew_tile_bytes(p, scans) bytes of scratch (the per-tile records made by the launch's first kernel)
 size_t deskew_tile_bytes(const DeskewPass &p, int scans);
