@@ -568,6 +568,42 @@ int omr_lined_picture_batch_device(const uint8_t *d_edges, int32_t n, int64_t ed
                                    const uint8_t bgr[3], uint8_t *d_out, int64_t out_stride_bytes, int64_t out_step,
                                    void *stream);
 
+/* ---- get_angle_with_hough for batches of scans ---------------------------------------
+ * n device-resident scans of one shape (scan i at d_scans + i * scan_stride_bytes, rows step_bytes apart; channels 1,
+ * 3 or 4, what omr_get_angle_with_hough accepts): Canny, HoughLinesP, the f32 vote within 0.1 degrees and its first
+ * maximum for the whole batch, the segments staying on the device.  angles / rc / n_lines: HOST arrays of n (n_lines
+ * may be NULL).  angles[i] has the f64 bits omr_get_angle_with_hough returns for scan i and rc[i] is OMR_OK; a scan
+ * without any segment gets rc[i] = OMR_ERR_ASSERT (that function's code) and angles[i] = 0.0 -- the call itself still
+ * returns OMR_OK: its own code reports bad arguments or a device failure only.
+ * d_lined (may be NULL): picture i -- byte for byte omr_get_angle_with_hough_ex's, the edge map as Canny left it in
+ * colour with every segment drawn on in (186, 88, 255) -- at d_lined + i * lined_stride_bytes, rows lined_step apart.
+ * The slot of a scan without a segment is NOT written (the per-call form makes no picture there either), nor are the
+ * bytes past 3 * cols of a row.
+ * OMR_ERR_BADARG: a null d_scans / angles / rc, n <= 0, step_bytes < cols * channels, a negative scan stride,
+ * lined_step < 3 * cols, lined_stride_bytes < rows * lined_step, d_lined == d_scans.  OMR_ERR_ASSERT: an empty image, a
+ * side of 32767 or more, a channel count other than 1, 3 or 4.  All are checked before any device work.
+ * Enqueues on `stream` and SYNCHRONISES it before it returns. */
+int omr_hough_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,
+                                  int32_t cols, int32_t channels, int64_t step_bytes, double min_line_length,
+                                  double max_line_gap, double *angles, int32_t *rc, int32_t *n_lines,
+                                  uint8_t *d_lined, int64_t lined_stride_bytes, int64_t lined_step, void *stream);
+/* The same for host images of any mix of shapes and channel counts (1 / 3 / 4 each), bucketed by (rows, cols,
+ * channels) as omr_get_angles_with_projections_batch does, on the current device: one upload and one device call per
+ * bucket (per 64 of its scans; uploads and picture downloads on up to 16 host threads), angles[i] / rc[i] / lined[i]
+ * belong to grays[i].  lined (n owned images,
+ * omr_image_free each) may be NULL; lined[i].data is NULL where rc[i] != OMR_OK.  Every image is checked as
+ * omr_get_angle_with_hough checks it before any device work, and an invalid one fails the whole call: angles and rc
+ * are not written, and no picture is returned. */
+int omr_get_angles_with_hough_batch(const omr_image *grays, int32_t n, double min_line_length, double max_line_gap,
+                                    double *angles, int32_t *rc, omr_image_owned *lined);
+/* For tests and inspection: the vote of hough.rs:72-89 alone, for n lists of f32 angles that live on the device --
+ * list k is d_angles[d_offsets[k] .. d_offsets[k + 1]) (d_offsets: n + 1 non-decreasing int32 on the DEVICE).
+ * d_winner[k] = the smallest i of list k with the largest #{ j : |a_i - a_j| < 0.1f }, in f32; -1 for an empty list.
+ * The offsets are TRUSTED: they live on the device and are not validated -- they must not decrease and every list
+ * must lie inside d_angles, or the kernel reads outside it.  Enqueue only, like omr_argmax_projection_device. */
+int omr_hough_vote_select_device(const float *d_angles, const int32_t *d_offsets, int32_t n, int32_t *d_winner,
+                                 void *stream);
+
 /* oics::omr::get_result_from_edges_detection(&Mat, f64, f64) -> Result<OmrResult> (omr.rs:231-302). */
 int omr_get_result_from_edges_detection(const omr_image *src, double edges_min_line_length,
                                         double edges_max_line_gap, double *angle, int32_t *status,

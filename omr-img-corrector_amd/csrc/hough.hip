@@ -949,4 +949,153 @@ hipError_t launch_angle_votes(const float *d_angles, int n, int as_f64, int32_t 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// The batch form of get_angle_with_hough (omr_hough_angles_batch_device) keeps a batch's segments on the device:
+// ppht_kernel leaves them in n slots of `cap` entries, the two kernels below turn the slots into the packed list and
+// the n + 1 offsets that the line picture (lined.hip) and the vote take, and vote_select_kernel answers with one index
+// per scan.  All three use 256 threads = 4 wavefronts of 64 and assume nothing about a scan's segment count.
+
+// off[0 .. n] = exclusive scan of min(n_lines[i], cap); one workgroup walks the counts 256 at a time.
+// flag[0] = the largest count that exceeds its slot (0: none), flag[1] = 1 when the total leaves the 32-bit range.
+// LDS: 16 bytes (the four wave totals of a pass).
+__global__ __launch_bounds__(256) void ppht_offsets_kernel(const int32_t *__restrict__ n_lines, int n, int cap,
+                                                           int32_t *__restrict__ off, int32_t *__restrict__ flag)
+{
+    __shared__ int32_t wtot[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t carry = 0;  // the same in every thread
+    int over = 0, wide = 0;
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + tid;
+        int c = i < n ? n_lines[i] : 0;
+        if (c > cap) over = max(over, c), c = cap;
+        if (c < 0) c = 0;
+        int v = c;  // inclusive scan over the wave: 64 counts of at most 65536 stay far inside 32 bits
+        for (int d = 1; d < 64; d <<= 1) {
+            const int u = __shfl_up(v, d);
+            if (lane >= d) v += u;
+        }
+        if (lane == 63) wtot[wave] = v;
+        __syncthreads();
+        int64_t before = carry;
+        int total = 0;
+        for (int w = 0; w < 4; w++) {
+            if (w < wave) before += wtot[w];
+            total += wtot[w];
+        }
+        const int64_t mine = before + v - c;
+        if (i < n) {
+            if (mine + c > 0x7fffffffll) wide = 1;
+            off[i] = (int32_t)(mine > 0x7fffffffll ? 0x7fffffffll : mine);
+        }
+        carry += total;
+        __syncthreads();  // wtot is free again
+    }
+    if (tid == 0) off[n] = (int32_t)(carry > 0x7fffffffll ? 0x7fffffffll : carry);
+    if (over) atomicMax(&flag[0], over);
+    if (wide) atomicOr(&flag[1], 1);
+}
+
+// packed[off[scan] + k] = slot `scan`'s segment k for k < off[scan + 1] - off[scan]: a thread per segment, 16 bytes each
+// (a slot starts at scan * cap * 16 bytes of an aligned allocation, the packed list is one).  No LDS.
+__global__ __launch_bounds__(256) void ppht_pack_kernel(const int4 *__restrict__ slots, int cap,
+                                                        const int32_t *__restrict__ off, int4 *__restrict__ packed)
+{
+    const int scan = blockIdx.x, k = blockIdx.y * 256 + threadIdx.x;
+    const int o = off[scan], m = off[scan + 1] - o;
+    if (k < m && k < cap) packed[(int64_t)o + k] = slots[(int64_t)scan * cap + k];
+}
+
+hipError_t launch_ppht_offsets(const int32_t *d_n_lines, int n, int cap, int32_t *d_off, int32_t *d_flag, hipStream_t s)
+{
+    if (n <= 0 || cap <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ppht_offsets_kernel, dim3(1), dim3(256), 0, s, d_n_lines, n, cap, d_off, d_flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppht_pack(const int32_t *d_slots, int cap, const int32_t *d_off, int n, int max_n, int32_t *d_packed,
+                            hipStream_t s)
+{
+    if (n <= 0 || max_n <= 0) return hipSuccess;
+    if (max_n > cap || (((uintptr_t)d_slots | (uintptr_t)d_packed) & 15)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ppht_pack_kernel, dim3(n, (max_n + 255) / 256), dim3(256), 0, s,
+                       reinterpret_cast<const int4 *>(d_slots), cap, d_off, reinterpret_cast<int4 *>(d_packed));
+    return hipGetLastError();
+}
+
+// hough.rs:72-89 for a batch, one workgroup per scan: c_i = #{ j : |a_i - a_j| < 0.1 } with the f32 subtraction and
+// the f32 constant of the reference, winner[scan] = the smallest i with the largest c_i (the reference's strict ">"
+// keeps the first maximum), -1 for a scan without a segment.  A pass gives thread t the VS_I angles i = i0 + t + 256 k;
+// the scan's angles go through LDS VS_TILE at a time, every lane reading the same four of them (a broadcast, no bank
+// conflict) and comparing them with its VS_I angles, so a list of m angles is staged ceil(m / 1024) times, not
+// ceil(m / 256); a partial tile is padded with +inf, whose distance to anything is not below 0.1.  Counts are integers
+// and the reduction orders (count, index) pairs, so the result does not depend on the order of the work.
+// LDS: VS_TILE * 4 = 4096 bytes of angles + 32 bytes of wave results.
+#define VS_TILE 1024
+#define VS_I 4
+__global__ __launch_bounds__(256) void vote_select_kernel(const float *__restrict__ ang, const int32_t *__restrict__ off,
+                                                          int32_t *__restrict__ winner)
+{
+    __shared__ float4 tile[VS_TILE / 4];
+    __shared__ int32_t wcount[4], windex[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int o = off[blockIdx.x], m = off[blockIdx.x + 1] - o;  // the same in every thread
+    if (m <= 0) {
+        if (tid == 0) winner[blockIdx.x] = -1;
+        return;
+    }
+    const float *a = ang + o;
+    float *tile_f = reinterpret_cast<float *>(tile);
+    int bc = -1, bi = 0x7fffffff;
+    for (int i0 = 0; i0 < m; i0 += 256 * VS_I) {
+        float ai[VS_I];
+        int c[VS_I];
+#pragma unroll
+        for (int k = 0; k < VS_I; k++) {
+            const int i = i0 + tid + 256 * k;
+            ai[k] = i < m ? a[i] : 0.0f;
+            c[k] = 0;
+        }
+        for (int j0 = 0; j0 < m; j0 += VS_TILE) {
+            const int jn = min(VS_TILE, m - j0);
+            __syncthreads();  // the previous tile has been read
+            for (int j = tid; j < ((jn + 3) & ~3); j += 256) tile_f[j] = j < jn ? a[j0 + j] : __builtin_inff();
+            __syncthreads();
+            for (int q = 0; q < (jn + 3) >> 2; q++) {
+                const float4 v = tile[q];
+#pragma unroll
+                for (int k = 0; k < VS_I; k++) {
+                    c[k] += fabsf(__fsub_rn(ai[k], v.x)) < 0.1f;
+                    c[k] += fabsf(__fsub_rn(ai[k], v.y)) < 0.1f;
+                    c[k] += fabsf(__fsub_rn(ai[k], v.z)) < 0.1f;
+                    c[k] += fabsf(__fsub_rn(ai[k], v.w)) < 0.1f;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < VS_I; k++) {  // i grows with k and with i0: ">" keeps the thread's first maximum
+            const int i = i0 + tid + 256 * k;
+            if (i < m && c[k] > bc) bc = c[k], bi = i;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const int oc = __shfl_down(bc, d), oi = __shfl_down(bi, d);
+        if (oc > bc || (oc == bc && oi < bi)) bc = oc, bi = oi;
+    }
+    if (lane == 0) wcount[wave] = bc, windex[wave] = bi;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; w++)
+            if (wcount[w] > bc || (wcount[w] == bc && windex[w] < bi)) bc = wcount[w], bi = windex[w];
+        winner[blockIdx.x] = bi;
+    }
+}
+
+hipError_t launch_vote_select(const float *d_angles, const int32_t *d_off, int n_scans, int32_t *d_winner, hipStream_t s)
+{
+    if (n_scans <= 0) return hipSuccess;
+    hipLaunchKernelGGL(vote_select_kernel, dim3(n_scans), dim3(256), 0, s, d_angles, d_off, d_winner);
+    return hipGetLastError();
+}
+
 }  // namespace omr

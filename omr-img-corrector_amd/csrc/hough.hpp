@@ -79,4 +79,17 @@ hipError_t launch_angle_votes(const float *d_angles, int n, int as_f64, int32_t 
 hipError_t launch_angle_votes_batch(const float *d_angles, const int64_t *d_off, int n_scans, int max_n, int as_f64,
                                     int32_t *d_counts, hipStream_t s);
 
+// ---- a batch's segments stay on the device (omr_hough_angles_batch_device)
+// d_off[0 .. n] = exclusive scan of min(n_lines[i], cap) -- with d_packed below the form lined.hip and the vote take.
+// d_flag (two words, zeroed by the caller): [0] = the largest count that exceeds cap, [1] = 1 when the total leaves the
+// 32-bit range.
+hipError_t launch_ppht_offsets(const int32_t *d_n_lines, int n, int cap, int32_t *d_off, int32_t *d_flag, hipStream_t s);
+// d_packed[d_off[i] + k][4] = segment k of slot i (d_slots: n x cap x 4, as ppht_kernel leaves them); max_n = the
+// longest list (<= cap).  Both buffers 16-byte aligned.
+hipError_t launch_ppht_pack(const int32_t *d_slots, int cap, const int32_t *d_off, int n, int max_n, int32_t *d_packed,
+                            hipStream_t s);
+// hough.rs:72-89 per scan, on the flat f32 angle list: d_winner[k] = the smallest i in [0, off[k + 1] - off[k]) with the
+// most j, |a_i - a_j| < 0.1f in f32; -1 for an empty scan.  One workgroup per scan, any list length.
+hipError_t launch_vote_select(const float *d_angles, const int32_t *d_off, int n_scans, int32_t *d_winner, hipStream_t s);
+
 }  // namespace omr

@@ -23,6 +23,7 @@
 #include "engine.hpp"
 #include "hough.hpp"
 #include "hough_host.hpp"
+#include "host_threads.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -57,9 +58,16 @@ int canny_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int ro
     return OMR_OK;
 }
 
-// HoughLinesP on n device-resident edge images (d_edges: packed, kept; d_rowcnt filled).
-int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, const HoughParams &hp, hipStream_t s,
-                std::vector<std::vector<int32_t>> *lines_out)
+// A HoughLinesP launch on n scans and what it owns on the device until the caller has read the result: n slots of `cap`
+// segments in `lines`, the segments found per scan in `nlines`
+struct PphtRun {
+    DevBuf rowoff, total, scanoff, nz, order, d_ttab, d_walk, d_rowbase, accum, lines, nlines, tiled, queue;
+    int cap = 0;
+};
+
+// enqueues HoughLinesP on n device-resident edge images (d_edges: packed, kept; d_rowcnt filled)
+static int ppht_launch(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, const HoughParams &hp, hipStream_t s,
+                       PphtRun *run)
 {
     const float rho = (float)hp.rho, theta = (float)hp.theta, irho = 1.0f / rho;
     if (!(rho > 0) || !(theta > 0)) return fail(OMR_ERR_BADARG, "rho and theta must be positive");
@@ -101,7 +109,9 @@ int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, 
     accum_stride += accum_stride & 1;
     const bool acc_u16 = rows + cols <= OMR_PPHT_U16_MAX_EXTENT;  // hough.hip: a bin's count is bounded by the diagonal
     const size_t bin_bytes = acc_u16 ? sizeof(uint16_t) : sizeof(int32_t);
-    DevBuf rowoff, total, scanoff, nz, order, d_ttab, d_walk, d_rowbase, accum, lines, nlines, tiled, queue;
+    DevBuf &rowoff = run->rowoff, &total = run->total, &scanoff = run->scanoff, &nz = run->nz, &order = run->order;
+    DevBuf &d_ttab = run->d_ttab, &d_walk = run->d_walk, &d_rowbase = run->d_rowbase, &accum = run->accum;
+    DevBuf &lines = run->lines, &nlines = run->nlines, &tiled = run->tiled, &queue = run->queue;
     OMR_HIP(rowoff.alloc(sizeof(int32_t) * (size_t)n * rows));
     OMR_HIP(total.alloc(sizeof(int32_t) * (size_t)n));
     OMR_HIP(launch_edges_rowscan(d_rowcnt, rows, n, rowoff.as<int32_t>(), total.as<int32_t>(), s));
@@ -161,6 +171,19 @@ int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, 
     a.n_scans = n;
     a.queue = queue.as<int32_t>();
     OMR_HIP(launch_ppht(a, g_scans_in_flight.load(std::memory_order_relaxed), s));
+    run->cap = cap;
+    return OMR_OK;
+}
+
+// HoughLinesP on n device-resident edge images -> per-scan segments on the host
+int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, const HoughParams &hp, hipStream_t s,
+                std::vector<std::vector<int32_t>> *lines_out)
+{
+    PphtRun run;
+    int rc = ppht_launch(d_edges, d_rowcnt, rows, cols, n, hp, s, &run);
+    if (rc) return rc;
+    const DevBuf &lines = run.lines, &nlines = run.nlines;
+    const int cap = run.cap;
     std::vector<int32_t> nl((size_t)n);
     OMR_HIP(hipMemcpyAsync(nl.data(), nlines.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
@@ -177,16 +200,19 @@ int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, 
 }
 
 // hough.rs:50-68 / omr.rs:257-267
-void line_angles(const std::vector<int32_t> &l, std::vector<float> *ang)
+static void line_angles(const int32_t *l, size_t n, float *ang)
 {
     const float pi32 = 3.14159274101257324f;  // std::f32::consts::PI
-    const size_t n = l.size() / 4;
-    ang->resize(n);
     for (size_t i = 0; i < n; i++) {
         const float x1 = (float)l[4 * i], y1 = (float)l[4 * i + 1], x2 = (float)l[4 * i + 2], y2 = (float)l[4 * i + 3];
         float angle = atan2f(y2 - y1, x2 - x1) * 180.0f / pi32;
-        (*ang)[i] = fmodf(angle, 45.0f);
+        ang[i] = fmodf(angle, 45.0f);
     }
+}
+void line_angles(const std::vector<int32_t> &l, std::vector<float> *ang)
+{
+    ang->resize(l.size() / 4);
+    line_angles(l.data(), l.size() / 4, ang->data());
 }
 
 // counts[i] = #{j : |a_i - a_j| < 0.1}: on the host for small sets, on the GPU otherwise
@@ -364,6 +390,124 @@ int lined_to_host(const uint8_t *d_edges, int rows, int cols, const int32_t *lin
     return rc;
 }
 
+// ---- get_angle_with_hough for a batch: the segments stay on the device (hough.hip: offsets, pack, vote-and-select)
+
+// fn(lo, hi) over [0, count) in contiguous pieces on a few host threads (the caller's alone for a small count)
+template <class Fn>
+static void host_fan_out(size_t count, size_t min_piece, Fn fn)
+{
+    // at most 16 threads, as on_threads (host_threads.hpp)
+    const size_t want = std::min<size_t>(std::min(std::thread::hardware_concurrency(), 16u), count / std::max<size_t>(min_piece, 1));
+    if (want < 2) return fn((size_t)0, count);
+    const size_t piece = (count + want - 1) / want;
+    std::vector<std::thread> pool;
+    for (size_t lo = 0; lo < count; lo += piece) pool.emplace_back(fn, lo, std::min(count, lo + piece));
+    for (auto &th : pool) th.join();
+}
+
+// every argument rule of omr_hough_angles_batch_device, before any device work
+static int hough_batch_check(const void *d_scans, int n, int64_t stride, int rows, int cols, int cn, int64_t step,
+                             const double *angles, const int32_t *rc_out, const void *d_lined, int64_t lstride, int64_t lstep)
+{
+    clear_error();
+    if (!d_scans || !angles || !rc_out) return fail(OMR_ERR_BADARG, "null pointer");
+    if (n <= 0) return fail(OMR_ERR_BADARG, "empty batch");
+    int rc = check_image_shape(rows, cols);
+    if (rc || (rc = cn_canny(cn))) return rc;
+    if (step < (int64_t)cols * cn) return fail(OMR_ERR_BADARG, "step_bytes too small");
+    if (stride < 0) return fail(OMR_ERR_BADARG, "negative scan stride");
+    if (d_lined) {
+        if (lstep < 3 * (int64_t)cols) return fail(OMR_ERR_BADARG, "step too small");
+        if (lstride < rows * lstep) return fail(OMR_ERR_BADARG, "picture stride smaller than a picture");
+        if (d_lined == d_scans) return fail(OMR_ERR_BADARG, "the picture cannot be made in place");
+    }
+    return OMR_OK;
+}
+
+// arguments already checked.  Synchronises `s`.
+static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
+                               const HoughParams &hp, double *angles, int32_t *rc_out, int32_t *n_lines, uint8_t *d_lined,
+                               int64_t lstride, int64_t lstep, hipStream_t s)
+{
+    PoolScope scope(s);
+    const size_t img = (size_t)rows * cols;
+    DevBuf map, flag, rowcnt, edges;
+    OMR_HIP(map.alloc((size_t)n * img));
+    OMR_HIP(flag.alloc(sizeof(int)));
+    OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
+    int rc = canny_device(d_scans, stride, step, rows, cols, cn, n, hp.low, hp.high, map.as<uint8_t>(), flag.as<int>(), s,
+                          rowcnt.as<int32_t>());
+    if (rc) return rc;
+    if (d_lined) {  // the pictures' background: HoughLinesP erases the points it has used from its input
+        OMR_HIP(edges.alloc(map.bytes));
+        OMR_HIP(hipMemcpyAsync(edges.p, map.p, (size_t)n * img, hipMemcpyDeviceToDevice, s));
+    }
+    PphtRun run;
+    if ((rc = ppht_launch(map.as<uint8_t>(), rowcnt.as<int32_t>(), rows, cols, n, hp, s, &run))) return rc;
+    // slots -> offsets (one small download) -> packed list (one download)
+    DevBuf d_off, d_over, d_packed;
+    std::vector<int32_t> off((size_t)n + 1);
+    int32_t over[2] = {0, 0};
+    OMR_HIP(d_off.alloc(sizeof(int32_t) * off.size()));
+    OMR_HIP(d_over.alloc(sizeof(over)));
+    OMR_HIP(hipMemsetAsync(d_over.p, 0, sizeof(over), s));
+    OMR_HIP(launch_ppht_offsets(run.nlines.as<int32_t>(), n, run.cap, d_off.as<int32_t>(), d_over.as<int32_t>(), s));
+    OMR_HIP(hipMemcpyAsync(off.data(), d_off.p, sizeof(int32_t) * off.size(), hipMemcpyDeviceToHost, s));
+    OMR_HIP(hipMemcpyAsync(over, d_over.p, sizeof(over), hipMemcpyDeviceToHost, s));
+    OMR_HIP(hipStreamSynchronize(s));
+    if (over[0]) return fail(OMR_ERR_NOMEM, "HoughLinesP: %d segments exceed the buffer of %d", over[0], run.cap);
+    if (over[1]) return fail(OMR_ERR_NOMEM, "HoughLinesP: the batch's segments exceed a list of 2^31 - 1");
+    const size_t total = (size_t)off[(size_t)n];
+    int max_n = 0;
+    for (int i = 0; i < n; i++) max_n = std::max(max_n, off[(size_t)i + 1] - off[(size_t)i]);
+    std::vector<int32_t> win((size_t)n, -1);
+    std::vector<float> ang(total);
+    if (total > 0) {
+        std::vector<int32_t> lines(total * 4);
+        OMR_HIP(d_packed.alloc(sizeof(int32_t) * 4 * total));
+        OMR_HIP(launch_ppht_pack(run.lines.as<int32_t>(), run.cap, d_off.as<int32_t>(), n, max_n, d_packed.as<int32_t>(), s));
+        OMR_HIP(hipMemcpyAsync(lines.data(), d_packed.p, sizeof(int32_t) * 4 * total, hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+        // the angles on the host (libm atan2f / fmodf, as the reference: the device's are not the host's bit for bit)
+        host_fan_out(total, 4096, [&](size_t lo, size_t hi) { line_angles(lines.data() + 4 * lo, hi - lo, ang.data() + lo); });
+        DevBuf d_ang, d_win;
+        OMR_HIP(d_ang.alloc(sizeof(float) * total));
+        OMR_HIP(d_win.alloc(sizeof(int32_t) * (size_t)n));
+        OMR_HIP(hipMemcpyAsync(d_ang.p, ang.data(), sizeof(float) * total, hipMemcpyHostToDevice, s));
+        OMR_HIP(launch_vote_select(d_ang.as<float>(), d_off.as<int32_t>(), n, d_win.as<int32_t>(), s));
+        OMR_HIP(hipMemcpyAsync(win.data(), d_win.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+    }
+    for (int i = 0; i < n; i++) {
+        const int32_t o = off[(size_t)i], m = off[(size_t)i + 1] - o;
+        if (n_lines) n_lines[i] = m;
+        if (m == 0) {  // the per-call form's error: the reference panics on angles[0], hough.rs:74
+            angles[i] = 0.0;
+            rc_out[i] = OMR_ERR_ASSERT;
+            continue;
+        }
+        if (win[(size_t)i] < 0 || win[(size_t)i] >= m) return fail(OMR_ERR_GPU, "vote_select_kernel: scan %d has no winner", i);
+        angles[i] = (double)ang[(size_t)o + (size_t)win[(size_t)i]];
+        rc_out[i] = OMR_OK;
+    }
+    if (!d_lined) return OMR_OK;
+    // pictures for the runs of scans that have segments: the slot of a scan without one is not written
+    for (int i0 = 0; i0 < n;) {
+        if (off[(size_t)i0 + 1] == off[(size_t)i0]) {
+            i0++;
+            continue;
+        }
+        int i1 = i0 + 1;
+        while (i1 < n && off[(size_t)i1 + 1] > off[(size_t)i1]) i1++;
+        if ((rc = lined_device(edges.as<uint8_t>() + (size_t)i0 * img, i1 - i0, (int64_t)img, cols, rows, cols,
+                               d_packed.as<int32_t>(), off.data() + i0, kLinedBgr, d_lined + (int64_t)i0 * lstride, lstride,
+                               lstep, s)))
+            return rc;
+        i0 = i1;
+    }
+    return OMR_OK;
+}
+
 }  // namespace hh
 }  // namespace omr
 
@@ -471,6 +615,108 @@ int omr_get_angle_with_hough_ex(const omr_image *gray, double min_line_length, d
                                 omr_image_owned *lined)
 {
     return angle_with_hough(gray, min_line_length, max_line_gap, angle_out, lined);
+}
+
+int omr_hough_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
+                                  int32_t channels, int64_t step_bytes, double min_line_length, double max_line_gap,
+                                  double *angles, int32_t *rc, int32_t *n_lines, uint8_t *d_lined, int64_t lined_stride_bytes,
+                                  int64_t lined_step, void *stream)
+{
+    int err = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, angles, rc, d_lined,
+                                lined_stride_bytes, lined_step);
+    if (err || (err = have_device())) return err;
+    HoughParams hp;
+    hp.min_line_length = min_line_length;
+    hp.max_line_gap = max_line_gap;
+    return hough_angles_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels, hp, angles, rc, n_lines, d_lined,
+                               lined_stride_bytes, lined_step, (hipStream_t)stream);
+}
+
+int omr_hough_vote_select_device(const float *d_angles, const int32_t *d_offsets, int32_t n, int32_t *d_winner, void *stream)
+{
+    clear_error();
+    if (!d_angles || !d_offsets || !d_winner) return fail(OMR_ERR_BADARG, "null pointer");
+    if (n <= 0) return fail(OMR_ERR_BADARG, "empty batch");
+    int rc = have_device();
+    if (rc) return rc;
+    OMR_HIP(launch_vote_select(d_angles, d_offsets, n, d_winner, (hipStream_t)stream));
+    return OMR_OK;
+}
+
+// one bucket of omr_get_angles_with_hough_batch: `members` index same-shape images of `grays`; at most HB_SCANS go to the
+// device at a time (an A4 gray scan holds about 60 MB there with its edge maps, accumulator and picture).  Uploads and
+// picture downloads run on several host threads (host_threads.hpp), as in the other host batches
+static int hough_host_bucket(const omr_image *grays, const std::vector<int> &members, const HoughParams &hp, double *angles,
+                             int32_t *rcs, omr_image_owned *lined)
+{
+    constexpr int HB_SCANS = 64;
+    const omr_image &first = grays[members[0]];
+    const int rows = first.rows, cols = first.cols, cn = first.channels;
+    const int64_t row = (int64_t)cols * cn, img = row * rows, pic = (int64_t)cols * 3 * rows;
+    LeasedStream st;
+    int rc = st.create();
+    if (rc) return rc;
+    const int total = (int)members.size(), zmax = std::min(HB_SCANS, total);
+    DevBuf in, pics;
+    OMR_HIP(in.alloc((size_t)img * zmax));
+    if (lined) OMR_HIP(pics.alloc((size_t)pic * zmax));
+    std::vector<double> a((size_t)zmax);
+    std::vector<int32_t> r((size_t)zmax);
+    for (int j0 = 0; j0 < total; j0 += zmax) {
+        const int m = std::min(zmax, total - j0);
+        if ((rc = upload_chunk(grays, members, j0, m, rows, row, in.as<uint8_t>(), img))) return rc;
+        if ((rc = hough_angles_device(in.as<uint8_t>(), m, img, row, rows, cols, cn, hp, a.data(), r.data(), nullptr,
+                                      lined ? pics.as<uint8_t>() : nullptr, pic, (int64_t)cols * 3, st.s)))
+            return rc;
+        for (int j = 0; j < m; j++) {
+            angles[members[(size_t)(j0 + j)]] = a[(size_t)j];
+            rcs[members[(size_t)(j0 + j)]] = r[(size_t)j];
+        }
+        if (!lined) continue;
+        // pictures -> fresh host images, from several threads, one staged copy each
+        rc = on_threads(m, [&](hipStream_t s, int lo, int hi) -> int {
+            for (int j = lo; j < hi; j++) {
+                if (r[(size_t)j] != OMR_OK) continue;
+                omr_image_owned &o = lined[members[(size_t)(j0 + j)]];
+                uint8_t *data = (uint8_t *)malloc((size_t)pic);
+                if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
+                o = omr_image_owned{data, rows, cols, 3, (int64_t)cols * 3};
+                int rc1 = staged_d2h(o.data, pics.as<uint8_t>() + (size_t)j * pic, (size_t)pic, s);
+                if (rc1) return rc1;
+            }
+            return OMR_OK;
+        });
+        if (rc) return rc;
+    }
+    return OMR_OK;
+}
+
+int omr_get_angles_with_hough_batch(const omr_image *grays, int32_t n, double min_line_length, double max_line_gap,
+                                    double *angles, int32_t *rc, omr_image_owned *lined)
+{
+    clear_error();
+    if (!grays || n < 1 || !angles || !rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (lined) memset(lined, 0, sizeof(*lined) * (size_t)n);
+    ShapeBuckets b;
+    // omr_get_angle_with_hough's checks, for every image before any device work
+    int err = bucket_by_shape(grays, n, [](const omr_image &im) { return check_image(&im, cn_canny); }, &b);
+    if (err || (err = have_device())) return err;
+    HoughParams hp;
+    hp.min_line_length = min_line_length;
+    hp.max_line_gap = max_line_gap;
+    // angles and codes go to the caller's arrays only when the whole call has succeeded
+    std::vector<double> ang((size_t)n);
+    std::vector<int32_t> rcs((size_t)n);
+    for (size_t k = 0; k < b.shapes.size() && err == OMR_OK; k++)
+        err = hough_host_bucket(grays, b.members[k], hp, ang.data(), rcs.data(), lined);
+    if (err) {
+        if (lined)
+            for (int i = 0; i < n; i++) omr_image_free(&lined[i]);
+        return err;
+    }
+    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
+    memcpy(rc, rcs.data(), sizeof(int32_t) * (size_t)n);
+    return OMR_OK;
 }
 
 int omr_lined_picture_batch_device(const uint8_t *d_edges, int32_t n, int64_t edge_stride_bytes, int64_t edge_step,

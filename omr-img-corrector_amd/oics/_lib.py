@@ -162,6 +162,12 @@ SYMBOLS = {
                                            C.c_void_p, C.c_int64, C.c_void_p]),
     "omr_lined_picture_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                  C.c_void_p, i32p, u8p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "omr_hough_angles_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                                C.c_double, C.c_double, f64p, i32p, i32p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_void_p]),
+    "omr_get_angles_with_hough_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_double, C.c_double, f64p, i32p,
+                                                  C.POINTER(OmrImageOwned)]),
+    "omr_hough_vote_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "omr_get_result_from_edges_detection": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, f64p, i32p, f64p,
                                                       C.c_int32, i32p]),
     "omr_edges_detection_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,

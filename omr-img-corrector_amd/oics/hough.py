@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import OmrImageOwned, check, i32p, lib, u8p
+from ._lib import OmrImage, OmrImageOwned, check, f64p, i32p, lib, u8p
 from .transfer import _mat, as_image
 
 
@@ -85,3 +85,42 @@ def get_angle_with_hough(gray_tm, min_line_length, max_line_gap, want_picture=Fa
     check(lib().omr_get_angle_with_hough_ex(C.byref(im), float(min_line_length), float(max_line_gap), C.byref(out),
                                             C.byref(owned)))
     return out.value, _take(owned)
+
+
+def hough_angles_batch_device(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, min_line_length, max_line_gap,
+                              d_lined=None, lined_stride_bytes=0, lined_step=0, stream=None):
+    """omr_hough_angles_batch_device: get_angle_with_hough on n same-shape device-resident scans (d_scans, d_lined:
+    device addresses).  Returns (angles float64 [n], rc int32 [n], n_lines int32 [n]): angles[i] has the bits the
+    per-call function returns, rc[i] is 0, or -215 with angle 0.0 for a scan without any segment.  With d_lined,
+    picture i (the per-call want_picture=True result, byte for byte) lands at d_lined + i * lined_stride_bytes, rows
+    lined_step apart; the slot of a scan without a segment is not written.  Synchronises `stream` before returning."""
+    n = int(n)
+    angles = np.zeros(max(n, 0), np.float64)
+    rc = np.zeros(max(n, 0), np.int32)
+    n_lines = np.zeros(max(n, 0), np.int32)
+    check(lib().omr_hough_angles_batch_device(d_scans, n, int(scan_stride_bytes), int(rows), int(cols), int(channels),
+                                              int(step_bytes), float(min_line_length), float(max_line_gap),
+                                              angles.ctypes.data_as(f64p), rc.ctypes.data_as(i32p),
+                                              n_lines.ctypes.data_as(i32p), d_lined, int(lined_stride_bytes),
+                                              int(lined_step), stream))
+    return angles, rc, n_lines
+
+
+def get_angles_with_hough(grays, min_line_length, max_line_gap, want_pictures=False):
+    """get_angle_with_hough for a batch (omr_get_angles_with_hough_batch): host images of any mix of shapes and of 1, 3
+    or 4 channels; same-shape images go through Canny, HoughLinesP and the vote together on the device.  Returns
+    (angles float64 [n], rc int32 [n]): angles[i] is the per-call angle of grays[i] (same bits) and rc[i] is 0, or -215
+    with angle 0.0 where the per-call function raises for want of a segment.  want_pictures=True adds a list of n
+    pictures ([rows, cols, 3] uint8, the per-call want_picture=True result), None where rc[i] != 0.  An invalid image
+    fails the whole call."""
+    keep = [as_image(_mat(g)) for g in grays]
+    n = len(keep)
+    arr = (OmrImage * max(n, 1))(*[im for _, im in keep])
+    angles = np.zeros(n, np.float64)
+    rc = np.zeros(n, np.int32)
+    owned = (OmrImageOwned * max(n, 1))() if want_pictures else None
+    check(lib().omr_get_angles_with_hough_batch(arr, n, float(min_line_length), float(max_line_gap),
+                                                angles.ctypes.data_as(f64p), rc.ctypes.data_as(i32p), owned))
+    if not want_pictures:
+        return angles, rc
+    return angles, rc, [_take(owned[i]) if owned[i].data else None for i in range(n)]

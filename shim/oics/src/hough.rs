@@ -1,8 +1,9 @@
-//! `oics::hough` (reference: packages/lib/src/hough.rs:17-100) -> omr_get_angle_with_hough / _ex.
+//! `oics::hough` (reference: packages/lib/src/hough.rs:17-100) -> omr_get_angle_with_hough / _ex,
+//! and its batch form omr_get_angles_with_hough_batch.
 use crate::bridge::{check, into_mat, view};
 use crate::ffi;
 use crate::transfer::TransformableMatrix;
-use opencv::core::Vector;
+use opencv::core::{Mat, Vector};
 use opencv::imgcodecs;
 use std::path::Path;
 
@@ -31,4 +32,72 @@ pub fn get_angle_with_hough(
         imgcodecs::imwrite(path.to_str().unwrap_or(file_name), &pic, &params)?;
     }
     Ok(angle)
+}
+
+/// What `get_angle_with_hough` answers for a scan in which HoughLinesP finds no segment (the reference panics on
+/// `angles[0]`, hough.rs:74), for the scans of a batch: the batch call itself has succeeded.
+fn scan_result(rc: i32, angle: f64) -> opencv::Result<f64> {
+    if rc == ffi::OMR_OK {
+        Ok(angle)
+    } else {
+        Err(opencv::Error::new(rc, String::from("no line segment found (the reference panics on angles[0], hough.rs:74)")))
+    }
+}
+
+/// `get_angle_with_hough` for a batch: images of any mix of shapes and of 1, 3 or 4 channels, one result per image at
+/// the image's own position, each the angle the per-call function returns (same f64 bits) or its error for a scan
+/// without any segment.  Same-shape images go through Canny, HoughLinesP and the vote together on the device.  An
+/// invalid image fails the whole batch: every entry then carries that error.
+pub fn get_angles_with_hough(
+    grays: &[&TransformableMatrix],
+    min_line_length: f64,
+    max_line_gap: f64,
+) -> Vec<opencv::Result<f64>> {
+    let n = grays.len();
+    let views: opencv::Result<Vec<ffi::OmrImage>> = grays.iter().map(|g| view(g.get_mat())).collect();
+    let views = match views {
+        Ok(v) => v,
+        Err(e) => return (0..n).map(|_| Err(opencv::Error::new(e.code, e.message.clone()))).collect(),
+    };
+    let mut angles = vec![0.0f64; n];
+    let mut rc = vec![0i32; n];
+    let call = check(unsafe {
+        ffi::omr_get_angles_with_hough_batch(views.as_ptr(), n as i32, min_line_length, max_line_gap, angles.as_mut_ptr(), rc.as_mut_ptr(), std::ptr::null_mut())
+    });
+    if let Err(e) = call {
+        return (0..n).map(|_| Err(opencv::Error::new(e.code, e.message.clone()))).collect();
+    }
+    (0..n).map(|i| scan_result(rc[i], angles[i])).collect()
+}
+
+/// The same with the picture `get_angle_with_hough` writes for every scan that has a result -- the edge map in colour
+/// with every segment drawn on (hough.rs:44-63) -- as a `Mat`; encoding and writing stay with the caller.
+pub fn get_angles_with_hough_with_pictures(
+    grays: &[&TransformableMatrix],
+    min_line_length: f64,
+    max_line_gap: f64,
+) -> Vec<opencv::Result<(f64, Mat)>> {
+    let n = grays.len();
+    let views: opencv::Result<Vec<ffi::OmrImage>> = grays.iter().map(|g| view(g.get_mat())).collect();
+    let views = match views {
+        Ok(v) => v,
+        Err(e) => return (0..n).map(|_| Err(opencv::Error::new(e.code, e.message.clone()))).collect(),
+    };
+    let mut angles = vec![0.0f64; n];
+    let mut rc = vec![0i32; n];
+    let mut lined: Vec<ffi::OmrImageOwned> = (0..n).map(|_| ffi::OmrImageOwned::empty()).collect();
+    let call = check(unsafe {
+        ffi::omr_get_angles_with_hough_batch(views.as_ptr(), n as i32, min_line_length, max_line_gap, angles.as_mut_ptr(), rc.as_mut_ptr(), lined.as_mut_ptr())
+    });
+    if let Err(e) = call {
+        return (0..n).map(|_| Err(opencv::Error::new(e.code, e.message.clone()))).collect();
+    }
+    lined
+        .into_iter()
+        .enumerate()
+        .map(|(i, pic)| {
+            let angle = scan_result(rc[i], angles[i])?;
+            Ok((angle, into_mat(pic)?))
+        })
+        .collect()
 }
