@@ -258,17 +258,16 @@ struct SlanePlan {
     DevBuf prog, d_tasks;
     std::vector<SlaneStrip> strips;  // [A][NS]
     std::vector<int32_t> tasks;      // candidate * NS + strip, in launch order
-    // the launch order in chunks of 32 candidates (slane_kernel's units): the work of one workgroup of a chunk and its size,
-    // and the units dealt to the XCDs for every composition of a launch met so far (slane_deal_units, slane.hip)
-    std::vector<double> chunk_weight;
+    // the launch order in chunks of 32 candidates (slane_kernel's units): their sizes, and the units dealt to the XCDs for
+    // every number of scan groups in use met so far (slane_deal_units, slane.hip)
     std::vector<int> chunk_size;
     struct UnitTab {
         DevBuf tab;
         int per_xcd = 0;
     };
-    mutable std::map<int, UnitTab> unit_tabs;  // key = ncq (strip groups x groups of scan groups)
+    mutable std::map<int, UnitTab> unit_tabs;  // key = scan groups in use
     mutable std::mutex unit_mu;
-    int units_for(int ncq, const int32_t **d_tab, int *per_xcd) const;
+    int units_for(int used, const int32_t **d_tab, int *per_xcd) const;
     // OMR_ERR_NOTIMPL when a candidate does not fit the scheme.  on_host: slane_plan.cpp's generator (the reference
     // implementation, 16 host threads + upload) instead of slane_build.hip's
     int build(const SweepTables &t, bool on_host = false);
@@ -283,6 +282,7 @@ struct SlaneScratch {
     size_t rows_bytes = 0;                       // of hrows
     uint32_t *bits_base = nullptr;  // the first scan group's bit image inside `bits` (aligned to SlaneGeom::group_stride())
     DevBuf bits, hrows, planes, descs[3], vsd, hsd, best, guard;  // descs[lg]: workgroups of (16 >> lg) strips x (1 << lg) scan groups
+    DevBuf wave_map;                                                // slane_wave_map for every workgroup with null strip places
     int create(const SlanePlan &p, int groups);
 };
 // packed: d_img holds scans already packed to 1 bit per pixel (black_max unused)

@@ -159,6 +159,7 @@ inline int slane_class(int most)
 {
     return most <= 2 ? 0 : most == 3 ? 3 : most == 4 ? 1 : most <= 7 ? most - 1 : most == 8 ? 2 : -1;
 }
+constexpr int SL_CLS_NULL = 7;  // SlaneTask::cls of a null task: a place of a workgroup without work (tools/gen_slane_asm.py, null_body)
 // Where word column d (0 .. 3, counted from the row's first column) of a source row of ncols columns sits among the row's four
 // ring registers, for a segment that starts in it (two_words: some of its bits come from column d + 1, so the register above
 // must hold that column).  Rows of 1, 2 or 4 columns: register d.  Rows of THREE columns are loaded as the pairs (0, 1) and
@@ -208,7 +209,7 @@ struct SlaneTask {
     uint32_t rsrc[4];    // buffer descriptor of the scan group's interleaved bit image
     uint32_t nrec;       // records as they are numbered (slane_records: a multiple of 64)
     uint32_t hpitch;     // bytes between pair rows of the row counts
-    int32_t cls;         // slot class: slots laid out / executed per word (slane_slots, slane_exec_slots)
+    int32_t cls;         // slot class: slots laid out / executed per word (slane_slots, slane_exec_slots); SL_CLS_NULL: a null task
     int32_t wave;        // the pair rows of its scan group's LDS accumulators this wave flushes: first (bits 4:0, SL_WAVE_FIRST_BITS),
                          // their number 0 .. 8 (bits 11:8, SL_WAVE_COUNT_SHIFT) -- tools/gen_slane_asm.py reads the same fields
     uint64_t planes;     // counter dump of (task, scan group): [word][SL_DUMP planes][64]
@@ -224,6 +225,50 @@ static_assert(offsetof(SlaneTask, seg) == 0 && offsetof(SlaneTask, fet) == 8 && 
                   offsetof(SlaneTask, cls) == 56 && offsetof(SlaneTask, wave) == 60 && offsetof(SlaneTask, planes) == 64 &&
                   offsetof(SlaneTask, lds_base) == 72 && offsetof(SlaneTask, nexec) == 76,
               "SlaneTask field offsets are part of the wave program");
+
+// Which (strip place, scan group) wave w of a workgroup with NULL STRIP PLACES takes: out[w] = place | scan group << 4.  The
+// workgroup has 1 << places_log places of which the first rp hold a strip, and 16 >> places_log scan groups of which the first
+// rs hold scans.  Waves w, w + 4, w + 8, w + 12 share a SIMD.  The rp * rs real waves are dealt to the four SIMDs as evenly as
+// they go (so no SIMD holds more than ceil(nulls / 4) null waves -- stacked on one SIMD they left it idle while the other
+// three set the workgroup's duration), and the waves of a strip stay on one SIMD as far as they fit: they run the same
+// program side by side and share its records through the scalar cache.  Pass 1 gives every strip the SIMD with the most
+// room, pass 2 puts what did not fit there wherever room is left; the null places fill the rest.
+inline void slane_wave_map(int places_log, int rp, int rs, uint8_t out[16])
+{
+    const int places = 1 << places_log, sgw = 16 >> places_log, R = rp * rs;
+    int room[4], held[4] = {0, 0, 0, 0}, left[16];
+    uint8_t simd[4][4];
+    for (int k = 0; k < 4; k++) room[k] = R / 4 + (k < R % 4 ? 1 : 0);
+    auto most_room = [&]() {
+        int best = 0;
+        for (int k = 1; k < 4; k++)
+            if (room[k] > room[best]) best = k;
+        return best;
+    };
+    auto put = [&](int k, int place, int sg) { simd[k][held[k]++] = (uint8_t)(place | sg << 4), room[k]--; };
+    for (int p = 0; p < rp; p++) {
+        const int k = most_room(), n = rs < room[k] ? rs : room[k];
+        for (int i = 0; i < n; i++) put(k, p, i);
+        left[p] = n;  // scan groups of the strip that are placed
+    }
+    for (int p = 0; p < rp; p++)
+        while (left[p] < rs) {
+            const int k = most_room(), n = rs - left[p] < room[k] ? rs - left[p] : room[k];
+            for (int i = 0; i < n; i++) put(k, p, left[p]++);
+        }
+    // the null places in order: places without a strip, then the scan groups without scans of the others
+    int k = 0;
+    auto put_null = [&](int place, int sg) {
+        while (held[k] == 4) k++;
+        simd[k][held[k]++] = (uint8_t)(place | sg << 4);
+    };
+    for (int p = rp; p < places; p++)
+        for (int sg = 0; sg < sgw; sg++) put_null(p, sg);
+    for (int p = 0; p < rp; p++)
+        for (int sg = rs; sg < sgw; sg++) put_null(p, sg);
+    for (int w = 0; w < 16; w++) out[w] = simd[w & 3][w >> 2];
+}
+constexpr int SL_WAVE_MAP_BYTES = 3 * 16 * 4 * 16;  // [sgw_log][rp - 1][rs - 1][wave], slane_kernel
 
 // slane_build.hip: the same programs generated on the device (the default; the host generator above is the reference
 // implementation).  Scratch per task (= candidate * NS + strip): cmin / cmax / first / last [task][rowsG], most [task],
@@ -258,11 +303,13 @@ hipError_t launch_slane_pack_cn(const uint8_t *d_img, int64_t scan_stride, int64
 hipError_t launch_slane_pack_bits(const uint32_t *d_packed, int64_t scan_stride_dwords, const SlaneGeom &g, int nscans,
                                   uint32_t *d_bits, hipStream_t s);
 // nsg_used = scan groups that carry scans in this launch, nsg = scan groups the scratch (and its descriptors) is laid out for
-hipError_t launch_slane(const SlaneTask *d_descs, int nsgq, int nsgp, int A, int NQ, int sgw_log, int32_t *d_guard,
-                        const int32_t *d_unit_tab, int per_xcd, hipStream_t s);
+// (idle_task: index of the table's idle task, which the waves of scan groups >= nsg_used take; d_wave_map: slane_wave_map's table)
+hipError_t launch_slane(const SlaneTask *d_descs, int nsgq, int nsgp, int nsg_used, int A, int NS, int NQ, int sgw_log, int64_t idle_task,
+                        const uint8_t *d_wave_map, int32_t *d_guard, const int32_t *d_unit_tab, int per_xcd, hipStream_t s);
 std::vector<int32_t> slane_deal_units(const std::vector<double> &chunk_weight, const std::vector<int> &chunk_size, int ncq, int *per_xcd);
 // std-dev of both projections of every scan, read where the sweep left them (d_planes: the waves' counter dumps; d_hproj: the
-// row counts, cleared behind the read when clear_rows).  nsg_run = scan groups the sweep ran (whole workgroups), >= nsg_used
+// row counts, cleared behind the read when clear_rows).  nsg_run = scan groups the sweep added row counts for, >= nsg_used
+// (slane_enqueue passes nsg_used: scan groups without scans are null tasks, they add nothing)
 hipError_t launch_slane_stddev(const uint32_t *d_planes, const int32_t *d_tasks, uint32_t *d_hproj, bool clear_rows, int A, const SlaneGeom &g,
                                int hpairs_per_cand, int hrow0, int nsg_used, int nsg_run, int nsg, int nscans, double *d_v_sd,
                                double *d_h_sd, hipStream_t s);

@@ -193,14 +193,8 @@ int SlanePlan::build(const SweepTables &t, bool on_host)
     tasks.clear();
     for (int a : order)
         for (int st = 0; st < NS; st++) tasks.push_back(a * NS + st);
-    chunk_weight.clear(), chunk_size.clear();
-    for (size_t c0 = 0; c0 < order.size(); c0 += SL_CHUNK) {
-        const size_t n = std::min<size_t>(SL_CHUNK, order.size() - c0);
-        double w = 0;
-        // (a workgroup's time ~ 5 + executed slots per word, measured: 0.70 ms at 2 slots, 1.21 ms at 7 -- tools/kstamps_lanes.py)
-        for (size_t i = 0; i < n; i++) w += 5.0 * NS + weight(order[c0 + i]);
-        chunk_weight.push_back(w / (double)n), chunk_size.push_back((int)n);
-    }
+    chunk_size.clear();
+    for (size_t c0 = 0; c0 < order.size(); c0 += SL_CHUNK) chunk_size.push_back((int)std::min<size_t>(SL_CHUNK, order.size() - c0));
     unit_tabs.clear();
     OMR_HIP(d_tasks.alloc(sizeof(int32_t) * tasks.size()));
     OMR_HIP(hipMemcpy(d_tasks.p, tasks.data(), sizeof(int32_t) * tasks.size(), hipMemcpyHostToDevice));
@@ -208,13 +202,31 @@ int SlanePlan::build(const SweepTables &t, bool on_host)
     return OMR_OK;
 }
 
-// the units of a launch of ncq (strip group, group of scan groups) combinations, dealt to the XCDs (made once per ncq)
-int SlanePlan::units_for(int ncq, const int32_t **d_tab, int *per_xcd) const
+// the units of a launch of `used` scan groups -- (chunk, strip group q, group of scan groups) -- dealt to the XCDs (made once per
+// `used`, which fixes the workgroup's composition).  A unit weighs what its workgroups' REAL waves weigh: a wave's time ~ 5 +
+// executed slots per word (measured: 0.70 ms at 2 slots, 1.21 ms at 7 -- tools/kstamps_lanes.py), null places cost next to
+// nothing and are spread over the SIMDs (slane_wave_map), so a strip group with null places, or a group of scan groups of
+// which only some hold scans, is lighter by their share.  slane_deal_units takes one weight per chunk: every unit goes in as a
+// chunk of its own (ncq = 1), which numbers the units exactly as slane_kernel does, chunk * ncq + cq.
+int SlanePlan::units_for(int used, const int32_t **d_tab, int *per_xcd) const
 {
     std::lock_guard<std::mutex> lk(unit_mu);
-    UnitTab &u = unit_tabs[ncq];
+    UnitTab &u = unit_tabs[used];
     if (!u.tab.p) {
-        const std::vector<int32_t> h = slane_deal_units(chunk_weight, chunk_size, ncq, &u.per_xcd);
+        const int lg = used <= 1 ? 0 : used == 2 ? 1 : 2, sgw = 1 << lg, places = 16 >> lg, NS = g.NS;
+        const int nsgq = (used + sgw - 1) / sgw, NQ = (NS + places - 1) / places;
+        std::vector<double> unit_weight;
+        std::vector<int> unit_size;
+        for (size_t c = 0; c < chunk_size.size(); c++)
+            for (int cq = 0; cq < NQ * nsgq; cq++) {
+                const int q = cq % NQ, sgq = cq / NQ, rs = std::min(sgw, used - sgq * sgw), n = chunk_size[c];
+                double w = 0;
+                for (int i = 0; i < n; i++)
+                    for (int st = q * places; st < std::min(NS, (q + 1) * places); st++)
+                        w += 5.0 + slane_exec_slots(strips[(size_t)tasks[(c * SL_CHUNK + (size_t)i) * NS + st]].cls);
+                unit_weight.push_back(w * rs / (double)n), unit_size.push_back(n);
+            }
+        const std::vector<int32_t> h = slane_deal_units(unit_weight, unit_size, 1, &u.per_xcd);
         OMR_HIP(u.tab.alloc(sizeof(int32_t) * h.size()));
         OMR_HIP(hipMemcpy(u.tab.p, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice));
     }
@@ -247,14 +259,27 @@ int SlaneScratch::create(const SlanePlan &p, int groups)
     // for each composition of a workgroup: 4 strips x 4 scan groups (sgw_log 2), 8 x 2 (1), 16 x 1 (0).  (2 x 8 for
     // launches of 512 scans was built and measured: 41.2 ms against 40.8 -- eight-way sharing of a program through the
     // scalar cache buys nothing over four-way.)
-    // Places beyond the last strip or the last scan group are null tasks: the empty program, buffer descriptors of
-    // size 0 (their fetches read zeros, their row-count adds are dropped), a spare slot for the counter dump.
+    // Places beyond the last strip or the last scan group are null tasks (cls = SL_CLS_NULL: the wave program's null body meets
+    // the workgroup and flushes its share of the row counts, nothing else; the streams, the image and the dump slot they name
+    // are never read).  Behind the table lies ONE idle task, for the waves of scan groups that hold no scans in a launch
+    // (slane_kernel decides that per launch from the scan groups in use): a null task with no pair rows to flush.
     OMR_HIP(planes.alloc(sizeof(uint32_t) * (ntasks * nsg + 1) * SL_K * SL_DUMP * SL_LANES));
     const uint64_t prog0 = (uint64_t)p.prog.p;
     for (int lg = 0; lg < 3; lg++) {
         const int sgw = 1 << lg, places = 16 >> lg;
         const int NSp = ((g.NS + places - 1) / places) * places, nsgp = ((nsg + sgw - 1) / sgw) * sgw;
-        std::vector<SlaneTask> h((size_t)p.A * NSp * nsgp);
+        std::vector<SlaneTask> h((size_t)p.A * NSp * nsgp + 1);
+        {
+            SlaneTask &k = h.back();
+            memset(&k, 0, sizeof k);
+            k.seg = prog0 + 4ull * (uint64_t)p.null_seg, k.fet = prog0 + 4ull * (uint64_t)p.null_fet;
+            k.hrsrc[0] = (uint32_t)(uint64_t)hrows.p, k.hrsrc[1] = (uint32_t)((uint64_t)hrows.p >> 32) & 0xffffu, k.hrsrc[3] = 0x00020000u;
+            k.rsrc[0] = (uint32_t)(uint64_t)bits_base, k.rsrc[1] = (uint32_t)((uint64_t)bits_base >> 32) & 0xffffu, k.rsrc[3] = 0x00020000u;
+            k.planes = (uint64_t)planes.p + 4ull * ((uint64_t)ntasks * nsg * SL_K * SL_DUMP * SL_LANES);
+            k.nrec = (uint32_t)p.nrec, k.nexec = (uint32_t)p.nexec, k.hpitch = (uint32_t)(nscp * 4);
+            k.cls = SL_CLS_NULL;  // wave = 0: no pair rows; lds_base = 0
+            k.pad2[0] = ~0ull;    // (-DSLANE_STAMP builds keep the workgroup's id here: none)
+        }
         for (int ai = 0; ai < p.A; ai++)
             for (int st = 0; st < NSp; st++) {
                 const size_t ti = (size_t)ai * g.NS + (st < g.NS ? st : 0);  // index into p.tasks (launch order)
@@ -285,7 +310,7 @@ int SlaneScratch::create(const SlanePlan &p, int groups)
                     k.nrec = (uint32_t)p.nrec;
                     k.nexec = (uint32_t)p.nexec;
                     k.hpitch = (uint32_t)(nscp * 4);
-                    k.cls = real ? S.cls : 0;
+                    k.cls = real ? S.cls : SL_CLS_NULL;
                     static_assert(SL_BLOCK / 2 <= (1 << SL_WAVE_FIRST_BITS) && 8 < (1 << SL_WAVE_COUNT_BITS), "SlaneTask::wave fields");
                     k.wave = first | (count << SL_WAVE_COUNT_SHIFT);
                     k.lds_base = (uint32_t)((sg % sgw) * 2 * (SL_BLOCK / 2) * SL_LANES * 4);
@@ -293,6 +318,14 @@ int SlaneScratch::create(const SlanePlan &p, int groups)
             }
         OMR_HIP(descs[lg].alloc(sizeof(SlaneTask) * h.size()));
         OMR_HIP(hipMemcpy(descs[lg].p, h.data(), sizeof(SlaneTask) * h.size(), hipMemcpyHostToDevice));
+    }
+    {   // which (place, scan group) a wave of a workgroup with null strip places takes: [sgw_log][real places - 1][real scan groups - 1][wave]
+        std::vector<uint8_t> m(SL_WAVE_MAP_BYTES, 0);
+        for (int lg = 0; lg < 3; lg++)
+            for (int rp = 1; rp <= 16 >> lg; rp++)
+                for (int rs = 1; rs <= 1 << lg; rs++) slane_wave_map(4 - lg, rp, rs, &m[(size_t)(((lg * 16 + (rp - 1)) * 4 + (rs - 1)) << 4)]);
+        OMR_HIP(wave_map.alloc(m.size()));
+        OMR_HIP(hipMemcpy(wave_map.p, m.data(), m.size(), hipMemcpyHostToDevice));
     }
     return OMR_OK;
 }
@@ -310,7 +343,7 @@ int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int
     if (packed && ((scan_stride & 3) != 0 || scan_stride < (int64_t)p.g.rows * p.g.NW * 4 || ((uintptr_t)d_img & 3) != 0))
         return fail(OMR_ERR_BADARG, "packed scans: rows x %d dwords each, 4-byte aligned", p.g.NW);
     const int used = (nscans + SL_LANES - 1) / SL_LANES;  // scan groups that hold scans; the descriptors are laid out for s.nsg
-    int nsg_run = used;  // scan groups the sweep adds row counts for: whole workgroups, as far as the scratch holds them
+    const int nsg_run = used;  // scan groups the sweep adds row counts for: the others of a workgroup are null tasks in this launch
     if (s.rows_dirty) {  // the previous launch was asked to keep its row counts (omr_batch_lanes_keep)
         OMR_HIP(hipMemsetAsync(s.hrows.p, 0, s.rows_bytes, stream));
         s.rows_dirty = false;
@@ -324,11 +357,11 @@ int slane_enqueue(const SlanePlan &p, SlaneScratch &s, const uint8_t *d_img, int
         const int nsgq = (used + sgw - 1) / sgw, NQ = (p.g.NS + places - 1) / places;
         const int32_t *d_tab = nullptr;
         int per_xcd = 0;
-        if (int rc = p.units_for(NQ * nsgq, &d_tab, &per_xcd)) return rc;
-        OMR_HIP(launch_slane(s.descs[lg].as<SlaneTask>(), nsgq, ((s.nsg + sgw - 1) / sgw) * sgw, p.A, NQ, lg, s.guard.as<int32_t>(),
-                             d_tab, per_xcd, stream));
+        if (int rc = p.units_for(used, &d_tab, &per_xcd)) return rc;
+        const int nsgp = ((s.nsg + sgw - 1) / sgw) * sgw, NSp = NQ * places;
+        OMR_HIP(launch_slane(s.descs[lg].as<SlaneTask>(), nsgq, nsgp, used, p.A, p.g.NS, NQ, lg, (int64_t)p.A * NSp * nsgp,
+                             s.wave_map.as<uint8_t>(), s.guard.as<int32_t>(), d_tab, per_xcd, stream));
         s.guard_pending = true;
-        nsg_run = std::min(nsgq * sgw, s.nsg);
     }
     if (ev1) OMR_HIP(hipEventRecord(ev1, stream));
     if (post_stream && ev_mid) {

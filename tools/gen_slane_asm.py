@@ -1,6 +1,8 @@
 """Generates omr-img-corrector_amd/csrc/slane_asm.inc: the scan-lane sweep's wave program as
 gfx950 assembly text; ONE asm statement that dispatches on the strip's segment-slot class (2 / 4 / 8 slots per word laid out) and,
 once per turn of 16 rows, on the turn's header (1 .. S slots executed: 2 + 4 + 8 loop bodies; program format v3, round 5).
+A null task -- a place of the workgroup without work -- takes a body of its own that only meets the workgroup and flushes its
+share of the row counts (null_body).
 
 Why assembly: the wave keeps its source words in a ring of 64 VGPRs addressed through the gfx9 VGPR index mode (M0),
 its segment descriptors live in SGPRs filled by s_load, and the column counters are a carry-save tree in fixed
@@ -88,6 +90,7 @@ FOFF = (80, 84, 88, 92)        # fetch records of sets A..D: two pair offsets, t
 NLOAD = 4                      # loads per row
 RSRC = 96                      # s[96:99]: the image's descriptor, its base moved to the pair being loaded (num_records = the pair)
 AHEAD = 4
+NULL_CLS = 7                   # SlaneTask::cls of a null task (SL_CLS_NULL, slane.hpp): a place of the workgroup without work
 
 
 def words2(out, sset, S, d0, d1, E, t):
@@ -364,8 +367,20 @@ def body(o, S, L):
           "s_sub_u32 s8, s8, %d" % TURN, "s_cmp_lg_u32 s8, 0", "s_cbranch_scc1 L%s_loop" % L]
 
 
+def null_body(o, L):
+    """A NULL task (cls = NULL_CLS): a place of the workgroup beyond the last strip, or a scan group that holds no scans in
+    this launch.  It has no rows of its own, only the duties of a member of the workgroup: it meets the others at the end of
+    every block of BLOCK rows -- the same turn count as theirs, taken from s8 -- and sends its share of its scan group's LDS
+    pair rows on (flush(): the same buffer bit and record counter as the real bodies; a share of 0 pair rows leaves only the
+    meeting).  No records, no segment slots, no source loads, no ring, no carry-save, no dump: between two meetings the wave
+    sleeps at the barrier and leaves its SIMD to the others."""
+    o.append("L%s_loop:" % L)
+    flush(o, "L%s" % L)
+    o += ["s_sub_u32 s8, s8, %d" % TURN, "s_cmp_lg_u32 s8, 0", "s_cbranch_scc1 L%s_loop" % L]
+
+
 def kernel():
-    """ONE statement: descriptor, dispatch on the slot class, the seven row loops, the counter dump.  (Three statements
+    """ONE statement: descriptor, dispatch on the slot class, the seven row loops, the counter dump; behind it the null body.  (Three statements
     behind a C++ branch keep the class live across them, and with nearly every register clobbered that costs a 129th
     VGPR -- a whole wave per SIMD.)"""
     o = []
@@ -376,6 +391,7 @@ def kernel():
         o.append("v_mov_b32 v%d, 0" % v)
     o.append("s_waitcnt lgkmcnt(0)")
     o.append("s_or_b32 s9, s9, s10")
+    o += ["s_cmp_eq_u32 s11, %d" % NULL_CLS, "s_cbranch_scc1 L%s_null" % U]  # a place without work: only the workgroup's duties
     # the descriptor the source loads go through: the image's, its base moved per pair (fetch()), num_records = one pair (a null
     # task's image has none: its loads read zeros without touching memory)
     o += ["s_mov_b32 s%d, s4" % RSRC, "s_mov_b32 s%d, s5" % (RSRC + 1), "s_min_u32 s%d, s6, 512" % (RSRC + 2), "s_mov_b32 s%d, s7" % (RSRC + 3)]
@@ -404,6 +420,10 @@ def kernel():
         if i and i % 16 == 0:
             o += ["s_add_u32 s16, s16, 4096", "s_addc_u32 s17, s17, 0"]
         o.append("global_store_dword %%[lane4], v%d, s[16:17] offset:%d" % (P[i // NPL] + i % NPL, (i % 16) * 256))
+    o.append("s_branch L%s_end" % U)
+    o.append("L%s_null:" % U)
+    null_body(o, "%s_null" % U)
+    o.append("L%s_end:" % U)
     o.append("s_waitcnt vmcnt(0)")
     return o
 

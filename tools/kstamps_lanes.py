@@ -1,7 +1,8 @@
 """Where and when the workgroups of ONE scan-lane launch ran (development aid; needs a library built with
 `tools/build_variant.sh stamp -DSLANE_STAMP`): per XCD the busy time of its CUs and the moment its last workgroup ended, so that
-a static imbalance of the launch order (slane.hip: ids go round-robin to the 8 XCDs) shows as XCDs that finish early.
-Usage: OMR_AB_LIB=omr-img-corrector_amd/lib/variants/libomrdeskew_stamp.so python3 tools/ab_lib.py tools/kstamps_lanes.py [scans]"""
+a static imbalance of the launch order (slane.hip: ids go round-robin to the 8 XCDs) shows as XCDs that finish early, and
+the durations of the workgroups by strip group q -- the last strip group of a candidate is the one with null places.
+Usage: OMR_AB_LIB=omr-img-corrector_amd/lib/variants/libomrdeskew_stamp.so python3 tools/ab_lib.py tools/kstamps_lanes.py [scans] [lanes of the context]"""
 import ctypes as C
 import os
 import sys
@@ -23,7 +24,7 @@ for i in range(n):
     buf[i] = torch.from_numpy(cards[i % 8][0]).to(dev)
 best = torch.zeros(n, dtype=torch.int32, device=dev)
 b = projection.Batch(ROWS, COLS, 10, 0.05, n_streams=1)
-b.set_lanes(n)
+b.set_lanes(int(sys.argv[2]) if len(sys.argv) > 2 else n)
 b.set_timing(True)
 for it in range(2):
     b.run_device(buf.data_ptr(), ROWS * COLS, COLS, n, 127, best.data_ptr())
@@ -42,6 +43,7 @@ t0 = st[ran, 0].min()
 start = (st[ran, 0] - t0).astype(np.float64) / 100.0  # us (100 MHz)
 end = (st[ran, 1] - t0).astype(np.float64) / 100.0
 xcc = (st[ran, 2] >> np.uint64(32)).astype(np.int64) & 15
+sq = (st[ran, 2] >> np.uint64(56)).astype(np.int64)  # strip group of the workgroup
 hw = (st[ran, 2] & np.uint64(0xffffffff)).astype(np.int64)
 cu = (hw >> 8) & 15
 se = (hw >> 13) & 7
@@ -60,4 +62,10 @@ d = end - start
 order = np.argsort(ids)
 # durations along the launch order: mean of consecutive blocks of 256 ids
 print("mean duration (us) per 256 consecutive ids:", " ".join("%.0f" % d[order][i:i + 256].mean() for i in range(0, len(ids), 256)))
+for q in sorted(set(sq.tolist())):
+    m = sq == q
+    print("strip group %2d: %5d workgroups, duration mean %.1f median %.1f min %.1f max %.1f us" % (q, int(m.sum()), d[m].mean(), np.median(d[m]), d[m].min(), d[m].max()))
+last = sq == sq.max()
+if last.any() and (~last).any():
+    print("last strip group against the others: mean %.1f / %.1f us = %.3f" % (d[last].mean(), d[~last].mean(), d[last].mean() / d[~last].mean()))
 b.close()
