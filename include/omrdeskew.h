@@ -796,12 +796,61 @@ int omr_get_angle_with_fft(const omr_image *gray_u8c1, double canny_threshold_1,
 int omr_get_angle_with_fft_ex(const omr_image *gray_u8c1, double canny_threshold_1, double canny_threshold_2,
                               double min_line_length, double max_line_gap, double *angle_out, omr_image_owned *lined);
 
+/* ---- get_angle_with_fft for batches of scans ------------------------------------------
+ * n device-resident 8-bit single-channel scans of one shape (scan i at d_scans + i * scan_stride_bytes, rows step_bytes
+ * apart): the log-spectrum pictures in groups of up to 8 scans a launch (as omr_fft_image_batch_device), then Canny
+ * (canny_threshold_1, canny_threshold_2), HoughLinesP (threshold 100) and the packed segment list for the whole batch,
+ * as omr_hough_angles_batch_device runs them, and the vote of fft.rs:197-247 on the host.  angles / n_lines: HOST
+ * arrays of n (n_lines may be NULL).  angles[i] has the f64 bits omr_get_angle_with_fft returns for scan i.  There is no
+ * per-scan code: as in the per-call form a scan without any segment gives angle 0.0 and succeeds.
+ * d_lined (may be NULL): picture i -- byte for byte omr_get_angle_with_fft_ex's -- at d_lined + i * lined_stride_bytes,
+ * rows lined_step apart.  EVERY slot is written: a scan without a segment gets the bare GRAY2BGR edge picture, as the
+ * per-call form gives (this is the difference from omr_hough_angles_batch_device, whose per-call form makes no picture
+ * there).  Bytes past 3 * cols of a picture row and bytes between pictures are not written.
+ * OMR_ERR_BADARG: a null d_scans / angles, n <= 0, step_bytes < cols, a negative scan stride, lined_step < 3 * cols,
+ * lined_stride_bytes < rows * lined_step, d_lined == d_scans.  OMR_ERR_ASSERT: an empty image, a side of 32767 or more.
+ * All are checked before any device work.  An axis length the transform does not take is reported as by
+ * omr_fft_image_batch_device (OMR_ERR_NOTIMPL, when the tables are built).
+ * Device memory: for the WHOLE batch at once the library allocates the log pictures and the edge maps (2 bytes a
+ * pixel) and, with pictures, a copy of the edge maps (3 in all); the caller's own picture buffer is another 3 bytes a
+ * pixel, 6 resident together.  On top come HoughLinesP's point lists (8 bytes per edge pixel), its accumulator and
+ * point mask per scan, and the transform's workspace of at most 1 GiB.  n is taken as it is, so the caller bounds it
+ * (the host form goes 64 scans at a time).
+ * Enqueues on `stream` and SYNCHRONISES it before it returns, on every path. */
+int omr_fft_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,
+                                int32_t cols, int64_t step_bytes, double canny_threshold_1, double canny_threshold_2,
+                                double min_line_length, double max_line_gap, double *angles, int32_t *n_lines,
+                                uint8_t *d_lined, int64_t lined_stride_bytes, int64_t lined_step, void *stream);
+/* The same for host images of any mix of shapes, bucketed by shape as omr_get_angles_with_hough_batch does, on the
+ * current device: one upload and one device call per bucket (per 64 of its scans; uploads and picture downloads on up
+ * to 16 host threads); angles[i] / lined[i] belong to grays[i].  lined (n owned images, omr_image_free each) may be
+ * NULL; every lined[i] is filled.  Every image is checked as omr_get_angle_with_fft checks it before any device work,
+ * and an invalid one fails the whole call: angles is not written, and no picture is returned. */
+int omr_get_angles_with_fft_batch(const omr_image *grays, int32_t n, double canny_threshold_1,
+                                  double canny_threshold_2, double min_line_length, double max_line_gap,
+                                  double *angles, omr_image_owned *lined);
+
 /* oics::omr::get_result_from_fourier_transform(&Mat, weak, strong, min_line_length, max_line_gap) ->
  * Result<OmrResult> (omr.rs:304-337) on the 3/4-channel scan. */
 int omr_get_result_from_fourier_transform(const omr_image *src, double canny_threshold_weak,
                                           double canny_threshold_strong, double fourier_min_line_length,
                                           double fourier_max_line_gap, double *angle, int32_t *status,
                                           double *candidates, int32_t cand_cap, int32_t *cand_len);
+/* The same on n device-resident colour scans of one shape (3 or 4 channels; layout as above): RGB2GRAY per scan, the
+ * log pictures of the batch, Canny(weak, strong) on them, then omr_edges_detection_batch_device's chain on the edge
+ * pictures.  angles / status / n_lines: HOST arrays of n (status and n_lines may be NULL); angles[i] / status[i] are
+ * omr_get_result_from_fourier_transform's for scan i, and a scan without any segment reports OMR_STATUS_NOT_A_RESULT
+ * and angle 0.0 where that function fails.  OMR_ERR_BADARG: a null d_scans / angles, n <= 0, step_bytes < cols *
+ * channels, a negative scan stride.  OMR_ERR_ASSERT: an empty image, a side of 32767 or more, channels other than 3
+ * or 4.  All are checked before any device work.  Device memory for the whole batch at once: the gray scans (reused
+ * for the edge pictures), the log pictures and the second Canny's edge maps, 3 bytes a pixel, plus HoughLinesP's point
+ * lists, accumulator and point mask per scan as in omr_edges_detection_batch_device, and the workspace (<= 1 GiB).
+ * Enqueues on `stream` and SYNCHRONISES it before it returns. */
+int omr_fourier_transform_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,
+                                       int32_t cols, int32_t channels, int64_t step_bytes, double canny_threshold_weak,
+                                       double canny_threshold_strong, double fourier_min_line_length,
+                                       double fourier_max_line_gap, double *angles, int32_t *status, int32_t *n_lines,
+                                       void *stream);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

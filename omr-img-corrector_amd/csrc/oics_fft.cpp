@@ -26,6 +26,7 @@
 #include "fft.hpp"
 #include "hough.hpp"
 #include "hough_host.hpp"
+#include "host_threads.hpp"
 #include "kernels.hpp"
 
 using namespace omr;
@@ -34,7 +35,6 @@ using namespace omr::hh;
 namespace {
 
 typedef std::complex<double> cd;
-const double kPi = 3.14159265358979323846;
 
 void fft_host(std::vector<cd> &a)  // iterative radix-2, in place, forward
 {
@@ -442,6 +442,106 @@ int download_owned(const uint8_t *d, int rows, int cols, omr_image_owned *out, h
     return rc;
 }
 
+// Scans carried by one launch of each kernel in the batch forms: the fixed cost between dependent launches (tens of
+// microseconds, as for the sweep) is paid once per group; the workspace holds <= 1 GiB of spectra
+int fft_group(int n, int rows, int cols)
+{
+    const int G = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, ((size_t)1 << 30) / (sizeof(cfloat) * (size_t)rows * (cols + 8))));
+    return std::min(G, 8);
+}
+
+// the magnitude_log pictures of n scans (scan i at d_scans + i * stride, rows `step` apart) -> d_log, packed n x rows x
+// cols, in groups of the workspace's size, the last one short.  Enqueues only
+int log_pictures(FftWork &w, const uint8_t *d_scans, int n, int64_t stride, int64_t step, uint8_t *d_log, hipStream_t s)
+{
+    const size_t px = (size_t)w.rows * w.cols;
+    for (int i = 0; i < n; i += w.group) {
+        const int g = std::min(w.group, n - i);
+        if (int rc = w.run(d_scans + (int64_t)i * stride, step, nullptr, d_log + (size_t)i * px, s, g, stride)) return rc;
+    }
+    return OMR_OK;
+}
+
+// The workspace and the buffers of a batch call go back when it returns, on every path: declared after them, this drains
+// the stream first
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+HoughParams fft_hough_params(double canny_threshold_1, double canny_threshold_2, double min_line_length, double max_line_gap)
+{
+    HoughParams hp;
+    hp.low = canny_threshold_1;
+    hp.high = canny_threshold_2;
+    hp.threshold = 100;  // fft.rs:184
+    hp.min_line_length = min_line_length;
+    hp.max_line_gap = max_line_gap;
+    return hp;
+}
+
+// get_angle_with_fft for n device-resident scans of one shape; arguments already checked.  Synchronises `s`.
+int fft_angles_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, const HoughParams &hp,
+                      double *angles, int32_t *n_lines, uint8_t *d_lined, int64_t lstride, int64_t lstep, hipStream_t s)
+{
+    PoolScope scope(s);
+    const size_t img = (size_t)rows * cols;
+    FftWork w;
+    DevBuf logs;
+    BatchSegments seg;
+    DrainOnExit drain{s};
+    int rc = w.create(rows, cols, s, fft_group(n, rows, cols));
+    if (rc) return rc;
+    OMR_HIP(logs.alloc((size_t)n * img));
+    if ((rc = log_pictures(w, d_scans, n, stride, step, logs.as<uint8_t>(), s))) return rc;
+    // Canny(c1, c2) and HoughLinesP(threshold 100) on the log pictures: the Hough batch's segment stage
+    if ((rc = batch_segments_device(logs.as<uint8_t>(), n, (int64_t)img, cols, rows, cols, 1, hp, d_lined != nullptr, s, &seg)))
+        return rc;
+    // fft.rs:197-247 per scan on the host: f64, libm atan2 (the device's is not the host's bit for bit)
+    std::vector<double> ang((size_t)n);
+    host_fan_out((size_t)n, 16, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) select_fft_rs(seg.lines.data() + 4 * (size_t)seg.off[i], seg.count((int)i), &ang[i]);
+    });
+    // every slot gets its picture: a scan without a segment the bare edges, as the per-call form gives
+    if (d_lined && (rc = lined_device(seg.edges.as<uint8_t>(), n, (int64_t)img, cols, rows, cols, seg.d_packed.as<int32_t>(),
+                                      seg.off.data(), kLinedBgr, d_lined, lstride, lstep, s)))
+        return rc;
+    for (int i = 0; i < n; i++) {
+        angles[i] = ang[(size_t)i];
+        if (n_lines) n_lines[i] = seg.count(i);
+    }
+    return OMR_OK;
+}
+
+// one bucket of omr_get_angles_with_fft_batch: `members` index same-shape images of `grays`; at most FB_SCANS go to the
+// device at a time (6 bytes a pixel there, plus the HoughLinesP state and the FFT workspace)
+int fft_host_bucket(const omr_image *grays, const std::vector<int> &members, const HoughParams &hp, double *angles,
+                    omr_image_owned *lined)
+{
+    constexpr int FB_SCANS = 64;
+    const omr_image &first = grays[members[0]];
+    const int rows = first.rows, cols = first.cols;
+    const int64_t img = (int64_t)cols * rows, pic = 3 * img;
+    LeasedStream st;
+    int rc = st.create();
+    if (rc) return rc;
+    const int total = (int)members.size(), zmax = std::min(FB_SCANS, total);
+    DevBuf in, pics;
+    OMR_HIP(in.alloc((size_t)img * zmax));
+    if (lined) OMR_HIP(pics.alloc((size_t)pic * zmax));
+    std::vector<double> a((size_t)zmax);
+    for (int j0 = 0; j0 < total; j0 += zmax) {
+        const int m = std::min(zmax, total - j0);
+        if ((rc = upload_chunk(grays, members, j0, m, rows, cols, in.as<uint8_t>(), img))) return rc;
+        if ((rc = fft_angles_device(in.as<uint8_t>(), m, img, cols, rows, cols, hp, a.data(), nullptr,
+                                    lined ? pics.as<uint8_t>() : nullptr, pic, (int64_t)cols * 3, st.s)))
+            return rc;
+        for (int j = 0; j < m; j++) angles[members[(size_t)(j0 + j)]] = a[(size_t)j];
+        if (lined && (rc = download_pictures(pics.as<uint8_t>(), m, rows, cols, members, j0, nullptr, lined))) return rc;
+    }
+    return OMR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -483,20 +583,11 @@ int omr_fft_image_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_s
     int rc = have_device();
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // several scans per launch of each kernel: the fixed cost between dependent launches (tens of microseconds, as
-    // for the sweep) is paid once per group; the workspace holds <= 1 GiB of spectra
-    const size_t px = (size_t)rows * cols;
-    int G = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, ((size_t)1 << 30) / (sizeof(cfloat) * (size_t)rows * (cols + 8))));
-    G = std::min(G, 8);
     FftWork w;
-    if ((rc = w.create(rows, cols, s, G))) return rc;
-    for (int i = 0; i < n; i += G) {
-        const int g = std::min(G, n - i);
-        if ((rc = w.run(d_scans + (int64_t)i * scan_stride_bytes, step_bytes, nullptr, d_magnitude_log + (size_t)i * px, s, g,
-                        scan_stride_bytes)))
-            return rc;
-    }
-    OMR_HIP(hipStreamSynchronize(s));  // the workspace is released on return
+    DrainOnExit drain{s};  // the workspace is released on return, error returns included
+    if ((rc = w.create(rows, cols, s, fft_group(n, rows, cols)))) return rc;
+    if ((rc = log_pictures(w, d_scans, n, scan_stride_bytes, step_bytes, d_magnitude_log, s))) return rc;
+    OMR_HIP(hipStreamSynchronize(s));  // (here for its error code)
     return OMR_OK;
 }
 
@@ -520,38 +611,14 @@ static int angle_with_fft(const omr_image *gray, double canny_threshold_1, doubl
     OMR_HIP(m8.alloc((size_t)rows * cols));
     OMR_HIP(l8.alloc((size_t)rows * cols));
     if ((rc = w.run(in.as<uint8_t>(), cols, m8.as<uint8_t>(), l8.as<uint8_t>(), st.s))) return rc;
-    HoughParams hp;
-    hp.low = canny_threshold_1;
-    hp.high = canny_threshold_2;
-    hp.threshold = 100;  // fft.rs:184
-    hp.min_line_length = min_line_length;
-    hp.max_line_gap = max_line_gap;
+    const HoughParams hp = fft_hough_params(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap);
     std::vector<std::vector<int32_t>> lines;
     DevBuf edges;  // the picture's background: the edges of the log spectrum as Canny left them
     if ((rc = edges_lines_device(l8.as<uint8_t>(), 0, cols, rows, cols, 1, 1, hp, st.s, &lines, lined ? &edges : nullptr)))
         return rc;
-    // fft.rs:197-247: f64 angles folded into [-45, 45]; the inner loop re-reads line i (quirk B10), so
-    // line i collects n - 1 votes iff its raw angle is within 0.1 of its folded angle, else none
     const std::vector<int32_t> &l = lines[0];
     const int n = (int)(l.size() / 4);
-    double average_angle = 0.0;
-    int max_votes = 0;
-    for (int i = 0; i < n; i++) {
-        const double x1 = l[4 * i], y1 = l[4 * i + 1], x2 = l[4 * i + 2], y2 = l[4 * i + 3];
-        const double raw = (atan2(y2 - y1, x2 - x1) * 180.0) / kPi;
-        const double angle = raw < -45.0 ? raw + 90.0 : (raw > 45.0 ? raw - 90.0 : raw);
-        int votes = 0;
-        for (int j = 0; j < n; j++) {
-            if (i == j) continue;
-            if (fabs(raw - angle) < 0.1) votes++;
-        }
-        if (votes > max_votes) {
-            max_votes = votes;
-            average_angle = angle;
-        }
-        if (max_votes == n - 1 && n > 1) break;  // nothing can beat n - 1 with a strict '>'
-    }
-    *angle_out = average_angle;
+    select_fft_rs(l.data(), n, angle_out);  // fft.rs:197-247
     if (!lined) return OMR_OK;
     return lined_to_host(edges.as<uint8_t>(), rows, cols, l.data(), n, kLinedBgr, st.s, lined);  // no segment: the bare edges
 }
@@ -566,6 +633,42 @@ int omr_get_angle_with_fft_ex(const omr_image *gray, double canny_threshold_1, d
                               double min_line_length, double max_line_gap, double *angle_out, omr_image_owned *lined)
 {
     return angle_with_fft(gray, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, angle_out, lined);
+}
+
+int omr_fft_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
+                                int64_t step_bytes, double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                                double max_line_gap, double *angles, int32_t *n_lines, uint8_t *d_lined,
+                                int64_t lined_stride_bytes, int64_t lined_step, void *stream)
+{
+    int rc = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, 1, step_bytes, angles != nullptr, d_lined,
+                               lined_stride_bytes, lined_step);
+    if (rc || (rc = have_device())) return rc;
+    return fft_angles_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols,
+                             fft_hough_params(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), angles,
+                             n_lines, d_lined, lined_stride_bytes, lined_step, (hipStream_t)stream);
+}
+
+int omr_get_angles_with_fft_batch(const omr_image *grays, int32_t n, double canny_threshold_1, double canny_threshold_2,
+                                  double min_line_length, double max_line_gap, double *angles, omr_image_owned *lined)
+{
+    clear_error();
+    if (!grays || n < 1 || !angles) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (lined) memset(lined, 0, sizeof(*lined) * (size_t)n);
+    ShapeBuckets b;
+    // omr_get_angle_with_fft's checks, for every image before any device work
+    int err = bucket_by_shape(grays, n, [](const omr_image &im) { return check_gray(&im); }, &b);
+    if (err || (err = have_device())) return err;
+    const HoughParams hp = fft_hough_params(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap);
+    // the angles go to the caller's array only when the whole call has succeeded
+    std::vector<double> ang((size_t)n);
+    for (size_t k = 0; k < b.shapes.size() && err == OMR_OK; k++) err = fft_host_bucket(grays, b.members[k], hp, ang.data(), lined);
+    if (err) {
+        if (lined)
+            for (int i = 0; i < n; i++) omr_image_free(&lined[i]);
+        return err;
+    }
+    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
+    return OMR_OK;
 }
 
 int omr_get_result_from_fourier_transform(const omr_image *src, double canny_threshold_weak,
@@ -611,6 +714,43 @@ int omr_get_result_from_fourier_transform(const omr_image *src, double canny_thr
     line_angles(lines[0], &ang);
     if ((rc = vote_counts(ang, true, st.s, &cnt))) return rc;
     return select_omr_rs(ang, cnt, angle, status, candidates, cand_cap, cand_len);
+}
+
+int omr_fourier_transform_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,
+                                       int32_t cols, int32_t channels, int64_t step_bytes, double canny_threshold_weak,
+                                       double canny_threshold_strong, double fourier_min_line_length,
+                                       double fourier_max_line_gap, double *angles, int32_t *status, int32_t *n_lines,
+                                       void *stream)
+{
+    int rc = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, angles != nullptr, nullptr, 0, 0);
+    if (rc) return rc;
+    if (channels != 3 && channels != 4) return fail(OMR_ERR_ASSERT, "cvtColor(RGB2GRAY) needs 3 or 4 channels (omr.rs:314)");
+    if ((rc = have_device())) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    PoolScope scope(s);
+    const size_t img = (size_t)rows * cols;
+    FftWork w;
+    DevBuf gray, logs, flag, rowcnt;
+    DrainOnExit drain{s};
+    OMR_HIP(gray.alloc((size_t)n * img));
+    for (int i = 0; i < n; i++)  // omr.rs:314 per scan (a stack of scans may exceed a launch's 65535 rows)
+        OMR_HIP(launch_rgb2gray(d_scans + (int64_t)i * scan_stride_bytes, step_bytes, rows, cols, channels,
+                                gray.as<uint8_t>() + (size_t)i * img, cols, s));
+    if ((rc = w.create(rows, cols, s, fft_group(n, rows, cols)))) return rc;
+    OMR_HIP(logs.alloc((size_t)n * img));
+    if ((rc = log_pictures(w, gray.as<uint8_t>(), n, (int64_t)img, cols, logs.as<uint8_t>(), s))) return rc;
+    // omr.rs:323-330 Canny(weak, strong) on the log pictures -- the edge pictures take the gray scans' place, which the
+    // transform has read by then -- and get_result_from_edges_detection on the EDGE pictures
+    uint8_t *edges = gray.as<uint8_t>();
+    OMR_HIP(flag.alloc(sizeof(int)));
+    OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
+    if ((rc = canny_device(logs.as<uint8_t>(), (int64_t)img, cols, rows, cols, 1, n, canny_threshold_weak, canny_threshold_strong,
+                           edges, flag.as<int>(), s, rowcnt.as<int32_t>())))
+        return rc;
+    HoughParams hp;
+    hp.min_line_length = fourier_min_line_length;
+    hp.max_line_gap = fourier_max_line_gap;
+    return edges_detection_device(edges, n, (int64_t)img, cols, rows, cols, 1, hp, angles, status, n_lines, s);
 }
 
 }  // extern "C"

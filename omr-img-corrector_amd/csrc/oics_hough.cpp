@@ -392,25 +392,12 @@ int lined_to_host(const uint8_t *d_edges, int rows, int cols, const int32_t *lin
 
 // ---- get_angle_with_hough for a batch: the segments stay on the device (hough.hip: offsets, pack, vote-and-select)
 
-// fn(lo, hi) over [0, count) in contiguous pieces on a few host threads (the caller's alone for a small count)
-template <class Fn>
-static void host_fan_out(size_t count, size_t min_piece, Fn fn)
-{
-    // at most 16 threads, as on_threads (host_threads.hpp)
-    const size_t want = std::min<size_t>(std::min(std::thread::hardware_concurrency(), 16u), count / std::max<size_t>(min_piece, 1));
-    if (want < 2) return fn((size_t)0, count);
-    const size_t piece = (count + want - 1) / want;
-    std::vector<std::thread> pool;
-    for (size_t lo = 0; lo < count; lo += piece) pool.emplace_back(fn, lo, std::min(count, lo + piece));
-    for (auto &th : pool) th.join();
-}
-
-// every argument rule of omr_hough_angles_batch_device, before any device work
-static int hough_batch_check(const void *d_scans, int n, int64_t stride, int rows, int cols, int cn, int64_t step,
-                             const double *angles, const int32_t *rc_out, const void *d_lined, int64_t lstride, int64_t lstep)
+// every argument rule of omr_hough_angles_batch_device (and of the FFT detectors' batch forms), before any device work
+int hough_batch_check(const void *d_scans, int n, int64_t stride, int rows, int cols, int cn, int64_t step, bool have_outputs,
+                      const void *d_lined, int64_t lstride, int64_t lstep)
 {
     clear_error();
-    if (!d_scans || !angles || !rc_out) return fail(OMR_ERR_BADARG, "null pointer");
+    if (!d_scans || !have_outputs) return fail(OMR_ERR_BADARG, "null pointer");
     if (n <= 0) return fail(OMR_ERR_BADARG, "empty batch");
     int rc = check_image_shape(rows, cols);
     if (rc || (rc = cn_canny(cn))) return rc;
@@ -424,29 +411,31 @@ static int hough_batch_check(const void *d_scans, int n, int64_t stride, int row
     return OMR_OK;
 }
 
-// arguments already checked.  Synchronises `s`.
-static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
-                               const HoughParams &hp, double *angles, int32_t *rc_out, int32_t *n_lines, uint8_t *d_lined,
-                               int64_t lstride, int64_t lstep, hipStream_t s)
+// Canny -> HoughLinesP -> packed segment list of a batch (hough_host.hpp).  map, flag, rowcnt, d_over and the PPHT run
+// are released on every return without a wait of their own: the caller's PoolScope makes that a drain of `s`
+int batch_segments_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
+                          const HoughParams &hp, bool keep_edges, hipStream_t s, BatchSegments *seg)
 {
-    PoolScope scope(s);
     const size_t img = (size_t)rows * cols;
-    DevBuf map, flag, rowcnt, edges;
+    DevBuf map, flag, rowcnt;
+    DevBuf &edges = seg->edges, &d_off = seg->d_off, &d_packed = seg->d_packed;
     OMR_HIP(map.alloc((size_t)n * img));
     OMR_HIP(flag.alloc(sizeof(int)));
     OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
     int rc = canny_device(d_scans, stride, step, rows, cols, cn, n, hp.low, hp.high, map.as<uint8_t>(), flag.as<int>(), s,
                           rowcnt.as<int32_t>());
     if (rc) return rc;
-    if (d_lined) {  // the pictures' background: HoughLinesP erases the points it has used from its input
+    if (keep_edges) {  // the pictures' background: HoughLinesP erases the points it has used from its input
         OMR_HIP(edges.alloc(map.bytes));
         OMR_HIP(hipMemcpyAsync(edges.p, map.p, (size_t)n * img, hipMemcpyDeviceToDevice, s));
     }
     PphtRun run;
     if ((rc = ppht_launch(map.as<uint8_t>(), rowcnt.as<int32_t>(), rows, cols, n, hp, s, &run))) return rc;
     // slots -> offsets (one small download) -> packed list (one download)
-    DevBuf d_off, d_over, d_packed;
-    std::vector<int32_t> off((size_t)n + 1);
+    DevBuf d_over;
+    std::vector<int32_t> &off = seg->off;
+    off.assign((size_t)n + 1, 0);
+    seg->lines.clear();
     int32_t over[2] = {0, 0};
     OMR_HIP(d_off.alloc(sizeof(int32_t) * off.size()));
     OMR_HIP(d_over.alloc(sizeof(over)));
@@ -457,17 +446,35 @@ static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, in
     OMR_HIP(hipStreamSynchronize(s));
     if (over[0]) return fail(OMR_ERR_NOMEM, "HoughLinesP: %d segments exceed the buffer of %d", over[0], run.cap);
     if (over[1]) return fail(OMR_ERR_NOMEM, "HoughLinesP: the batch's segments exceed a list of 2^31 - 1");
-    const size_t total = (size_t)off[(size_t)n];
+    const size_t total = seg->total();
     int max_n = 0;
-    for (int i = 0; i < n; i++) max_n = std::max(max_n, off[(size_t)i + 1] - off[(size_t)i]);
+    for (int i = 0; i < n; i++) max_n = std::max(max_n, seg->count(i));
+    if (total > 0) {
+        seg->lines.resize(total * 4);
+        OMR_HIP(d_packed.alloc(sizeof(int32_t) * 4 * total));
+        OMR_HIP(launch_ppht_pack(run.lines.as<int32_t>(), run.cap, d_off.as<int32_t>(), n, max_n, d_packed.as<int32_t>(), s));
+        OMR_HIP(hipMemcpyAsync(seg->lines.data(), d_packed.p, sizeof(int32_t) * 4 * total, hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+    }
+    return OMR_OK;
+}
+
+// arguments already checked.  Synchronises `s`.
+static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
+                               const HoughParams &hp, double *angles, int32_t *rc_out, int32_t *n_lines, uint8_t *d_lined,
+                               int64_t lstride, int64_t lstep, hipStream_t s)
+{
+    PoolScope scope(s);
+    const size_t img = (size_t)rows * cols;
+    BatchSegments seg;
+    int rc = batch_segments_device(d_scans, n, stride, step, rows, cols, cn, hp, d_lined != nullptr, s, &seg);
+    if (rc) return rc;
+    const std::vector<int32_t> &off = seg.off, &lines = seg.lines;
+    const DevBuf &edges = seg.edges, &d_off = seg.d_off, &d_packed = seg.d_packed;
+    const size_t total = seg.total();
     std::vector<int32_t> win((size_t)n, -1);
     std::vector<float> ang(total);
     if (total > 0) {
-        std::vector<int32_t> lines(total * 4);
-        OMR_HIP(d_packed.alloc(sizeof(int32_t) * 4 * total));
-        OMR_HIP(launch_ppht_pack(run.lines.as<int32_t>(), run.cap, d_off.as<int32_t>(), n, max_n, d_packed.as<int32_t>(), s));
-        OMR_HIP(hipMemcpyAsync(lines.data(), d_packed.p, sizeof(int32_t) * 4 * total, hipMemcpyDeviceToHost, s));
-        OMR_HIP(hipStreamSynchronize(s));
         // the angles on the host (libm atan2f / fmodf, as the reference: the device's are not the host's bit for bit)
         host_fan_out(total, 4096, [&](size_t lo, size_t hi) { line_angles(lines.data() + 4 * lo, hi - lo, ang.data() + lo); });
         DevBuf d_ang, d_win;
@@ -506,6 +513,79 @@ static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, in
         i0 = i1;
     }
     return OMR_OK;
+}
+
+// omr.rs:231-302 for n device-resident scans of one shape: the body of omr_edges_detection_batch_device (and, on the
+// edge pictures of the log spectra, the last stage of omr_fourier_transform_batch_device)
+int edges_detection_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
+                           const HoughParams &hp, double *angles, int32_t *status, int32_t *n_lines, hipStream_t s)
+{
+    std::vector<std::vector<int32_t>> lines;
+    int rc;
+    if ((rc = edges_lines_device(d_scans, stride, step, rows, cols, cn, n, hp, s, &lines))) return rc;
+    // angles on host threads (libm atan2f, as the reference), one vote launch for the whole batch
+    std::vector<std::vector<float>> ang((size_t)n);
+    {
+        const int nt = (int)std::max(1u, std::min<unsigned>((unsigned)n, std::min(std::thread::hardware_concurrency(), 32u)));
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nt; t++)
+            pool.emplace_back([&, t]() {
+                for (int i = t; i < n; i += nt) line_angles(lines[i], &ang[i]);
+            });
+        for (auto &th : pool) th.join();
+    }
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    int max_n = 0;
+    for (int i = 0; i < n; i++) {
+        off[i + 1] = off[i] + (int64_t)ang[i].size();
+        max_n = std::max(max_n, (int)ang[i].size());
+    }
+    std::vector<int32_t> cnt_all((size_t)off[n]);
+    if (off[n] > 0) {
+        std::vector<float> flat((size_t)off[n]);
+        for (int i = 0; i < n; i++) std::copy(ang[i].begin(), ang[i].end(), flat.begin() + off[i]);
+        DevBuf da, dc, doff;
+        OMR_HIP(da.alloc(sizeof(float) * flat.size()));
+        OMR_HIP(dc.alloc(sizeof(int32_t) * flat.size()));
+        OMR_HIP(doff.alloc(sizeof(int64_t) * off.size()));
+        OMR_HIP(hipMemcpyAsync(da.p, flat.data(), sizeof(float) * flat.size(), hipMemcpyHostToDevice, s));
+        OMR_HIP(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, s));
+        OMR_HIP(launch_angle_votes_batch(da.as<float>(), doff.as<int64_t>(), n, max_n, 1, dc.as<int32_t>(), s));
+        OMR_HIP(hipMemcpyAsync(cnt_all.data(), dc.p, sizeof(int32_t) * flat.size(), hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
+    }
+    for (int i = 0; i < n; i++) {
+        if (n_lines) n_lines[i] = (int32_t)ang[i].size();
+        if (ang[i].empty()) {  // the reference would panic (quirk B11): report "not a result"
+            angles[i] = 0.0;
+            if (status) status[i] = OMR_STATUS_NOT_A_RESULT;
+            continue;
+        }
+        std::vector<int32_t> cnt(cnt_all.begin() + off[i], cnt_all.begin() + off[i + 1]);
+        int32_t st = 0, nc = 0;
+        if ((rc = select_omr_rs(ang[i], cnt, &angles[i], &st, nullptr, 0, &nc))) return rc;
+        if (status) status[i] = st;
+    }
+    return OMR_OK;
+}
+
+// pictures -> fresh host images, from several threads, one staged copy each (hough_host.hpp)
+int download_pictures(const uint8_t *d_pics, int m, int rows, int cols, const std::vector<int> &members, int j0,
+                      const int32_t *skip, omr_image_owned *lined)
+{
+    const size_t pic = (size_t)cols * 3 * rows;
+    return on_threads(m, [&](hipStream_t s, int lo, int hi) -> int {
+        for (int j = lo; j < hi; j++) {
+            if (skip && skip[j] != OMR_OK) continue;
+            omr_image_owned &o = lined[members[(size_t)(j0 + j)]];
+            uint8_t *data = (uint8_t *)malloc(pic);
+            if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
+            o = omr_image_owned{data, rows, cols, 3, (int64_t)cols * 3};
+            int rc1 = staged_d2h(o.data, d_pics + (size_t)j * pic, pic, s);
+            if (rc1) return rc1;
+        }
+        return OMR_OK;
+    });
 }
 
 }  // namespace hh
@@ -622,7 +702,7 @@ int omr_hough_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t sca
                                   double *angles, int32_t *rc, int32_t *n_lines, uint8_t *d_lined, int64_t lined_stride_bytes,
                                   int64_t lined_step, void *stream)
 {
-    int err = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, angles, rc, d_lined,
+    int err = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, angles && rc, d_lined,
                                 lined_stride_bytes, lined_step);
     if (err || (err = have_device())) return err;
     HoughParams hp;
@@ -673,19 +753,7 @@ static int hough_host_bucket(const omr_image *grays, const std::vector<int> &mem
             rcs[members[(size_t)(j0 + j)]] = r[(size_t)j];
         }
         if (!lined) continue;
-        // pictures -> fresh host images, from several threads, one staged copy each
-        rc = on_threads(m, [&](hipStream_t s, int lo, int hi) -> int {
-            for (int j = lo; j < hi; j++) {
-                if (r[(size_t)j] != OMR_OK) continue;
-                omr_image_owned &o = lined[members[(size_t)(j0 + j)]];
-                uint8_t *data = (uint8_t *)malloc((size_t)pic);
-                if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
-                o = omr_image_owned{data, rows, cols, 3, (int64_t)cols * 3};
-                int rc1 = staged_d2h(o.data, pics.as<uint8_t>() + (size_t)j * pic, (size_t)pic, s);
-                if (rc1) return rc1;
-            }
-            return OMR_OK;
-        });
+        rc = download_pictures(pics.as<uint8_t>(), m, rows, cols, members, j0, r.data(), lined);
         if (rc) return rc;
     }
     return OMR_OK;
@@ -801,53 +869,8 @@ int omr_edges_detection_batch_device(const uint8_t *d_scans, int32_t n, int64_t 
     HoughParams hp;
     hp.min_line_length = min_line_length;
     hp.max_line_gap = max_line_gap;
-    std::vector<std::vector<int32_t>> lines;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = edges_lines_device(d_scans, scan_stride_bytes, step_bytes, rows, cols, channels, n, hp, s, &lines))) return rc;
-    // angles on host threads (libm atan2f, as the reference), one vote launch for the whole batch
-    std::vector<std::vector<float>> ang((size_t)n);
-    {
-        const int nt = (int)std::max(1u, std::min<unsigned>((unsigned)n, std::min(std::thread::hardware_concurrency(), 32u)));
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; t++)
-            pool.emplace_back([&, t]() {
-                for (int i = t; i < n; i += nt) line_angles(lines[i], &ang[i]);
-            });
-        for (auto &th : pool) th.join();
-    }
-    std::vector<int64_t> off((size_t)n + 1, 0);
-    int max_n = 0;
-    for (int i = 0; i < n; i++) {
-        off[i + 1] = off[i] + (int64_t)ang[i].size();
-        max_n = std::max(max_n, (int)ang[i].size());
-    }
-    std::vector<int32_t> cnt_all((size_t)off[n]);
-    if (off[n] > 0) {
-        std::vector<float> flat((size_t)off[n]);
-        for (int i = 0; i < n; i++) std::copy(ang[i].begin(), ang[i].end(), flat.begin() + off[i]);
-        DevBuf da, dc, doff;
-        OMR_HIP(da.alloc(sizeof(float) * flat.size()));
-        OMR_HIP(dc.alloc(sizeof(int32_t) * flat.size()));
-        OMR_HIP(doff.alloc(sizeof(int64_t) * off.size()));
-        OMR_HIP(hipMemcpyAsync(da.p, flat.data(), sizeof(float) * flat.size(), hipMemcpyHostToDevice, s));
-        OMR_HIP(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, s));
-        OMR_HIP(launch_angle_votes_batch(da.as<float>(), doff.as<int64_t>(), n, max_n, 1, dc.as<int32_t>(), s));
-        OMR_HIP(hipMemcpyAsync(cnt_all.data(), dc.p, sizeof(int32_t) * flat.size(), hipMemcpyDeviceToHost, s));
-        OMR_HIP(hipStreamSynchronize(s));
-    }
-    for (int i = 0; i < n; i++) {
-        if (n_lines) n_lines[i] = (int32_t)ang[i].size();
-        if (ang[i].empty()) {  // the reference would panic (quirk B11): report "not a result"
-            angles[i] = 0.0;
-            if (status) status[i] = OMR_STATUS_NOT_A_RESULT;
-            continue;
-        }
-        std::vector<int32_t> cnt(cnt_all.begin() + off[i], cnt_all.begin() + off[i + 1]);
-        int32_t st = 0, nc = 0;
-        if ((rc = select_omr_rs(ang[i], cnt, &angles[i], &st, nullptr, 0, &nc))) return rc;
-        if (status) status[i] = st;
-    }
-    return OMR_OK;
+    return edges_detection_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels, hp, angles, status, n_lines,
+                                  (hipStream_t)stream);
 }
 
 // omr.rs:351-399

@@ -204,8 +204,16 @@ SYMBOLS = {
     "omr_get_angle_with_fft": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double, C.c_double, f64p]),
     "omr_get_angle_with_fft_ex": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double, C.c_double, f64p,
                                             C.POINTER(OmrImageOwned)]),
+    "omr_fft_angles_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_double,
+                                              C.c_double, C.c_double, C.c_double, f64p, i32p, C.c_void_p, C.c_int64, C.c_int64,
+                                              C.c_void_p]),
+    "omr_get_angles_with_fft_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                f64p, C.POINTER(OmrImageOwned)]),
     "omr_get_result_from_fourier_transform": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double,
                                                         C.c_double, f64p, i32p, f64p, C.c_int32, i32p]),
+    "omr_fourier_transform_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, f64p, i32p,
+                                                     i32p, C.c_void_p]),
     "omr_scale": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_shrink_to": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_resize": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),

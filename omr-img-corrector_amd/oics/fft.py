@@ -1,7 +1,9 @@
 """oics::fft (packages/lib/src/fft.rs) through the C ABI."""
 import ctypes as C
 
-from ._lib import OmrImageOwned, check, lib
+import numpy as np
+
+from ._lib import OmrImage, OmrImageOwned, check, f64p, i32p, lib
 from .hough import LINED_COLOR, _take, lined_picture as _lined_picture, lined_picture_batch_device as _lined_batch
 from .transfer import _mat, as_image
 
@@ -42,3 +44,37 @@ def get_angle_with_fft(gray_tm, canny_threshold_1, canny_threshold_2, min_line_l
     owned = OmrImageOwned()
     check(lib().omr_get_angle_with_fft_ex(*args, C.byref(owned)))
     return out.value, _take(owned)
+
+
+def fft_angles_batch_device(d_scans, n, scan_stride_bytes, rows, cols, step_bytes, canny_threshold_1, canny_threshold_2,
+                            min_line_length, max_line_gap, d_lined=None, lined_stride_bytes=0, lined_step=0, stream=None):
+    """omr_fft_angles_batch_device: get_angle_with_fft on n same-shape device-resident 8-bit single-channel scans
+    (d_scans, d_lined: device addresses).  Returns (angles float64 [n], n_lines int32 [n]): angles[i] has the bits the
+    per-call function returns, 0.0 for a scan without any segment.  With d_lined, picture i (the per-call
+    want_picture=True result, byte for byte) lands at d_lined + i * lined_stride_bytes, rows lined_step apart; every
+    slot is written, the bare edge picture where there is no segment.  Synchronises `stream` before returning."""
+    n = int(n)
+    angles = np.zeros(max(n, 0), np.float64)
+    n_lines = np.zeros(max(n, 0), np.int32)
+    check(lib().omr_fft_angles_batch_device(d_scans, n, int(scan_stride_bytes), int(rows), int(cols), int(step_bytes),
+                                            float(canny_threshold_1), float(canny_threshold_2), float(min_line_length),
+                                            float(max_line_gap), angles.ctypes.data_as(f64p), n_lines.ctypes.data_as(i32p),
+                                            d_lined, int(lined_stride_bytes), int(lined_step), stream))
+    return angles, n_lines
+
+
+def get_angles_with_fft(grays, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, want_pictures=False):
+    """get_angle_with_fft for a batch (omr_get_angles_with_fft_batch): 8-bit single-channel host images of any mix of
+    shapes; same-shape images go through the transform, Canny and HoughLinesP together on the device.  Returns angles
+    float64 [n], angles[i] the per-call angle of grays[i] (same bits).  want_pictures=True returns (angles, pictures):
+    n pictures [rows, cols, 3] uint8, the per-call want_picture=True results.  An invalid image fails the whole call."""
+    keep = [as_image(_mat(g)) for g in grays]
+    n = len(keep)
+    arr = (OmrImage * max(n, 1))(*[im for _, im in keep])
+    angles = np.zeros(n, np.float64)
+    owned = (OmrImageOwned * max(n, 1))() if want_pictures else None
+    check(lib().omr_get_angles_with_fft_batch(arr, n, float(canny_threshold_1), float(canny_threshold_2),
+                                              float(min_line_length), float(max_line_gap), angles.ctypes.data_as(f64p), owned))
+    if not want_pictures:
+        return angles
+    return angles, [_take(owned[i]) for i in range(n)]

@@ -76,6 +76,22 @@ def edges_detection_batch_device(d_scans_ptr, n, scan_stride, rows, cols, channe
     return angles, status, nl
 
 
+def fourier_transform_batch_device(d_scans_ptr, n, scan_stride, rows, cols, channels, step, canny_threshold_weak,
+                                   canny_threshold_strong, fourier_min_line_length, fourier_max_line_gap, stream=None):
+    """get_result_from_fourier_transform on n device-resident colour scans (3 or 4 channels) -> (angles, status,
+    n_lines); a scan without any segment reports status NotAResult and angle 0.0"""
+    n = int(n)
+    angles = np.zeros(max(n, 0), np.float64)
+    status = np.zeros(max(n, 0), np.int32)
+    nl = np.zeros(max(n, 0), np.int32)
+    check(lib().omr_fourier_transform_batch_device(d_scans_ptr, n, int(scan_stride), int(rows), int(cols), int(channels),
+                                                   int(step), float(canny_threshold_weak), float(canny_threshold_strong),
+                                                   float(fourier_min_line_length), float(fourier_max_line_gap),
+                                                   angles.ctypes.data_as(f64p), status.ctypes.data_as(i32p),
+                                                   nl.ctypes.data_as(i32p), stream))
+    return angles, status, nl
+
+
 def hough_set_scans_in_flight(scans):
     """Tuning knob of edges_detection_batch_device (include/omrdeskew.h): scans the sequential Hough stage works on at
     once; 0 = the library's default.  Returns the previous setting."""

@@ -1,4 +1,5 @@
-//! `oics::fft` (reference: packages/lib/src/fft.rs) -> omr_get_fft_image / omr_get_angle_with_fft / _ex.
+//! `oics::fft` (reference: packages/lib/src/fft.rs) -> omr_get_fft_image / omr_get_angle_with_fft / _ex,
+//! and the batch form omr_get_angles_with_fft_batch.
 use crate::bridge::{check, into_mat, view};
 use crate::ffi;
 use crate::transfer::TransformableMatrix;
@@ -51,4 +52,46 @@ pub fn get_angle_with_fft(
         imgcodecs::imwrite(path.to_str().unwrap_or(file_name), &pic, &params)?;
     }
     Ok(angle)
+}
+
+/// `get_angle_with_fft` for a batch: 8-bit single-channel images of any mix of shapes, one angle per image at the image's
+/// own position, each the angle the per-call function returns (same f64 bits; 0.0 where no segment is found, as there).
+/// Same-shape images go through the transform, Canny and HoughLinesP together on the device.  An invalid image fails
+/// the whole batch.
+pub fn get_angles_with_fft(
+    grays: &[&TransformableMatrix],
+    canny_threshold_1: f64,
+    canny_threshold_2: f64,
+    min_line_length: f64,
+    max_line_gap: f64,
+) -> opencv::Result<Vec<f64>> {
+    let n = grays.len();
+    let views: Vec<ffi::OmrImage> = grays.iter().map(|g| view(g.get_mat())).collect::<opencv::Result<_>>()?;
+    let mut angles = vec![0.0f64; n];
+    check(unsafe {
+        ffi::omr_get_angles_with_fft_batch(views.as_ptr(), n as i32, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, angles.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    Ok(angles)
+}
+
+/// The same with the picture `get_angle_with_fft` writes for every scan -- the edges of the log spectrum in colour with
+/// every segment drawn on (fft.rs:173-213), the bare edges where there is none -- as a `Mat`; encoding and writing stay
+/// with the caller.
+pub fn get_angles_with_fft_with_pictures(
+    grays: &[&TransformableMatrix],
+    canny_threshold_1: f64,
+    canny_threshold_2: f64,
+    min_line_length: f64,
+    max_line_gap: f64,
+) -> opencv::Result<Vec<(f64, Mat)>> {
+    let n = grays.len();
+    let views: Vec<ffi::OmrImage> = grays.iter().map(|g| view(g.get_mat())).collect::<opencv::Result<_>>()?;
+    let mut angles = vec![0.0f64; n];
+    let mut lined: Vec<ffi::OmrImageOwned> = (0..n).map(|_| ffi::OmrImageOwned::empty()).collect();
+    check(unsafe {
+        ffi::omr_get_angles_with_fft_batch(views.as_ptr(), n as i32, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, angles.as_mut_ptr(), lined.as_mut_ptr())
+    })?;
+    // every picture is taken over (and so released) even when an earlier one fails to convert
+    let mats: Vec<opencv::Result<Mat>> = lined.into_iter().map(into_mat).collect();
+    mats.into_iter().enumerate().map(|(i, m)| Ok((angles[i], m?))).collect()
 }
