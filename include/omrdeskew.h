@@ -763,6 +763,41 @@ int omr_projection_batch_run_device(omr_projection_batch *pb, const uint8_t *d_s
  * expect the device-resident omr_projection_batch_run_device to be the fast path. */
 int omr_get_angles_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t max_angle, double step,
                                           double resize_scale, double *angles, int32_t *best_idx);
+/* ---- ... and the deskewed full-size scans: the reference's benchmark flow, core/src/main.rs:68-95
+ * (get_angle_with_projections on the shrunk working image, then rotate_mat of the full-size original by that angle).
+ * Largest CONTAIN canvas any candidate angle gives at the context's FULL shape rows x cols (not the working shape), cols
+ * rounded up to 4 as omr_batch_deskew_canvas does: what every output slot of omr_projection_batch_deskew_device must
+ * hold.  Planned when the context is created: host arithmetic, no device call.  OMR_ERR_BADARG for a null argument;
+ * OMR_ERR_ASSERT when a candidate's canvas reaches 32767 on a side (omr_rotate fails there too). */
+int omr_projection_batch_deskew_canvas(omr_projection_batch *pb, int32_t *max_rows, int32_t *max_cols);
+/* omr_projection_batch_run_device's front end, sweep and arg-max, then every full-size scan warped by its own winner --
+ * read on the device, no host round trip in between -- into d_out + i * out_stride_bytes (rows out_step_bytes apart;
+ * the canvas fills the slot's top left, the slot's other bytes are not written): CONTAIN, scale 1, BORDER_CONSTANT with
+ * border_value (channel c = border_value[c]), the context's channel count; interp OMR_INTER_NEAREST or
+ * OMR_INTER_LINEAR.  Host arrays: out_size (2 n: rows, cols of canvas i), angle (n), best_idx (n, may be NULL), written
+ * once, at the end.  angle[i] has the f64 bits of omr_get_angle_with_projections, and canvas i is byte for byte what
+ * omr_rotate_device writes for scan i and that angle.
+ * OMR_ERR_BADARG: what omr_projection_batch_run_device refuses, a null border_value / d_out / out_size / angle, or a
+ * slot smaller than the canvas (out_step_bytes < max_cols x channels, out_stride_bytes < max_rows x out_step_bytes);
+ * OMR_ERR_NOTIMPL: any other interp, as omr_batch_deskew_device_cn.  Every argument is checked before any device work,
+ * and a refused call writes nothing.  Synchronous.
+ * Performance note: as for omr_batch_deskew_device_cn, the warp stages source boxes in LDS only when d_scans,
+ * scan_stride_bytes and step_bytes are multiples of 4, and only while a tile's source box fits (colour: winners up to
+ * about 27 degrees; beyond, taps come from global memory: DESIGN.md section 4.3). */
+int omr_projection_batch_deskew_device(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                                       int64_t step_bytes, int32_t n, int32_t interp, const uint8_t border_value[4],
+                                       uint8_t *d_out, int64_t out_stride_bytes, int64_t out_step_bytes,
+                                       int32_t *out_size, double *angle, int32_t *best_idx);
+/* The same for host images of any mix of shapes, bucketed and run through cached contexts exactly as
+ * omr_get_angles_with_projections_batch does; rotated (n owned images, omr_image_free each) gets image i's deskewed
+ * canvas: what omr_rotate(srcs[i], angles[i], 1.0, interp, border_value, OMR_CLIP_CONTAIN) returns.  A bucket a batch
+ * context does not take (4 channels, a sweep it cannot plan) goes image by image through
+ * omr_get_angle_with_projections and omr_rotate.  interp other than NEAREST / LINEAR: OMR_ERR_NOTIMPL.  On an error of
+ * the whole call nothing is written and no image is returned.  Device memory: a run carries up to 32 scans of a shape,
+ * each with its scan and an output slot of the largest canvas (26 + 54 MB for an A4 colour sheet at +-45 degrees). */
+int omr_deskew_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t max_angle, double step,
+                                      double resize_scale, int32_t interp, const uint8_t border_value[4],
+                                      double *angles, int32_t *best_idx, omr_image_owned *rotated);
 
 /* ---- FFT deskew path ------------------------------------------------------
  * The 2-D DFT is float32 like the reference's (dft on CV_32F); it is a different factorisation than

@@ -413,24 +413,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         t_run += t3 - t2;
         if (!a.rotated) continue;
         // canvases -> fresh host images, from several threads: packed on the device, then one staged copy each
-        rc = on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {
-            DevBuf pack;
-            OMR_HIP(pack.alloc((size_t)out_stride));
-            for (int j = lo; j < hi; j++) {
-                if (src[(size_t)j] != OMR_OK) continue;
-                const int r = size[2 * (size_t)j], c = size[2 * (size_t)j + 1];
-                omr_image_owned &o = a.rotated[idx[(size_t)(j0 + j)]];
-                const int64_t ostep = (int64_t)c * cn;
-                uint8_t *data = (uint8_t *)malloc((size_t)r * ostep);
-                if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
-                o = omr_image_owned{data, r, c, cn, ostep};
-                OMR_HIP(hipMemcpy2DAsync(pack.p, (size_t)ostep, dout.as<uint8_t>() + (size_t)j * out_stride, (size_t)out_step,
-                                         (size_t)ostep, (size_t)r, hipMemcpyDeviceToDevice, s));
-                int rc1 = staged_d2h(o.data, pack.p, (size_t)r * ostep, s);
-                if (rc1) return rc1;
-            }
-            return OMR_OK;
-        });
+        rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), src.data(), idx, j0, z, a.rotated);
         if (rc) return rc;
         t_down += now_ms() - t3;
     }

@@ -1,7 +1,9 @@
-// host_threads.hpp -- what the entry points that start in host memory share above the engine: the host-thread fan-out
-// and chunk upload of the batch forms (correct_batch.cpp, projection_batch.cpp) and the keyed cache of shared contexts
+// host_threads.hpp -- what the entry points that start in host memory share above the engine: the host-thread fan-out,
+// chunk upload and canvas download of the batch forms (correct_batch.cpp, projection_batch.cpp) and the keyed cache of shared contexts
 // (those two, and the per-call drivers' sweep plans in oics_host.cpp).
 #pragma once
+#include <stdlib.h>
+
 #include <algorithm>
 #include <list>
 #include <memory>
@@ -57,6 +59,32 @@ inline int upload_chunk(const omr_image *srcs, const std::vector<int> &idx, int 
             if (rc) return rc;
         }
         OMR_HIP(hipStreamSynchronize(s));
+        return OMR_OK;
+    });
+}
+
+// Canvases of a chunk -> fresh host images, from several threads: canvas j (size[2 j] rows x size[2 j + 1] cols x cn, at the
+// top left of slot j of d_out, rows out_step apart) is packed on the device and comes down in one staged copy into
+// out[idx[j0 + j]], which the caller frees with omr_image_free.  skip (may be null): canvas j stays where skip[j] != 0.
+inline int download_canvases(const uint8_t *d_out, int64_t out_stride, int64_t out_step, int cn, const int32_t *size,
+                             const int32_t *skip, const std::vector<int> &idx, int j0, int z, omr_image_owned *out)
+{
+    return on_threads(z, [&](hipStream_t s, int lo, int hi) -> int {
+        DevBuf pack;
+        OMR_HIP(pack.alloc((size_t)out_stride));
+        for (int j = lo; j < hi; j++) {
+            if (skip && skip[j] != OMR_OK) continue;
+            const int r = size[2 * (size_t)j], c = size[2 * (size_t)j + 1];
+            omr_image_owned &o = out[idx[(size_t)(j0 + j)]];
+            const int64_t ostep = (int64_t)c * cn;
+            uint8_t *data = (uint8_t *)malloc((size_t)r * ostep);
+            if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
+            o = omr_image_owned{data, r, c, cn, ostep};
+            OMR_HIP(hipMemcpy2DAsync(pack.p, (size_t)ostep, d_out + (size_t)j * out_stride, (size_t)out_step, (size_t)ostep, (size_t)r,
+                                     hipMemcpyDeviceToDevice, s));
+            int rc1 = staged_d2h(o.data, pack.p, (size_t)r * ostep, s);
+            if (rc1) return rc1;
+        }
         return OMR_OK;
     });
 }

@@ -6,8 +6,12 @@
 //               tables of a fractional shrink are built when the context is created and stay on the device.
 //   sweep       the context's omr_batch_ctx for the working shape: gray (quirk B8) and threshold(127) fused into its
 //               bit-packing loads, arg-max on the device.
+//   deskew      (omr_projection_batch_deskew_device) the batch warp (deskew.hip) of the FULL-SIZE
+//               scans by the sweep's winners, read on the device: the context keeps a second candidate set, planned
+//               for rows x cols instead of the working shape.
 //
-// Scan i's angle is omr_get_angle_with_projections' for the same scan, as f64 bits.
+// Scan i's angle is omr_get_angle_with_projections' for the same scan, as f64 bits; its canvas is omr_rotate's for that
+// angle, byte for byte.
 #include <math.h>
 #include <string.h>
 
@@ -25,7 +29,9 @@ using namespace omr::hh;
 
 namespace {
 
-const int kChunk = 256;  // scans per run of the host form's contexts
+const int kChunk = 256;     // scans per run of the host form's contexts
+const int kDeskewChunk = 32;  // ... when the deskewed canvases come back with the angles
+const int kWarpChunk = 64;  // scans per launch of the deskew warp: bounds the tile records (2.4 MB per A4 colour scan's canvas)
 
 // scale_self's size and resize()'s dispatch for it, on the host (COPY: the working images are the scans)
 struct Working {
@@ -74,6 +80,11 @@ struct omr_projection_batch {
     DevBuf work, best, vsd, hsd;
     AreaTables area;  // AREA_GENERAL
     std::vector<int32_t> h_best;
+    // the deskew: the candidates' CONTAIN canvases and warp tables at rows x cols, planned at create (host arithmetic),
+    // on the device from the first deskew call on; tile records and canvas sizes per run
+    DeskewTables dk;
+    DevBuf dk_tiles, dk_size;
+    std::vector<int32_t> h_size;
     std::mutex mu;
     ~omr_projection_batch()
     {
@@ -109,11 +120,10 @@ int front_end(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_str
     return OMR_OK;
 }
 
-int run_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n, double *angle,
-               int32_t *best_idx, double *v_sd, double *h_sd)
+// front end, sweep and arg-max of n scans: the winners are in pb->best (and the scores in pb->vsd / hsd) when it returns
+int sweep_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n, bool scores)
 {
     const size_t A = (size_t)pb->A;
-    const bool scores = v_sd || h_sd;
     int rc;
     if (scores) {
         if ((rc = grow(&pb->vsd, sizeof(double) * (size_t)n * A))) return rc;
@@ -127,16 +137,63 @@ int run_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_st
                                       resized ? pb->wstep : step, pb->cn, n, 127, pb->best.as<int32_t>(),
                                       scores ? pb->vsd.as<double>() : nullptr, scores ? pb->hsd.as<double>() : nullptr)))
         return rc;
-    if ((rc = omr_batch_sync(pb->sweep))) return rc;
+    return omr_batch_sync(pb->sweep);
+}
+
+// the winners to the host (after whatever else the call queued on pb->s), and the angles they mean
+int winners_to_host(omr_projection_batch *pb, int n, double *angle, int32_t *best_idx)
+{
     OMR_HIP(hipMemcpyAsync(pb->h_best.data(), pb->best.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, pb->s));
-    if (v_sd) OMR_HIP(hipMemcpyAsync(v_sd, pb->vsd.p, sizeof(double) * (size_t)n * A, hipMemcpyDeviceToHost, pb->s));
-    if (h_sd) OMR_HIP(hipMemcpyAsync(h_sd, pb->hsd.p, sizeof(double) * (size_t)n * A, hipMemcpyDeviceToHost, pb->s));
     OMR_HIP(hipStreamSynchronize(pb->s));
     for (int i = 0; i < n; i++) {
         const int idx = pb->h_best[(size_t)i];
         angle[i] = ((double)idx - (double)pb->N) * pb->step;  // projection.rs:189-190
         if (best_idx) best_idx[i] = idx;
     }
+    return OMR_OK;
+}
+
+int run_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n, double *angle,
+               int32_t *best_idx, double *v_sd, double *h_sd)
+{
+    const size_t A = (size_t)pb->A;
+    int rc;
+    if ((rc = sweep_locked(pb, d_scans, scan_stride, step, n, v_sd || h_sd))) return rc;
+    if (v_sd) OMR_HIP(hipMemcpyAsync(v_sd, pb->vsd.p, sizeof(double) * (size_t)n * A, hipMemcpyDeviceToHost, pb->s));
+    if (h_sd) OMR_HIP(hipMemcpyAsync(h_sd, pb->hsd.p, sizeof(double) * (size_t)n * A, hipMemcpyDeviceToHost, pb->s));
+    return winners_to_host(pb, n, angle, best_idx);
+}
+
+// the border's bytes as DeskewPass::border takes them (3 channels: channel c = byte c)
+int packed_border(int cn, const uint8_t bv[4])
+{
+    return cn == 1 ? (int)bv[0] : (int)((uint32_t)bv[0] | ((uint32_t)bv[1] << 8) | ((uint32_t)bv[2] << 16));
+}
+
+// sweep, then the warp of the full-size scans by pb->best on pb->s; winners and canvas sizes come down once, at the end
+int deskew_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride, int64_t step, int n, int interp,
+                  const uint8_t border_value[4], uint8_t *d_out, int64_t out_stride, int64_t out_step, int32_t *out_size,
+                  double *angle, int32_t *best_idx)
+{
+    int rc;
+    if (!pb->dk.on_device && (rc = pb->dk.upload(nullptr))) return rc;  // once per context
+    if ((rc = sweep_locked(pb, d_scans, scan_stride, step, n, false))) return rc;
+    DeskewPass p = pb->dk.pass();
+    p.scan_stride = scan_stride, p.sstep = step, p.srows = pb->rows, p.scols = pb->cols;
+    p.out_stride = out_stride, p.dstep = out_step;
+    p.border = packed_border(pb->cn, border_value);
+    p.cn = pb->cn;
+    if ((rc = grow(&pb->dk_tiles, deskew_tile_bytes(p, std::min(pb->max_scans, kWarpChunk))))) return rc;
+    for (int i0 = 0; i0 < n; i0 += kWarpChunk) {  // the launches of a stream run one after the other: one set of records
+        p.src = d_scans + (size_t)i0 * scan_stride;
+        p.dst = d_out + (size_t)i0 * out_stride;
+        p.best = pb->best.as<int32_t>() + i0;
+        p.out_size = pb->dk_size.as<int32_t>() + 2 * (size_t)i0;
+        OMR_HIP(launch_deskew_warp(p, std::min(kWarpChunk, n - i0), interp, pb->dk_tiles.p, pb->s));
+    }
+    OMR_HIP(hipMemcpyAsync(pb->h_size.data(), pb->dk_size.p, 2 * sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, pb->s));
+    if ((rc = winners_to_host(pb, n, angle, best_idx))) return rc;
+    memcpy(out_size, pb->h_size.data(), 2 * sizeof(int32_t) * (size_t)n);
     return OMR_OK;
 }
 
@@ -171,6 +228,10 @@ struct HostArgs {
     double *angles;
     int32_t *best_idx;
     int device;
+    // omr_deskew_with_projections_batch: the deskewed images as well (null: the angles alone)
+    omr_image_owned *rotated = nullptr;
+    int interp = OMR_INTER_NEAREST;
+    const uint8_t *border = nullptr;
 };
 
 // the per-call function, image by image: the buckets a batch context does not take
@@ -180,6 +241,7 @@ int bucket_per_call(const HostArgs &a, const std::vector<int> &idx)
         int rc = omr_get_angle_with_projections(&a.srcs[i], a.max_angle, a.step, a.scale, 1, &a.angles[i]);
         if (rc) return rc;
         if (a.best_idx) a.best_idx[i] = (int32_t)llround(a.angles[i] / a.step) + a.N;
+        if (a.rotated && (rc = omr_rotate(&a.srcs[i], a.angles[i], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &a.rotated[i]))) return rc;
     }
     return OMR_OK;
 }
@@ -195,26 +257,70 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     }
     if (rc) return rc;
     omr_projection_batch *pb = pbp.get();
-    const int m = (int)idx.size(), zmax = std::min(m, kChunk);
+    if (a.rotated && !pb->dk.count()) return bucket_per_call(a, idx);  // a canvas the warp's tables cannot hold
+    // with canvases a run carries 32 scans: scan and slot of an A4 colour sheet are 26 + 54 MB on the device
+    const int m = (int)idx.size(), zmax = std::min(m, a.rotated ? kDeskewChunk : kChunk);
     const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    LeasedStream st;  // the batch's device buffer comes from the block cache and returns to it when the call ends
+    const int64_t out_step = (int64_t)pb->dk.cols * cn, out_stride = out_step * pb->dk.rows;
+    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
     if ((rc = st.create())) return rc;
-    DevBuf din;
+    DevBuf din, dout;
     OMR_HIP(din.alloc((size_t)zmax * in_stride));
+    if (a.rotated) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
     std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> best((size_t)zmax);
+    std::vector<int32_t> best((size_t)zmax), size(2 * (size_t)zmax);
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
         // host memory -> device, from several threads
         if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
-        if ((rc = omr_projection_batch_run_device(pb, din.as<uint8_t>(), in_stride, row, z, ang.data(), best.data(), nullptr, nullptr)))
-            return rc;
+        rc = a.rotated ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
+                                                            out_stride, out_step, size.data(), ang.data(), best.data())
+                       : omr_projection_batch_run_device(pb, din.as<uint8_t>(), in_stride, row, z, ang.data(), best.data(), nullptr, nullptr);
+        if (rc) return rc;
         for (int j = 0; j < z; j++) {
             const int i = idx[(size_t)(j0 + j)];
             a.angles[i] = ang[(size_t)j];
             if (a.best_idx) a.best_idx[i] = best[(size_t)j];
         }
+        // canvases -> fresh host images, from several threads
+        if (a.rotated && (rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), nullptr, idx, j0, z, a.rotated)))
+            return rc;
     }
+    return OMR_OK;
+}
+
+// both host forms: every image checked as the per-call function checks it, then bucket by bucket; the caller's arrays
+// are written only when the whole call has succeeded
+int host_form(const omr_image *srcs, int n, uint16_t max_angle, double step, double scale, double *angles, int32_t *best_idx,
+              omr_image_owned *rotated, int interp, const uint8_t *border)
+{
+    int N = 0;
+    if (candidate_count(max_angle, step, &N) <= 0)
+        return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
+    ShapeBuckets b;
+    // omr_get_angle_with_projections' checks, for every image before any device work
+    int rc = bucket_by_shape(srcs, n, [&](const omr_image &im) -> int {
+        Working w;
+        int rc = check_image(&im, cn_gray_source);
+        return rc ? rc : working_size(im.rows, im.cols, scale, &w);
+    }, &b);
+    if (rc || (rc = have_device())) return rc;
+    int dev = 0;
+    OMR_HIP(hipGetDevice(&dev));
+    std::vector<double> ang((size_t)n);
+    std::vector<int32_t> best((size_t)n);
+    std::vector<omr_image_owned> rot(rotated ? (size_t)n : 0, omr_image_owned{nullptr, 0, 0, 0, 0});
+    HostArgs a{srcs, max_angle, step, scale, N, ang.data(), best.data(), dev};
+    a.rotated = rotated ? rot.data() : nullptr, a.interp = interp, a.border = border;
+    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
+        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
+    if (rc) {
+        for (auto &o : rot) omr_image_free(&o);
+        return rc;
+    }
+    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
+    if (best_idx) memcpy(best_idx, best.data(), sizeof(int32_t) * (size_t)n);
+    if (rotated) memcpy(rotated, rot.data(), sizeof(omr_image_owned) * (size_t)n);
     return OMR_OK;
 }
 
@@ -255,8 +361,16 @@ int omr_projection_batch_create(int32_t rows, int32_t cols, int32_t channels, ui
     pb->device = device, pb->rows = rows, pb->cols = cols, pb->cn = channels, pb->max_scans = max_scans;
     pb->step = step, pb->N = N, pb->A = A, pb->w = w;
     pb->h_best.assign((size_t)max_scans, 0);
+    pb->h_size.assign(2 * (size_t)max_scans, 0);
+    {  // the deskew's candidate set, at the full shape: host arithmetic, so that the canvas query needs no device.  A shape
+       // whose canvases leave the image limit keeps its sweep; the deskew entry points then refuse
+        std::vector<double> angles((size_t)A);
+        for (int i = 0; i < A; i++) angles[(size_t)i] = (double)(i - N) * step;
+        if (pb->dk.plan(rows, cols, angles.data(), A)) clear_error();
+    }
     OMR_HIP(hipStreamCreateWithFlags(&pb->s, hipStreamNonBlocking));
     OMR_HIP(pb->best.alloc(sizeof(int32_t) * (size_t)max_scans));
+    OMR_HIP(pb->dk_size.alloc(2 * sizeof(int32_t) * (size_t)max_scans));
     if (w.d.kind != ResizeDispatch::COPY) {
         pb->wstep = ((int64_t)w.wc * channels + 3) & ~(int64_t)3;
         pb->wstride = ((int64_t)w.wr * pb->wstep + 255) & ~(int64_t)255;
@@ -331,34 +445,59 @@ int omr_projection_batch_run_device(omr_projection_batch *pb, const uint8_t *d_s
     return rc;
 }
 
+int omr_projection_batch_deskew_canvas(omr_projection_batch *pb, int32_t *max_rows, int32_t *max_cols)
+{
+    clear_error();
+    if (!pb || !max_rows || !max_cols) return fail(OMR_ERR_BADARG, "null argument");
+    if (!pb->dk.count()) return fail(OMR_ERR_ASSERT, "a candidate's canvas leaves the image limit");
+    *max_rows = pb->dk.rows, *max_cols = pb->dk.cols;
+    return OMR_OK;
+}
+
+int omr_projection_batch_deskew_device(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan_stride_bytes,
+                                       int64_t step_bytes, int32_t n, int32_t interp, const uint8_t border_value[4],
+                                       uint8_t *d_out, int64_t out_stride_bytes, int64_t out_step_bytes, int32_t *out_size,
+                                       double *angle, int32_t *best_idx)
+{
+    clear_error();
+    int rc = check_scans(pb, d_scans, scan_stride_bytes, step_bytes, n);
+    if (rc) return rc;
+    if (!border_value || !d_out || !out_size || !angle) return fail(OMR_ERR_BADARG, "null argument");
+    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
+        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
+    if (!pb->dk.count()) return fail(OMR_ERR_ASSERT, "a candidate's canvas leaves the image limit");
+    // (by division: rows x pitch of an absurd pitch would leave 64 bits)
+    if (out_step_bytes < (int64_t)pb->dk.cols * pb->cn || out_stride_bytes / pb->dk.rows < out_step_bytes)
+        return fail(OMR_ERR_BADARG, "every output slot must hold the largest canvas, %d x %d x %d channels (omr_projection_batch_deskew_canvas)",
+                    pb->dk.rows, pb->dk.cols, pb->cn);
+    std::lock_guard<std::mutex> lk(pb->mu);
+    OMR_HIP(hipSetDevice(pb->device));
+    rc = deskew_locked(pb, d_scans, scan_stride_bytes, step_bytes, n, interp, border_value, d_out, out_stride_bytes, out_step_bytes,
+                       out_size, angle, best_idx);
+    if (rc) {  // nothing of this call may still run when the next one starts
+        (void)hipStreamSynchronize(pb->s);
+        (void)omr_batch_sync(pb->sweep);
+    }
+    return rc;
+}
+
 int omr_get_angles_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t max_angle, double step, double resize_scale,
                                           double *angles, int32_t *best_idx)
 {
     clear_error();
     if (!srcs || n < 1 || !angles) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    int N = 0;
-    if (candidate_count(max_angle, step, &N) <= 0)
-        return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
-    ShapeBuckets b;
-    // omr_get_angle_with_projections' checks, for every image before any device work
-    int rc = bucket_by_shape(srcs, n, [&](const omr_image &im) -> int {
-        Working w;
-        int rc = check_image(&im, cn_gray_source);
-        return rc ? rc : working_size(im.rows, im.cols, resize_scale, &w);
-    }, &b);
-    if (rc || (rc = have_device())) return rc;
-    int dev = 0;
-    OMR_HIP(hipGetDevice(&dev));
-    // results go to the caller's arrays only when the whole call has succeeded
-    std::vector<double> ang((size_t)n);
-    std::vector<int32_t> best((size_t)n);
-    const HostArgs a{srcs, max_angle, step, resize_scale, N, ang.data(), best.data(), dev};
-    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
-    if (rc) return rc;
-    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
-    if (best_idx) memcpy(best_idx, best.data(), sizeof(int32_t) * (size_t)n);
-    return OMR_OK;
+    return host_form(srcs, n, max_angle, step, resize_scale, angles, best_idx, nullptr, OMR_INTER_NEAREST, nullptr);
+}
+
+int omr_deskew_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t max_angle, double step, double resize_scale,
+                                      int32_t interp, const uint8_t border_value[4], double *angles, int32_t *best_idx,
+                                      omr_image_owned *rotated)
+{
+    clear_error();
+    if (!srcs || n < 1 || !border_value || !angles || !rotated) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
+        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
+    return host_form(srcs, n, max_angle, step, resize_scale, angles, best_idx, rotated, interp, border_value);
 }
 
 }  // extern "C"

@@ -198,6 +198,11 @@ SYMBOLS = {
                                                   f64p]),
     "omr_get_angles_with_projections_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_double,
                                                         f64p, i32p]),
+    "omr_projection_batch_deskew_canvas": (C.c_int, [C.c_void_p, i32p, i32p]),
+    "omr_projection_batch_deskew_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, u8p,
+                                                     C.c_void_p, C.c_int64, C.c_int64, i32p, f64p, i32p]),
+    "omr_deskew_with_projections_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_double,
+                                                    C.c_int32, u8p, f64p, i32p, C.POINTER(OmrImageOwned)]),
     "omr_get_fft_image": (C.c_int, [C.POINTER(OmrImage), C.POINTER(OmrImageOwned), C.POINTER(OmrImageOwned)]),
     "omr_fft_image_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                              C.c_void_p, C.c_void_p]),

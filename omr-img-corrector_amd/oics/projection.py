@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import check, f64p, i32p, lib, u32p
-from .transfer import _mat, as_image
+from .transfer import _mat, _take_owned, as_image
 
 
 def get_angle_with_projections(src_img, max_angle, step, resize_scale, threads):
@@ -31,6 +31,33 @@ def get_angles_with_projections(srcs, max_angle, step, resize_scale, want_idx=Fa
     check(lib().omr_get_angles_with_projections_batch(arr, n, int(max_angle), float(step), float(resize_scale),
                                                       ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p) if want_idx else None))
     return (ang[:n], idx[:n]) if want_idx else ang[:n]
+
+
+def _border4(border):
+    bv = [int(border)] * 4 if isinstance(border, int) else [int(v) for v in border] + [0] * (4 - len(border))
+    return (C.c_uint8 * 4)(*bv[:4])
+
+
+def get_angles_and_deskew(srcs, max_angle, step, resize_scale, interp=1, border=(255, 255, 255), want_idx=False):
+    """The reference benchmark's flow for a batch (omr_deskew_with_projections_batch; core/src/main.rs:68-95):
+    get_angle_with_projections on every image, then rotate_mat of the full-size image by its angle (CONTAIN, scale 1,
+    constant border; interp 0 = NEAREST, 1 = LINEAR).  Host images of any mix of shapes.  Returns (angles, images):
+    angles[i] is the per-call angle of srcs[i] (same f64 bits), images[i] the array transfer.rotate_mat gives for it.
+    want_idx: (angles, best_idx, images)."""
+    from ._lib import OmrImage, OmrImageOwned
+    keep, arr = [], (OmrImage * max(len(srcs), 1))()
+    for i, s in enumerate(srcs):
+        a, im = as_image(_mat(s))
+        keep.append(a)
+        arr[i] = im
+    n = len(srcs)
+    ang = np.zeros(max(n, 1), np.float64)
+    idx = np.zeros(max(n, 1), np.int32)
+    owned = (OmrImageOwned * max(n, 1))()
+    check(lib().omr_deskew_with_projections_batch(arr, n, int(max_angle), float(step), float(resize_scale), int(interp),
+                                                  _border4(border), ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p), owned))
+    images = [_take_owned(owned[i]) for i in range(n)]
+    return (ang[:n], idx[:n], images) if want_idx else (ang[:n], images)
 
 
 def projection_batch_working_size(rows, cols, resize_scale):
@@ -70,6 +97,22 @@ class ProjectionBatch:
                                                     idx.ctypes.data_as(i32p), vs.ctypes.data_as(f64p) if want_sd else None,
                                                     hs.ctypes.data_as(f64p) if want_sd else None))
         return ang, idx, vs, hs
+
+    def deskew_canvas(self):
+        """(rows, cols) every output slot of deskew_device must hold: the largest CONTAIN canvas of the candidates at the
+        full shape (no device call)"""
+        r, c = C.c_int32(), C.c_int32()
+        check(lib().omr_projection_batch_deskew_canvas(self.handle, C.byref(r), C.byref(c)))
+        return r.value, c.value
+
+    def deskew_device(self, d_scans, scan_stride, step_bytes, n, interp, border, d_out, out_stride, out_step):
+        """run_device, then every full-size scan warped by its own winner into d_out + i * out_stride:
+        (angles, best_idx, out_size [n, 2] = rows, cols of canvas i)"""
+        ang, idx, size = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros((n, 2), np.int32)
+        check(lib().omr_projection_batch_deskew_device(self.handle, d_scans, scan_stride, step_bytes, n, int(interp), _border4(border),
+                                                       d_out, out_stride, out_step, size.ctypes.data_as(i32p),
+                                                       ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p)))
+        return ang, idx, size
 
     def close(self):
         if self.handle:
@@ -241,10 +284,8 @@ class Batch:
                          out_step, d_out_size=None, d_best=None):
         """deskew_device for scans of `channels` interleaved channels; border = one value per channel (a sequence) or
         one for all; every slot holds the largest canvas with channels * max_cols bytes per row at least"""
-        bv = [int(border)] * 4 if isinstance(border, int) else [int(v) for v in border] + [0] * (4 - len(border))
-        arr = (C.c_uint8 * 4)(*bv[:4])
         check(lib().omr_batch_deskew_device_cn(self.handle, d_scans, scan_stride, step_bytes, channels, n, black_max, interp,
-                                               arr, d_out, out_stride, out_step, d_out_size, d_best))
+                                               _border4(border), d_out, out_stride, out_step, d_out_size, d_best))
 
     def sync(self):
         check(lib().omr_batch_sync(self.handle))
