@@ -694,8 +694,9 @@ int omr_correct_batch_front_device(omr_correct_batch *cb, const uint8_t *d_scans
  * one of its sheets OMR_ERR_ASSERT, as per call.  Runs of up to 256 sheets per shape go through a context the library
  * keeps for later calls with the same device, shape and parameters (the last 4 are kept); uploads and the copies of
  * the rotated sheets into fresh host images run on up to 16 host threads.  On an error of the whole call no image is
- * returned.  Today this form is SLOWER than omr_correct_default from 16 host threads when the rotated images are
- * wanted (about 650 sheets/s against 825 on 1150 x 1240 sheets, 3 183 at A4: profiles/r06_correct_batch.md); the
+ * returned.  When the rotated IMAGES are wanted this form is slower than omr_correct_default from 16 host threads (about
+ * 650 sheets/s against 825 on 1150 x 1240 sheets, 3 183 at A4: profiles/r06_correct_batch.md); when the FILES are
+ * wanted, omr_correct_default_batch_jpeg below is the faster way (figures and their baseline there).  The
  * device-resident omr_correct_batch_run_device is the fast path. */
 int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t projection_max_angle,
                               double projection_angle_step, int32_t projection_max_width,
@@ -886,6 +887,55 @@ int omr_fourier_transform_batch_device(const uint8_t *d_scans, int32_t n, int64_
                                        double canny_threshold_strong, double fourier_min_line_length,
                                        double fourier_max_line_gap, double *angles, int32_t *status, int32_t *n_lines,
                                        void *stream);
+
+/* ---- baseline JPEG encoding on the device ---------------------------------------------------
+ * What imwrite(.., JPEG, quality) writes: byte for byte, SOI to EOI, libjpeg's stream after jpeg_set_defaults +
+ * jpeg_set_quality(quality, TRUE) -- JFIF 1.01 APP0 (no units, density 1 x 1), one DQT per table, SOF0, the standard
+ * Huffman tables of Annex K, no restart interval, not optimised, not progressive, forward DCT JDCT_ISLOW.  3 channels
+ * (BGR in memory) give YCbCr 4:2:0, interleaved; 1 channel gives a single-component scan.  quality outside 1..100 is
+ * clamped (0 -> 1, above 100 -> 100), as libjpeg and imwrite do.  4 channels: OMR_ERR_NOTIMPL; 2: OMR_ERR_ASSERT.
+ * Decoding is not part of the library.
+ *
+ * The two quantisation tables of `quality` in natural (not zig-zag) order.  Host only. */
+int omr_jpeg_quant_tables(int32_t quality, uint16_t luma[64], uint16_t chroma[64]);
+/* An upper bound of the stream's length for a rows x cols x channels image of any content at any quality: the header
+ * (at most 623 bytes), every block of the scan at its longest code (a DC code of 11 bits with 11 value bits, 63 AC codes
+ * of 16 bits with 10 value bits: 1660 bits) with every byte stuffed, and EOI.  OMR_ERR_ASSERT for an empty image or a
+ * side above 65535.  Host only. */
+int omr_jpeg_bound(int32_t rows, int32_t cols, int32_t channels, int64_t *bytes);
+/* n device-resident images, image i at d_imgs + i * img_stride_bytes with rows step_bytes apart, each in a slot of rows x
+ * cols x channels.  sizes: HOST array of n x (rows, cols) -- the layout of out_size of omr_correct_batch_run_device and
+ * omr_projection_batch_deskew_device, whose canvases feed straight in -- or NULL when every image fills its slot; an
+ * entry is at most the slot's size and its image lies at the slot's top left; a 0 x 0 entry gives out_len[i] = 0 and
+ * leaves its output slot untouched.  Stream i starts at d_out + i * out_stride_bytes (>= omr_jpeg_bound of the slot) and
+ * is out_len[i] bytes long (HOST array); nothing is written behind it.  OMR_ERR_BADARG: a null d_imgs / d_out / out_len,
+ * n < 0, step_bytes < cols x channels, img_stride_bytes < rows x step_bytes, a sizes entry that is negative, half empty
+ * or larger than the slot, out_stride_bytes below the bound.  OMR_ERR_ASSERT besides the shapes above: a slot whose
+ * scan could take more than 2^32 bits (about 2.58 million blocks: bit offsets inside an image are 32-bit).  Every argument is
+ * checked before any device work.  Synchronous, on a stream of its own, which has drained on every return path. */
+int omr_jpeg_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes, int64_t step_bytes, int32_t rows,
+                                 int32_t cols, int32_t channels, const int32_t *sizes, int32_t n, int32_t quality,
+                                 uint8_t *d_out, int64_t out_stride_bytes, int64_t *out_len);
+/* A host image -> its stream in `out` (cap bytes), *len = the stream's length.  cap too small (out may be NULL when cap
+ * is 0): OMR_ERR_NOMEM with *len = the length needed, nothing written. */
+int omr_jpeg_encode(const omr_image *src, int32_t quality, uint8_t *out, int64_t cap, int64_t *len);
+/* omr_correct_default_batch with every sheet's rotated canvas encoded on the device and only the streams downloaded:
+ * jpeg[i] (malloc'ed, release with omr_bytes_free) holds jpeg_len[i] bytes, NULL / 0 where scan_rc[i] != 0.  Same
+ * buckets, context cache and results; on an error of the whole call no stream is returned.  A shape whose canvas slot
+ * (omr_correct_batch_canvas) could take more than 2^32 bits of scan data -- colour sheets from about 7400 x 7400 --
+ * refuses the call with OMR_ERR_ASSERT before any device work.  Where the files are the result this form is the FASTER
+ * one.  Measured at quality 100 (profiles/r17_jpeg.md): 1.2 k sheets/s on the dataset's sheets (about 1150 x 1240, four
+ * shapes) and 0.7 k at A4.  The baseline is Pillow (libjpeg-turbo) called from 16 Python threads behind
+ * omr_correct_default_batch, 80 and 6 sheets/s, or inside 16 threads of omr_correct_default, 78 and 6.5: 15 x and about
+ * 110 x.  Those threads encode no faster than one (31 ms per A4 sheet, 2.8 ms per dataset sheet on one core); a host with
+ * an encoder process per core was not measured and would be bound by the correction (650 to 825 sheets/s on dataset-size
+ * sheets) or by about 520 A4 sheets/s of encoding. */
+int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t projection_max_angle,
+                                   double projection_angle_step, int32_t projection_max_width,
+                                   int32_t projection_max_height, double hough_min_line_length,
+                                   double hough_max_line_gap, int32_t quality, double *rotate_angle, int32_t *need_check,
+                                   int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len);
+void omr_bytes_free(uint8_t *bytes);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

@@ -29,6 +29,7 @@
 #include "engine.hpp"
 #include "hough_host.hpp"
 #include "host_threads.hpp"
+#include "jpeg.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -331,6 +332,45 @@ struct HostArgs {
     int32_t *need_check, *scan_rc;
     omr_image_owned *rotated;
     int device;
+    // the JPEG form (omr_correct_default_batch_jpeg): streams instead of canvases
+    uint8_t **jpeg = nullptr;
+    int64_t *jpeg_len = nullptr;
+    int32_t quality = 0;
+};
+
+// The streams of a chunk's canvases -> fresh host buffers: a device buffer of exactly the streams' size per group of the
+// encoder, then one staged copy per stream from several threads.  Stream j belongs to sheet idx[j0 + j].
+struct StreamSink : JpegSink {
+    const HostArgs &a;
+    const std::vector<int> &idx;
+    int j0;
+    DevBuf buf;
+    std::vector<int64_t> off;
+    StreamSink(const HostArgs &args, const std::vector<int> &members, int first) : a(args), idx(members), j0(first) {}
+    int place(int, int cnt, const int64_t *len, uint8_t **d_out, int64_t *o) override
+    {
+        int64_t total = 0;
+        off.assign((size_t)cnt, 0);
+        for (int j = 0; j < cnt; j++) off[(size_t)j] = o[j] = total, total += (len[j] + 255) & ~(int64_t)255;
+        buf.release();
+        OMR_HIP(buf.alloc((size_t)std::max<int64_t>(total, 256)));
+        *d_out = buf.as<uint8_t>();
+        return OMR_OK;
+    }
+    int done(int i0, int cnt, const int64_t *len) override
+    {
+        return on_threads(cnt, [&](hipStream_t s, int lo, int hi) -> int {
+            for (int j = lo; j < hi; j++) {
+                if (len[j] == 0) continue;
+                const int i = idx[(size_t)(j0 + i0 + j)];
+                uint8_t *data = (uint8_t *)malloc((size_t)len[j]);
+                if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
+                a.jpeg[i] = data, a.jpeg_len[i] = len[j];
+                if (int rc = staged_d2h(data, buf.as<uint8_t>() + off[(size_t)j], (size_t)len[j], s)) return rc;
+            }
+            return OMR_OK;
+        });
+    }
 };
 
 struct CtxKey {
@@ -390,7 +430,8 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     if ((rc = st.create())) return rc;
     DevBuf din, dout;
     OMR_HIP(din.alloc((size_t)zmax * in_stride));
-    if (a.rotated) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
+    const bool want_canvas = a.rotated || a.jpeg;
+    if (want_canvas) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
     std::vector<double> ang((size_t)zmax);
     std::vector<int32_t> chk((size_t)zmax), src((size_t)zmax), size(2 * (size_t)zmax);
     for (int j0 = 0; j0 < m; j0 += zmax) {
@@ -401,7 +442,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         double t2 = now_ms();
         t_up += t2 - t1;
         if ((rc = omr_correct_batch_run_device(cb, din.as<uint8_t>(), in_stride, row, z, ang.data(), chk.data(), src.data(),
-                                               a.rotated ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data())))
+                                               want_canvas ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data())))
             return rc;
         for (int j = 0; j < z; j++) {
             const int i = idx[(size_t)(j0 + j)];
@@ -411,6 +452,14 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         }
         double t3 = now_ms();
         t_run += t3 - t2;
+        if (a.jpeg) {  // the canvases stay on the device: encoded there, only the streams come down
+            for (int j = 0; j < z; j++)
+                if (src[(size_t)j] != OMR_OK) size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
+            StreamSink sink(a, idx, j0);
+            if ((rc = jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s))) return rc;
+            t_down += now_ms() - t3;
+            continue;
+        }
         if (!a.rotated) continue;
         // canvases -> fresh host images, from several threads: packed on the device, then one staged copy each
         rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), src.data(), idx, j0, z, a.rotated);
@@ -421,6 +470,43 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         fprintf(stderr, "omr_correct_default_batch %d x %dx%dx%d: context %.2f ms, upload %.2f ms, device %.2f ms, canvases %.2f ms\n", m,
                 rows, cols, cn, t_ctx, t_up, t_run, t_down);
     return OMR_OK;
+}
+
+// omr_correct_default_batch and its JPEG form: buckets, contexts and results are the same; `rotated` (may be null) receives
+// the canvases, or `jpeg` / `jpeg_len` (null for the plain form) their streams
+int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
+                         int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
+                         double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
+                         omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, int32_t quality)
+{
+    if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    ShapeBuckets b;
+    int rc = bucket_by_shape(srcs, n, [](const omr_image &im) { return check_image(&im, cn_correct_batch); }, &b);
+    if (rc) return rc;
+    if (rotated)
+        for (int i = 0; i < n; i++) rotated[i] = omr_image_owned{nullptr, 0, 0, 0, 0};
+    if (jpeg) {
+        for (int i = 0; i < n; i++) jpeg[i] = nullptr, jpeg_len[i] = 0;
+        // the encoder's bit offsets are 32-bit: a shape whose canvas slot could take more refuses the call, before any device work
+        for (const ImageShape &sh : b.shapes) {
+            int R, C;
+            canvas_of(sh.rows, sh.cols, &R, &C);
+            if ((rc = jpeg_check_scan_bits(R, C, sh.cn))) return rc;
+        }
+    }
+    if ((rc = have_device())) return rc;
+    int dev = 0;
+    OMR_HIP(hipGetDevice(&dev));
+    HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+               hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
+    a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.quality = quality;
+    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
+        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
+    if (rc && rotated)
+        for (int i = 0; i < n; i++) omr_image_free(&rotated[i]);
+    if (rc && jpeg)
+        for (int i = 0; i < n; i++) free(jpeg[i]), jpeg[i] = nullptr, jpeg_len[i] = 0;
+    return rc;
 }
 
 }  // namespace
@@ -550,22 +636,21 @@ int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t project
                               omr_image_owned *rotated)
 {
     clear_error();
-    if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    ShapeBuckets b;
-    int rc = bucket_by_shape(srcs, n, [](const omr_image &im) { return check_image(&im, cn_correct_batch); }, &b);
-    if (rc) return rc;
-    if (rotated)
-        for (int i = 0; i < n; i++) rotated[i] = omr_image_owned{nullptr, 0, 0, 0, 0};
-    if ((rc = have_device())) return rc;
-    int dev = 0;
-    OMR_HIP(hipGetDevice(&dev));
-    const HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
-                     hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
-    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
-    if (rc && rotated)
-        for (int i = 0; i < n; i++) omr_image_free(&rotated[i]);
-    return rc;
+    return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, nullptr,
+                                nullptr, 0);
+}
+
+int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
+                                   int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
+                                   double hough_max_line_gap, int32_t quality, double *rotate_angle, int32_t *need_check,
+                                   int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len)
+{
+    clear_error();
+    if (!jpeg || !jpeg_len) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, jpeg,
+                                jpeg_len, quality);
 }
 
 }  // extern "C"

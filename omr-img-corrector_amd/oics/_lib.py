@@ -219,6 +219,15 @@ SYMBOLS = {
     "omr_fourier_transform_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                      C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, f64p, i32p,
                                                      i32p, C.c_void_p]),
+    "omr_jpeg_quant_tables": (C.c_int, [C.c_int32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
+    "omr_jpeg_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "omr_jpeg_encode_batch_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p,
+                                               C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "omr_jpeg_encode": (C.c_int, [C.POINTER(OmrImage), C.c_int32, u8p, C.c_int64, C.POINTER(C.c_int64)]),
+    "omr_correct_default_batch_jpeg": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_int32,
+                                                 C.c_int32, C.c_double, C.c_double, C.c_int32, f64p, i32p, i32p,
+                                                 C.POINTER(u8p), C.POINTER(C.c_int64)]),
+    "omr_bytes_free": (None, [u8p]),
     "omr_scale": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_shrink_to": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_resize": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),

@@ -1,0 +1,52 @@
+"""Baseline JPEG encoding on the device (omr_jpeg_*): byte for byte what imwrite(.., JPEG, quality) writes."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, i32p, lib, u8p
+from .transfer import _mat, as_image
+
+
+def quant_tables(quality):
+    """omr_jpeg_quant_tables -> (luma, chroma), uint16 [64] each, natural order"""
+    luma, chroma = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    u16p = C.POINTER(C.c_uint16)
+    check(lib().omr_jpeg_quant_tables(int(quality), luma.ctypes.data_as(u16p), chroma.ctypes.data_as(u16p)))
+    return luma, chroma
+
+
+def bound(rows, cols, channels):
+    """omr_jpeg_bound: an upper bound of the stream's length in bytes"""
+    out = C.c_int64()
+    check(lib().omr_jpeg_bound(int(rows), int(cols), int(channels), C.byref(out)))
+    return out.value
+
+
+def encode_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, channels, sizes, n, quality, d_out,
+                        out_stride_bytes):
+    """omr_jpeg_encode_batch_device: n device-resident images in slots of rows x cols x channels (d_imgs, d_out: device
+    addresses; sizes: None or int32 [n, 2] of (rows, cols) per image).  Returns out_len int64 [n]: stream i is
+    out_len[i] bytes at d_out + i * out_stride_bytes (0: a 0 x 0 entry, slot untouched).  Synchronous."""
+    n = int(n)
+    out_len = np.zeros(max(n, 0), np.int64)
+    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
+    check(lib().omr_jpeg_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
+                                             int(channels), None if sz is None else sz.ctypes.data_as(i32p), n, int(quality),
+                                             d_out, int(out_stride_bytes), out_len.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out_len
+
+
+def encode(mat, quality=100):
+    """omr_jpeg_encode: a host image (gray or BGR) -> the stream as bytes.  One call in the usual case: the first buffer
+    holds the raw image's size plus the header, which all but noise at the highest qualities stays below; a stream that
+    does not fit answers -4 with its length, and a second call encodes again into a buffer of that length."""
+    a, im = as_image(_mat(mat))
+    n = C.c_int64()
+    L = lib()
+    buf = np.empty(min(im.rows * im.cols * im.channels + 1024, bound(im.rows, im.cols, im.channels)), np.uint8)
+    rc = L.omr_jpeg_encode(C.byref(im), int(quality), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
+    if rc == -4:
+        buf = np.empty(n.value, np.uint8)
+        rc = L.omr_jpeg_encode(C.byref(im), int(quality), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
+    check(rc)
+    return buf[: n.value].tobytes()

@@ -209,6 +209,38 @@ def correct_default_batch(src_mats, projection_max_angle, projection_angle_step,
     return [(float(ang[i]), bool(chk[i]), imgs[i], int(rc[i])) for i in range(n)]
 
 
+def correct_default_batch_jpeg(src_mats, projection_max_angle, projection_angle_step, projection_max_width,
+                               projection_max_height, hough_min_line_length, hough_max_line_gap, quality=100):
+    """omr_correct_default_batch_jpeg: correct_default_batch with every rotated sheet encoded on the device ->
+    [(rotate_angle, need_check, JPEG bytes or None, scan_rc)] in input order"""
+    from ._lib import OmrImage, u8p
+    keep, ims = [], []
+    for m in src_mats:
+        a, im = as_image(_mat(m))
+        keep.append(a)
+        ims.append(im)
+    n = len(ims)
+    arr = (OmrImage * max(n, 1))(*ims)
+    ang = np.zeros(n, np.float64)
+    chk = np.zeros(n, np.int32)
+    rc = np.zeros(n, np.int32)
+    ptrs = (u8p * max(n, 1))()
+    lens = np.zeros(max(n, 1), np.int64)
+    check(lib().omr_correct_default_batch_jpeg(arr, n, int(projection_max_angle), float(projection_angle_step),
+                                               int(projection_max_width), int(projection_max_height),
+                                               float(hough_min_line_length), float(hough_max_line_gap), int(quality),
+                                               ang.ctypes.data_as(f64p), chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p),
+                                               ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64))))
+    out = []
+    for i in range(n):
+        data = None
+        if ptrs[i]:
+            data = C.string_at(ptrs[i], int(lens[i]))
+            lib().omr_bytes_free(ptrs[i])
+        out.append((float(ang[i]), bool(chk[i]), data, int(rc[i])))
+    return out
+
+
 def get_result_from_fourier_transform(src_mat, canny_threshold_weak, canny_threshold_strong, fourier_min_line_length,
                                       fourier_max_line_gap):
     """omr.rs:304-337"""

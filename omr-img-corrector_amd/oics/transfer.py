@@ -47,6 +47,12 @@ class TransformableMatrix:
     def from_matrix(cls, mat):
         return cls(np.array(mat, dtype=np.uint8, copy=True))  # transfer.rs:55-59 deep clone
 
+    def encode_jpeg(self, quality=100):
+        """The bytes im_write(.., JPEG, quality) puts into its file (transfer.rs:169-186), encoded on the GPU
+        (omr_jpeg_encode): gray or BGR."""
+        from . import jpeg
+        return jpeg.encode(self.matrix, quality)
+
     def get_mat(self):
         return self.matrix
 

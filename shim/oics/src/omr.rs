@@ -121,3 +121,70 @@ pub fn correct_default(
     imgcodecs::imwrite(output_file, &out, &params)?;
     Ok((angle, need_check != 0))
 }
+
+/// `correct_default` for many files at once (omr_correct_default_batch_jpeg): imread(COLOR) per input on host threads, one
+/// batch call that corrects the sheets and encodes every rotated canvas as JPEG (quality 100) on the GPU, then
+/// `std::fs::write` per output.  Returns (rotation angle, need_check) per file.  A sheet the per-call function fails on
+/// fails the call with that sheet's code, names it, and no output file is written; an output that cannot be written
+/// fails the call with its index, the outputs before it being on disk.  Not in the reference crate.
+pub fn correct_defaults(
+    inputs: &[&str],
+    outputs: &[&str],
+    projection_max_angle: u16,
+    projection_angle_step: f64,
+    projection_max_width: i32,
+    projection_max_height: i32,
+    hough_min_line_length: f64,
+    hough_max_line_gap: f64,
+) -> opencv::Result<Vec<(f64, bool)>> {
+    if inputs.len() != outputs.len() || inputs.is_empty() {
+        return Err(opencv::Error::new(ffi::OMR_ERR_BADARG, String::from("inputs and outputs must pair up")));
+    }
+    let n = inputs.len();
+    let threads = n.min(16);
+    let mut mats: Vec<opencv::Result<Mat>> = Vec::with_capacity(n);
+    std::thread::scope(|sc| {
+        let handles: Vec<_> = (0..threads)
+            .map(|t| {
+                sc.spawn(move || {
+                    (t..n).step_by(threads).map(|i| (i, imgcodecs::imread(inputs[i], imgcodecs::IMREAD_COLOR))).collect::<Vec<_>>()
+                })
+            })
+            .collect();
+        let mut got: Vec<(usize, opencv::Result<Mat>)> = handles.into_iter().flat_map(|h| h.join().unwrap()).collect();
+        got.sort_by_key(|e| e.0);
+        mats.extend(got.into_iter().map(|e| e.1));
+    });
+    let mats: Vec<Mat> = mats.into_iter().collect::<opencv::Result<Vec<_>>>()?;
+    let views: Vec<ffi::OmrImage> = mats.iter().map(view).collect::<opencv::Result<Vec<_>>>()?;
+    let mut angle = vec![0.0f64; n];
+    let (mut need_check, mut scan_rc) = (vec![0i32; n], vec![0i32; n]);
+    let mut jpeg: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+    let mut jpeg_len = vec![0i64; n];
+    check(unsafe {
+        ffi::omr_correct_default_batch_jpeg(views.as_ptr(), n as i32, projection_max_angle, projection_angle_step,
+                                            projection_max_width, projection_max_height, hough_min_line_length,
+                                            hough_max_line_gap, 100, angle.as_mut_ptr(), need_check.as_mut_ptr(),
+                                            scan_rc.as_mut_ptr(), jpeg.as_mut_ptr(), jpeg_len.as_mut_ptr())
+    })?;
+    // all or nothing: no file is written unless every sheet was corrected
+    let failed = (0..n).find(|&i| scan_rc[i] != 0);
+    let mut result: opencv::Result<()> = match failed {
+        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("correct_default failed on {} (sheet {}); no output file was written", inputs[i], i))),
+        None => Ok(()),
+    };
+    for i in 0..n {
+        if jpeg[i].is_null() {
+            continue;
+        }
+        if result.is_ok() {
+            let bytes = unsafe { std::slice::from_raw_parts(jpeg[i], jpeg_len[i] as usize) };
+            if let Err(e) = std::fs::write(outputs[i], bytes) {
+                result = Err(opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (output {}; outputs before it are written): {}", outputs[i], i, e)));
+            }
+        }
+        unsafe { ffi::omr_bytes_free(jpeg[i]) };
+    }
+    result?;
+    Ok((0..n).map(|i| (angle[i], need_check[i] != 0)).collect())
+}

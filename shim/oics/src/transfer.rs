@@ -218,3 +218,24 @@ pub fn get_projection_standard_deviations(src: &TransformableMatrix) -> Result<(
     check(unsafe { ffi::omr_get_projection_standard_deviations(&view(&src.matrix)?, &mut v_sd, &mut h_sd) })?;
     Ok((v_sd, h_sd))
 }
+
+/// The bytes `im_write(.., ImageFormat::JPEG, quality)` puts into its file, encoded on the GPU (omr_jpeg_encode): what
+/// libjpeg writes for the Mat after jpeg_set_defaults + jpeg_set_quality.  Gray or BGR, 8-bit.  Not in the reference crate.
+/// One call in the usual case: the first buffer holds the raw image's size plus the header; a stream that does not fit
+/// (noise at the highest qualities) answers OMR_ERR_NOMEM with its length, and a second call encodes again into that.
+pub fn encode_jpeg(m: &TransformableMatrix, quality: i32) -> Result<Vec<u8>, opencv::Error> {
+    let v = view(&m.matrix)?;
+    let mut bound = 0i64;
+    check(unsafe { ffi::omr_jpeg_bound(v.rows, v.cols, v.channels, &mut bound) })?;
+    let raw = v.rows as i64 * v.cols as i64 * v.channels as i64 + 1024;
+    let mut out = vec![0u8; raw.min(bound) as usize];
+    let mut len = 0i64;
+    let mut rc = unsafe { ffi::omr_jpeg_encode(&v, quality, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    if rc == ffi::OMR_ERR_NOMEM {
+        out = vec![0u8; len as usize];
+        rc = unsafe { ffi::omr_jpeg_encode(&v, quality, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    }
+    check(rc)?;
+    out.truncate(len as usize);
+    Ok(out)
+}
