@@ -894,7 +894,7 @@ int omr_fourier_transform_batch_device(const uint8_t *d_scans, int32_t n, int64_
  * Huffman tables of Annex K, no restart interval, not optimised, not progressive, forward DCT JDCT_ISLOW.  3 channels
  * (BGR in memory) give YCbCr 4:2:0, interleaved; 1 channel gives a single-component scan.  quality outside 1..100 is
  * clamped (0 -> 1, above 100 -> 100), as libjpeg and imwrite do.  4 channels: OMR_ERR_NOTIMPL; 2: OMR_ERR_ASSERT.
- * Decoding is not part of the library.
+ * Decoding: the omr_jpeg_info / omr_jpeg_decode* section below.
  *
  * The two quantisation tables of `quality` in natural (not zig-zag) order.  Host only. */
 int omr_jpeg_quant_tables(int32_t quality, uint16_t luma[64], uint16_t chroma[64]);
@@ -936,6 +936,67 @@ int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t pr
                                    double hough_max_line_gap, int32_t quality, double *rotate_angle, int32_t *need_check,
                                    int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len);
 void omr_bytes_free(uint8_t *bytes);
+
+/* ---- baseline JPEG decoding on the device ---------------------------------------------------
+ * What imread returns: byte for byte libjpeg's output with its defaults (JDCT_ISLOW, fancy up-sampling, no scaling).
+ * Streams taken: SOF0, 8 bit, Huffman, one interleaved scan; 1 component at 1 x 1, or 3 components (YCbCr) with Y at
+ * 1 x 1, 2 x 1 or 2 x 2 and chroma at 1 x 1 (4:4:4, 4:2:2, 4:2:0); any DHT / DQT tables, with or without a restart
+ * interval, any APPn / COM segments.  channels = 1 gives the Y plane (of a gray or a colour stream), channels = 3 BGR in
+ * memory (B = G = R for a gray stream).
+ * OMR_ERR_NOTIMPL, never a wrong picture: SOF1 / SOF2 and the other frame types, 12-bit samples, arithmetic coding, more
+ * than one scan, 4 components, other sampling factors, an Adobe APP14 segment or component ids R G B, 16-bit
+ * quantisation tables, DNL, an EXIF orientation other than 1 (imread would turn the image).
+ * OMR_ERR_BADARG: a malformed header -- no SOI, a segment running past the end, a table that SOS names but nobody
+ * defined, a size of 0.  OMR_ERR_ASSERT: entropy data that ends early, runs into an invalid code, has other restart
+ * markers than DRI predicts or leaves blocks over (the image's content is then unspecified); entropy data of 2^32 bits
+ * or more.  Where libjpeg's C code masks out-of-range IDCT results into its range-limit table the kernels saturate, as
+ * libjpeg-turbo's SIMD code does; on what an encoder writes the two agree.
+ * Measured at 256 host streams a call, upload included (profiles/r18_jpeg_decode.md): 22.5 k of the dataset's sheets a
+ * second, 476 A4 colour images/s at quality 100 and 933 at 95; Pillow (libjpeg-turbo) from 16 threads of the same machine
+ * decodes 1096, 105 and 122.  From files to files, omr_correct_default_batch_streams below corrects 1264 dataset sheets/s
+ * and 140 A4 sheets/s, 2.2 x and 2.3 x omr_correct_default_batch_jpeg with Pillow's decode of its inputs on 16 threads
+ * inside the timed region (585 and 62).
+ *
+ * What a stream's header says: its size, components (1 or 3) and Y's sampling factors as in SOF (0x11, 0x21, 0x22).
+ * Returns 0, OMR_ERR_NOTIMPL or OMR_ERR_BADARG by the rules above; the size is filled in whenever SOF was readable
+ * (else 0).  Any output pointer may be NULL.  Host only. */
+int omr_jpeg_info(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *components, int32_t *sampling);
+/* n streams in HOST memory -> device-resident images, image i at d_out + i * out_stride_bytes at the top left of a slot of
+ * rows x cols x channels with rows step_bytes apart; bytes of a slot outside its image are untouched.  out_size[2 i],
+ * [2 i + 1] = image i's rows, cols (HOST array, the layout omr_jpeg_encode_batch_device and the batch contexts take; 0 x 0
+ * where rc[i] != 0), rc[i] = 0 or the image's code by the rules above, OMR_ERR_BADARG also for an image larger than the
+ * slot (HOST array).  The call itself returns 0 whatever the rc[i].  OMR_ERR_BADARG for the call: n < 0, a null pointer
+ * (a null streams[i] included), channels other than 1 or 3, an empty slot, step_bytes < cols x channels,
+ * out_stride_bytes < rows x step_bytes.  Every argument and every header is checked before any device work; a call all
+ * of whose streams are refused does none.  Synchronous, on a stream of its own, which has drained on every return path. */
+int omr_jpeg_decode_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                 uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
+                                 int32_t *out_size, int32_t *rc);
+/* imread of one buffer: the stream -> a packed host image of `channels` channels (release with omr_image_free). */
+int omr_jpeg_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_image_owned *dst);
+/* Measurement aid.  Reports what the calling thread's last decode (any of the entry points that decode, on this thread)
+ * took, then switches the collection on (enable != 0) or off for the thread's next ones: *sub_bits = the subsequence
+ * length the library is built with, *groups = the groups of launches, *rounds = the most synchronisation rounds a group
+ * needed (round 0 included), stage_ms[0 .. 5] = device time summed over the groups of upload and clearing, un-stuffing,
+ * the synchronisation rounds (their host round trips included), the coefficient pass, the inverse DCT, up-sampling and
+ * colour.  All zero when the collection was off.  While on, every group records seven events; results do not change.
+ * Any output pointer may be NULL. */
+int omr_jpeg_decode_stats(int32_t enable, int32_t *sub_bits, int32_t *groups, int32_t *rounds, double *stage_ms);
+/* correct_default from file contents to file contents: omr_correct_default_batch_jpeg with the sheets given as baseline
+ * JPEG streams in host memory (what imread(IMREAD_COLOR) would be given).  The headers are parsed and the sheets bucketed
+ * by shape on the host; each bucket is decoded to BGR straight into the scan slots of the cached omr_correct_batch
+ * context, corrected and its canvases encoded on the device, so only streams cross the link in either direction.
+ * Outputs as omr_correct_default_batch_jpeg, and identical to what that function returns for imread's decode of the same
+ * streams.  A sheet the decoder refuses or whose header is malformed (the rules of omr_jpeg_decode_batch_device) gets
+ * that code in scan_rc[i], angle 0 and no output, before any device work; one whose entropy data is damaged gets
+ * OMR_ERR_ASSERT there; the other sheets are unaffected.  OMR_ERR_BADARG for the call: a null pointer (a null streams[i]
+ * included), n < 1, a negative length. */
+int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                      uint16_t projection_max_angle, double projection_angle_step,
+                                      int32_t projection_max_width, int32_t projection_max_height,
+                                      double hough_min_line_length, double hough_max_line_gap, int32_t quality,
+                                      double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg,
+                                      int64_t *jpeg_len);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

@@ -30,6 +30,7 @@
 #include "hough_host.hpp"
 #include "host_threads.hpp"
 #include "jpeg.hpp"
+#include "jpeg_dec.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -336,6 +337,10 @@ struct HostArgs {
     uint8_t **jpeg = nullptr;
     int64_t *jpeg_len = nullptr;
     int32_t quality = 0;
+    // the streams form (omr_correct_default_batch_streams): srcs carries the shapes only, the sheets are decoded on the device
+    const uint8_t *const *streams = nullptr;
+    const int64_t *stream_len = nullptr;
+    const JdecHeader *hdr = nullptr;
 };
 
 // The streams of a chunk's canvases -> fresh host buffers: a device buffer of exactly the streams' size per group of the
@@ -434,16 +439,34 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     if (want_canvas) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
     std::vector<double> ang((size_t)zmax);
     std::vector<int32_t> chk((size_t)zmax), src((size_t)zmax), size(2 * (size_t)zmax);
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    std::vector<JdecHeader> zhdr;
+    std::vector<int32_t> zskip, zrc;
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
         double t1 = now_ms();
-        // host memory -> device, from several threads
-        if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
+        if (a.streams) {  // the chunk's streams -> BGR in the scan slots, decoded on the device
+            zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z);
+            zskip.assign((size_t)z, 0), zrc.assign((size_t)z, 0);
+            for (int j = 0; j < z; j++) {
+                const int i = idx[(size_t)(j0 + j)];
+                zs[(size_t)j] = a.streams[i], zlen[(size_t)j] = a.stream_len[i], zhdr[(size_t)j] = a.hdr[i];
+            }
+            if ((rc = jpeg_decode_device(zs.data(), zlen.data(), zhdr.data(), zskip.data(), z, cn, din.as<uint8_t>(), in_stride, row,
+                                         zrc.data(), st.s)))
+                return rc;
+        } else if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) {  // host memory -> device
+            return rc;
+        }
         double t2 = now_ms();
         t_up += t2 - t1;
         if ((rc = omr_correct_batch_run_device(cb, din.as<uint8_t>(), in_stride, row, z, ang.data(), chk.data(), src.data(),
                                                want_canvas ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data())))
             return rc;
+        if (a.streams)  // a sheet whose entropy data was damaged: its slot's content means nothing, its code and no output
+            for (int j = 0; j < z; j++)
+                if (zrc[(size_t)j]) src[(size_t)j] = zrc[(size_t)j], ang[(size_t)j] = 0.0, chk[(size_t)j] = 0;
         for (int j = 0; j < z; j++) {
             const int i = idx[(size_t)(j0 + j)];
             a.angle[i] = ang[(size_t)j];
@@ -472,12 +495,15 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     return OMR_OK;
 }
 
-// omr_correct_default_batch and its JPEG form: buckets, contexts and results are the same; `rotated` (may be null) receives
-// the canvases, or `jpeg` / `jpeg_len` (null for the plain form) their streams
+// omr_correct_default_batch, its JPEG form and its streams form: buckets, contexts and results are the same; `rotated`
+// (may be null) receives the canvases, or `jpeg` / `jpeg_len` (null for the plain form) their streams.  The streams form
+// gives streams / stream_len / hdr per sheet and srcs[i] with that sheet's shape (its data is not read).
 int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
                          int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
                          double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
-                         omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, int32_t quality)
+                         omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, int32_t quality,
+                         const uint8_t *const *streams = nullptr, const int64_t *stream_len = nullptr,
+                         const JdecHeader *hdr = nullptr)
 {
     if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     ShapeBuckets b;
@@ -500,6 +526,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
     HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
     a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.quality = quality;
+    a.streams = streams, a.stream_len = stream_len, a.hdr = hdr;
     for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
         rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
     if (rc && rotated)
@@ -651,6 +678,55 @@ int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t pr
     return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                                 hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, jpeg,
                                 jpeg_len, quality);
+}
+
+int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
+                                      double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
+                                      double hough_min_line_length, double hough_max_line_gap, int32_t quality,
+                                      double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg,
+                                      int64_t *jpeg_len)
+{
+    clear_error();
+    if (!streams || !len || n < 1 || !rotate_angle || !need_check || !scan_rc || !jpeg || !jpeg_len)
+        return fail(OMR_ERR_BADARG, "bad batch arguments");
+    for (int i = 0; i < n; i++)
+        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
+    // the headers, on the host: a sheet the decoder refuses keeps its code and leaves the batch here
+    std::vector<JdecHeader> hdr;
+    std::vector<int> at;
+    std::vector<omr_image> views;
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    hdr.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        rotate_angle[i] = 0.0, need_check[i] = 0, jpeg[i] = nullptr, jpeg_len[i] = 0;
+        hdr.emplace_back();
+        JdecHeader &h = hdr.back();
+        if ((scan_rc[i] = jdec_parse(streams[i], len[i], &h)) != OMR_OK) {
+            hdr.pop_back();
+            continue;
+        }
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]);
+        views.push_back(omr_image{streams[i], h.rows, h.cols, 3, (int64_t)h.cols * 3});
+    }
+    clear_error();
+    const int g = (int)at.size();
+    if (g == 0) return OMR_OK;  // every sheet refused: the codes are in scan_rc, there is no device work
+    std::vector<double> ang((size_t)g);
+    std::vector<int32_t> chk((size_t)g), src((size_t)g);
+    std::vector<uint8_t *> out((size_t)g);
+    std::vector<int64_t> out_len((size_t)g);
+    const int rc = correct_default_host(views.data(), g, projection_max_angle, projection_angle_step, projection_max_width,
+                                        projection_max_height, hough_min_line_length, hough_max_line_gap, ang.data(), chk.data(),
+                                        src.data(), nullptr, out.data(), out_len.data(), quality, zs.data(), zlen.data(),
+                                        hdr.data());
+    if (rc) return rc;
+    for (int k = 0; k < g; k++) {
+        const int i = at[(size_t)k];
+        rotate_angle[i] = ang[(size_t)k], need_check[i] = chk[(size_t)k], scan_rc[i] = src[(size_t)k];
+        jpeg[i] = out[(size_t)k], jpeg_len[i] = out_len[(size_t)k];
+    }
+    return OMR_OK;
 }
 
 }  // extern "C"

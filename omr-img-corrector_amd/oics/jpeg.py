@@ -1,10 +1,12 @@
-"""Baseline JPEG encoding on the device (omr_jpeg_*): byte for byte what imwrite(.., JPEG, quality) writes."""
+"""Baseline JPEG on the device (omr_jpeg_*): encoding byte for byte what imwrite(.., JPEG, quality) writes, decoding
+byte for byte what imread returns."""
 import ctypes as C
 
 import numpy as np
 
 from ._lib import check, i32p, lib, u8p
-from .transfer import _mat, as_image
+from ._lib import OmrImageOwned
+from .transfer import _mat, _take_owned, as_image
 
 
 def quant_tables(quality):
@@ -50,3 +52,52 @@ def encode(mat, quality=100):
         rc = L.omr_jpeg_encode(C.byref(im), int(quality), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
     check(rc)
     return buf[: n.value].tobytes()
+
+
+def _buf(stream):
+    return np.frombuffer(bytes(stream), np.uint8)
+
+
+def info(stream):
+    """omr_jpeg_info -> (rows, cols, components, sampling): what the header says (sampling: Y's factors as in SOF, 0x11,
+    0x21 or 0x22).  Raises OmrError for a stream the decoder refuses (-213) or a malformed header (-5)."""
+    b = _buf(stream)
+    r, c, n, sm = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().omr_jpeg_info(b.ctypes.data, b.size, C.byref(r), C.byref(c), C.byref(n), C.byref(sm)))
+    return r.value, c.value, n.value, sm.value
+
+
+def decode(stream, channels=3):
+    """omr_jpeg_decode: imread of one buffer -> (rows, cols) for channels = 1, (rows, cols, 3) BGR for channels = 3."""
+    b = _buf(stream)
+    out = OmrImageOwned()
+    check(lib().omr_jpeg_decode(b.ctypes.data, b.size, int(channels), C.byref(out)))
+    return _take_owned(out)
+
+
+def decode_batch(streams, channels, d_out, out_stride_bytes, step_bytes, rows, cols):
+    """omr_jpeg_decode_batch_device: host streams -> device-resident images, image i at the top left of the slot at
+    d_out + i * out_stride_bytes (d_out: a device address).  Returns (out_size int32 [n, 2], rc int32 [n]): the images'
+    (rows, cols), 0 x 0 where rc[i] != 0.  Synchronous."""
+    bufs = [_buf(s) for s in streams]
+    n = len(bufs)
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    lens = np.array([b.size for b in bufs], np.int64)
+    out_size, rc = np.zeros((max(n, 1), 2), np.int32), np.zeros(max(n, 1), np.int32)
+    check(lib().omr_jpeg_decode_batch_device(ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), d_out,
+                                             int(out_stride_bytes), int(step_bytes), int(rows), int(cols),
+                                             out_size.ctypes.data_as(i32p), rc.ctypes.data_as(i32p)))
+    return out_size[:n], rc[:n]
+
+
+STAGES = ("upload and clearing", "un-stuffing", "synchronisation rounds", "coefficients", "inverse DCT", "colour")
+
+
+def decode_stats(enable=True):
+    """omr_jpeg_decode_stats (measurement aid): what this thread's last decode took -> (sub_bits, groups, rounds,
+    [ms per stage of STAGES]); then switches the collection on or off for the thread's next decodes."""
+    bits, groups, rounds = C.c_int32(), C.c_int32(), C.c_int32()
+    ms = np.zeros(len(STAGES), np.float64)
+    check(lib().omr_jpeg_decode_stats(int(bool(enable)), C.byref(bits), C.byref(groups), C.byref(rounds),
+                                      ms.ctypes.data_as(C.POINTER(C.c_double))))
+    return bits.value, groups.value, rounds.value, [float(v) for v in ms]

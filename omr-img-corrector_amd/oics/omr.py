@@ -241,6 +241,39 @@ def correct_default_batch_jpeg(src_mats, projection_max_angle, projection_angle_
     return out
 
 
+def correct_default_batch_streams(streams, projection_max_angle, projection_angle_step, projection_max_width,
+                                  projection_max_height, hough_min_line_length, hough_max_line_gap, quality=100):
+    """omr_correct_default_batch_streams: correct_default from file contents to file contents.  streams: baseline JPEG
+    streams (bytes or uint8 arrays), decoded to BGR, corrected and encoded on the device -> [(rotate_angle, need_check,
+    JPEG bytes or None, scan_rc)] in input order; scan_rc is the decoder's code for a sheet it refused."""
+    from ._lib import u8p
+    bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
+            for s in streams]
+    bufs = [b if b.size else np.zeros(1, np.uint8) for b in bufs]
+    n = len(bufs)
+    sp = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    sl = np.array([len(s) for s in streams] + [0], np.int64)
+    ang = np.zeros(max(n, 1), np.float64)
+    chk = np.zeros(max(n, 1), np.int32)
+    rc = np.zeros(max(n, 1), np.int32)
+    ptrs = (u8p * max(n, 1))()
+    lens = np.zeros(max(n, 1), np.int64)
+    check(lib().omr_correct_default_batch_streams(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(projection_max_angle),
+                                                  float(projection_angle_step), int(projection_max_width),
+                                                  int(projection_max_height), float(hough_min_line_length),
+                                                  float(hough_max_line_gap), int(quality), ang.ctypes.data_as(f64p),
+                                                  chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), ptrs,
+                                                  lens.ctypes.data_as(C.POINTER(C.c_int64))))
+    out = []
+    for i in range(n):
+        data = None
+        if ptrs[i]:
+            data = C.string_at(ptrs[i], int(lens[i]))
+            lib().omr_bytes_free(ptrs[i])
+        out.append((float(ang[i]), bool(chk[i]), data, int(rc[i])))
+    return out
+
+
 def get_result_from_fourier_transform(src_mat, canny_threshold_weak, canny_threshold_strong, fourier_min_line_length,
                                       fourier_max_line_gap):
     """omr.rs:304-337"""

@@ -47,6 +47,12 @@ class TransformableMatrix:
     def from_matrix(cls, mat):
         return cls(np.array(mat, dtype=np.uint8, copy=True))  # transfer.rs:55-59 deep clone
 
+    @classmethod
+    def from_jpeg_bytes(cls, stream, channels=3):
+        """What im_read gives for a file with these bytes (transfer.rs:147-167), decoded on the GPU (omr_jpeg_decode)."""
+        from . import jpeg
+        return cls(jpeg.decode(stream, channels))
+
     def encode_jpeg(self, quality=100):
         """The bytes im_write(.., JPEG, quality) puts into its file (transfer.rs:169-186), encoded on the GPU
         (omr_jpeg_encode): gray or BGR."""

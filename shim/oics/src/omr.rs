@@ -188,3 +188,62 @@ pub fn correct_defaults(
     result?;
     Ok((0..n).map(|i| (angle[i], need_check[i] != 0)).collect())
 }
+
+/// `correct_default` for many files at once with nothing but file contents crossing to the GPU and back
+/// (omr_correct_default_batch_streams): `std::fs::read` per input, one batch call that decodes the baseline JPEG streams,
+/// corrects the sheets and encodes every rotated canvas as JPEG (quality 100) on the GPU, then `std::fs::write` per output.
+/// Returns (rotation angle, need_check) per file.  A sheet the decoder refuses (progressive, CMYK, an EXIF orientation, ..:
+/// OMR_ERR_NOTIMPL) or cannot decode fails the call with that sheet's code and names it, and no output file is written:
+/// the caller sends such files through `correct_defaults`, whose imread takes them.  Not in the reference crate.
+pub fn correct_default_files(
+    inputs: &[&str],
+    outputs: &[&str],
+    projection_max_angle: u16,
+    projection_angle_step: f64,
+    projection_max_width: i32,
+    projection_max_height: i32,
+    hough_min_line_length: f64,
+    hough_max_line_gap: f64,
+) -> opencv::Result<Vec<(f64, bool)>> {
+    if inputs.len() != outputs.len() || inputs.is_empty() {
+        return Err(opencv::Error::new(ffi::OMR_ERR_BADARG, String::from("inputs and outputs must pair up")));
+    }
+    let n = inputs.len();
+    let mut files: Vec<Vec<u8>> = Vec::with_capacity(n);
+    for (i, path) in inputs.iter().enumerate() {
+        files.push(std::fs::read(path).map_err(|e| opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (input {}): {}", path, i, e)))?);
+    }
+    let mut ptrs: Vec<*const u8> = files.iter().map(|f| f.as_ptr()).collect();
+    let lens: Vec<i64> = files.iter().map(|f| f.len() as i64).collect();
+    let mut angle = vec![0.0f64; n];
+    let (mut need_check, mut scan_rc) = (vec![0i32; n], vec![0i32; n]);
+    let mut jpeg: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+    let mut jpeg_len = vec![0i64; n];
+    check(unsafe {
+        ffi::omr_correct_default_batch_streams(ptrs.as_mut_ptr(), lens.as_ptr(), n as i32, projection_max_angle,
+                                               projection_angle_step, projection_max_width, projection_max_height,
+                                               hough_min_line_length, hough_max_line_gap, 100, angle.as_mut_ptr(),
+                                               need_check.as_mut_ptr(), scan_rc.as_mut_ptr(), jpeg.as_mut_ptr(),
+                                               jpeg_len.as_mut_ptr())
+    })?;
+    // all or nothing: no file is written unless every sheet was decoded and corrected
+    let failed = (0..n).find(|&i| scan_rc[i] != 0);
+    let mut result: opencv::Result<()> = match failed {
+        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("correct_default failed on {} (sheet {}); no output file was written", inputs[i], i))),
+        None => Ok(()),
+    };
+    for i in 0..n {
+        if jpeg[i].is_null() {
+            continue;
+        }
+        if result.is_ok() {
+            let bytes = unsafe { std::slice::from_raw_parts(jpeg[i], jpeg_len[i] as usize) };
+            if let Err(e) = std::fs::write(outputs[i], bytes) {
+                result = Err(opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (output {}; outputs before it are written): {}", outputs[i], i, e)));
+            }
+        }
+        unsafe { ffi::omr_bytes_free(jpeg[i]) };
+    }
+    result?;
+    Ok((0..n).map(|i| (angle[i], need_check[i] != 0)).collect())
+}

@@ -239,3 +239,13 @@ pub fn encode_jpeg(m: &TransformableMatrix, quality: i32) -> Result<Vec<u8>, ope
     out.truncate(len as usize);
     Ok(out)
 }
+
+/// What `im_read` gives for a file with these bytes (`imread(.., IMREAD_COLOR)` for `channels` = 3, `IMREAD_GRAYSCALE`
+/// for 1), decoded on the GPU (omr_jpeg_decode): libjpeg's output with its defaults, byte for byte.  Baseline streams;
+/// one the decoder refuses (progressive, CMYK, an EXIF orientation, ..) is an error with code OMR_ERR_NOTIMPL, so that
+/// the caller can hand the file to its host codec.  Not in the reference crate.
+pub fn decode_jpeg(stream: &[u8], channels: i32) -> Result<TransformableMatrix, opencv::Error> {
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_jpeg_decode(stream.as_ptr(), stream.len() as i64, channels, &mut out) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
+}
