@@ -983,12 +983,14 @@ int omr_jpeg_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_im
  * Any output pointer may be NULL. */
 int omr_jpeg_decode_stats(int32_t enable, int32_t *sub_bits, int32_t *groups, int32_t *rounds, double *stage_ms);
 /* correct_default from file contents to file contents: omr_correct_default_batch_jpeg with the sheets given as baseline
- * JPEG streams in host memory (what imread(IMREAD_COLOR) would be given).  The headers are parsed and the sheets bucketed
- * by shape on the host; each bucket is decoded to BGR straight into the scan slots of the cached omr_correct_batch
- * context, corrected and its canvases encoded on the device, so only streams cross the link in either direction.
- * Outputs as omr_correct_default_batch_jpeg, and identical to what that function returns for imread's decode of the same
- * streams.  A sheet the decoder refuses or whose header is malformed (the rules of omr_jpeg_decode_batch_device) gets
- * that code in scan_rc[i], angle 0 and no output, before any device work; one whose entropy data is damaged gets
+ * JPEG or PNG streams in host memory (what imread(IMREAD_COLOR) would be given).  A stream that begins with PNG's eight
+ * signature bytes (89 50 4E 47 0D 0A 1A 0A) goes by the rules of omr_png_decode_batch_device below, every other one by
+ * those of omr_jpeg_decode_batch_device; one batch, and one bucket, may hold both kinds.  The headers are parsed and the
+ * sheets bucketed by shape on the host; each bucket is decoded to BGR straight into the scan slots of the cached
+ * omr_correct_batch context, corrected and its canvases encoded on the device, so only streams cross the link in either
+ * direction.  Outputs (JPEG streams, whatever the input was) as omr_correct_default_batch_jpeg, and identical to what that
+ * function returns for imread's decode of the same streams.  A sheet its decoder refuses or whose header is malformed gets
+ * that code in scan_rc[i], angle 0 and no output, before any device work; one whose image data is damaged gets
  * OMR_ERR_ASSERT there; the other sheets are unaffected.  OMR_ERR_BADARG for the call: a null pointer (a null streams[i]
  * included), n < 1, a negative length. */
 int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -997,6 +999,55 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
                                       double hough_min_line_length, double hough_max_line_gap, int32_t quality,
                                       double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg,
                                       int64_t *jpeg_len);
+
+/* ---- PNG decoding on the device ---------------------------------------------------------------
+ * What imread returns, byte for byte: libpng's rows after the transforms OpenCV 4.6 sets up -- palette -> RGB, gray of
+ * 1 / 2 / 4 bits -> 8 bits, alpha dropped (no blending, no gamma), RGB -> BGR in memory, gray replicated for 3 channels.
+ * Streams taken: non-interlaced; colour types 0, 2, 3, 4, 6 at bit depth 8, colour types 0 and 3 also at 1, 2 and 4;
+ * any IDAT split, any deflate block kinds, any window size, every filter type; ancillary chunks are skipped without a
+ * CRC check (tRNS, gAMA, iCCP, sRGB included).  channels = 3 from any of them, channels = 1 from colour types 0 and 4.
+ * OMR_ERR_NOTIMPL, never a wrong picture: Adam7 interlace, 16-bit samples, channels = 1 from a colour or paletted stream
+ * (libpng's rgb_to_gray arithmetic is not cvtColor's), an eXIf chunk with an orientation other than 1 (imread would turn
+ * the image), an acTL chunk before the first IDAT (APNG).
+ * OMR_ERR_BADARG, malformed structure: no signature, a chunk running past the end, IHDR missing, not first, with a size
+ * of 0 or an illegal depth / type pair, an unknown critical chunk, no IDAT, IDAT chunks that are not consecutive, a
+ * paletted image without PLTE, a PLTE whose length is no multiple of 3 (or that stands behind IDAT), a bad zlib header
+ * (CM = 8, window <= 32 K, no FDICT, FCHECK).
+ * OMR_ERR_ASSERT, damaged data (the image's content is then unspecified): a critical chunk's CRC, a missing IEND, an
+ * invalid deflate code or code set, a distance before the start, input running out, a wrong Adler-32, inflated data
+ * shorter or longer than the image needs, a filter byte above 4, a palette index beyond PLTE; a size above imread's own
+ * limits (2^20 rows or columns, 2^30 pixels: imread fails there too), raw data of 2^32 bytes or IDAT data of 2^28 bytes
+ * or more.  This refuses a little more than libpng, which warns and carries on for surplus data
+ * or a wrong checksum; a refused file goes to the host codec.
+ * Measured at 256 host streams a call, upload included (profiles/r19_png_decode.md): 940 dataset sheets a second from
+ * 8-bit gray PNG, 608 from RGB PNG and 2568 A4 1-bit sheets, where Pillow from 16 threads of the same machine decodes 687,
+ * 550 and 144.  NOT faster on long streams: 10 noise-like A4 colour cards (15 MB each) a second against Pillow's 50; one
+ * wave inflates one stream, and the stage times blame inflate.  Nor from files to files: on PNG inputs
+ * omr_correct_default_batch_streams corrects 292 gray dataset sheets/s where Pillow's decode on 16 threads in front of
+ * omr_correct_default_batch_jpeg gives 427; it saves the raw upload and the host's cores.
+ *
+ * What a stream's IHDR says.  Returns 0, OMR_ERR_NOTIMPL, OMR_ERR_BADARG or OMR_ERR_ASSERT by the rules above, as far as
+ * the chunk headers decide them (no CRC is computed); the fields are filled in whenever IHDR was readable (else 0).  Any
+ * output pointer may be NULL.  Host only. */
+int omr_png_info(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *color_type, int32_t *bit_depth);
+/* n streams in HOST memory -> device-resident images, image i at d_out + i * out_stride_bytes at the top left of a slot of
+ * rows x cols x channels with rows step_bytes apart; bytes of a slot outside its image are untouched.  out_size[2 i],
+ * [2 i + 1] = image i's rows, cols (HOST array, the layout omr_jpeg_encode_batch_device and the batch contexts take; 0 x 0
+ * where rc[i] != 0), rc[i] = 0 or the image's code by the rules above, OMR_ERR_BADARG also for an image larger than the
+ * slot (HOST array).  The call itself returns 0 whatever the rc[i].  OMR_ERR_BADARG for the call: n < 0, a null pointer
+ * (a null streams[i] included), channels other than 1 or 3, an empty slot, step_bytes < cols x channels,
+ * out_stride_bytes < rows x step_bytes.  Every argument and every header is checked before any device work; a call all
+ * of whose streams are refused does none.  Synchronous, on a stream of its own, which has drained on every return path. */
+int omr_png_decode_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
+                                int32_t *out_size, int32_t *rc);
+/* imread of one buffer: the stream -> a packed host image of `channels` channels (release with omr_image_free). */
+int omr_png_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_image_owned *dst);
+/* Measurement aid.  Reports what the calling thread's last PNG decode took, then switches the collection on (enable != 0)
+ * or off for the thread's next ones: *groups = the groups of launches, stage_ms[0 .. 3] = device time summed over the
+ * groups of the upload, inflate, Adler-32, unfilter and convert.  All zero when the collection was off.  While on, every
+ * group records five events; results do not change.  Any output pointer may be NULL. */
+int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

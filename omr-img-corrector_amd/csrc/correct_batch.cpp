@@ -31,6 +31,7 @@
 #include "host_threads.hpp"
 #include "jpeg.hpp"
 #include "jpeg_dec.hpp"
+#include "png_dec.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -341,6 +342,8 @@ struct HostArgs {
     const uint8_t *const *streams = nullptr;
     const int64_t *stream_len = nullptr;
     const JdecHeader *hdr = nullptr;
+    const PdecHeader *png_hdr = nullptr;  // sheet i is a PNG stream where is_png[i] != 0: png_hdr[i] holds, hdr[i] does not
+    const uint8_t *is_png = nullptr;
 };
 
 // The streams of a chunk's canvases -> fresh host buffers: a device buffer of exactly the streams' size per group of the
@@ -442,19 +445,27 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
     std::vector<const uint8_t *> zs;
     std::vector<int64_t> zlen;
     std::vector<JdecHeader> zhdr;
-    std::vector<int32_t> zskip, zrc;
+    std::vector<PdecHeader> zpng;
+    std::vector<int32_t> zskip, zskip_png, zrc;
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
         double t1 = now_ms();
         if (a.streams) {  // the chunk's streams -> BGR in the scan slots, decoded on the device
-            zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z);
-            zskip.assign((size_t)z, 0), zrc.assign((size_t)z, 0);
+            // a bucket may hold both kinds: each decoder fills its own members' slots and skips the other's
+            zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z);
+            zskip.assign((size_t)z, 0), zskip_png.assign((size_t)z, 0), zrc.assign((size_t)z, 0);
+            int pngs = 0;
             for (int j = 0; j < z; j++) {
                 const int i = idx[(size_t)(j0 + j)];
-                zs[(size_t)j] = a.streams[i], zlen[(size_t)j] = a.stream_len[i], zhdr[(size_t)j] = a.hdr[i];
+                zs[(size_t)j] = a.streams[i], zlen[(size_t)j] = a.stream_len[i];
+                if (a.is_png[i]) zpng[(size_t)j] = a.png_hdr[i], zskip[(size_t)j] = 1, pngs++;
+                else zhdr[(size_t)j] = a.hdr[i], zskip_png[(size_t)j] = 1;
             }
-            if ((rc = jpeg_decode_device(zs.data(), zlen.data(), zhdr.data(), zskip.data(), z, cn, din.as<uint8_t>(), in_stride, row,
-                                         zrc.data(), st.s)))
+            if (pngs < z && (rc = jpeg_decode_device(zs.data(), zlen.data(), zhdr.data(), zskip.data(), z, cn, din.as<uint8_t>(),
+                                                     in_stride, row, zrc.data(), st.s)))
+                return rc;
+            if (pngs && (rc = png_decode_device(zs.data(), zlen.data(), zpng.data(), zskip_png.data(), z, cn, din.as<uint8_t>(),
+                                                in_stride, row, zrc.data(), st.s)))
                 return rc;
         } else if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) {  // host memory -> device
             return rc;
@@ -464,7 +475,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         if ((rc = omr_correct_batch_run_device(cb, din.as<uint8_t>(), in_stride, row, z, ang.data(), chk.data(), src.data(),
                                                want_canvas ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data())))
             return rc;
-        if (a.streams)  // a sheet whose entropy data was damaged: its slot's content means nothing, its code and no output
+        if (a.streams)  // a sheet whose image data was damaged: its slot's content means nothing, its code and no output
             for (int j = 0; j < z; j++)
                 if (zrc[(size_t)j]) src[(size_t)j] = zrc[(size_t)j], ang[(size_t)j] = 0.0, chk[(size_t)j] = 0;
         for (int j = 0; j < z; j++) {
@@ -503,7 +514,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
                          double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
                          omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, int32_t quality,
                          const uint8_t *const *streams = nullptr, const int64_t *stream_len = nullptr,
-                         const JdecHeader *hdr = nullptr)
+                         const JdecHeader *hdr = nullptr, const PdecHeader *png_hdr = nullptr, const uint8_t *is_png = nullptr)
 {
     if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     ShapeBuckets b;
@@ -526,7 +537,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
     HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
     a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.quality = quality;
-    a.streams = streams, a.stream_len = stream_len, a.hdr = hdr;
+    a.streams = streams, a.stream_len = stream_len, a.hdr = hdr, a.png_hdr = png_hdr, a.is_png = is_png;
     for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
         rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
     if (rc && rotated)
@@ -693,6 +704,8 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
         if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
     // the headers, on the host: a sheet the decoder refuses keeps its code and leaves the batch here
     std::vector<JdecHeader> hdr;
+    std::vector<PdecHeader> png_hdr;
+    std::vector<uint8_t> is_png;
     std::vector<int> at;
     std::vector<omr_image> views;
     std::vector<const uint8_t *> zs;
@@ -700,14 +713,16 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
     hdr.reserve((size_t)n);
     for (int i = 0; i < n; i++) {
         rotate_angle[i] = 0.0, need_check[i] = 0, jpeg[i] = nullptr, jpeg_len[i] = 0;
-        hdr.emplace_back();
-        JdecHeader &h = hdr.back();
-        if ((scan_rc[i] = jdec_parse(streams[i], len[i], &h)) != OMR_OK) {
-            hdr.pop_back();
+        hdr.emplace_back(), png_hdr.emplace_back();
+        const bool png = pdec_is_png(streams[i], len[i]);
+        scan_rc[i] = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back());
+        if (scan_rc[i] != OMR_OK) {
+            hdr.pop_back(), png_hdr.pop_back();
             continue;
         }
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]);
-        views.push_back(omr_image{streams[i], h.rows, h.cols, 3, (int64_t)h.cols * 3});
+        const int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), is_png.push_back(png);
+        views.push_back(omr_image{streams[i], rows, cols, 3, (int64_t)cols * 3});
     }
     clear_error();
     const int g = (int)at.size();
@@ -719,7 +734,7 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
     const int rc = correct_default_host(views.data(), g, projection_max_angle, projection_angle_step, projection_max_width,
                                         projection_max_height, hough_min_line_length, hough_max_line_gap, ang.data(), chk.data(),
                                         src.data(), nullptr, out.data(), out_len.data(), quality, zs.data(), zlen.data(),
-                                        hdr.data());
+                                        hdr.data(), png_hdr.data(), is_png.data());
     if (rc) return rc;
     for (int k = 0; k < g; k++) {
         const int i = at[(size_t)k];

@@ -10,6 +10,7 @@
 #include "../../include/omrdeskew.h"
 #include "engine.hpp"
 #include "jpeg_dec.hpp"
+#include "png_dec.hpp"
 
 using namespace omr;
 
@@ -44,26 +45,7 @@ void derive(const Dht &h, JdecHuff *t)
 int exif_orientation(const uint8_t *b, int64_t n)
 {
     if (n < 14 || memcmp(b, "Exif\0\0", 6)) return 1;
-    const uint8_t *t = b + 6;
-    n -= 6;
-    bool le;
-    if (!memcmp(t, "II*\0", 4)) le = true;
-    else if (!memcmp(t, "MM\0*", 4)) le = false;
-    else return 1;
-    auto u16 = [&](int64_t o) { return le ? t[o] | t[o + 1] << 8 : t[o] << 8 | t[o + 1]; };
-    auto u32 = [&](int64_t o) {
-        return le ? (int64_t)t[o] | (int64_t)t[o + 1] << 8 | (int64_t)t[o + 2] << 16 | (int64_t)t[o + 3] << 24
-                  : (int64_t)t[o] << 24 | (int64_t)t[o + 1] << 16 | (int64_t)t[o + 2] << 8 | (int64_t)t[o + 3];
-    };
-    const int64_t ifd = u32(4);
-    if (ifd + 2 > n) return 1;
-    const int cnt = u16(ifd);
-    for (int e = 0; e < cnt; e++) {
-        const int64_t o = ifd + 2 + 12 * (int64_t)e;
-        if (o + 12 > n) break;
-        if (u16(o) == 0x0112) return u16(o + 8);
-    }
-    return 1;
+    return exif_orientation_tiff(b + 6, n - 6);
 }
 
 int check_channels(int channels)
@@ -358,6 +340,29 @@ int omr::jdec_parse(const uint8_t *s, int64_t len, JdecHeader *h)
     if ((len - p) * 8 > (int64_t)0xffffffffLL - 65536)
         return fail(OMR_ERR_ASSERT, "entropy data of %lld bytes exceeds 2^32 bits: not supported", (long long)(len - p));
     return OMR_OK;
+}
+
+int omr::exif_orientation_tiff(const uint8_t *t, int64_t n)
+{
+    if (n < 8) return 1;
+    bool le;
+    if (!memcmp(t, "II*\0", 4)) le = true;
+    else if (!memcmp(t, "MM\0*", 4)) le = false;
+    else return 1;
+    auto u16 = [&](int64_t o) { return le ? t[o] | t[o + 1] << 8 : t[o] << 8 | t[o + 1]; };
+    auto u32 = [&](int64_t o) {
+        return le ? (int64_t)t[o] | (int64_t)t[o + 1] << 8 | (int64_t)t[o + 2] << 16 | (int64_t)t[o + 3] << 24
+                  : (int64_t)t[o] << 24 | (int64_t)t[o + 1] << 16 | (int64_t)t[o + 2] << 8 | (int64_t)t[o + 3];
+    };
+    const int64_t ifd = u32(4);
+    if (ifd + 2 > n) return 1;
+    const int cnt = u16(ifd);
+    for (int e = 0; e < cnt; e++) {
+        const int64_t o = ifd + 2 + 12 * (int64_t)e;
+        if (o + 12 > n) break;
+        if (u16(o) == 0x0112) return u16(o + 8);
+    }
+    return 1;
 }
 
 JdecStats &omr::jdec_stats()

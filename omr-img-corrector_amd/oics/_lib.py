@@ -233,6 +233,11 @@ SYMBOLS = {
                                                C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
     "omr_jpeg_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_jpeg_decode_stats": (C.c_int, [C.c_int32, i32p, i32p, i32p, f64p]),
+    "omr_png_info": (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, i32p, i32p]),
+    "omr_png_decode_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
+    "omr_png_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OmrImageOwned)]),
+    "omr_png_decode_stats": (C.c_int, [C.c_int32, i32p, f64p]),
     "omr_correct_default_batch_streams": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_uint16,
                                                     C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                                     f64p, i32p, i32p, C.POINTER(u8p), C.POINTER(C.c_int64)]),

@@ -190,9 +190,10 @@ pub fn correct_defaults(
 }
 
 /// `correct_default` for many files at once with nothing but file contents crossing to the GPU and back
-/// (omr_correct_default_batch_streams): `std::fs::read` per input, one batch call that decodes the baseline JPEG streams,
-/// corrects the sheets and encodes every rotated canvas as JPEG (quality 100) on the GPU, then `std::fs::write` per output.
-/// Returns (rotation angle, need_check) per file.  A sheet the decoder refuses (progressive, CMYK, an EXIF orientation, ..:
+/// (omr_correct_default_batch_streams): `std::fs::read` per input, one batch call that decodes the streams (baseline JPEG
+/// or PNG, told apart by PNG's signature; one batch may hold both), corrects the sheets and encodes every rotated canvas
+/// as JPEG (quality 100) on the GPU, then `std::fs::write` per output.  Returns (rotation angle, need_check) per file.  A
+/// sheet its decoder refuses (progressive or CMYK JPEG, interlaced or 16-bit PNG, an EXIF orientation, ..:
 /// OMR_ERR_NOTIMPL) or cannot decode fails the call with that sheet's code and names it, and no output file is written:
 /// the caller sends such files through `correct_defaults`, whose imread takes them.  Not in the reference crate.
 pub fn correct_default_files(
@@ -229,7 +230,7 @@ pub fn correct_default_files(
     // all or nothing: no file is written unless every sheet was decoded and corrected
     let failed = (0..n).find(|&i| scan_rc[i] != 0);
     let mut result: opencv::Result<()> = match failed {
-        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("correct_default failed on {} (sheet {}); no output file was written", inputs[i], i))),
+        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("correct_default failed on {} (sheet {}): the JPEG / PNG decoder or the correction answered {}; no output file was written", inputs[i], i, scan_rc[i]))),
         None => Ok(()),
     };
     for i in 0..n {

@@ -249,3 +249,14 @@ pub fn decode_jpeg(stream: &[u8], channels: i32) -> Result<TransformableMatrix, 
     check(unsafe { ffi::omr_jpeg_decode(stream.as_ptr(), stream.len() as i64, channels, &mut out) })?;
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
+
+/// What `im_read` gives for a PNG file with these bytes (`imread(.., IMREAD_COLOR)` for `channels` = 3,
+/// `IMREAD_GRAYSCALE` for 1), decoded on the GPU (omr_png_decode): libpng's rows after OpenCV's transforms, byte for byte.
+/// Non-interlaced streams of 8 bits or fewer; one the decoder refuses (Adam7, 16-bit, gray from a colour stream, an EXIF
+/// orientation, APNG) is an error with code OMR_ERR_NOTIMPL, so that the caller can hand the file to its host codec.  Not
+/// in the reference crate.
+pub fn decode_png(stream: &[u8], channels: i32) -> Result<TransformableMatrix, opencv::Error> {
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_png_decode(stream.as_ptr(), stream.len() as i64, channels, &mut out) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
+}
