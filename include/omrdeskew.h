@@ -1049,6 +1049,69 @@ int omr_png_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_ima
  * group records five events; results do not change.  Any output pointer may be NULL. */
 int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
 
+/* ---- PNG encoding on the device ---------------------------------------------------------------
+ * A lossless exit for device-resident images: a valid PNG stream that every conforming decoder turns back into the image
+ * byte for byte.  PNG has no canonical byte stream, so this is NOT what imwrite(.., PNG) writes byte for byte; it is
+ * deterministic: the stream of an image is a function of its pixels, its shape and `compression` alone -- not of its place
+ * in the batch, n, the other images, the base address, the pitch or the run.
+ * channels: 1 gives colour type 0; 3 (BGR in memory) colour type 2, RGB in the file; 4 (BGRA) colour type 6, RGBA with
+ * alpha kept, as imwrite does; 2: OMR_ERR_ASSERT.  Bit depth 8, not interlaced.
+ * The stream: the signature, IHDR, ONE IDAT chunk, IEND, every chunk with its CRC-32 (computed on the device), no
+ * ancillary chunks.  IDAT holds a zlib stream: the header 78 01 (deflate, 32 K window), deflate blocks, the Adler-32 of
+ * the filtered data.  Every row takes the filter with the smallest sum of absolute values (libpng's heuristic; ties: the
+ * lowest type).  The filtered data is cut into blocks of 16384 bytes; each is written as a dynamic, a fixed or a stored
+ * block, whichever is shortest (ties: stored, fixed, dynamic), and every block but the last is followed by an empty
+ * stored block, so blocks start on byte boundaries.
+ * compression is imwrite's IMWRITE_PNG_COMPRESSION, clamped to 0 .. 9: 0 writes stored blocks only; 1 .. 9 all select the
+ * one compressed method -- the levels are NOT told apart.  That method looks for matches at three distances only (1, the
+ * bytes of a pixel, the same byte one row up, where that is within 32768) and parses greedily in pieces of 512 bytes.
+ * **It compresses less than zlib does** where content repeats at other distances: measured (profiles/r20_png_encode.md)
+ * 0.101 of the raw size on colour dataset sheets where zlib level 6 with Paeth gives 0.067, and 0.007 on thresholded A4
+ * cards where imwrite's defaults give 0.005; on gray sheets and noisy cards it equals imwrite's defaults (0.121 / 0.122,
+ * 0.570 / 0.571).  At 256 device-resident canvases a call it writes 17.1 k gray and 5.7 k colour dataset sheets/s and 452
+ * A4 colour cards/s; Pillow at compress_level 1 on 16 threads of the same machine writes 1049, 109 and 10.
+ * Sizes above imread's own limits (2^20 rows or columns, 2^30 pixels) are refused with OMR_ERR_ASSERT, and so is a size
+ * whose IDAT chunk could exceed 2^31 - 1 bytes (2 + raw + 5 x blocks + 4, raw = rows x (1 + cols x channels)): offsets
+ * inside one image are 32 bits wide, offsets into the batch's buffers 64.
+ *
+ * An upper bound of the stream's length for a rows x cols x channels image of any content at any level:
+ * 43 + raw + 5 x ceil(raw / 16384) + 20 -- signature, IHDR, IDAT's frame and the zlib header; every block stored;
+ * Adler-32, IDAT's CRC and IEND.  OMR_ERR_ASSERT by the rules above.  Host only. */
+int omr_png_bound(int32_t rows, int32_t cols, int32_t channels, int64_t *bytes);
+/* n device-resident images -> n streams.  Slots, sizes (NULL allowed, 0 x 0 entries, an image at its slot's top left),
+ * d_out / out_stride_bytes (>= omr_png_bound of the slot) / out_len and the OMR_ERR_BADARG rules are exactly
+ * omr_jpeg_encode_batch_device's: nothing is written at or behind out_len[i], a 0 x 0 entry leaves its slot untouched.
+ * Every argument is checked before any device work.  Synchronous, on a stream of its own, which has drained on every
+ * return path. */
+int omr_png_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes, int64_t step_bytes, int32_t rows,
+                                int32_t cols, int32_t channels, const int32_t *sizes, int32_t n, int32_t compression,
+                                uint8_t *d_out, int64_t out_stride_bytes, int64_t *out_len);
+/* A host image -> its stream in `out` (cap bytes), *len = the stream's length.  cap too small (out may be NULL when cap
+ * is 0): OMR_ERR_NOMEM with *len = the length needed, nothing written. */
+int omr_png_encode(const omr_image *src, int32_t compression, uint8_t *out, int64_t cap, int64_t *len);
+/* Measurement aid, as omr_png_decode_stats.  Reports what the calling thread's last PNG encode took, then switches the
+ * collection on (enable != 0) or off for the thread's next ones: *groups = the groups of launches, stage_ms[0 .. 5] =
+ * device time summed over the groups of the filter, Adler-32, matches and parse, code sets and placement, the bit writer,
+ * and copy + CRC-32 + wrap (which includes the host's placing of the streams).  All zero when the collection was off.
+ * While on, every group records seven events; results do not change.  Any output pointer may be NULL. */
+int omr_png_encode_stats(int32_t enable, int32_t *groups, double *stage_ms);
+/* omr_correct_default_batch_jpeg with the PNG encoder behind the batch colour warp: png[i] (malloc'ed, release with
+ * omr_bytes_free) holds png_len[i] bytes that decode to sheet i's rotated canvas exactly, NULL / 0 where scan_rc[i] != 0.
+ * Buckets, context cache, rotate_angle, need_check and scan_rc are the JPEG form's.  A shape whose canvas slot
+ * (omr_correct_batch_canvas) omr_png_bound refuses refuses the call with OMR_ERR_ASSERT before any device work. */
+int omr_correct_default_batch_png(const omr_image *srcs, int32_t n, uint16_t projection_max_angle,
+                                  double projection_angle_step, int32_t projection_max_width,
+                                  int32_t projection_max_height, double hough_min_line_length,
+                                  double hough_max_line_gap, int32_t compression, double *rotate_angle, int32_t *need_check,
+                                  int32_t *scan_rc, uint8_t **png, int64_t *png_len);
+/* omr_correct_default_batch_streams (JPEG and PNG inputs, mixed) with PNG streams as its outputs. */
+int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                          uint16_t projection_max_angle, double projection_angle_step,
+                                          int32_t projection_max_width, int32_t projection_max_height,
+                                          double hough_min_line_length, double hough_max_line_gap, int32_t compression,
+                                          double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **png,
+                                          int64_t *png_len);
+
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);
 int omr_get_standard_deviation(const double *v, size_t n, double *out);

@@ -32,6 +32,7 @@
 #include "jpeg.hpp"
 #include "jpeg_dec.hpp"
 #include "png_dec.hpp"
+#include "png_enc.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -338,6 +339,7 @@ struct HostArgs {
     uint8_t **jpeg = nullptr;
     int64_t *jpeg_len = nullptr;
     int32_t quality = 0;
+    bool png_out = false;  // the PNG forms: the streams are PNG, `quality` is the compression level
     // the streams form (omr_correct_default_batch_streams): srcs carries the shapes only, the sheets are decoded on the device
     const uint8_t *const *streams = nullptr;
     const int64_t *stream_len = nullptr;
@@ -490,7 +492,9 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
             for (int j = 0; j < z; j++)
                 if (src[(size_t)j] != OMR_OK) size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
             StreamSink sink(a, idx, j0);
-            if ((rc = jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s))) return rc;
+            rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
+                           : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
+            if (rc) return rc;
             t_down += now_ms() - t3;
             continue;
         }
@@ -514,7 +518,8 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
                          double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
                          omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, int32_t quality,
                          const uint8_t *const *streams = nullptr, const int64_t *stream_len = nullptr,
-                         const JdecHeader *hdr = nullptr, const PdecHeader *png_hdr = nullptr, const uint8_t *is_png = nullptr)
+                         const JdecHeader *hdr = nullptr, const PdecHeader *png_hdr = nullptr, const uint8_t *is_png = nullptr,
+                         bool png_out = false)
 {
     if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     ShapeBuckets b;
@@ -528,7 +533,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
         for (const ImageShape &sh : b.shapes) {
             int R, C;
             canvas_of(sh.rows, sh.cols, &R, &C);
-            if ((rc = jpeg_check_scan_bits(R, C, sh.cn))) return rc;
+            if ((rc = png_out ? penc_check_shape(R, C, sh.cn) : jpeg_check_scan_bits(R, C, sh.cn))) return rc;
         }
     }
     if ((rc = have_device())) return rc;
@@ -536,7 +541,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
     OMR_HIP(hipGetDevice(&dev));
     HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
-    a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.quality = quality;
+    a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.quality = quality, a.png_out = png_out;
     a.streams = streams, a.stream_len = stream_len, a.hdr = hdr, a.png_hdr = png_hdr, a.is_png = is_png;
     for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
         rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
@@ -691,11 +696,27 @@ int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t pr
                                 jpeg_len, quality);
 }
 
-int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
-                                      double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
-                                      double hough_min_line_length, double hough_max_line_gap, int32_t quality,
-                                      double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg,
-                                      int64_t *jpeg_len)
+int omr_correct_default_batch_png(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
+                                  int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
+                                  double hough_max_line_gap, int32_t compression, double *rotate_angle, int32_t *need_check,
+                                  int32_t *scan_rc, uint8_t **png, int64_t *png_len)
+{
+    clear_error();
+    if (!png || !png_len) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, png,
+                                png_len, compression, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+// omr_correct_default_batch_streams and its PNG form: `jpeg` receives the streams of either kind
+int correct_default_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
+                            double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
+                            double hough_min_line_length, double hough_max_line_gap, int32_t quality, double *rotate_angle,
+                            int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len, bool png_out)
 {
     clear_error();
     if (!streams || !len || n < 1 || !rotate_angle || !need_check || !scan_rc || !jpeg || !jpeg_len)
@@ -734,7 +755,7 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
     const int rc = correct_default_host(views.data(), g, projection_max_angle, projection_angle_step, projection_max_width,
                                         projection_max_height, hough_min_line_length, hough_max_line_gap, ang.data(), chk.data(),
                                         src.data(), nullptr, out.data(), out_len.data(), quality, zs.data(), zlen.data(),
-                                        hdr.data(), png_hdr.data(), is_png.data());
+                                        hdr.data(), png_hdr.data(), is_png.data(), png_out);
     if (rc) return rc;
     for (int k = 0; k < g; k++) {
         const int i = at[(size_t)k];
@@ -742,6 +763,33 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
         jpeg[i] = out[(size_t)k], jpeg_len[i] = out_len[(size_t)k];
     }
     return OMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
+                                      double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
+                                      double hough_min_line_length, double hough_max_line_gap, int32_t quality,
+                                      double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg,
+                                      int64_t *jpeg_len)
+{
+    return correct_default_streams(streams, len, n, projection_max_angle, projection_angle_step, projection_max_width,
+                                   projection_max_height, hough_min_line_length, hough_max_line_gap, quality, rotate_angle,
+                                   need_check, scan_rc, jpeg, jpeg_len, false);
+}
+
+int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                          uint16_t projection_max_angle, double projection_angle_step,
+                                          int32_t projection_max_width, int32_t projection_max_height,
+                                          double hough_min_line_length, double hough_max_line_gap, int32_t compression,
+                                          double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **png,
+                                          int64_t *png_len)
+{
+    return correct_default_streams(streams, len, n, projection_max_angle, projection_angle_step, projection_max_width,
+                                   projection_max_height, hough_min_line_length, hough_max_line_gap, compression, rotate_angle,
+                                   need_check, scan_rc, png, png_len, true);
 }
 
 }  // extern "C"

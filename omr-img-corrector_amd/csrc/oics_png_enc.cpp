@@ -1,0 +1,304 @@
+// oics_png_enc.cpp -- host side of the PNG encoder (png_enc.hip): the bound of a stream's length,
+// the shapes it refuses, the launches of a group and the entry points omr_png_bound / omr_png_encode*.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/omrdeskew.h"
+#include "engine.hpp"
+#include "png_enc.hpp"
+
+using namespace omr;
+
+namespace {
+
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// raw bytes of one group of launches; the workspace is about five times that (raw, two bytes of match / token entry per
+// raw byte, the bit buffer, the code tables)
+constexpr int64_t kGroupRaw = (int64_t)512 << 20;
+constexpr int kGroupImages = 4096;
+
+int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+int64_t blocks_of(int64_t raw) { return (raw + PENC_BLOCK - 1) / PENC_BLOCK; }
+
+struct StageEvents {
+    hipEvent_t e[PENC_STAGES + 1] = {};
+    int n = 0;
+    int create()
+    {
+        for (; n <= PENC_STAGES; n++) OMR_HIP(hipEventCreate(&e[n]));
+        return OMR_OK;
+    }
+    ~StageEvents()
+    {
+        for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]);
+    }
+};
+
+// one group: images [i0, i0 + g)
+int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn, const int32_t *sizes, int i0, int g,
+                 int compression, JpegSink &sink, hipStream_t s)
+{
+    std::vector<PencImg> im((size_t)g);
+    std::vector<PencDyn> dyn((size_t)g);
+    std::vector<int64_t> len((size_t)g, 0), off((size_t)g, 0);
+    DrainOnExit drain{s};  // behind the host objects that asynchronous copies read or write, before the device buffers
+    PencStats &stats = penc_stats();
+    StageEvents ev;
+    if (stats.on)
+        if (int r = ev.create()) return r;
+    auto mark = [&](int k) -> int {
+        if (stats.on) OMR_HIP(hipEventRecord(ev.e[k], s));
+        return OMR_OK;
+    };
+    int64_t raw_bytes = 0, blocks = 0, max_raw = 0;
+    int max_rows = 0;
+    for (int j = 0; j < g; j++) {
+        PencImg &m = im[(size_t)j];
+        memset(&m, 0, sizeof m);
+        const int r = sizes[2 * (size_t)(i0 + j)], c = sizes[2 * (size_t)(i0 + j) + 1];
+        const int64_t raw = r > 0 ? penc_raw_bytes(r, c, cn) : 0;
+        m.src_off = (int64_t)(i0 + j) * img_stride;
+        m.raw_off = raw_bytes, m.blk0 = blocks;
+        m.raw_len = (uint32_t)raw, m.nblk = (uint32_t)blocks_of(raw), m.npiece = (uint32_t)((raw + PENC_PIECE - 1) / PENC_PIECE);
+        m.rows = r, m.cols = c, m.row_bytes = c * cn;
+        raw_bytes += up16(raw), blocks += m.nblk;
+        max_raw = std::max(max_raw, raw), max_rows = std::max(max_rows, r);
+    }
+    uint8_t *d_out = nullptr;
+    if (blocks == 0) {  // nothing but 0 x 0 entries
+        if (int rc = sink.place(i0, g, len.data(), &d_out, off.data())) return rc;
+        return sink.done(i0, g, len.data());
+    }
+    const int max_blocks = (int)blocks_of(max_raw), max_pieces = (int)((max_raw + PENC_PIECE - 1) / PENC_PIECE);
+    const bool stored_only = compression == 0;
+    DevBuf d_im, d_dyn, raw, mt, pcnt, pbit, blk, codes, hdr, zbuf;
+    OMR_HIP(d_im.alloc(sizeof(PencImg) * (size_t)g));
+    OMR_HIP(d_dyn.alloc(sizeof(PencDyn) * (size_t)g));
+    OMR_HIP(raw.alloc((size_t)raw_bytes));
+    OMR_HIP(blk.alloc(sizeof(PencBlk) * (size_t)blocks));
+    if (!stored_only) {
+        OMR_HIP(mt.alloc((size_t)raw_bytes * 2));
+        OMR_HIP(pcnt.alloc((size_t)blocks * PENC_BLOCK_PIECES * 2));
+        OMR_HIP(pbit.alloc((size_t)blocks * PENC_BLOCK_PIECES * 4));
+        OMR_HIP(codes.alloc((size_t)blocks * PENC_CODES * 4));
+        OMR_HIP(hdr.alloc((size_t)blocks * PENC_HDR_WORDS * 4));
+        OMR_HIP(zbuf.alloc((size_t)blocks * PENC_ZBLOCK));
+    }
+    PencPass p;
+    memset(&p, 0, sizeof p);
+    p.src = d_imgs, p.step = step, p.imgs = d_im.as<PencImg>(), p.dyn = d_dyn.as<PencDyn>(), p.n = g, p.cn = cn;
+    p.stored_only = stored_only;
+    p.raw = raw.as<uint8_t>(), p.mt = mt.as<uint16_t>(), p.piece_cnt = pcnt.as<uint16_t>(), p.piece_bit = pbit.as<uint32_t>();
+    p.blk = blk.as<PencBlk>(), p.codes = codes.as<uint32_t>(), p.hdr = hdr.as<uint32_t>(), p.zbuf = zbuf.as<uint32_t>();
+    // 1. everything up to the blocks' sizes; the host learns every stream's length
+    OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(PencImg) * (size_t)g, hipMemcpyHostToDevice, s));
+    OMR_HIP(hipMemsetAsync(d_dyn.p, 0, sizeof(PencDyn) * (size_t)g, s));
+    int rc = mark(0);
+    if (rc || (rc = penc_launch_filter(p, max_rows, s)) || (rc = mark(1)) || (rc = penc_launch_adler(p, max_raw, s)) || (rc = mark(2)))
+        return rc;
+    if (!stored_only && (rc = penc_launch_parse(p, max_raw, max_pieces, s))) return rc;
+    if ((rc = mark(3)) || (rc = penc_launch_blocks(p, max_blocks, s)) || (rc = mark(4))) return rc;
+    if (!stored_only) {
+        OMR_HIP(hipMemsetAsync(zbuf.p, 0, (size_t)blocks * PENC_ZBLOCK, s));
+        if ((rc = penc_launch_bits(p, max_blocks, s))) return rc;
+    }
+    if ((rc = mark(5))) return rc;
+    OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(PencDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
+    OMR_HIP(hipStreamSynchronize(s));
+    for (int j = 0; j < g; j++)
+        if (im[(size_t)j].nblk) len[(size_t)j] = (int64_t)PENC_BEFORE + dyn[(size_t)j].deflate_len + PENC_AFTER;
+    // 2. the streams, where the caller wants them
+    if ((rc = sink.place(i0, g, len.data(), &d_out, off.data()))) return rc;
+    for (int j = 0; j < g; j++) im[(size_t)j].out_off = off[(size_t)j];
+    p.out = d_out;
+    OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(PencImg) * (size_t)g, hipMemcpyHostToDevice, s));
+    if ((rc = penc_launch_streams(p, max_blocks, s)) || (rc = mark(6))) return rc;
+    OMR_HIP(hipStreamSynchronize(s));
+    if (stats.on) {
+        stats.groups++;
+        for (int k = 0; k < PENC_STAGES; k++) {
+            float ms = 0;
+            OMR_HIP(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+            stats.ms[k] += ms;
+        }
+    }
+    return sink.done(i0, g, len.data());
+}
+
+// the public device form's sink: slot i of the caller's buffer, lengths into the caller's host array
+struct SlotSink : JpegSink {
+    uint8_t *d_out;
+    int64_t stride;
+    int64_t *out_len;
+    int place(int i0, int cnt, const int64_t *len, uint8_t **out, int64_t *off) override
+    {
+        *out = d_out;
+        for (int j = 0; j < cnt; j++) off[j] = (int64_t)(i0 + j) * stride, out_len[i0 + j] = len[j];
+        return OMR_OK;
+    }
+    int done(int, int, const int64_t *) override { return OMR_OK; }
+};
+
+// omr_png_encode's sink: one stream, into the caller's host buffer when it fits
+struct HostSink : JpegSink {
+    uint8_t *out;
+    int64_t cap, len = 0;
+    hipStream_t s;
+    DevBuf buf;
+    bool fits = false;
+    int place(int, int, const int64_t *l, uint8_t **d_out, int64_t *off) override
+    {
+        len = l[0], off[0] = 0;
+        OMR_HIP(buf.alloc((size_t)len));
+        *d_out = buf.as<uint8_t>();
+        return OMR_OK;
+    }
+    int done(int, int, const int64_t *) override
+    {
+        fits = out && len <= cap;
+        return fits ? staged_d2h(out, buf.p, (size_t)len, s) : OMR_OK;
+    }
+};
+
+int check_batch_args(const void *d_imgs, const void *d_out, const void *out_len, int n)
+{
+    if (!d_imgs || !d_out || !out_len) return fail(OMR_ERR_BADARG, "null argument");
+    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
+    return OMR_OK;
+}
+
+}  // namespace
+
+int64_t omr::penc_raw_bytes(int rows, int cols, int cn) { return (int64_t)rows * (1 + (int64_t)cols * cn); }
+
+int64_t omr::penc_bound(int rows, int cols, int cn)
+{
+    const int64_t raw = penc_raw_bytes(rows, cols, cn);
+    return PENC_BEFORE + raw + PENC_STORED_HEAD * blocks_of(raw) + PENC_AFTER;
+}
+
+int omr::penc_check_shape(int rows, int cols, int cn)
+{
+    if (cn != 1 && cn != 3 && cn != 4) return fail(OMR_ERR_ASSERT, "PNG takes 1, 3 or 4 channels, got %d", cn);
+    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_ASSERT, "empty image");
+    if (rows > PENC_MAX_SIDE || cols > PENC_MAX_SIDE || (int64_t)rows * cols > PENC_MAX_PIXELS)
+        return fail(OMR_ERR_ASSERT, "%d x %d is above imread's limits (2^20 a side, 2^30 pixels): not supported", rows, cols);
+    const int64_t raw = penc_raw_bytes(rows, cols, cn);
+    if (2 + raw + PENC_STORED_HEAD * blocks_of(raw) + 4 > PENC_MAX_IDAT)
+        return fail(OMR_ERR_ASSERT, "a %d x %d x %d image may take an IDAT chunk of 2^31 bytes or more: not supported", rows, cols, cn);
+    return OMR_OK;
+}
+
+PencStats &omr::penc_stats()
+{
+    static thread_local PencStats st;
+    return st;
+}
+
+int omr::png_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn, const int32_t *sizes, int n,
+                           int compression, JpegSink &sink, hipStream_t s)
+{
+    PencStats &stats = penc_stats();
+    stats.groups = 0;
+    for (double &v : stats.ms) v = 0;
+    compression = std::min(std::max(compression, 0), 9);
+    for (int i = 0; i < n; i++)
+        if (sizes[2 * (size_t)i] > 0)
+            if (int rc = penc_check_shape(sizes[2 * (size_t)i], sizes[2 * (size_t)i + 1], cn)) return rc;
+    DrainOnExit drain{s};
+    for (int i0 = 0; i0 < n;) {
+        int g = 0;
+        int64_t raw = 0;
+        while (i0 + g < n && g < kGroupImages) {
+            const int r = sizes[2 * (size_t)(i0 + g)], c = sizes[2 * (size_t)(i0 + g) + 1];
+            const int64_t b = r > 0 ? penc_raw_bytes(r, c, cn) : 0;
+            if (g > 0 && raw + b > kGroupRaw) break;
+            raw += b, g++;
+        }
+        if (int rc = encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, compression, sink, s)) return rc;
+        i0 += g;
+    }
+    return OMR_OK;
+}
+
+extern "C" {
+
+int omr_png_bound(int32_t rows, int32_t cols, int32_t channels, int64_t *bytes)
+{
+    clear_error();
+    if (!bytes) return fail(OMR_ERR_BADARG, "null bytes");
+    if (int rc = penc_check_shape(rows, cols, channels)) return rc;
+    *bytes = penc_bound(rows, cols, channels);
+    return OMR_OK;
+}
+
+int omr_png_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
+                                int32_t channels, const int32_t *sizes, int32_t n, int32_t compression, uint8_t *d_out,
+                                int64_t out_stride_bytes, int64_t *out_len)
+{
+    clear_error();
+    int rc = check_batch_args(d_imgs, d_out, out_len, n);
+    if (rc || (rc = penc_check_shape(rows, cols, channels))) return rc;
+    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
+    if (img_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "img_stride_bytes < rows x step_bytes");
+    std::vector<int32_t> sz(2 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int r = sizes ? sizes[2 * (size_t)i] : rows, c = sizes ? sizes[2 * (size_t)i + 1] : cols;
+        if (r < 0 || c < 0 || r > rows || c > cols || ((r == 0) != (c == 0)))
+            return fail(OMR_ERR_BADARG, "sizes[%d] = %d x %d does not fit the %d x %d slot", i, r, c, rows, cols);
+        sz[2 * (size_t)i] = r, sz[2 * (size_t)i + 1] = c;
+    }
+    if (out_stride_bytes < penc_bound(rows, cols, channels))
+        return fail(OMR_ERR_BADARG, "out_stride_bytes below omr_png_bound (%lld)", (long long)penc_bound(rows, cols, channels));
+    if (n == 0) return OMR_OK;
+    if ((rc = have_device())) return rc;
+    LeasedStream st;
+    if ((rc = st.create())) return rc;
+    SlotSink sink;
+    sink.d_out = d_out, sink.stride = out_stride_bytes, sink.out_len = out_len;
+    return png_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz.data(), n, compression, sink, st.s);
+}
+
+int omr_png_encode(const omr_image *src, int32_t compression, uint8_t *out, int64_t cap, int64_t *len)
+{
+    clear_error();
+    if (!src || !src->data || !len || cap < 0 || (!out && cap > 0)) return fail(OMR_ERR_BADARG, "null argument");
+    int rc = penc_check_shape(src->rows, src->cols, src->channels);
+    if (rc) return rc;
+    if (src->step_bytes < (int64_t)src->cols * src->channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
+    if ((rc = have_device())) return rc;
+    LeasedStream st;
+    if ((rc = st.create())) return rc;
+    const int64_t row = (int64_t)src->cols * src->channels;
+    DevBuf in;
+    OMR_HIP(in.alloc((size_t)(row * src->rows)));
+    if ((rc = upload_rows(in.p, (size_t)row, src->data, (size_t)src->step_bytes, (size_t)row, (size_t)src->rows, st.s))) return rc;
+    const int32_t size[2] = {src->rows, src->cols};
+    HostSink sink;
+    sink.out = out, sink.cap = cap, sink.s = st.s;
+    rc = png_encode_device(in.as<uint8_t>(), row * src->rows, row, src->channels, size, 1, compression, sink, st.s);
+    if (rc) return rc;
+    *len = sink.len;
+    if (!sink.fits) return fail(OMR_ERR_NOMEM, "the stream takes %lld bytes, the buffer holds %lld", (long long)sink.len, (long long)cap);
+    return OMR_OK;
+}
+
+int omr_png_encode_stats(int32_t enable, int32_t *groups, double *stage_ms)
+{
+    clear_error();
+    PencStats &st = penc_stats();
+    if (groups) *groups = st.groups;
+    if (stage_ms)
+        for (int k = 0; k < PENC_STAGES; k++) stage_ms[k] = st.ms[k];
+    st.on = enable != 0;
+    return OMR_OK;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
+#include "png_adler.hpp"
 #include "png_dec.hpp"
 
 namespace omr {
@@ -327,45 +328,21 @@ __global__ __launch_bounds__(64) void pdec_inflate_kernel(PdecPass p)
     }
 }
 
-// Adler-32 = (1 + sum b_i) mod 65521 | (n + sum (n - i) b_i) mod 65521 << 16: every thread takes 256 bytes, a workgroup
-// PDEC_ADLER_CHUNK, and adds its part of the two sums (each below 65521 x 256) to the image's
+// Adler-32: the sums per PDEC_ADLER_CHUNK bytes are png_adler.hpp's, shared with the encoder
+static_assert(PDEC_ADLER_CHUNK == PNG_ADLER_CHUNK, "the host sizes the grid by PDEC_ADLER_CHUNK");
 __global__ __launch_bounds__(256) void pdec_adler_kernel(PdecPass p)
 {
     const PdecImg *im = p.imgs + blockIdx.y;
     PdecDyn *dyn = p.dyn + blockIdx.y;
     if (im->skip || dyn->err) return;
-    const uint32_t n = im->raw_len;
-    const uint64_t at = (uint64_t)blockIdx.x * PDEC_ADLER_CHUNK + (uint64_t)threadIdx.x * 256;
-    __shared__ unsigned long long sa[256], sb[256];
-    unsigned long long a = 0, b = 0;
-    if (at < n) {
-        const uint8_t *q = p.raw + im->raw_off + at;
-        const uint32_t m = (uint32_t)min((uint64_t)256, (uint64_t)n - at);
-        uint32_t s1 = 0, s2 = 0;
-        for (uint32_t j = 0; j < m; j++) s1 += q[j], s2 += (m - j) * q[j];
-        const uint64_t rest = (uint64_t)n - at - m;  // bytes behind this thread's
-        a = s1;
-        b = (s2 + (rest % 65521u) * s1) % 65521u;
-    }
-    sa[threadIdx.x] = a, sb[threadIdx.x] = b;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) sa[threadIdx.x] += sa[threadIdx.x + d], sb[threadIdx.x] += sb[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && (uint64_t)blockIdx.x * PDEC_ADLER_CHUNK < n) {
-        atomicAdd(&dyn->a_sum, sa[0] % 65521u);
-        atomicAdd(&dyn->b_sum, sb[0] % 65521u);
-    }
+    adler_chunk_sums(p.raw + im->raw_off, im->raw_len, blockIdx.x, &dyn->a_sum, &dyn->b_sum);
 }
 
 __global__ void pdec_verdict_kernel(PdecPass p)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n || p.imgs[i].skip || p.dyn[i].err) return;
-    const uint32_t a = (uint32_t)((1 + p.dyn[i].a_sum) % 65521u);
-    const uint32_t b = (uint32_t)((p.imgs[i].raw_len % 65521u + p.dyn[i].b_sum) % 65521u);
-    if ((b << 16 | a) != p.dyn[i].adler_want) p.dyn[i].err = PDEC_ERR_ADLER;
+    if (adler_finish(p.imgs[i].raw_len, p.dyn[i].a_sum, p.dyn[i].b_sum) != p.dyn[i].adler_want) p.dyn[i].err = PDEC_ERR_ADLER;
 }
 
 __device__ inline int paeth(int a, int b, int c)

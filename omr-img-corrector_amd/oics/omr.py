@@ -209,10 +209,19 @@ def correct_default_batch(src_mats, projection_max_angle, projection_angle_step,
     return [(float(ang[i]), bool(chk[i]), imgs[i], int(rc[i])) for i in range(n)]
 
 
-def correct_default_batch_jpeg(src_mats, projection_max_angle, projection_angle_step, projection_max_width,
-                               projection_max_height, hough_min_line_length, hough_max_line_gap, quality=100):
-    """omr_correct_default_batch_jpeg: correct_default_batch with every rotated sheet encoded on the device ->
-    [(rotate_angle, need_check, JPEG bytes or None, scan_rc)] in input order"""
+def _streams_out(n, ang, chk, rc, ptrs, lens):
+    out = []
+    for i in range(n):
+        data = None
+        if ptrs[i]:
+            data = C.string_at(ptrs[i], int(lens[i]))
+            lib().omr_bytes_free(ptrs[i])
+        out.append((float(ang[i]), bool(chk[i]), data, int(rc[i])))
+    return out
+
+
+def _batch_encoded(symbol, src_mats, params, level):
+    """the host-image flow functions that return streams: omr_correct_default_batch_jpeg / _png"""
     from ._lib import OmrImage, u8p
     keep, ims = [], []
     for m in src_mats:
@@ -226,26 +235,16 @@ def correct_default_batch_jpeg(src_mats, projection_max_angle, projection_angle_
     rc = np.zeros(n, np.int32)
     ptrs = (u8p * max(n, 1))()
     lens = np.zeros(max(n, 1), np.int64)
-    check(lib().omr_correct_default_batch_jpeg(arr, n, int(projection_max_angle), float(projection_angle_step),
-                                               int(projection_max_width), int(projection_max_height),
-                                               float(hough_min_line_length), float(hough_max_line_gap), int(quality),
-                                               ang.ctypes.data_as(f64p), chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p),
-                                               ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64))))
-    out = []
-    for i in range(n):
-        data = None
-        if ptrs[i]:
-            data = C.string_at(ptrs[i], int(lens[i]))
-            lib().omr_bytes_free(ptrs[i])
-        out.append((float(ang[i]), bool(chk[i]), data, int(rc[i])))
-    return out
+    max_angle, angle_step, max_width, max_height, min_line_length, max_line_gap = params
+    check(getattr(lib(), symbol)(arr, n, int(max_angle), float(angle_step), int(max_width), int(max_height),
+                                 float(min_line_length), float(max_line_gap), int(level), ang.ctypes.data_as(f64p),
+                                 chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), ptrs,
+                                 lens.ctypes.data_as(C.POINTER(C.c_int64))))
+    return _streams_out(n, ang, chk, rc, ptrs, lens)
 
 
-def correct_default_batch_streams(streams, projection_max_angle, projection_angle_step, projection_max_width,
-                                  projection_max_height, hough_min_line_length, hough_max_line_gap, quality=100):
-    """omr_correct_default_batch_streams: correct_default from file contents to file contents.  streams: baseline JPEG
-    streams (bytes or uint8 arrays), decoded to BGR, corrected and encoded on the device -> [(rotate_angle, need_check,
-    JPEG bytes or None, scan_rc)] in input order; scan_rc is the decoder's code for a sheet it refused."""
+def _streams_encoded(symbol, streams, params, level):
+    """the flow functions from streams to streams: omr_correct_default_batch_streams / _streams_png"""
     from ._lib import u8p
     bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
             for s in streams]
@@ -258,20 +257,49 @@ def correct_default_batch_streams(streams, projection_max_angle, projection_angl
     rc = np.zeros(max(n, 1), np.int32)
     ptrs = (u8p * max(n, 1))()
     lens = np.zeros(max(n, 1), np.int64)
-    check(lib().omr_correct_default_batch_streams(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(projection_max_angle),
-                                                  float(projection_angle_step), int(projection_max_width),
-                                                  int(projection_max_height), float(hough_min_line_length),
-                                                  float(hough_max_line_gap), int(quality), ang.ctypes.data_as(f64p),
-                                                  chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), ptrs,
-                                                  lens.ctypes.data_as(C.POINTER(C.c_int64))))
-    out = []
-    for i in range(n):
-        data = None
-        if ptrs[i]:
-            data = C.string_at(ptrs[i], int(lens[i]))
-            lib().omr_bytes_free(ptrs[i])
-        out.append((float(ang[i]), bool(chk[i]), data, int(rc[i])))
-    return out
+    max_angle, angle_step, max_width, max_height, min_line_length, max_line_gap = params
+    check(getattr(lib(), symbol)(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(max_angle), float(angle_step),
+                                 int(max_width), int(max_height), float(min_line_length), float(max_line_gap), int(level),
+                                 ang.ctypes.data_as(f64p), chk.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), ptrs,
+                                 lens.ctypes.data_as(C.POINTER(C.c_int64))))
+    return _streams_out(n, ang, chk, rc, ptrs, lens)
+
+
+def correct_default_batch_jpeg(src_mats, projection_max_angle, projection_angle_step, projection_max_width,
+                               projection_max_height, hough_min_line_length, hough_max_line_gap, quality=100):
+    """omr_correct_default_batch_jpeg: correct_default_batch with every rotated sheet encoded on the device ->
+    [(rotate_angle, need_check, JPEG bytes or None, scan_rc)] in input order"""
+    return _batch_encoded("omr_correct_default_batch_jpeg", src_mats,
+                          (projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                           hough_min_line_length, hough_max_line_gap), quality)
+
+
+def correct_default_batch_png(src_mats, projection_max_angle, projection_angle_step, projection_max_width,
+                              projection_max_height, hough_min_line_length, hough_max_line_gap, compression=1):
+    """omr_correct_default_batch_png: correct_default_batch_jpeg with lossless PNG streams ->
+    [(rotate_angle, need_check, PNG bytes or None, scan_rc)] in input order"""
+    return _batch_encoded("omr_correct_default_batch_png", src_mats,
+                          (projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                           hough_min_line_length, hough_max_line_gap), compression)
+
+
+def correct_default_batch_streams(streams, projection_max_angle, projection_angle_step, projection_max_width,
+                                  projection_max_height, hough_min_line_length, hough_max_line_gap, quality=100):
+    """omr_correct_default_batch_streams: correct_default from file contents to file contents.  streams: baseline JPEG
+    streams (bytes or uint8 arrays), decoded to BGR, corrected and encoded on the device -> [(rotate_angle, need_check,
+    JPEG bytes or None, scan_rc)] in input order; scan_rc is the decoder's code for a sheet it refused."""
+    return _streams_encoded("omr_correct_default_batch_streams", streams,
+                            (projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                             hough_min_line_length, hough_max_line_gap), quality)
+
+
+def correct_default_batch_streams_png(streams, projection_max_angle, projection_angle_step, projection_max_width,
+                                      projection_max_height, hough_min_line_length, hough_max_line_gap, compression=1):
+    """omr_correct_default_batch_streams_png: correct_default_batch_streams (JPEG and PNG inputs, mixed) with lossless PNG
+    streams as its outputs -> [(rotate_angle, need_check, PNG bytes or None, scan_rc)] in input order"""
+    return _streams_encoded("omr_correct_default_batch_streams_png", streams,
+                            (projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                             hough_min_line_length, hough_max_line_gap), compression)
 
 
 def get_result_from_fourier_transform(src_mat, canny_threshold_weak, canny_threshold_strong, fourier_min_line_length,

@@ -65,6 +65,12 @@ class TransformableMatrix:
         from . import jpeg
         return jpeg.encode(self.matrix, quality)
 
+    def encode_png(self, compression=1):
+        """A PNG stream that decodes to this image exactly (im_write(.., PNG, level), transfer.rs:162-179), encoded on
+        the GPU (omr_png_encode): gray, BGR or BGRA.  Lossless and deterministic, not imwrite's bytes."""
+        from . import png
+        return png.encode(self.matrix, compression)
+
     def get_mat(self):
         return self.matrix
 

@@ -248,3 +248,115 @@ pub fn correct_default_files(
     result?;
     Ok((0..n).map(|i| (angle[i], need_check[i] != 0)).collect())
 }
+
+/// The tail of the flow functions that write PNG files: all or nothing -- no file is written unless every sheet was
+/// corrected (`what` names the stages that may have answered a code) --, then `std::fs::write` per output; every stream is
+/// released with omr_bytes_free on every path.
+fn write_streams(inputs: &[&str], outputs: &[&str], scan_rc: &[i32], streams: &[*mut u8], lens: &[i64], what: &str) -> opencv::Result<()> {
+    let n = inputs.len();
+    let mut result: opencv::Result<()> = match (0..n).find(|&i| scan_rc[i] != 0) {
+        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("correct_default failed on {} (sheet {}): {} answered {}; no output file was written", inputs[i], i, what, scan_rc[i]))),
+        None => Ok(()),
+    };
+    for i in 0..n {
+        if streams[i].is_null() {
+            continue;
+        }
+        if result.is_ok() {
+            let bytes = unsafe { std::slice::from_raw_parts(streams[i], lens[i] as usize) };
+            if let Err(e) = std::fs::write(outputs[i], bytes) {
+                result = Err(opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (output {}; outputs before it are written): {}", outputs[i], i, e)));
+            }
+        }
+        unsafe { ffi::omr_bytes_free(streams[i]) };
+    }
+    result
+}
+
+/// `correct_defaults` with lossless outputs (omr_correct_default_batch_png): imread(COLOR) per input on host threads, one
+/// batch call that corrects the sheets and encodes every rotated canvas as PNG (`compression` is imwrite's
+/// IMWRITE_PNG_COMPRESSION: 0 stores, 1 .. 9 all compress alike) on the GPU, then `std::fs::write` per output.  Returns
+/// (rotation angle, need_check) per file; errors as `correct_defaults`.  Not in the reference crate.
+pub fn correct_defaults_png(
+    inputs: &[&str],
+    outputs: &[&str],
+    projection_max_angle: u16,
+    projection_angle_step: f64,
+    projection_max_width: i32,
+    projection_max_height: i32,
+    hough_min_line_length: f64,
+    hough_max_line_gap: f64,
+    compression: i32,
+) -> opencv::Result<Vec<(f64, bool)>> {
+    if inputs.len() != outputs.len() || inputs.is_empty() {
+        return Err(opencv::Error::new(ffi::OMR_ERR_BADARG, String::from("inputs and outputs must pair up")));
+    }
+    let n = inputs.len();
+    let threads = n.min(16);
+    let mut mats: Vec<opencv::Result<Mat>> = Vec::with_capacity(n);
+    std::thread::scope(|sc| {
+        let handles: Vec<_> = (0..threads)
+            .map(|t| {
+                sc.spawn(move || {
+                    (t..n).step_by(threads).map(|i| (i, imgcodecs::imread(inputs[i], imgcodecs::IMREAD_COLOR))).collect::<Vec<_>>()
+                })
+            })
+            .collect();
+        let mut got: Vec<(usize, opencv::Result<Mat>)> = handles.into_iter().flat_map(|h| h.join().unwrap()).collect();
+        got.sort_by_key(|e| e.0);
+        mats.extend(got.into_iter().map(|e| e.1));
+    });
+    let mats: Vec<Mat> = mats.into_iter().collect::<opencv::Result<Vec<_>>>()?;
+    let views: Vec<ffi::OmrImage> = mats.iter().map(view).collect::<opencv::Result<Vec<_>>>()?;
+    let mut angle = vec![0.0f64; n];
+    let (mut need_check, mut scan_rc) = (vec![0i32; n], vec![0i32; n]);
+    let mut png: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+    let mut png_len = vec![0i64; n];
+    check(unsafe {
+        ffi::omr_correct_default_batch_png(views.as_ptr(), n as i32, projection_max_angle, projection_angle_step,
+                                           projection_max_width, projection_max_height, hough_min_line_length,
+                                           hough_max_line_gap, compression, angle.as_mut_ptr(), need_check.as_mut_ptr(),
+                                           scan_rc.as_mut_ptr(), png.as_mut_ptr(), png_len.as_mut_ptr())
+    })?;
+    write_streams(inputs, outputs, &scan_rc, &png, &png_len, "the correction")?;
+    Ok((0..n).map(|i| (angle[i], need_check[i] != 0)).collect())
+}
+
+/// `correct_default_files` with lossless outputs (omr_correct_default_batch_streams_png): JPEG or PNG files in, PNG files
+/// out, with nothing but file contents crossing to the GPU and back.  `compression` as for `correct_defaults_png`; errors
+/// as `correct_default_files`.  Not in the reference crate.
+pub fn correct_default_files_png(
+    inputs: &[&str],
+    outputs: &[&str],
+    projection_max_angle: u16,
+    projection_angle_step: f64,
+    projection_max_width: i32,
+    projection_max_height: i32,
+    hough_min_line_length: f64,
+    hough_max_line_gap: f64,
+    compression: i32,
+) -> opencv::Result<Vec<(f64, bool)>> {
+    if inputs.len() != outputs.len() || inputs.is_empty() {
+        return Err(opencv::Error::new(ffi::OMR_ERR_BADARG, String::from("inputs and outputs must pair up")));
+    }
+    let n = inputs.len();
+    let mut files: Vec<Vec<u8>> = Vec::with_capacity(n);
+    for (i, path) in inputs.iter().enumerate() {
+        files.push(std::fs::read(path).map_err(|e| opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (input {}): {}", path, i, e)))?);
+    }
+    let mut ptrs: Vec<*const u8> = files.iter().map(|f| f.as_ptr()).collect();
+    let lens: Vec<i64> = files.iter().map(|f| f.len() as i64).collect();
+    let mut angle = vec![0.0f64; n];
+    let (mut need_check, mut scan_rc) = (vec![0i32; n], vec![0i32; n]);
+    let mut png: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+    let mut png_len = vec![0i64; n];
+    check(unsafe {
+        ffi::omr_correct_default_batch_streams_png(ptrs.as_mut_ptr(), lens.as_ptr(), n as i32, projection_max_angle,
+                                                   projection_angle_step, projection_max_width, projection_max_height,
+                                                   hough_min_line_length, hough_max_line_gap, compression, angle.as_mut_ptr(),
+                                                   need_check.as_mut_ptr(), scan_rc.as_mut_ptr(), png.as_mut_ptr(),
+                                                   png_len.as_mut_ptr())
+    })?;
+    write_streams(inputs, outputs, &scan_rc, &png, &png_len, "the JPEG / PNG decoder or the correction")?;
+    Ok((0..n).map(|i| (angle[i], need_check[i] != 0)).collect())
+}

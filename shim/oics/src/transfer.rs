@@ -240,6 +240,28 @@ pub fn encode_jpeg(m: &TransformableMatrix, quality: i32) -> Result<Vec<u8>, ope
     Ok(out)
 }
 
+/// A PNG stream that decodes to the Mat exactly, encoded on the GPU (omr_png_encode): what `im_write(.., ImageFormat::PNG,
+/// level)` is for, lossless and deterministic, but not imwrite's bytes (PNG has no canonical stream).  Gray, BGR or BGRA,
+/// 8-bit; `compression` is IMWRITE_PNG_COMPRESSION: 0 stores, 1 .. 9 all compress alike.  Not in the reference crate.
+/// One call in the usual case: the first buffer holds half the raw image's size; a stream that does not fit answers
+/// OMR_ERR_NOMEM with its length, and a second call encodes again into that.
+pub fn encode_png(m: &TransformableMatrix, compression: i32) -> Result<Vec<u8>, opencv::Error> {
+    let v = view(&m.matrix)?;
+    let mut bound = 0i64;
+    check(unsafe { ffi::omr_png_bound(v.rows, v.cols, v.channels, &mut bound) })?;
+    let raw = v.rows as i64 * v.cols as i64 * v.channels as i64 / 2 + 1024;
+    let mut out = vec![0u8; raw.min(bound) as usize];
+    let mut len = 0i64;
+    let mut rc = unsafe { ffi::omr_png_encode(&v, compression, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    if rc == ffi::OMR_ERR_NOMEM {
+        out = vec![0u8; len as usize];
+        rc = unsafe { ffi::omr_png_encode(&v, compression, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    }
+    check(rc)?;
+    out.truncate(len as usize);
+    Ok(out)
+}
+
 /// What `im_read` gives for a file with these bytes (`imread(.., IMREAD_COLOR)` for `channels` = 3, `IMREAD_GRAYSCALE`
 /// for 1), decoded on the GPU (omr_jpeg_decode): libjpeg's output with its defaults, byte for byte.  Baseline streams;
 /// one the decoder refuses (progressive, CMYK, an EXIF orientation, ..) is an error with code OMR_ERR_NOTIMPL, so that
