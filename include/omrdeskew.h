@@ -1112,6 +1112,55 @@ int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const i
                                           double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **png,
                                           int64_t *png_len);
 
+/* ---- deskew with projections from file contents to file contents ------------------------------
+ * The reference's benchmark flow, core/src/main.rs:68-95 -- imread, get_angle_with_projections, rotate_mat of the
+ * original (CONTAIN, scale 1, BORDER_CONSTANT), imwrite -- for batches: omr_deskew_with_projections_batch with the scans
+ * given as baseline JPEG or PNG streams in host memory and the deskewed canvases returned as JPEG streams.  The streams
+ * are told apart by PNG's signature as omr_correct_default_batch_streams does; one batch, and one bucket, may hold both
+ * kinds, and each kind goes by its decoder's rules (omr_jpeg_decode_batch_device, omr_png_decode_batch_device).  The
+ * headers are parsed and the scans bucketed by shape on the host; each bucket is decoded straight into the scan slots of
+ * the cached omr_projection_batch context, swept, warped by the winners on the device and encoded there, in runs of 32
+ * scans (256 when no outputs are asked for), so only streams cross the link in either direction.
+ * channels: 3 is imread(IMREAD_COLOR) -- a gray stream gives B = G = R -- and a 3-component output; 1 is the gray
+ * convenience of omr_get_angle_with_projections: the Y plane of a JPEG, colour types 0 and 4 of a PNG (OMR_ERR_NOTIMPL in
+ * scan_rc[i] for the others), a single-component JPEG or a colour-type-0 PNG out.  Anything else: OMR_ERR_BADARG.
+ * For every scan with scan_rc[i] == 0: angles[i] has the f64 bits of omr_get_angle_with_projections on imread's decode
+ * of the stream, best_idx[i] (may be NULL) its candidate, and jpeg[i] (malloc'ed, release with omr_bytes_free; jpeg_len[i]
+ * bytes) is byte for byte omr_jpeg_encode(omr_rotate(decode, angles[i], 1.0, interp, border_value, OMR_CLIP_CONTAIN),
+ * quality).  A scan's result does not depend on its place in the batch, on n or on the other scans.
+ * A scan whose header its decoder refuses or finds malformed gets that code in scan_rc[i], angle 0, best_idx -1 and no
+ * output, on the host, before any device work; one whose image data turns out damaged gets OMR_ERR_ASSERT there; one for
+ * which the per-call function would fail (a working size that truncates to 0) that code.  The other scans are unaffected
+ * and the call returns 0; a call whose every stream is refused does no device work.
+ * jpeg and jpeg_len may both be NULL: the angles-only form (get_angle_with_projections from files), which allocates no
+ * canvas slot.
+ * OMR_ERR_BADARG for the call: a null streams / len / angles / scan_rc / streams[i], n < 1, a negative length, exactly one
+ * of jpeg and jpeg_len null, a null border_value when outputs are wanted, an empty candidate range, a resize_scale that is
+ * <= 0 or not finite.  OMR_ERR_NOTIMPL: interp other than NEAREST / LINEAR.  OMR_ERR_ASSERT, before any device work: a
+ * shape whose deskew canvas (omr_projection_batch_deskew_canvas) could take more than 2^32 bits of scan data.  On an
+ * error of the whole call nothing is returned and nothing is left allocated.
+ * A bucket the batch context does not take (a sweep it cannot plan, a canvas the warp's tables cannot hold) goes scan by
+ * scan through omr_jpeg_decode / omr_png_decode, omr_get_angle_with_projections, omr_rotate and omr_jpeg_encode, so every
+ * scan that chain accepts is accepted here, with the same bytes.
+ * Measured (profiles/r21_projection_streams.md) at (45, 0.2, 0.2), LINEAR, quality 100: 5.5 k dataset sheets/s from gray
+ * JPEG at 256 files a call (6.3 k with channels = 1), 332 / 432 A4 colour cards/s from JPEG at quality 100 / 95 at 64 files a
+ * call.  The per-call pair omr_get_angle_with_projections + omr_rotate from 16 threads with Pillow on both ends gives 76
+ * and 10 / 10 (73 x, 32 x / 42 x), Pillow's decode + omr_deskew_with_projections_batch + Pillow's save 71 and 9 / 9; both
+ * are bound by Pillow's quality-100 save, whose threads encode no faster than one.  The decode is 106 of 119 ms of a chunk
+ * of 32 A4 cards.  NOT faster from RGB PNG: 77 dataset sheets/s against 76 and 69 (1.0 x, 1.1 x) -- one wave inflates one
+ * stream and a run carries 32 scans, so at most 32 waves inflate at a time. */
+int omr_deskew_with_projections_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                              uint16_t max_angle, double step, double resize_scale, int32_t interp,
+                                              const uint8_t border_value[4], int32_t quality, double *angles,
+                                              int32_t *best_idx, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len);
+/* The same with PNG streams as its outputs (omr_png_encode's, for `compression`): png[i] decodes to the deskewed canvas
+ * exactly.  The call-level OMR_ERR_ASSERT is omr_png_bound's refusal of the canvas. */
+int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                                  int32_t channels, uint16_t max_angle, double step, double resize_scale,
+                                                  int32_t interp, const uint8_t border_value[4], int32_t compression,
+                                                  double *angles, int32_t *best_idx, int32_t *scan_rc, uint8_t **png,
+                                                  int64_t *png_len);
+
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);
 int omr_get_standard_deviation(const double *v, size_t n, double *out);

@@ -33,6 +33,7 @@
 #include "jpeg_dec.hpp"
 #include "png_dec.hpp"
 #include "png_enc.hpp"
+#include "stream_sink.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -348,41 +349,6 @@ struct HostArgs {
     const uint8_t *is_png = nullptr;
 };
 
-// The streams of a chunk's canvases -> fresh host buffers: a device buffer of exactly the streams' size per group of the
-// encoder, then one staged copy per stream from several threads.  Stream j belongs to sheet idx[j0 + j].
-struct StreamSink : JpegSink {
-    const HostArgs &a;
-    const std::vector<int> &idx;
-    int j0;
-    DevBuf buf;
-    std::vector<int64_t> off;
-    StreamSink(const HostArgs &args, const std::vector<int> &members, int first) : a(args), idx(members), j0(first) {}
-    int place(int, int cnt, const int64_t *len, uint8_t **d_out, int64_t *o) override
-    {
-        int64_t total = 0;
-        off.assign((size_t)cnt, 0);
-        for (int j = 0; j < cnt; j++) off[(size_t)j] = o[j] = total, total += (len[j] + 255) & ~(int64_t)255;
-        buf.release();
-        OMR_HIP(buf.alloc((size_t)std::max<int64_t>(total, 256)));
-        *d_out = buf.as<uint8_t>();
-        return OMR_OK;
-    }
-    int done(int i0, int cnt, const int64_t *len) override
-    {
-        return on_threads(cnt, [&](hipStream_t s, int lo, int hi) -> int {
-            for (int j = lo; j < hi; j++) {
-                if (len[j] == 0) continue;
-                const int i = idx[(size_t)(j0 + i0 + j)];
-                uint8_t *data = (uint8_t *)malloc((size_t)len[j]);
-                if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
-                a.jpeg[i] = data, a.jpeg_len[i] = len[j];
-                if (int rc = staged_d2h(data, buf.as<uint8_t>() + off[(size_t)j], (size_t)len[j], s)) return rc;
-            }
-            return OMR_OK;
-        });
-    }
-};
-
 struct CtxKey {
     int device, rows, cols, cn;
     uint16_t max_angle;
@@ -491,7 +457,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
         if (a.jpeg) {  // the canvases stay on the device: encoded there, only the streams come down
             for (int j = 0; j < z; j++)
                 if (src[(size_t)j] != OMR_OK) size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
-            StreamSink sink(a, idx, j0);
+            StreamSink sink(a.jpeg, a.jpeg_len, idx, j0);
             rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
                            : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
             if (rc) return rc;

@@ -9,6 +9,9 @@
 //   deskew      (omr_projection_batch_deskew_device) the batch warp (deskew.hip) of the FULL-SIZE
 //               scans by the sweep's winners, read on the device: the context keeps a second candidate set, planned
 //               for rows x cols instead of the working shape.
+//   streams     (omr_deskew_with_projections_batch_streams) the same from file contents to file
+//               contents: JPEG / PNG streams decoded on the device straight into the scan slots, the canvases encoded
+//               there, only streams on the link.
 //
 // Scan i's angle is omr_get_angle_with_projections' for the same scan, as f64 bits; its canvas is omr_rotate's for that
 // angle, byte for byte.
@@ -23,6 +26,11 @@
 #include "engine.hpp"
 #include "host_threads.hpp"
 #include "hough_host.hpp"
+#include "jpeg.hpp"
+#include "jpeg_dec.hpp"
+#include "png_dec.hpp"
+#include "png_enc.hpp"
+#include "stream_sink.hpp"
 
 using namespace omr;
 using namespace omr::hh;
@@ -498,6 +506,258 @@ int omr_deskew_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t
     if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
         return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
     return host_form(srcs, n, max_angle, step, resize_scale, angles, best_idx, rotated, interp, border_value);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- the streams form: file contents in, file contents out --------------------------------------
+// Everything is indexed by the accepted sheets (those whose header parsed and whose working size exists), in call order.
+struct StreamArgs {
+    const uint8_t *const *streams;
+    const int64_t *len;
+    const JdecHeader *hdr;
+    const PdecHeader *png_hdr;  // sheet k is a PNG stream where is_png[k] != 0: png_hdr[k] holds, hdr[k] does not
+    const uint8_t *is_png;
+    int cn;
+    uint16_t max_angle;
+    double step, scale;
+    int N;
+    int interp;
+    const uint8_t *border;
+    int quality;  // the PNG form: the compression level
+    bool png_out;
+    double *angles;
+    int32_t *best_idx, *scan_rc;
+    uint8_t **out;  // null (with out_len): the angles alone
+    int64_t *out_len;
+    int device;
+};
+
+// a code of the per-call chain that belongs to its sheet (any other ends the call)
+bool sheet_code(int rc) { return rc == OMR_ERR_ASSERT || rc == OMR_ERR_BADARG || rc == OMR_ERR_NOTIMPL; }
+
+// the per-call chain, sheet by sheet: the buckets a batch context does not take
+int streams_per_call(const StreamArgs &a, const std::vector<int> &idx)
+{
+    for (int k : idx) {
+        omr_image_owned img{nullptr, 0, 0, 0, 0}, rot{nullptr, 0, 0, 0, 0};
+        uint8_t *bytes = nullptr;
+        int64_t cap = 0, used = 0;
+        int rc = a.is_png[k] ? omr_png_decode(a.streams[k], a.len[k], a.cn, &img) : omr_jpeg_decode(a.streams[k], a.len[k], a.cn, &img);
+        const omr_image view{img.data, img.rows, img.cols, img.channels, img.step_bytes};
+        if (!rc) rc = omr_get_angle_with_projections(&view, a.max_angle, a.step, a.scale, 1, &a.angles[k]);
+        if (!rc && a.out) {
+            rc = omr_rotate(&view, a.angles[k], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &rot);
+            if (!rc) rc = a.png_out ? omr_png_bound(rot.rows, rot.cols, rot.channels, &cap) : omr_jpeg_bound(rot.rows, rot.cols, rot.channels, &cap);
+            if (!rc && !(bytes = (uint8_t *)malloc((size_t)cap))) rc = fail(OMR_ERR_NOMEM, "out of host memory");
+            const omr_image canvas{rot.data, rot.rows, rot.cols, rot.channels, rot.step_bytes};
+            if (!rc) rc = a.png_out ? omr_png_encode(&canvas, a.quality, bytes, cap, &used) : omr_jpeg_encode(&canvas, a.quality, bytes, cap, &used);
+        }
+        omr_image_free(&img);
+        omr_image_free(&rot);
+        if (rc) {
+            free(bytes);
+            if (!sheet_code(rc)) return rc;
+            a.scan_rc[k] = rc, a.angles[k] = 0.0, a.best_idx[k] = -1;
+            continue;
+        }
+        a.best_idx[k] = (int32_t)llround(a.angles[k] / a.step) + a.N;
+        if (a.out) {
+            uint8_t *fit = (uint8_t *)realloc(bytes, (size_t)std::max<int64_t>(used, 1));  // the bound is several times the stream
+            a.out[k] = fit ? fit : bytes, a.out_len[k] = used;
+        }
+    }
+    clear_error();
+    return OMR_OK;
+}
+
+int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<int> &idx)
+{
+    const int cn = a.cn;
+    std::shared_ptr<omr_projection_batch> pbp;
+    int rc = cached_context(CtxKey{a.device, rows, cols, cn, a.max_angle, a.step, a.scale}, &pbp);
+    if (rc == OMR_ERR_NOTIMPL || rc == OMR_ERR_BADARG || rc == OMR_ERR_ASSERT) {  // a sweep the batch context cannot plan
+        clear_error();
+        return streams_per_call(a, idx);
+    }
+    if (rc) return rc;
+    omr_projection_batch *pb = pbp.get();
+    if (a.out && !pb->dk.count()) return streams_per_call(a, idx);  // a canvas the warp's tables cannot hold
+    const int m = (int)idx.size(), zmax = std::min(m, a.out ? kDeskewChunk : kChunk);
+    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
+    const int64_t out_step = (int64_t)pb->dk.cols * cn, out_stride = out_step * pb->dk.rows;
+    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
+    if ((rc = st.create())) return rc;
+    DevBuf din, dout;
+    OMR_HIP(din.alloc((size_t)zmax * in_stride));
+    if (a.out) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
+    std::vector<double> ang((size_t)zmax);
+    std::vector<int32_t> best((size_t)zmax), size(2 * (size_t)zmax);
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    std::vector<JdecHeader> zhdr;
+    std::vector<PdecHeader> zpng;
+    std::vector<int32_t> zskip, zskip_png, zrc;
+    for (int j0 = 0; j0 < m; j0 += zmax) {
+        const int z = std::min(zmax, m - j0);
+        // the chunk's streams -> the scan slots, decoded on the device; a bucket may hold both kinds: each decoder fills
+        // its own members' slots and skips the other's
+        zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z);
+        zskip.assign((size_t)z, 0), zskip_png.assign((size_t)z, 0), zrc.assign((size_t)z, 0);
+        int pngs = 0;
+        for (int j = 0; j < z; j++) {
+            const int k = idx[(size_t)(j0 + j)];
+            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k];
+            if (a.is_png[k]) zpng[(size_t)j] = a.png_hdr[k], zskip[(size_t)j] = 1, pngs++;
+            else zhdr[(size_t)j] = a.hdr[k], zskip_png[(size_t)j] = 1;
+        }
+        if (pngs < z && (rc = jpeg_decode_device(zs.data(), zlen.data(), zhdr.data(), zskip.data(), z, cn, din.as<uint8_t>(),
+                                                 in_stride, row, zrc.data(), st.s)))
+            return rc;
+        if (pngs && (rc = png_decode_device(zs.data(), zlen.data(), zpng.data(), zskip_png.data(), z, cn, din.as<uint8_t>(),
+                                            in_stride, row, zrc.data(), st.s)))
+            return rc;
+        rc = a.out ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
+                                                        out_stride, out_step, size.data(), ang.data(), best.data())
+                   : omr_projection_batch_run_device(pb, din.as<uint8_t>(), in_stride, row, z, ang.data(), best.data(), nullptr, nullptr);
+        if (rc) return rc;
+        for (int j = 0; j < z; j++) {
+            const int k = idx[(size_t)(j0 + j)];
+            if (zrc[(size_t)j]) {  // damaged image data: the slot's content means nothing; its code and no output
+                a.scan_rc[k] = zrc[(size_t)j], a.angles[k] = 0.0, a.best_idx[k] = -1;
+                size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
+            } else {
+                a.angles[k] = ang[(size_t)j], a.best_idx[k] = best[(size_t)j];
+            }
+        }
+        if (!a.out) continue;
+        // the canvases stay on the device: encoded there, only the streams come down
+        StreamSink sink(a.out, a.out_len, idx, j0);
+        rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
+                       : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
+        if (rc) return rc;
+    }
+    return OMR_OK;
+}
+
+// omr_deskew_with_projections_batch_streams and its PNG form: `out` receives the streams of either kind
+int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, uint16_t max_angle, double step,
+                   double scale, int32_t interp, const uint8_t *border, int32_t quality, double *angles, int32_t *best_idx,
+                   int32_t *scan_rc, uint8_t **out, int64_t *out_len, bool png_out)
+{
+    clear_error();
+    if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
+    if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
+    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "channels must be 1 or 3, got %d", channels);
+    for (int i = 0; i < n; i++)
+        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
+    int N = 0;
+    if (candidate_count(max_angle, step, &N) <= 0)
+        return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
+    if (!isfinite(scale) || scale <= 0.0) return fail(OMR_ERR_BADARG, "resize_scale must be finite and positive");
+    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
+        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
+    // the headers, on the host: a sheet its decoder refuses, or for which the per-call function would fail, keeps its
+    // code and leaves the batch here
+    std::vector<int32_t> code((size_t)n, OMR_OK);
+    std::vector<JdecHeader> hdr;
+    std::vector<PdecHeader> png_hdr;
+    std::vector<uint8_t> is_png;
+    std::vector<int> at;
+    std::vector<omr_image> views;
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    hdr.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        hdr.emplace_back(), png_hdr.emplace_back();
+        const bool png = pdec_is_png(streams[i], len[i]);
+        int rc = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back());
+        if (!rc && png) rc = pdec_check_channels(png_hdr.back(), channels);
+        const int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
+        Working w;
+        if (!rc) rc = working_size(rows, cols, scale, &w);
+        if ((code[(size_t)i] = rc)) {
+            hdr.pop_back(), png_hdr.pop_back();
+            continue;
+        }
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), is_png.push_back(png);
+        views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
+    }
+    clear_error();
+    const int g = (int)at.size();
+    std::vector<double> ang((size_t)g, 0.0);
+    std::vector<int32_t> best((size_t)g, -1), src((size_t)g, OMR_OK);
+    std::vector<uint8_t *> bytes((size_t)g, nullptr);
+    std::vector<int64_t> bytes_len((size_t)g, 0);
+    int rc = OMR_OK;
+    if (g) {
+        ShapeBuckets b;
+        if ((rc = bucket_by_shape(views.data(), g, [](const omr_image &) { return (int)OMR_OK; }, &b))) return rc;
+        if (out) {  // the encoders' offsets inside an image are 32-bit: a shape whose canvas slot could exceed them refuses the
+                    // call, before any device work (a shape without a canvas goes sheet by sheet)
+            const int A = candidate_count(max_angle, step, nullptr);
+            std::vector<double> cand((size_t)A);
+            for (int i = 0; i < A; i++) cand[(size_t)i] = (double)(i - N) * step;
+            for (const ImageShape &sh : b.shapes) {
+                DeskewTables dk;
+                if (dk.plan(sh.rows, sh.cols, cand.data(), A)) {
+                    clear_error();
+                    continue;
+                }
+                if ((rc = png_out ? penc_check_shape(dk.rows, dk.cols, sh.cn) : jpeg_check_scan_bits(dk.rows, dk.cols, sh.cn))) return rc;
+            }
+        }
+        if ((rc = have_device())) return rc;
+        int dev = 0;
+        OMR_HIP(hipGetDevice(&dev));
+        StreamArgs a{zs.data(), zlen.data(), hdr.data(), png_hdr.data(), is_png.data(), channels, max_angle, step, scale, N, interp,
+                     border, quality, png_out, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
+                     out ? bytes_len.data() : nullptr, dev};
+        for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
+        if (rc) {
+            for (uint8_t *p : bytes) free(p);
+            return rc;
+        }
+    }
+    // every sheet is decided: the caller's arrays are written only now
+    for (int i = 0; i < n; i++) {
+        angles[i] = 0.0, scan_rc[i] = code[(size_t)i];
+        if (best_idx) best_idx[i] = -1;
+        if (out) out[i] = nullptr, out_len[i] = 0;
+    }
+    for (int k = 0; k < g; k++) {
+        const int i = at[(size_t)k];
+        angles[i] = ang[(size_t)k], scan_rc[i] = src[(size_t)k];
+        if (best_idx) best_idx[i] = best[(size_t)k];
+        if (out) out[i] = bytes[(size_t)k], out_len[i] = bytes_len[(size_t)k];
+    }
+    return OMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int omr_deskew_with_projections_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                              uint16_t max_angle, double step, double resize_scale, int32_t interp,
+                                              const uint8_t border_value[4], int32_t quality, double *angles,
+                                              int32_t *best_idx, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len)
+{
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, quality, angles, best_idx,
+                          scan_rc, jpeg, jpeg_len, false);
+}
+
+int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                                  int32_t channels, uint16_t max_angle, double step, double resize_scale,
+                                                  int32_t interp, const uint8_t border_value[4], int32_t compression,
+                                                  double *angles, int32_t *best_idx, int32_t *scan_rc, uint8_t **png,
+                                                  int64_t *png_len)
+{
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, compression, angles,
+                          best_idx, scan_rc, png, png_len, true);
 }
 
 }  // extern "C"

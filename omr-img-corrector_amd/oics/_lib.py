@@ -252,6 +252,14 @@ SYMBOLS = {
     "omr_correct_default_batch_streams_png": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_uint16,
                                                         C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                                         f64p, i32p, i32p, C.POINTER(u8p), C.POINTER(C.c_int64)]),
+    "omr_deskew_with_projections_batch_streams": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
+                                                            C.c_int32, C.c_uint16, C.c_double, C.c_double, C.c_int32, u8p,
+                                                            C.c_int32, f64p, i32p, i32p, C.POINTER(u8p),
+                                                            C.POINTER(C.c_int64)]),
+    "omr_deskew_with_projections_batch_streams_png": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
+                                                                C.c_int32, C.c_uint16, C.c_double, C.c_double, C.c_int32, u8p,
+                                                                C.c_int32, f64p, i32p, i32p, C.POINTER(u8p),
+                                                                C.POINTER(C.c_int64)]),
     "omr_scale": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_shrink_to": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_resize": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),

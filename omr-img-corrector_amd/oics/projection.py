@@ -60,6 +60,55 @@ def get_angles_and_deskew(srcs, max_angle, step, resize_scale, interp=1, border=
     return (ang[:n], idx[:n], images) if want_idx else (ang[:n], images)
 
 
+def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, level, channels, png, want_out):
+    """omr_deskew_with_projections_batch_streams / _png -> (angles, best_idx, scan_rc, [bytes or None] or None)"""
+    from ._lib import u8p
+    bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
+            for s in streams]
+    bufs = [b if b.size else np.zeros(1, np.uint8) for b in bufs]
+    n = len(bufs)
+    sp = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    sl = np.array([len(s) for s in streams] + [0], np.int64)
+    ang = np.zeros(max(n, 1), np.float64)
+    idx = np.zeros(max(n, 1), np.int32)
+    rc = np.zeros(max(n, 1), np.int32)
+    ptrs = (u8p * max(n, 1))()
+    lens = np.zeros(max(n, 1), np.int64)
+    fn = lib().omr_deskew_with_projections_batch_streams_png if png else lib().omr_deskew_with_projections_batch_streams
+    check(fn(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), int(max_angle), float(step), float(resize_scale),
+             int(interp), _border4(border), int(level), ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p),
+             rc.ctypes.data_as(i32p), ptrs if want_out else None,
+             lens.ctypes.data_as(C.POINTER(C.c_int64)) if want_out else None))
+    out = None
+    if want_out:
+        out = [None] * n
+        for i in range(n):
+            if ptrs[i]:
+                out[i] = C.string_at(ptrs[i], int(lens[i]))
+                lib().omr_bytes_free(ptrs[i])
+    return ang[:n], idx[:n], rc[:n], out
+
+
+def deskew_streams(streams, max_angle, step, resize_scale, interp=1, border=(255, 255, 255), quality=100, channels=3,
+                   png=False, want_idx=False):
+    """The reference benchmark's flow from file contents to file contents (omr_deskew_with_projections_batch_streams,
+    png=True: _streams_png; core/src/main.rs:68-95).  streams: baseline JPEG or PNG file contents (bytes or uint8 arrays,
+    both kinds in one batch), decoded, swept, rotated (CONTAIN, scale 1, constant border; interp 0 = NEAREST, 1 = LINEAR)
+    and encoded on the device; `quality` is the PNG form's compression level.  channels: 3 as imread(IMREAD_COLOR), or 1
+    for gray.  Returns (angles, scan_rc, outputs): angles[i] is the per-call angle of imread's decode of streams[i] (same
+    f64 bits), scan_rc[i] 0 or the code of a sheet that was refused or damaged, outputs[i] the encoded canvas as bytes
+    (None where scan_rc[i] != 0).  want_idx: (angles, best_idx, scan_rc, outputs)."""
+    ang, idx, rc, out = _deskew_streams(streams, max_angle, step, resize_scale, interp, border, quality, channels, png, True)
+    return (ang, idx, rc, out) if want_idx else (ang, rc, out)
+
+
+def get_angles_from_streams(streams, max_angle, step, resize_scale, channels=3, want_idx=False):
+    """deskew_streams' angles alone (get_angle_with_projections from files): no canvas is made.  Returns (angles,
+    scan_rc); want_idx: (angles, best_idx, scan_rc)."""
+    ang, idx, rc, _ = _deskew_streams(streams, max_angle, step, resize_scale, 1, (255, 255, 255), 100, channels, False, False)
+    return (ang, idx, rc) if want_idx else (ang, rc)
+
+
 def projection_batch_working_size(rows, cols, resize_scale):
     """(wrows, wcols, front mode): scale_self's size (transfer.rs:66-91) and how the batch front end gets there"""
     r, c, m = C.c_int32(), C.c_int32(), C.c_int32()

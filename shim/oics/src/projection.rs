@@ -1,6 +1,6 @@
 //! `oics::projection` (reference: packages/lib/src/projection.rs:17-194) -> omr_get_angle_with_projections,
-//! its batch form omr_get_angles_with_projections_batch, and the batch that also rotates the full-size images,
-//! omr_deskew_with_projections_batch.
+//! its batch form omr_get_angles_with_projections_batch, the batch that also rotates the full-size images,
+//! omr_deskew_with_projections_batch, and that flow from files to files, omr_deskew_with_projections_batch_streams.
 use crate::bridge::{border_bytes, check, into_mat, view};
 use crate::ffi;
 use crate::transfer::TransformableMatrix;
@@ -72,4 +72,89 @@ pub fn deskew_with_projections(
     // every image is taken over before the first error is reported, so none of the library's buffers is lost
     let mats: Vec<opencv::Result<Mat>> = outs.into_iter().map(into_mat).collect();
     mats.into_iter().zip(angles).map(|(m, a)| Ok((a, m?))).collect()
+}
+
+/// `std::fs::read` per input, the one batch call `run` (streams in, streams out), then `std::fs::write` per output.  All or
+/// nothing: no file is written unless every scan was decoded and deskewed; every stream is released with omr_bytes_free
+/// on every path.
+fn files_through<F>(inputs: &[&str], outputs: &[&str], run: F) -> opencv::Result<Vec<f64>>
+where
+    F: FnOnce(*mut *const u8, *const i64, i32, *mut f64, *mut i32, *mut *mut u8, *mut i64) -> i32,
+{
+    if inputs.len() != outputs.len() || inputs.is_empty() {
+        return Err(opencv::Error::new(ffi::OMR_ERR_BADARG, String::from("inputs and outputs must pair up")));
+    }
+    let n = inputs.len();
+    let mut files: Vec<Vec<u8>> = Vec::with_capacity(n);
+    for (i, path) in inputs.iter().enumerate() {
+        files.push(std::fs::read(path).map_err(|e| opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (input {}): {}", path, i, e)))?);
+    }
+    let mut ptrs: Vec<*const u8> = files.iter().map(|f| f.as_ptr()).collect();
+    let lens: Vec<i64> = files.iter().map(|f| f.len() as i64).collect();
+    let mut angles = vec![0.0f64; n];
+    let mut scan_rc = vec![0i32; n];
+    let mut streams: Vec<*mut u8> = vec![std::ptr::null_mut(); n];
+    let mut stream_len = vec![0i64; n];
+    check(run(ptrs.as_mut_ptr(), lens.as_ptr(), n as i32, angles.as_mut_ptr(), scan_rc.as_mut_ptr(), streams.as_mut_ptr(), stream_len.as_mut_ptr()))?;
+    let mut result: opencv::Result<()> = match (0..n).find(|&i| scan_rc[i] != 0) {
+        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("deskew_with_projections failed on {} (scan {}): the JPEG / PNG decoder or the deskew answered {}; no output file was written", inputs[i], i, scan_rc[i]))),
+        None => Ok(()),
+    };
+    for i in 0..n {
+        if streams[i].is_null() {
+            continue;
+        }
+        if result.is_ok() {
+            let bytes = unsafe { std::slice::from_raw_parts(streams[i], stream_len[i] as usize) };
+            if let Err(e) = std::fs::write(outputs[i], bytes) {
+                result = Err(opencv::Error::new(ffi::OMR_ERR_BADARG, format!("{} (output {}; outputs before it are written): {}", outputs[i], i, e)));
+            }
+        }
+        unsafe { ffi::omr_bytes_free(streams[i]) };
+    }
+    result?;
+    Ok(angles)
+}
+
+/// The reference benchmark's whole loop (core/src/main.rs:68-95: imread, `get_angle_with_projections`, `rotate_mat` of the
+/// original with CONTAIN, `im_write(.., JPEG, quality)`) for many files at once, with nothing but file contents crossing
+/// to the GPU and back (omr_deskew_with_projections_batch_streams).  Inputs are baseline JPEG or PNG files, told apart by
+/// PNG's signature; one batch may hold both.  Returns the angle per file (the per-call function's f64 bits); output i is
+/// byte for byte what the per-call chain encodes for input i.  A scan its decoder refuses (progressive JPEG, interlaced
+/// PNG, ..: OMR_ERR_NOTIMPL) or cannot decode fails the call with that scan's code and names it, and no output file is
+/// written: the caller sends such files through `deskew_with_projections`, whose imread takes them.  Not in the
+/// reference crate.
+pub fn deskew_files_with_projections(
+    inputs: &[&str],
+    outputs: &[&str],
+    max_angle: u16,
+    angle_step: f64,
+    resize_scale: f64,
+    flags: i32,
+    border_value: Scalar,
+    quality: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, jpeg, jpeg_len| unsafe {
+        ffi::omr_deskew_with_projections_batch_streams(streams, len, n, 3, max_angle, angle_step, resize_scale, flags, border.as_ptr(), quality, angles, std::ptr::null_mut(), scan_rc, jpeg, jpeg_len)
+    })
+}
+
+/// `deskew_files_with_projections` with lossless outputs (omr_deskew_with_projections_batch_streams_png): JPEG or PNG
+/// files in, PNG files out.  `compression` is imwrite's IMWRITE_PNG_COMPRESSION (0: stored blocks, 1 .. 9: the one
+/// compressed method).  Not in the reference crate.
+pub fn deskew_files_with_projections_png(
+    inputs: &[&str],
+    outputs: &[&str],
+    max_angle: u16,
+    angle_step: f64,
+    resize_scale: f64,
+    flags: i32,
+    border_value: Scalar,
+    compression: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, png, png_len| unsafe {
+        ffi::omr_deskew_with_projections_batch_streams_png(streams, len, n, 3, max_angle, angle_step, resize_scale, flags, border.as_ptr(), compression, angles, std::ptr::null_mut(), scan_rc, png, png_len)
+    })
 }
