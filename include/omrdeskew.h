@@ -1049,6 +1049,65 @@ int omr_png_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_ima
  * group records five events; results do not change.  Any output pointer may be NULL. */
 int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
 
+/* ---- imread: EXIF orientation and the two decoders behind one door -----------------------------
+ * imread(IMREAD_COLOR) -- the first line of correct_default and of TransformableMatrix::new -- turns a JPEG by the
+ * orientation its EXIF block carries; phones and sheet-fed scanners write such files for every portrait capture.  The
+ * codes mean what OpenCV's ExifTransform (and Pillow's ImageOps.exif_transpose) does:
+ *   1 copy   2 flip left-right   3 turn by 180 degrees   4 flip top-bottom   5 transpose
+ *   6 transpose, then flip left-right (90 degrees clockwise)   7 transpose, then flip both (transverse)
+ *   8 transpose, then flip top-bottom (90 degrees counter-clockwise)
+ * For 5..8 the result has the source's columns as its rows.  The order of the bytes inside a pixel is kept.
+ *
+ * n device-resident images of 1 or 3 byte channels, each turned by its own code and each of its own size, in one launch.
+ * Image i lies at the top left of the slot d_src + i * src_stride_bytes of rows x cols (rows src_step_bytes apart) and is
+ * written to the top left of the slot d_dst + i * dst_stride_bytes of dst_rows x dst_cols (rows dst_step_bytes apart): the
+ * destination slots have a shape of their own, which the caller passes, so a batch of portrait captures needs no square
+ * slots.  sizes: HOST array of 2 n entries (rows, cols of image i, the layout of the decoders' out_size), or NULL: every
+ * image fills its slot; a 0 x 0 entry is skipped and leaves its slot untouched.  orient: HOST array of n codes.
+ * out_size[2 i], [2 i + 1] (HOST array) = the turned image's rows, cols.  Bytes of a destination slot outside the turned
+ * image are not written.  Out of place only.
+ * OMR_ERR_BADARG, all before any device work: n < 0, a null pointer (sizes excepted), channels other than 1 or 3, an empty
+ * slot, a step below cols x channels or a stride below rows x step on either side, an image larger than its source slot
+ * or with one side 0, a code outside 1..8, a turned image that does not fit the destination slot, source and destination
+ * slots whose byte ranges meet.  Synchronous, on a stream of its own, which has drained on every return path.
+ * Measured (profiles/r22_orient.md) at 256 resident A4 colour images a call: 7.25 .. 7.28 ms for every code, 1.84 TB/s of
+ * bytes moved, 0.23 of the 8 TB/s HBM roofline -- the transposing codes run at the speed of the copy; what binds all
+ * eight is the address arithmetic per gathered byte and one dword in flight per lane, not LDS banks. */
+int omr_orient_batch_device(const uint8_t *d_src, int64_t src_stride_bytes, int64_t src_step_bytes, int32_t rows, int32_t cols,
+                            uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step_bytes, int32_t dst_rows,
+                            int32_t dst_cols, int32_t channels, const int32_t *sizes, const int32_t *orient, int32_t n,
+                            int32_t *out_size);
+/* A host image of 1 or 3 channels turned by `orientation` (1..8) -> a packed host image (release with omr_image_free).
+ * OMR_ERR_BADARG for other channel counts or codes. */
+int omr_orient(const omr_image *src, int32_t orientation, omr_image_owned *dst);
+
+#define OMR_IMREAD_IGNORE_ORIENTATION 128 /* imgcodecs::IMREAD_IGNORE_ORIENTATION: decode a JPEG as stored */
+#define OMR_IMREAD_KIND_JPEG 0
+#define OMR_IMREAD_KIND_PNG 1
+/* What imread would return for this stream.  A stream that begins with PNG's eight signature bytes is a PNG
+ * (*kind = OMR_IMREAD_KIND_PNG) and goes by omr_png_info's rules, every other one by omr_jpeg_info's, with one difference:
+ * a JPEG whose EXIF orientation is 2..8 is accepted.  *rows, *cols: the size AFTER the turn (as stored with
+ * OMR_IMREAD_IGNORE_ORIENTATION, or when the stream is refused); *components: 1 or 3 as stored (a PNG: 1 for colour types
+ * 0 and 4, else 3); *orientation: the code found (1: none), whatever `flags` says.  flags: 0 or
+ * OMR_IMREAD_IGNORE_ORIENTATION, anything else OMR_ERR_BADARG.  Any output pointer may be NULL.  Host only.
+ * OMR_ERR_NOTIMPL, never a wrong picture: a JPEG whose orientation value is outside 1..8 (without the flag), and a PNG
+ * whose eXIf chunk gives an orientation other than 1 (with or without it).  What OpenCV 4.6 does with either could not be
+ * established: its EXIF reader is fed from JPEG markers, and eXIf support in its PNG reader may be later than 4.6. */
+int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *rows, int32_t *cols, int32_t *components,
+                    int32_t *orientation, int32_t *kind);
+/* imread for a batch: omr_jpeg_decode_batch_device / omr_png_decode_batch_device (JPEG and PNG may be mixed, told apart
+ * as above; every argument, out_size, rc and the OMR_ERR_BADARG rules as theirs, plus `flags` as above), each stream by its
+ * decoder's rules, except that a JPEG whose orientation is 2..8 is decoded and turned: "fits the slot" is judged on the
+ * turned size, out_size holds the turned size.  Streams that need no turn are decoded straight into their slots; the
+ * others into a scratch buffer, which one launch turns into their slots.  With OMR_IMREAD_IGNORE_ORIENTATION a JPEG is
+ * decoded as stored. */
+int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
+                            uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
+                            int32_t *out_size, int32_t *rc);
+/* imread of one buffer, JPEG or PNG: the stream -> a packed host image of `channels` channels (release with
+ * omr_image_free), turned by its EXIF orientation unless `flags` says otherwise. */
+int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t flags, omr_image_owned *dst);
+
 /* ---- PNG encoding on the device ---------------------------------------------------------------
  * A lossless exit for device-resident images: a valid PNG stream that every conforming decoder turns back into the image
  * byte for byte.  PNG has no canonical byte stream, so this is NOT what imwrite(.., PNG) writes byte for byte; it is
@@ -1117,7 +1176,9 @@ int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const i
  * original (CONTAIN, scale 1, BORDER_CONSTANT), imwrite -- for batches: omr_deskew_with_projections_batch with the scans
  * given as baseline JPEG or PNG streams in host memory and the deskewed canvases returned as JPEG streams.  The streams
  * are told apart by PNG's signature as omr_correct_default_batch_streams does; one batch, and one bucket, may hold both
- * kinds, and each kind goes by its decoder's rules (omr_jpeg_decode_batch_device, omr_png_decode_batch_device).  The
+ * kinds, and each kind goes by its decoder's rules (omr_jpeg_decode_batch_device, omr_png_decode_batch_device), with the
+ * one difference of omr_imread_batch_device: a JPEG whose EXIF orientation is 2..8 is decoded and turned as imread turns
+ * it, and counts by its turned shape (omr_correct_default_batch_streams does not do this yet and answers -213).  The
  * headers are parsed and the scans bucketed by shape on the host; each bucket is decoded straight into the scan slots of
  * the cached omr_projection_batch context, swept, warped by the winners on the device and encoded there, in runs of 32
  * scans (256 when no outputs are asked for), so only streams cross the link in either direction.

@@ -99,13 +99,17 @@ int jdec_launch_finish(const JdecPass &p, int max_groups, uint32_t max_blocks, i
 
 // ---- host side (oics_jpeg_dec.cpp)
 // What a stream's header says.  jdec_parse returns 0, OMR_ERR_NOTIMPL, OMR_ERR_BADARG (or OMR_ERR_ASSERT for entropy data
-// of 2^32 bits or more) with the thread's error text set; rows / cols are filled whenever SOF was readable.
+// of 2^32 bits or more) with the thread's error text set; rows / cols are filled whenever SOF was readable.  orient: the
+// EXIF orientation the last APP1 segment that carries one gives (1: none).  With refuse_orientation, a value other than 1
+// is OMR_ERR_NOTIMPL -- the contract of omr_jpeg_info / omr_jpeg_decode*; the imread layer (orient.hpp) passes false and
+// turns the image.
 struct JdecHeader {
     int32_t rows = 0, cols = 0, ncomp = 0, hs = 0, vs = 0, ri = 0;
+    int32_t orient = 1;
     int64_t data = 0;  // offset of the entropy data
     JdecTables tab;
 };
-int jdec_parse(const uint8_t *stream, int64_t len, JdecHeader *h);
+int jdec_parse(const uint8_t *stream, int64_t len, JdecHeader *h, bool refuse_orientation = true);
 // n parsed streams (hdr[i]; skip[i] != 0: not decoded) into slots d_out + i * out_stride of `channels` channels, rows
 // `step` apart; every image fits its slot (checked by the caller).  rc[i] = OMR_ERR_ASSERT where the entropy data is not a
 // scan of its header.  Synchronises `s`; its workspace comes from the calling thread's pool scope.

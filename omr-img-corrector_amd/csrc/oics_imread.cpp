@@ -1,0 +1,329 @@
+// oics_imread.cpp -- host side of the orientation transforms (orient.hip) and the imread layer above the two decoders
+// (DESIGN.md section 4.23): omr_orient*, omr_imread*.  imread(IMREAD_COLOR) turns a JPEG by its EXIF orientation; the
+// decoders' own entry points refuse such a stream, this layer decodes it into a scratch buffer and turns it on the device.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/omrdeskew.h"
+#include "engine.hpp"
+#include "orient.hpp"
+
+using namespace omr;
+
+namespace {
+
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+int check_channels(int channels)
+{
+    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "a decoded image has 1 or 3 channels, got %d", channels);
+    return OMR_OK;
+}
+
+int cn_orient(int cn)
+{
+    if (cn != 1 && cn != 3) return fail(OMR_ERR_BADARG, "an image to turn has 1 or 3 channels, got %d", cn);
+    return OMR_OK;
+}
+
+int check_code(int code)
+{
+    if (code < 1 || code > 8) return fail(OMR_ERR_BADARG, "EXIF orientation %d (1..8)", code);
+    return OMR_OK;
+}
+
+int check_flags(int flags)
+{
+    if (flags & ~OMR_IMREAD_IGNORE_ORIENTATION) return fail(OMR_ERR_BADARG, "flags %d (0 or OMR_IMREAD_IGNORE_ORIENTATION)", flags);
+    return OMR_OK;
+}
+
+// the slot rules of the decoders' batch entry points
+int check_slots(const void *p, int64_t stride, int64_t step, int rows, int cols, int channels, const char *side)
+{
+    if (!p) return fail(OMR_ERR_BADARG, "null %s", side);
+    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "empty %s slot", side);
+    if (step < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "%s: step_bytes < cols x channels", side);
+    if (stride / rows < step) return fail(OMR_ERR_BADARG, "%s: stride_bytes < rows x step_bytes", side);
+    return OMR_OK;
+}
+
+// one parsed stream of the imread entry points
+struct Parsed {
+    bool png = false;
+    int rc = OMR_OK;
+    int rows = 0, cols = 0;  // as imread returns it: after the turn
+    int components = 0, orient = 1;
+};
+
+// header, kind and the turned size; h / ph: where the kind's header goes
+Parsed parse_stream(const uint8_t *s, int64_t len, bool ignore, JdecHeader *h, PdecHeader *ph)
+{
+    Parsed p;
+    p.png = pdec_is_png(s, len);
+    if (p.png) {
+        p.rc = pdec_parse(s, len, ph);
+        p.rows = ph->rows, p.cols = ph->cols, p.orient = ph->orient;
+        p.components = ph->rows ? (ph->color_type == 0 || ph->color_type == 4 ? 1 : 3) : 0;
+        return p;
+    }
+    p.rc = jdec_parse(s, len, h, false);
+    p.rows = h->rows, p.cols = h->cols, p.components = h->ncomp, p.orient = h->orient;
+    if (p.rc) return p;
+    const int turn = imread_turn_of(*h, ignore);
+    if (turn < 0) p.rc = turn;
+    else if (turn && orient_transposes(h->orient)) std::swap(p.rows, p.cols);
+    return p;
+}
+
+}  // namespace
+
+int omr::imread_turn_of(const JdecHeader &h, bool ignore)
+{
+    if (ignore || h.orient == 1) return 0;
+    if (h.orient < 1 || h.orient > 8)
+        return fail(OMR_ERR_NOTIMPL, "EXIF orientation %d is outside 1..8: what imread does with it is not established", h.orient);
+    return 1;
+}
+
+int omr::orient_device(const uint8_t *d_src, int64_t sstep, uint8_t *d_dst, int64_t dstep, int cn, std::vector<OrientImg> *recs,
+                       hipStream_t s)
+{
+    const size_t n = recs->size();
+    if (n == 0) return OMR_OK;
+    DrainOnExit drain{s};  // the records' host copy and their device buffer stay until the stream has drained
+    DevBuf d_recs;
+    OMR_HIP(d_recs.alloc(sizeof(OrientImg) * n));
+    for (size_t i0 = 0; i0 < n; i0 += 65535) {
+        const int g = (int)std::min<size_t>(65535, n - i0);
+        int max_tiles = 1;
+        orient_plan(recs->data() + i0, g, cn, &max_tiles);
+        OMR_HIP(hipMemcpyAsync(d_recs.as<OrientImg>() + i0, recs->data() + i0, sizeof(OrientImg) * (size_t)g, hipMemcpyHostToDevice, s));
+        OMR_HIP(orient_launch(d_src, sstep, d_dst, dstep, cn, d_recs.as<OrientImg>() + i0, g, max_tiles, s));
+    }
+    OMR_HIP(hipStreamSynchronize(s));
+    return OMR_OK;
+}
+
+int omr::imread_decode_device(const uint8_t *const *streams, const int64_t *len, const JdecHeader *hdr, const PdecHeader *png_hdr,
+                              const uint8_t *is_png, const int32_t *skip, int n, int channels, bool ignore, uint8_t *d_out,
+                              int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s)
+{
+    std::vector<int32_t> skip_jpeg((size_t)n, 1), skip_png((size_t)n, 1);
+    std::vector<int> turn;
+    int pngs = 0, direct = 0;
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        if (is_png[i]) skip_png[(size_t)i] = 0, pngs++;
+        else if (!ignore && hdr[i].orient != 1) turn.push_back(i);
+        else skip_jpeg[(size_t)i] = 0, direct++;
+    }
+    int r = OMR_OK;
+    if (direct && (r = jpeg_decode_device(streams, len, hdr, skip_jpeg.data(), n, channels, d_out, out_stride, step, rc, s))) return r;
+    if (pngs && (r = png_decode_device(streams, len, png_hdr, skip_png.data(), n, channels, d_out, out_stride, step, rc, s))) return r;
+    if (turn.empty()) return OMR_OK;
+
+    // the members to turn, as a run of their own: decoded as stored into scratch slots that hold the largest of them
+    const int m = (int)turn.size();
+    int srows = 1, scols = 1;
+    std::vector<const uint8_t *> ts((size_t)m);
+    std::vector<int64_t> tlen((size_t)m);
+    std::vector<JdecHeader> thdr((size_t)m);
+    std::vector<int32_t> tskip((size_t)m, 0), trc((size_t)m, 0);
+    for (int t = 0; t < m; t++) {
+        const int i = turn[(size_t)t];
+        ts[(size_t)t] = streams[i], tlen[(size_t)t] = len[i], thdr[(size_t)t] = hdr[i];
+        srows = std::max(srows, hdr[i].rows), scols = std::max(scols, hdr[i].cols);
+    }
+    const int64_t tstep = ((int64_t)scols * channels + 3) & ~(int64_t)3, tstride = tstep * srows;
+    DrainOnExit drain{s};
+    DevBuf scratch;
+    OMR_HIP(scratch.alloc((size_t)tstride * (size_t)m));
+    if ((r = jpeg_decode_device(ts.data(), tlen.data(), thdr.data(), tskip.data(), m, channels, scratch.as<uint8_t>(), tstride, tstep,
+                                trc.data(), s)))
+        return r;
+    std::vector<OrientImg> recs;
+    for (int t = 0; t < m; t++) {
+        const int i = turn[(size_t)t];
+        if (trc[(size_t)t]) {  // damaged entropy data: the slot stays as it is
+            rc[i] = trc[(size_t)t];
+            continue;
+        }
+        recs.push_back(OrientImg{(int64_t)t * tstride, (int64_t)i * out_stride, hdr[i].rows, hdr[i].cols, hdr[i].orient, 0});
+    }
+    return orient_device(scratch.as<uint8_t>(), tstep, d_out, step, channels, &recs, s);
+}
+
+extern "C" {
+
+int omr_orient_batch_device(const uint8_t *d_src, int64_t src_stride_bytes, int64_t src_step_bytes, int32_t rows, int32_t cols,
+                            uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step_bytes, int32_t dst_rows, int32_t dst_cols,
+                            int32_t channels, const int32_t *sizes, const int32_t *orient, int32_t n, int32_t *out_size)
+{
+    clear_error();
+    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
+    if (!orient || !out_size) return fail(OMR_ERR_BADARG, "null argument");
+    if (int r = check_channels(channels)) return r;
+    if (int r = check_slots(d_src, src_stride_bytes, src_step_bytes, rows, cols, channels, "source")) return r;
+    if (int r = check_slots(d_dst, dst_stride_bytes, dst_step_bytes, dst_rows, dst_cols, channels, "destination")) return r;
+    if (n == 0) return OMR_OK;
+    std::vector<OrientImg> recs;
+    for (int i = 0; i < n; i++) {
+        const int r = sizes ? sizes[2 * (size_t)i] : rows, c = sizes ? sizes[2 * (size_t)i + 1] : cols;
+        if (int e = check_code(orient[i])) return e;
+        if (r < 0 || c < 0 || r > rows || c > cols || (r == 0) != (c == 0))
+            return fail(OMR_ERR_BADARG, "image %d is %d x %d, its slot %d x %d", i, r, c, rows, cols);
+        const bool t = orient_transposes(orient[i]);
+        const int tr = t ? c : r, tc = t ? r : c;
+        if (tr > dst_rows || tc > dst_cols)
+            return fail(OMR_ERR_BADARG, "image %d is %d x %d after the turn, its destination slot %d x %d", i, tr, tc, dst_rows, dst_cols);
+        if (r) recs.push_back(OrientImg{(int64_t)i * src_stride_bytes, (int64_t)i * dst_stride_bytes, r, c, orient[i], 0});
+    }
+    // out of place only: the bytes the slots span must not meet
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    const uint64_t sext = (uint64_t)(n - 1) * (uint64_t)src_stride_bytes + (uint64_t)(rows - 1) * (uint64_t)src_step_bytes + (uint64_t)cols * channels;
+    const uint64_t dext = (uint64_t)(n - 1) * (uint64_t)dst_stride_bytes + (uint64_t)(dst_rows - 1) * (uint64_t)dst_step_bytes + (uint64_t)dst_cols * channels;
+    if (s0 < d0 + dext && d0 < s0 + sext) return fail(OMR_ERR_BADARG, "the source and destination slots overlap (out of place only)");
+    for (int i = 0; i < n; i++) {
+        const int r = sizes ? sizes[2 * (size_t)i] : rows, c = sizes ? sizes[2 * (size_t)i + 1] : cols;
+        const bool t = orient_transposes(orient[i]);
+        out_size[2 * (size_t)i] = t ? c : r, out_size[2 * (size_t)i + 1] = t ? r : c;
+    }
+    if (recs.empty()) return OMR_OK;
+    if (int r = have_device()) return r;
+    LeasedStream st;
+    if (int r = st.create()) return r;
+    return orient_device(d_src, src_step_bytes, d_dst, dst_step_bytes, channels, &recs, st.s);
+}
+
+int omr_orient(const omr_image *src, int32_t orientation, omr_image_owned *dst)
+{
+    clear_error();
+    if (!dst) return fail(OMR_ERR_BADARG, "null argument");
+    int r = check_image(src, cn_orient);
+    if (r || (r = check_code(orientation))) return r;
+    if ((r = have_device())) return r;
+    LeasedStream st;
+    if ((r = st.create())) return r;
+    const int cn = src->channels;
+    const bool t = orient_transposes(orientation);
+    const int trows = t ? src->cols : src->rows, tcols = t ? src->rows : src->cols;
+    const int64_t sstep = (int64_t)src->cols * cn, dstep = (int64_t)tcols * cn, bytes = sstep * src->rows;
+    DrainOnExit drain{st.s};
+    DevBuf in, out;
+    OMR_HIP(in.alloc((size_t)bytes));
+    OMR_HIP(out.alloc((size_t)bytes));
+    if ((r = upload_rows(in.p, (size_t)sstep, src->data, (size_t)src->step_bytes, (size_t)sstep, (size_t)src->rows, st.s))) return r;
+    std::vector<OrientImg> recs{OrientImg{0, 0, src->rows, src->cols, orientation, 0}};
+    if ((r = orient_device(in.as<uint8_t>(), sstep, out.as<uint8_t>(), dstep, cn, &recs, st.s))) return r;
+    *dst = omr_image_owned{nullptr, trows, tcols, cn, dstep};
+    dst->data = (uint8_t *)malloc((size_t)bytes);
+    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
+    r = staged_d2h(dst->data, out.p, (size_t)bytes, st.s);
+    if (r) omr_image_free(dst);
+    return r;
+}
+
+int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *rows, int32_t *cols, int32_t *components,
+                    int32_t *orientation, int32_t *kind)
+{
+    clear_error();
+    if (!stream || len < 0) return fail(OMR_ERR_BADARG, "null stream");
+    if (int r = check_flags(flags)) return r;
+    std::vector<JdecHeader> h(1);
+    PdecHeader ph;
+    const Parsed p = parse_stream(stream, len, (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0, &h[0], &ph);
+    if (rows) *rows = p.rows;
+    if (cols) *cols = p.cols;
+    if (components) *components = p.components;
+    if (orientation) *orientation = p.orient;
+    if (kind) *kind = p.png ? OMR_IMREAD_KIND_PNG : OMR_IMREAD_KIND_JPEG;
+    return p.rc;
+}
+
+int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
+                            uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
+                            int32_t *out_size, int32_t *rc)
+{
+    clear_error();
+    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
+    if (!streams || !len || !d_out || !out_size || !rc) return fail(OMR_ERR_BADARG, "null argument");
+    if (int r = check_channels(channels)) return r;
+    if (int r = check_flags(flags)) return r;
+    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "empty slot");
+    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
+    if (out_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "out_stride_bytes < rows x step_bytes");
+    for (int i = 0; i < n; i++)
+        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
+    if (n == 0) return OMR_OK;
+    const bool ignore = (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0;
+    std::vector<JdecHeader> hdr((size_t)n);
+    std::vector<PdecHeader> png_hdr((size_t)n);
+    std::vector<uint8_t> is_png((size_t)n, 0);
+    std::vector<int32_t> skip((size_t)n, 0);
+    int good = 0;
+    for (int i = 0; i < n; i++) {
+        const Parsed p = parse_stream(streams[i], len[i], ignore, &hdr[(size_t)i], &png_hdr[(size_t)i]);
+        is_png[(size_t)i] = p.png;
+        rc[i] = p.rc;
+        if (rc[i] == OMR_OK && p.png) rc[i] = pdec_check_channels(png_hdr[(size_t)i], channels);
+        if (rc[i] == OMR_OK && (p.rows > rows || p.cols > cols))
+            rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d as imread returns it, the slot %d x %d", i, p.rows, p.cols, rows, cols);
+        skip[(size_t)i] = rc[i] != OMR_OK;
+        out_size[2 * (size_t)i] = skip[(size_t)i] ? 0 : p.rows;
+        out_size[2 * (size_t)i + 1] = skip[(size_t)i] ? 0 : p.cols;
+        good += !skip[(size_t)i];
+    }
+    if (good == 0) return OMR_OK;  // every stream refused: the codes are in rc, there is no device work
+    clear_error();
+    if (int r = have_device()) return r;
+    LeasedStream st;
+    if (int r = st.create()) return r;
+    const int r = imread_decode_device(streams, len, hdr.data(), png_hdr.data(), is_png.data(), skip.data(), n, channels, ignore, d_out,
+                                       out_stride_bytes, step_bytes, rc, st.s);
+    for (int i = 0; r == OMR_OK && i < n; i++)
+        if (rc[i]) out_size[2 * (size_t)i] = out_size[2 * (size_t)i + 1] = 0;
+    return r;
+}
+
+int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t flags, omr_image_owned *dst)
+{
+    clear_error();
+    if (!stream || len < 0 || !dst) return fail(OMR_ERR_BADARG, "null argument");
+    if (int r = check_channels(channels)) return r;
+    if (int r = check_flags(flags)) return r;
+    const bool ignore = (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0;
+    std::vector<JdecHeader> h(1);
+    std::vector<PdecHeader> ph(1);
+    const Parsed p = parse_stream(stream, len, ignore, &h[0], &ph[0]);
+    int r = p.rc;
+    if (!r && p.png) r = pdec_check_channels(ph[0], channels);
+    if (r) return r;
+    if ((r = have_device())) return r;
+    LeasedStream st;
+    if ((r = st.create())) return r;
+    const int64_t step = (int64_t)p.cols * channels, bytes = step * p.rows;
+    DrainOnExit drain{st.s};
+    DevBuf out;
+    OMR_HIP(out.alloc((size_t)bytes));
+    const uint8_t is_png = p.png;
+    int32_t rc1 = 0;
+    if ((r = imread_decode_device(&stream, &len, h.data(), ph.data(), &is_png, nullptr, 1, channels, ignore, out.as<uint8_t>(), bytes, step,
+                                  &rc1, st.s)))
+        return r;
+    if (rc1) return fail(rc1, "the image data is damaged (what its decoder, omr_jpeg_decode or omr_png_decode, reports as OMR_ERR_ASSERT)");
+    *dst = omr_image_owned{nullptr, p.rows, p.cols, channels, step};
+    dst->data = (uint8_t *)malloc((size_t)bytes);
+    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
+    r = staged_d2h(dst->data, out.p, (size_t)bytes, st.s);
+    if (r) omr_image_free(dst);
+    return r;
+}
+
+}  // extern "C"

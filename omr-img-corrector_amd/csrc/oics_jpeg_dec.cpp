@@ -218,9 +218,10 @@ int decode_group(const uint8_t *const *streams, const int64_t *len, const JdecHe
 
 }  // namespace
 
-int omr::jdec_parse(const uint8_t *s, int64_t len, JdecHeader *h)
+int omr::jdec_parse(const uint8_t *s, int64_t len, JdecHeader *h, bool refuse_orientation)
 {
     h->rows = h->cols = h->ncomp = h->hs = h->vs = h->ri = 0;
+    h->orient = 1;
     h->data = 0;
     if (len < 4 || s[0] != 0xFF || s[1] != 0xD8) return fail(OMR_ERR_BADARG, "not a JPEG stream: no SOI");
     uint8_t qt[4][64];
@@ -316,7 +317,8 @@ int omr::jdec_parse(const uint8_t *s, int64_t len, JdecHeader *h)
     if (adobe) return fail(OMR_ERR_NOTIMPL, "streams with an Adobe APP14 segment are not implemented");
     if (nf == 3 && !jfif && frame[0][0] == 'R' && frame[1][0] == 'G' && frame[2][0] == 'B')
         return fail(OMR_ERR_NOTIMPL, "component ids R G B (not YCbCr) are not implemented");
-    if (orient != 1) return fail(OMR_ERR_NOTIMPL, "EXIF orientation %d is not implemented (imread would turn the image)", orient);
+    h->orient = orient;
+    if (orient != 1 && refuse_orientation) return fail(OMR_ERR_NOTIMPL, "EXIF orientation %d is not implemented (imread would turn the image)", orient);
     for (int i = 0; i < nf; i++) {
         const bool ok = i == 0 ? (frame[0][1] == 1 && frame[0][2] == 1) || (nf == 3 && frame[0][1] == 2 && frame[0][2] <= 2 && frame[0][2] >= 1)
                                : frame[i][1] == 1 && frame[i][2] == 1;

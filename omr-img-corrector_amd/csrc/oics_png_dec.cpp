@@ -178,6 +178,7 @@ bool omr::pdec_is_png(const uint8_t *s, int64_t len) { return len >= 8 && !memcm
 int omr::pdec_parse(const uint8_t *s, int64_t len, PdecHeader *h)
 {
     h->rows = h->cols = h->color_type = h->depth = h->npal = 0;
+    h->orient = 1;
     h->idat.clear(), h->critical.clear(), h->idat_bytes = 0;
     memset(h->pal, 0, sizeof h->pal);
     if (!pdec_is_png(s, len)) return fail(OMR_ERR_BADARG, "not a PNG stream: no signature");
@@ -226,6 +227,7 @@ int omr::pdec_parse(const uint8_t *s, int64_t len, PdecHeader *h)
         }
         p += 12 + n;
     }
+    h->orient = orient;
     if (!have_ihdr) return fail(OMR_ERR_BADARG, "no IHDR");
     if (h->idat.empty()) return fail(OMR_ERR_BADARG, "no IDAT");
     if (h->color_type == 3 && !have_plte) return fail(OMR_ERR_BADARG, "a paletted image without PLTE");

@@ -74,6 +74,7 @@ struct PdecPiece {
 struct PdecHeader {
     int32_t rows = 0, cols = 0, color_type = 0, depth = 0;
     int32_t npal = 0;
+    int32_t orient = 1;  // the eXIf chunk's orientation (1: none); anything else is refused
     uint8_t pal[768];
     std::vector<PdecPiece> idat;
     std::vector<PdecPiece> critical;  // every critical chunk from its type field on: type + payload, the CRC behind

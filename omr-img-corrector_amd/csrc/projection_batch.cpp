@@ -28,6 +28,7 @@
 #include "hough_host.hpp"
 #include "jpeg.hpp"
 #include "jpeg_dec.hpp"
+#include "orient.hpp"
 #include "png_dec.hpp"
 #include "png_enc.hpp"
 #include "stream_sink.hpp"
@@ -545,7 +546,7 @@ int streams_per_call(const StreamArgs &a, const std::vector<int> &idx)
         omr_image_owned img{nullptr, 0, 0, 0, 0}, rot{nullptr, 0, 0, 0, 0};
         uint8_t *bytes = nullptr;
         int64_t cap = 0, used = 0;
-        int rc = a.is_png[k] ? omr_png_decode(a.streams[k], a.len[k], a.cn, &img) : omr_jpeg_decode(a.streams[k], a.len[k], a.cn, &img);
+        int rc = omr_imread(a.streams[k], a.len[k], a.cn, 0, &img);
         const omr_image view{img.data, img.rows, img.cols, img.channels, img.step_bytes};
         if (!rc) rc = omr_get_angle_with_projections(&view, a.max_angle, a.step, a.scale, 1, &a.angles[k]);
         if (!rc && a.out) {
@@ -599,25 +600,24 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
     std::vector<int64_t> zlen;
     std::vector<JdecHeader> zhdr;
     std::vector<PdecHeader> zpng;
-    std::vector<int32_t> zskip, zskip_png, zrc;
+    std::vector<uint8_t> zkind;
+    std::vector<int32_t> zrc;
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
         // the chunk's streams -> the scan slots, decoded on the device; a bucket may hold both kinds: each decoder fills
         // its own members' slots and skips the other's
+        // (JPEG members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer of the
+        // chunk, which one launch turns into their slots)
         zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z);
-        zskip.assign((size_t)z, 0), zskip_png.assign((size_t)z, 0), zrc.assign((size_t)z, 0);
-        int pngs = 0;
+        zkind.resize((size_t)z), zrc.assign((size_t)z, 0);
         for (int j = 0; j < z; j++) {
             const int k = idx[(size_t)(j0 + j)];
-            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k];
-            if (a.is_png[k]) zpng[(size_t)j] = a.png_hdr[k], zskip[(size_t)j] = 1, pngs++;
-            else zhdr[(size_t)j] = a.hdr[k], zskip_png[(size_t)j] = 1;
+            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k], zkind[(size_t)j] = a.is_png[k];
+            if (a.is_png[k]) zpng[(size_t)j] = a.png_hdr[k];
+            else zhdr[(size_t)j] = a.hdr[k];
         }
-        if (pngs < z && (rc = jpeg_decode_device(zs.data(), zlen.data(), zhdr.data(), zskip.data(), z, cn, din.as<uint8_t>(),
-                                                 in_stride, row, zrc.data(), st.s)))
-            return rc;
-        if (pngs && (rc = png_decode_device(zs.data(), zlen.data(), zpng.data(), zskip_png.data(), z, cn, din.as<uint8_t>(),
-                                            in_stride, row, zrc.data(), st.s)))
+        if ((rc = imread_decode_device(zs.data(), zlen.data(), zhdr.data(), zpng.data(), zkind.data(), nullptr, z, cn, false,
+                                       din.as<uint8_t>(), in_stride, row, zrc.data(), st.s)))
             return rc;
         rc = a.out ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
                                                         out_stride, out_step, size.data(), ang.data(), best.data())
@@ -674,9 +674,12 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
     for (int i = 0; i < n; i++) {
         hdr.emplace_back(), png_hdr.emplace_back();
         const bool png = pdec_is_png(streams[i], len[i]);
-        int rc = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back());
+        int rc = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back(), false);
         if (!rc && png) rc = pdec_check_channels(png_hdr.back(), channels);
-        const int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
+        int turn = 0;  // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
+        if (!rc && !png && (turn = imread_turn_of(hdr.back(), false)) < 0) rc = turn;
+        int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
+        if (turn > 0 && orient_transposes(hdr.back().orient)) std::swap(rows, cols);
         Working w;
         if (!rc) rc = working_size(rows, cols, scale, &w);
         if ((code[(size_t)i] = rc)) {

@@ -26,6 +26,9 @@ OMR_MORPH_ERODE, OMR_MORPH_DILATE = 0, 1
 # front-end modes of omr_projection_batch_* (include/omrdeskew.h)
 OMR_PROJECTION_FRONT_NONE, OMR_PROJECTION_FRONT_AREA_INT = 0, 1
 OMR_PROJECTION_FRONT_AREA_GENERAL, OMR_PROJECTION_FRONT_LINEAR = 2, 3
+# flags and stream kinds of omr_imread* (include/omrdeskew.h)
+OMR_IMREAD_IGNORE_ORIENTATION = 128
+OMR_IMREAD_KIND_JPEG, OMR_IMREAD_KIND_PNG = 0, 1
 
 
 class OmrImage(C.Structure):
@@ -238,6 +241,13 @@ SYMBOLS = {
                                               C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
     "omr_png_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_png_decode_stats": (C.c_int, [C.c_int32, i32p, f64p]),
+    "omr_orient_batch_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, i32p]),
+    "omr_orient": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.POINTER(OmrImageOwned)]),
+    "omr_imread_info": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, i32p, i32p, i32p, i32p, i32p]),
+    "omr_imread_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
+    "omr_imread": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_correct_default_batch_streams": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_uint16,
                                                     C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                                     f64p, i32p, i32p, C.POINTER(u8p), C.POINTER(C.c_int64)]),

@@ -232,6 +232,28 @@ def rotate_mat(src, angle, scale, flags, border_mode=0, border_value=(255.0, 255
     return TransformableMatrix(arr)
 
 
+def orient(src, orientation):
+    """omr_orient: a gray or 3-channel image turned by an EXIF orientation code 1..8 (what imread does to a JPEG that
+    carries one: OpenCV's ExifTransform, Pillow's exif_transpose) -> a new TransformableMatrix."""
+    return TransformableMatrix(_owned_call(lib().omr_orient, _mat(src), C.c_int32(int(orientation))))
+
+
+def orient_batch_device(d_src, src_stride_bytes, src_step, rows, cols, d_dst, dst_stride_bytes, dst_step, dst_rows, dst_cols,
+                        channels, sizes, orientations):
+    """omr_orient_batch_device: n device-resident images (d_src, d_dst: device addresses as ints) in slots of rows x cols,
+    image i turned by orientations[i] into the top left of its slot of dst_rows x dst_cols; sizes: None (every image fills
+    its slot) or int32 [n, 2].  -> out_size int32 [n, 2], the turned images' (rows, cols).  Synchronous."""
+    o = np.ascontiguousarray(orientations, np.int32).reshape(-1)
+    n = o.size
+    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
+    out = np.zeros((max(n, 1), 2), np.int32)
+    check(lib().omr_orient_batch_device(C.c_void_p(int(d_src)), int(src_stride_bytes), int(src_step), int(rows), int(cols),
+                                        C.c_void_p(int(d_dst)), int(dst_stride_bytes), int(dst_step), int(dst_rows),
+                                        int(dst_cols), int(channels), None if sz is None else sz.ctypes.data_as(_lib.i32p),
+                                        o.ctypes.data_as(_lib.i32p), n, out.ctypes.data_as(_lib.i32p)))
+    return out[:n]
+
+
 def _angles(angles):
     a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
     return a, (a.ctypes.data_as(f64p) if a.size else None)

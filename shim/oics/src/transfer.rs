@@ -282,3 +282,21 @@ pub fn decode_png(stream: &[u8], channels: i32) -> Result<TransformableMatrix, o
     check(unsafe { ffi::omr_png_decode(stream.as_ptr(), stream.len() as i64, channels, &mut out) })?;
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
+
+/// An image turned by an EXIF orientation code 1..8 (omr_orient), on the GPU: what `imread` does to a JPEG that carries
+/// one (OpenCV's ExifTransform).  Gray or BGR, 8-bit.  Not in the reference crate.
+pub fn orient(m: &TransformableMatrix, orientation: i32) -> Result<TransformableMatrix, opencv::Error> {
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_orient(&view(&m.matrix)?, orientation, &mut out) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
+}
+
+/// What `im_read` gives for a file with these bytes, JPEG or PNG (told apart by PNG's signature), decoded on the GPU
+/// (omr_imread): `decode_jpeg` / `decode_png`, and a JPEG with an EXIF orientation 2..8 is turned as `imread` turns it.
+/// `flags`: 0, or `ImReadFlags::from(ImReadFlags::IgnoreOrientation)` (= `ffi::OMR_IMREAD_IGNORE_ORIENTATION`) to decode
+/// as stored.  Not in the reference crate.
+pub fn imread(stream: &[u8], channels: i32, flags: i32) -> Result<TransformableMatrix, opencv::Error> {
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_imread(stream.as_ptr(), stream.len() as i64, channels, flags, &mut out) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
+}
