@@ -373,6 +373,18 @@ int omr_resize(const omr_image *src, int32_t width, int32_t height, omr_image_ow
  * transfer.rs:487-519.  All pointers are device pointers; steps are row pitches in bytes. */
 int omr_rgb_to_gray_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols,
                            int32_t channels, uint8_t *d_dst, int64_t dst_step, void *stream);
+/* transfer_rgb_image_to_gray_image for a batch: n device-resident scans of one shape, 3 or 4 channels, scan i at d_src +
+ * i * src_stride_bytes (rows src_step apart), its gray image at d_dst + i * dst_stride_bytes (rows dst_step apart), in one
+ * launch (one per 65535 scans).  Every output byte is what omr_rgb_to_gray_device writes for that scan: COLOR_RGB2GRAY
+ * applied to BGR memory order (quirk B8).  Any base address and any pitch: aligned dwords are read and written along the
+ * rows, ragged row ends byte by byte, so nothing outside a row's cols * channels bytes is read and nothing outside its
+ * cols bytes is written.  Enqueues only, like omr_rgb_to_gray_device.
+ * OMR_ERR_BADARG: a null pointer, n <= 0, src_step < cols * channels, dst_step < cols, a stride below rows * step on
+ * either side, source and destination ranges that overlap.  OMR_ERR_ASSERT: an empty image, a side of 32767 or more,
+ * channels other than 3 or 4.  Every argument is checked before any device work. */
+int omr_rgb_to_gray_batch_device(const uint8_t *d_src, int32_t n, int64_t src_stride_bytes, int64_t src_step, int32_t rows,
+                                 int32_t cols, int32_t channels, uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step,
+                                 void *stream);
 /* erode(3x3 MORPH_ELLIPSE = cross, iterations = 3, BORDER_CONSTANT, default border): omr.rs:98-112 */
 int omr_erode3_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols,
                       uint8_t *d_dst, int64_t dst_step, void *stream);
@@ -1221,6 +1233,86 @@ int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams,
                                                   int32_t interp, const uint8_t border_value[4], int32_t compression,
                                                   double *angles, int32_t *best_idx, int32_t *scan_rc, uint8_t **png,
                                                   int64_t *png_len);
+
+/* ---- deskew with the Hough and FFT detectors for batches ----------------------------------------
+ * The other two legs of the reference's benchmark, core/src/main.rs:96-170: get_angle_with_hough / get_angle_with_fft on
+ * transfer_rgb_image_to_gray_image(original), then rotate_mat of the ORIGINAL by that angle, then im_write -- with the same
+ * three doors the projection leg has (device memory, host images, file contents).  Every stage is an existing one, run as
+ * it is: omr_rgb_to_gray_batch_device into the library's scratch for 3-channel scans (1-channel scans are the detector's
+ * input as they are), omr_hough_angles_batch_device (channels = 1) or omr_fft_angles_batch_device, omr_rotate_batch_device_ex
+ * on the originals.  channels is 1 or 3 (4: OMR_ERR_NOTIMPL, anything else OMR_ERR_ASSERT).
+ * For every scan i: angles[i] has the f64 bits of omr_get_angle_with_hough / omr_get_angle_with_fft on omr_rgb_to_gray of the
+ * scan, and canvas i is byte for byte omr_rotate_device_ex(scan i, angles[i], 1.0, flags, border_mode, border_value, clip).
+ * A scan in which the Hough detector finds no segment keeps omr_hough_angles_batch_device's rule -- rc[i] = OMR_ERR_ASSERT,
+ * angles[i] = 0.0 -- and has no canvas: its out_size is 0 x 0 and its slot is NOT written; the call still returns 0 and the
+ * other scans are unaffected.  The FFT detector gives such a scan the angle 0.0 and succeeds (fft.rs:197-247): rc[i] is
+ * always 0 there, and rc may be NULL.
+ *
+ * omr_detector_deskew_canvas (host only): the slot every canvas fits.  The detectors' angles are not bounded, so for
+ * OMR_CLIP_CONTAIN this is the worst case over all angles, the diagonal rounded up, for rows and cols alike (one more where
+ * the diagonal is a whole number, which rounding can exceed); rows x cols for OMR_CLIP_DEFAULT.  OMR_ERR_ASSERT: an empty
+ * image, a side or a slot of 32767 or more; OMR_ERR_BADARG: a null output, an unknown clip.
+ *
+ * omr_hough_deskew_batch_device / omr_fft_deskew_batch_device: n device-resident scans of one shape, scan i at d_scans +
+ * i * scan_stride_bytes, rows step_bytes apart; canvas i at the top left of the slot d_out + i * out_stride_bytes, rows
+ * out_step_bytes apart, its (rows, cols) in the HOST array out_size at [2i], [2i + 1]; the slot's bytes outside the canvas
+ * are not written.  angles / rc / n_lines (may be NULL) / out_size: HOST arrays of n.  The argument rules are the union of the
+ * detector's and of omr_rotate_batch_device_ex's, with the slot that of omr_detector_deskew_canvas: OMR_ERR_BADARG for a null
+ * d_scans / d_out / border_value / out_size / angles (/ rc for Hough), n <= 0, step_bytes < cols * channels, a negative scan
+ * stride, unknown flag bits, border mode or clip, out_step_bytes < channels * max_cols, out_stride_bytes < max_rows *
+ * out_step_bytes, source and destination ranges that overlap; OMR_ERR_NOTIMPL for interpolation 5..7; OMR_ERR_ASSERT for
+ * an empty or oversized image.  All are checked before any device work, and a refused call writes nothing.  Enqueues on
+ * `stream` and SYNCHRONISES it before it returns, as the detectors do. */
+int omr_detector_deskew_canvas(int32_t rows, int32_t cols, int32_t clip, int32_t *max_rows, int32_t *max_cols);
+int omr_hough_deskew_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
+                                  int32_t channels, int64_t step_bytes, double min_line_length, double max_line_gap,
+                                  int32_t flags, int32_t border_mode, const uint8_t border_value[4], int32_t clip,
+                                  uint8_t *d_out, int64_t out_stride_bytes, int64_t out_step_bytes, int32_t *out_size,
+                                  double *angles, int32_t *rc, int32_t *n_lines, void *stream);
+int omr_fft_deskew_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
+                                int32_t channels, int64_t step_bytes, double canny_threshold_1, double canny_threshold_2,
+                                double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                const uint8_t border_value[4], int32_t clip, uint8_t *d_out, int64_t out_stride_bytes,
+                                int64_t out_step_bytes, int32_t *out_size, double *angles, int32_t *rc, int32_t *n_lines,
+                                void *stream);
+/* The same for host images of any mix of shapes, 1 or 3 channels each, bucketed by (rows, cols, channels) as
+ * omr_deskew_with_projections_batch does, on the current device, up to 32 scans of a shape a run (scan and slot of an A4
+ * colour sheet are 26 + 55 MB on the device).  angles[i] / rc[i] / rotated[i] belong to srcs[i]; rotated[i] is an owned
+ * image (omr_image_free), what omr_rotate_ex gives for srcs[i] and angles[i] (BORDER_TRANSPARENT starts from zeros, as
+ * there), or has .data == NULL where rc[i] != 0.  rc may be NULL in the FFT form.  Every image is checked before any
+ * device work and an invalid one fails the whole call: nothing is written and no image is returned. */
+int omr_deskew_with_hough_batch(const omr_image *srcs, int32_t n, double min_line_length, double max_line_gap, int32_t flags,
+                                int32_t border_mode, const uint8_t border_value[4], int32_t clip, double *angles, int32_t *rc,
+                                omr_image_owned *rotated);
+int omr_deskew_with_fft_batch(const omr_image *srcs, int32_t n, double canny_threshold_1, double canny_threshold_2,
+                              double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                              const uint8_t border_value[4], int32_t clip, double *angles, int32_t *rc,
+                              omr_image_owned *rotated);
+/* ... and from file contents to file contents: the streams are baseline JPEG or PNG files, mixed, and go through the imread
+ * layer exactly as in omr_deskew_with_projections_batch_streams (headers parsed and scans bucketed by shape on the host,
+ * an EXIF-tagged JPEG turned and bucketed by its turned shape, decoded on the device straight into the scan slots); the
+ * canvases are encoded on the device, so only streams cross the link.  channels: 3 is imread(IMREAD_COLOR), 1 the gray
+ * form, as there.  format 0: out[i] is byte for byte omr_jpeg_encode(canvas, quality_or_compression); format 1:
+ * omr_png_encode's stream for that compression level, which decodes to the canvas exactly.  out[i] is malloc'ed (release
+ * with omr_bytes_free), out_len[i] bytes long.  A scan whose header its decoder refuses or finds malformed gets that code
+ * in scan_rc[i], angle 0 and no output, before any device work; one whose image data turns out damaged gets OMR_ERR_ASSERT
+ * there, as does one in which the Hough detector finds no segment, and one whose canvas slot would leave the image limit.
+ * The other scans are unaffected and the call returns 0.  out and out_len may both be NULL: the angles alone, no canvas
+ * is made.  OMR_ERR_BADARG for the call: a null streams / len / angles / scan_rc / streams[i], n < 1, a negative length,
+ * exactly one of out and out_len null, a null border_value when outputs are wanted, channels other than 1 or 3, a format
+ * other than 0 or 1, unknown flag bits, border mode or clip.  OMR_ERR_NOTIMPL: interpolation 5..7.  OMR_ERR_ASSERT, before
+ * any device work: a shape whose canvas slot the encoder cannot take (omr_jpeg_bound / omr_png_bound's refusal).  On an
+ * error of the whole call nothing is returned and nothing is left allocated. */
+int omr_deskew_with_hough_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                        double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                        const uint8_t border_value[4], int32_t clip, int32_t format,
+                                        int32_t quality_or_compression, double *angles, int32_t *scan_rc, uint8_t **out,
+                                        int64_t *out_len);
+int omr_deskew_with_fft_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                      double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                                      double max_line_gap, int32_t flags, int32_t border_mode, const uint8_t border_value[4],
+                                      int32_t clip, int32_t format, int32_t quality_or_compression, double *angles,
+                                      int32_t *scan_rc, uint8_t **out, int64_t *out_len);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

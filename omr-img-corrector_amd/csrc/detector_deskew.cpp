@@ -1,0 +1,464 @@
+// detector_deskew.cpp -- the Hough and FFT legs of the reference's benchmark (core/src/main.rs:96-170: find the angle of
+// transfer_rgb_image_to_gray_image(original), rotate_mat the ORIGINAL by it, im_write) for batches:
+//
+//   device   omr_hough_deskew_batch_device / omr_fft_deskew_batch_device (their entry points stand with their detectors in
+//            oics_hough.cpp / oics_fft.cpp): the batch gray kernel (stages.hip) into scratch for colour scans, the batch
+//            detector as it is, omr_rotate_batch_device_ex on the originals by the angles it found.
+//   host     omr_deskew_with_hough_batch / omr_deskew_with_fft_batch: host images of any mix of shapes, bucketed by shape,
+//            32 scans of a shape a run.
+//   streams  omr_deskew_with_hough_batch_streams / omr_deskew_with_fft_batch_streams: file contents in through the imread
+//            layer (oics_imread.cpp), file contents out through the device encoders; only streams cross the link.
+//
+// Scan i's angle has the per-call detector's f64 bits for omr_rgb_to_gray of the scan; its canvas is omr_rotate_device_ex's
+// for that angle, byte for byte.  No kernel of its own.
+#include <float.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/omrdeskew.h"
+#include "detector_deskew.hpp"
+#include "engine.hpp"
+#include "host_threads.hpp"
+#include "jpeg.hpp"
+#include "jpeg_dec.hpp"
+#include "orient.hpp"
+#include "png_dec.hpp"
+#include "png_enc.hpp"
+#include "stream_sink.hpp"
+
+using namespace omr;
+
+namespace {
+
+const int kDeskewChunk = 32;  // scans of a shape per run when canvases are made: omr_deskew_with_projections_batch's bound
+const int kAnglesChunk = 64;  // ... when only the angles are asked for: the detectors' own host batches' bound
+
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// the flow on checked arguments.  skip (may be null): scans that are neither detected on nor rotated (their angle 0.0,
+// their code left to the caller).  rc is never null here.  max_rows x max_cols: detector_canvas's answer; d_out may be
+// null: the angles alone.  Synchronises `s`.
+int deskew_run(const Detector &d, const uint8_t *d_scans, int n, int64_t stride, int rows, int cols, int cn, int64_t step,
+               int flags, int border_mode, const uint8_t *border_value, int clip, int max_rows, int max_cols, uint8_t *d_out,
+               int64_t out_stride, int64_t out_step, int32_t *out_size, double *angles, int32_t *rc, int32_t *n_lines,
+               const int32_t *skip, hipStream_t s)
+{
+    PoolScope scope(s);
+    DevBuf gray;
+    DrainOnExit drain{s};  // the scratch goes back on return, error returns included: nothing queued may still read it
+    const uint8_t *det = d_scans;
+    int64_t det_stride = stride, det_step = step;
+    if (cn == 3) {  // transfer_rgb_image_to_gray_image of every scan, one launch
+        const int64_t img = (int64_t)rows * cols;
+        OMR_HIP(gray.alloc((size_t)n * (size_t)img));
+        OMR_HIP(launch_rgb2gray_batch(d_scans, stride, step, rows, cols, 3, n, gray.as<uint8_t>(), img, cols, s));
+        det = gray.as<uint8_t>(), det_stride = img, det_step = cols;
+    }
+    int err;
+    if (d.fft) {
+        err = omr_fft_angles_batch_device(det, n, det_stride, rows, cols, det_step, d.canny_1, d.canny_2, d.min_line_length,
+                                          d.max_line_gap, angles, n_lines, nullptr, 0, 0, s);
+        for (int i = 0; !err && i < n; i++) rc[i] = OMR_OK;  // no segment: angle 0.0, and a success (fft.rs:197-247)
+    } else {
+        err = omr_hough_angles_batch_device(det, n, det_stride, rows, cols, 1, det_step, d.min_line_length, d.max_line_gap, angles, rc,
+                                            n_lines, nullptr, 0, 0, s);
+    }
+    if (err) return err;
+    for (int i = 0; skip && i < n; i++)
+        if (skip[i]) angles[i] = 0.0;
+    if (!d_out) return OMR_OK;
+    // rotate_mat of the ORIGINAL scans, run by run of the scans that have an angle: the slot of one without is not written
+    for (int i0 = 0; i0 < n;) {
+        if (rc[i0] != OMR_OK || (skip && skip[i0])) {
+            out_size[2 * i0] = out_size[2 * i0 + 1] = 0;
+            i0++;
+            continue;
+        }
+        int i1 = i0 + 1;
+        while (i1 < n && rc[i1] == OMR_OK && !(skip && skip[i1])) i1++;
+        if ((err = omr_rotate_batch_device_ex(d_scans + (int64_t)i0 * stride, i1 - i0, stride, step, rows, cols, cn, angles + i0, 1.0, flags,
+                                              border_mode, border_value, clip, d_out + (int64_t)i0 * out_stride, out_stride, out_step,
+                                              max_rows, max_cols, out_size + 2 * i0, s)))
+            return err;
+        i0 = i1;
+    }
+    OMR_HIP(hipStreamSynchronize(s));  // (runs of up to 3 scans only enqueue)
+    return OMR_OK;
+}
+
+// what the host and streams forms share of the call's rules: the rotate's flags, border mode and clip
+int check_rotate_args(int flags, int border_mode, int clip)
+{
+    WarpMode m;
+    int rc = rotate_ex_args(flags, border_mode, &m);
+    if (rc) return rc;
+    if (clip != OMR_CLIP_DEFAULT && clip != OMR_CLIP_CONTAIN) return fail(OMR_ERR_BADARG, "unknown clip strategy %d", clip);
+    return OMR_OK;
+}
+
+// a host image these flows take: omr_get_angle_with_hough's rules for the pointer, shape and pitch, 1 or 3 channels, and a
+// canvas slot that exists
+int check_scan(const omr_image &im, int clip)
+{
+    int rc = check_image(&im, cn_projection_batch);
+    if (rc) return rc;
+    int mr, mc;
+    return detector_canvas(im.rows, im.cols, clip, &mr, &mc);
+}
+
+// ---- host images -------------------------------------------------------------------------------------------------------
+struct HostArgs {
+    Detector d;
+    const omr_image *srcs;
+    int flags, border_mode;
+    const uint8_t *border;
+    int clip;
+    double *angles;
+    int32_t *rc;
+    omr_image_owned *rotated;
+};
+
+int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector<int> &idx)
+{
+    int mr = 0, mc = 0;
+    int rc = detector_canvas(rows, cols, a.clip, &mr, &mc);
+    if (rc) return rc;
+    // a run carries 32 scans: scan and slot of an A4 colour sheet are 26 + 55 MB on the device
+    const int m = (int)idx.size(), zmax = std::min(m, kDeskewChunk);
+    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
+    const int64_t out_step = ((int64_t)mc * cn + 3) & ~(int64_t)3, out_stride = out_step * mr;
+    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
+    if ((rc = st.create())) return rc;
+    DevBuf din, dout;
+    OMR_HIP(din.alloc((size_t)zmax * in_stride));
+    OMR_HIP(dout.alloc((size_t)zmax * out_stride));
+    std::vector<double> ang((size_t)zmax);
+    std::vector<int32_t> codes((size_t)zmax), size(2 * (size_t)zmax);
+    for (int j0 = 0; j0 < m; j0 += zmax) {
+        const int z = std::min(zmax, m - j0);
+        if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
+        // BORDER_TRANSPARENT starts from zero-filled canvases, as omr_rotate_ex does
+        if (a.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(dout.p, 0, (size_t)z * out_stride, st.s));
+        if ((rc = deskew_run(a.d, din.as<uint8_t>(), z, in_stride, rows, cols, cn, row, a.flags, a.border_mode, a.border, a.clip, mr, mc,
+                             dout.as<uint8_t>(), out_stride, out_step, size.data(), ang.data(), codes.data(), nullptr, nullptr, st.s)))
+            return rc;
+        for (int j = 0; j < z; j++) {
+            const int i = idx[(size_t)(j0 + j)];
+            a.angles[i] = ang[(size_t)j], a.rc[i] = codes[(size_t)j];
+        }
+        // canvases -> fresh host images, from several threads; a scan without an angle has none
+        if ((rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), codes.data(), idx, j0, z, a.rotated)))
+            return rc;
+    }
+    return OMR_OK;
+}
+
+// both host forms: every image checked before any device work, then bucket by bucket; the caller's arrays are written only
+// when the whole call has succeeded
+int host_form(const Detector &d, const omr_image *srcs, int n, int flags, int border_mode, const uint8_t *border, int clip,
+              double *angles, int32_t *rc_out, omr_image_owned *rotated)
+{
+    clear_error();
+    if (!srcs || n < 1 || !border || !angles || !rotated || (!d.fft && !rc_out)) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    int rc = check_rotate_args(flags, border_mode, clip);
+    if (rc) return rc;
+    ShapeBuckets b;
+    if ((rc = bucket_by_shape(srcs, n, [clip](const omr_image &im) { return check_scan(im, clip); }, &b))) return rc;
+    if ((rc = have_device())) return rc;
+    std::vector<double> ang((size_t)n, 0.0);
+    std::vector<int32_t> codes((size_t)n, OMR_OK);
+    std::vector<omr_image_owned> rot((size_t)n, omr_image_owned{nullptr, 0, 0, 0, 0});
+    const HostArgs a{d, srcs, flags, border_mode, border, clip, ang.data(), codes.data(), rot.data()};
+    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
+        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
+    if (rc) {
+        for (auto &o : rot) omr_image_free(&o);
+        return rc;
+    }
+    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
+    if (rc_out) memcpy(rc_out, codes.data(), sizeof(int32_t) * (size_t)n);
+    memcpy(rotated, rot.data(), sizeof(omr_image_owned) * (size_t)n);
+    return OMR_OK;
+}
+
+// ---- file contents in, file contents out -------------------------------------------------------------------------------
+// Everything is indexed by the accepted sheets (those whose header parsed and whose canvas slot exists), in call order.
+struct StreamArgs {
+    Detector d;
+    const uint8_t *const *streams;
+    const int64_t *len;
+    const JdecHeader *hdr;
+    const PdecHeader *png_hdr;  // sheet k is a PNG stream where is_png[k] != 0: png_hdr[k] holds, hdr[k] does not
+    const uint8_t *is_png;
+    int cn, flags, border_mode;
+    const uint8_t *border;
+    int clip, level;
+    bool png_out;
+    double *angles;
+    int32_t *scan_rc;
+    uint8_t **out;  // null (with out_len): the angles alone
+    int64_t *out_len;
+};
+
+int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<int> &idx)
+{
+    const int cn = a.cn;
+    int mr = 0, mc = 0, rc;
+    if (a.out && (rc = detector_canvas(rows, cols, a.clip, &mr, &mc))) return rc;
+    const int m = (int)idx.size(), zmax = std::min(m, a.out ? kDeskewChunk : kAnglesChunk);
+    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
+    const int64_t out_step = ((int64_t)mc * cn + 3) & ~(int64_t)3, out_stride = out_step * mr;
+    LeasedStream st;
+    if ((rc = st.create())) return rc;
+    DevBuf din, dout;
+    OMR_HIP(din.alloc((size_t)zmax * in_stride));
+    if (a.out) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
+    std::vector<double> ang((size_t)zmax);
+    std::vector<int32_t> codes((size_t)zmax), size(2 * (size_t)zmax, 0), zrc;
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    std::vector<JdecHeader> zhdr;
+    std::vector<PdecHeader> zpng;
+    std::vector<uint8_t> zkind;
+    for (int j0 = 0; j0 < m; j0 += zmax) {
+        const int z = std::min(zmax, m - j0);
+        // the chunk's streams -> the scan slots through the imread layer: each decoder fills its own members' slots, JPEG
+        // members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer and orient.hip
+        zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z);
+        zkind.resize((size_t)z), zrc.assign((size_t)z, 0);
+        for (int j = 0; j < z; j++) {
+            const int k = idx[(size_t)(j0 + j)];
+            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k], zkind[(size_t)j] = a.is_png[k];
+            if (a.is_png[k]) zpng[(size_t)j] = a.png_hdr[k];
+            else zhdr[(size_t)j] = a.hdr[k];
+        }
+        if ((rc = imread_decode_device(zs.data(), zlen.data(), zhdr.data(), zpng.data(), zkind.data(), nullptr, z, cn, false,
+                                       din.as<uint8_t>(), in_stride, row, zrc.data(), st.s)))
+            return rc;
+        // damaged image data: the slot's content means nothing.  Cleared, so that the detector finds a blank scan there
+        // whatever the slot held; its angle and canvas are not made
+        for (int j = 0; j < z; j++)
+            if (zrc[(size_t)j]) OMR_HIP(hipMemsetAsync(din.as<uint8_t>() + (size_t)j * in_stride, 255, (size_t)in_stride, st.s));
+        if (a.out && a.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(dout.p, 0, (size_t)z * out_stride, st.s));
+        if ((rc = deskew_run(a.d, din.as<uint8_t>(), z, in_stride, rows, cols, cn, row, a.flags, a.border_mode, a.border, a.clip, mr, mc,
+                             a.out ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data(), ang.data(), codes.data(), nullptr,
+                             zrc.data(), st.s)))
+            return rc;
+        for (int j = 0; j < z; j++) {
+            const int k = idx[(size_t)(j0 + j)];
+            a.scan_rc[k] = zrc[(size_t)j] ? zrc[(size_t)j] : codes[(size_t)j];
+            a.angles[k] = a.scan_rc[k] ? 0.0 : ang[(size_t)j];
+        }
+        if (!a.out) continue;
+        // the canvases stay on the device: encoded there, only the streams come down (a 0 x 0 canvas has none)
+        StreamSink sink(a.out, a.out_len, idx, j0);
+        rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s)
+                       : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s);
+        if (rc) return rc;
+    }
+    return OMR_OK;
+}
+
+int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
+                 int32_t border_mode, const uint8_t *border, int32_t clip, int32_t format, int32_t level, double *angles,
+                 int32_t *scan_rc, uint8_t **out, int64_t *out_len)
+{
+    clear_error();
+    if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
+    if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
+    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "channels must be 1 or 3, got %d", channels);
+    if (format != 0 && format != 1) return fail(OMR_ERR_BADARG, "format %d (0 = JPEG, 1 = PNG)", format);
+    for (int i = 0; i < n; i++)
+        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
+    int rc = check_rotate_args(flags, border_mode, clip);
+    if (rc) return rc;
+    const bool png_out = format == 1;
+    // the headers, on the host: a sheet its decoder refuses, or whose canvas slot leaves the image limit, keeps its code and
+    // leaves the batch here
+    std::vector<int32_t> code((size_t)n, OMR_OK);
+    std::vector<JdecHeader> hdr;
+    std::vector<PdecHeader> png_hdr;
+    std::vector<uint8_t> is_png;
+    std::vector<int> at;
+    std::vector<omr_image> views;
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    hdr.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        hdr.emplace_back(), png_hdr.emplace_back();
+        const bool png = pdec_is_png(streams[i], len[i]);
+        int r = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back(), false);
+        if (!r && png) r = pdec_check_channels(png_hdr.back(), channels);
+        int turn = 0;  // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
+        if (!r && !png && (turn = imread_turn_of(hdr.back(), false)) < 0) r = turn;
+        int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
+        if (turn > 0 && orient_transposes(hdr.back().orient)) std::swap(rows, cols);
+        int mr, mc;
+        if (!r) r = out ? detector_canvas(rows, cols, clip, &mr, &mc) : check_image_shape(rows, cols);
+        if ((code[(size_t)i] = r)) {
+            hdr.pop_back(), png_hdr.pop_back();
+            continue;
+        }
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), is_png.push_back(png);
+        views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
+    }
+    clear_error();
+    const int g = (int)at.size();
+    std::vector<double> ang((size_t)g, 0.0);
+    std::vector<int32_t> src((size_t)g, OMR_OK);
+    std::vector<uint8_t *> bytes((size_t)g, nullptr);
+    std::vector<int64_t> bytes_len((size_t)g, 0);
+    if (g) {
+        ShapeBuckets b;
+        if ((rc = bucket_by_shape(views.data(), g, [](const omr_image &) { return (int)OMR_OK; }, &b))) return rc;
+        if (out) {  // the encoders' offsets inside an image are 32-bit: a shape whose canvas slot could exceed them refuses the
+                    // call, before any device work
+            for (const ImageShape &sh : b.shapes) {
+                int mr, mc;
+                if ((rc = detector_canvas(sh.rows, sh.cols, clip, &mr, &mc))) return rc;
+                if ((rc = png_out ? penc_check_shape(mr, mc, sh.cn) : jpeg_check_scan_bits(mr, mc, sh.cn))) return rc;
+            }
+        }
+        if ((rc = have_device())) return rc;
+        const StreamArgs a{d, zs.data(), zlen.data(), hdr.data(), png_hdr.data(), is_png.data(), channels, flags, border_mode, border,
+                           clip, level, png_out, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
+        for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
+        if (rc) {
+            for (uint8_t *p : bytes) free(p);
+            return rc;
+        }
+    }
+    // every sheet is decided: the caller's arrays are written only now
+    for (int i = 0; i < n; i++) {
+        angles[i] = 0.0, scan_rc[i] = code[(size_t)i];
+        if (out) out[i] = nullptr, out_len[i] = 0;
+    }
+    for (int k = 0; k < g; k++) {
+        const int i = at[(size_t)k];
+        angles[i] = ang[(size_t)k], scan_rc[i] = src[(size_t)k];
+        if (out) out[i] = bytes[(size_t)k], out_len[i] = bytes_len[(size_t)k];
+    }
+    return OMR_OK;
+}
+
+Detector hough_detector(double min_line_length, double max_line_gap)
+{
+    Detector d;
+    d.min_line_length = min_line_length, d.max_line_gap = max_line_gap;
+    return d;
+}
+
+Detector fft_detector(double canny_1, double canny_2, double min_line_length, double max_line_gap)
+{
+    Detector d;
+    d.fft = true, d.canny_1 = canny_1, d.canny_2 = canny_2, d.min_line_length = min_line_length, d.max_line_gap = max_line_gap;
+    return d;
+}
+
+}  // namespace
+
+int omr::detector_canvas(int rows, int cols, int clip, int *max_rows, int *max_cols)
+{
+    int rc = check_image_shape(rows, cols);
+    if (rc) return rc;
+    if (clip == OMR_CLIP_DEFAULT) {
+        *max_rows = rows, *max_cols = cols;
+        return OMR_OK;
+    }
+    if (clip != OMR_CLIP_CONTAIN) return fail(OMR_ERR_BADARG, "unknown clip strategy %d", clip);
+    // transfer.rs:487-498: width = ceil(rows |sin| + cols |cos|), height = ceil(cols |sin| + rows |cos|).  Either is at
+    // most the diagonal; sin and cos of one rounded argument, two products and a sum can lift the computed value above it
+    // by a few units in the last place, which matters where the diagonal is a whole number: 16 of them are allowed for
+    const double diag = ceil(hypot((double)rows, (double)cols) * (1.0 + 16.0 * DBL_EPSILON));
+    if (diag >= 32767.0) return fail(OMR_ERR_ASSERT, "a canvas of %d x %d could reach %.0f a side (32767 or more)", cols, rows, diag);
+    *max_rows = *max_cols = (int)diag;
+    return OMR_OK;
+}
+
+int omr::detector_deskew_device(const Detector &d, const uint8_t *d_scans, int n, int64_t stride, int rows, int cols, int cn,
+                                int64_t step, int flags, int border_mode, const uint8_t *border_value, int clip, uint8_t *d_out,
+                                int64_t out_stride, int64_t out_step, int32_t *out_size, double *angles, int32_t *rc_out,
+                                int32_t *n_lines, hipStream_t s)
+{
+    clear_error();
+    // the detector's rules, then the batch rotate's: all of them before any device work
+    if (!d_scans || !d_out || !border_value || !out_size || !angles || (!d.fft && !rc_out)) return fail(OMR_ERR_BADARG, "null pointer");
+    if (n <= 0) return fail(OMR_ERR_BADARG, "empty batch");
+    int rc = check_image_shape(rows, cols);
+    if (rc || (rc = cn_projection_batch(cn))) return rc;
+    if (step < (int64_t)cols * cn) return fail(OMR_ERR_BADARG, "step_bytes too small");
+    if (stride < 0) return fail(OMR_ERR_BADARG, "negative scan stride");
+    if ((rc = check_rotate_args(flags, border_mode, clip))) return rc;
+    int mr = 0, mc = 0;
+    if ((rc = detector_canvas(rows, cols, clip, &mr, &mc))) return rc;
+    // (by division: rows x pitch of an absurd pitch would leave 64 bits)
+    if (out_step < (int64_t)mc * cn || out_stride / mr < out_step)
+        return fail(OMR_ERR_BADARG, "every output slot must hold %d x %d x %d channels (omr_detector_deskew_canvas)", mr, mc, cn);
+    // [first byte, last byte) of everything the call may read and may write
+    const uintptr_t s0 = (uintptr_t)d_scans, s1 = s0 + (uint64_t)(n - 1) * stride + (uint64_t)(rows - 1) * step + (uint64_t)cols * cn;
+    const uintptr_t t0 = (uintptr_t)d_out, t1 = t0 + (uint64_t)(n - 1) * out_stride + (uint64_t)(mr - 1) * out_step + (uint64_t)mc * cn;
+    if (s0 < t1 && t0 < s1) return fail(OMR_ERR_BADARG, "source and destination overlap");
+    if ((rc = have_device())) return rc;
+    std::vector<int32_t> codes;
+    if (!rc_out) codes.assign((size_t)n, OMR_OK), rc_out = codes.data();
+    return deskew_run(d, d_scans, n, stride, rows, cols, cn, step, flags, border_mode, border_value, clip, mr, mc, d_out, out_stride,
+                      out_step, out_size, angles, rc_out, n_lines, nullptr, s);
+}
+
+extern "C" {
+
+int omr_detector_deskew_canvas(int32_t rows, int32_t cols, int32_t clip, int32_t *max_rows, int32_t *max_cols)
+{
+    clear_error();
+    if (!max_rows || !max_cols) return fail(OMR_ERR_BADARG, "null output");
+    int mr = 0, mc = 0;
+    int rc = detector_canvas(rows, cols, clip, &mr, &mc);
+    if (rc) return rc;
+    *max_rows = mr, *max_cols = mc;
+    return OMR_OK;
+}
+
+int omr_deskew_with_hough_batch(const omr_image *srcs, int32_t n, double min_line_length, double max_line_gap, int32_t flags,
+                                int32_t border_mode, const uint8_t border_value[4], int32_t clip, double *angles, int32_t *rc,
+                                omr_image_owned *rotated)
+{
+    return host_form(hough_detector(min_line_length, max_line_gap), srcs, n, flags, border_mode, border_value, clip, angles, rc, rotated);
+}
+
+int omr_deskew_with_fft_batch(const omr_image *srcs, int32_t n, double canny_threshold_1, double canny_threshold_2,
+                              double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                              const uint8_t border_value[4], int32_t clip, double *angles, int32_t *rc, omr_image_owned *rotated)
+{
+    return host_form(fft_detector(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), srcs, n, flags, border_mode,
+                     border_value, clip, angles, rc, rotated);
+}
+
+int omr_deskew_with_hough_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                        double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                        const uint8_t border_value[4], int32_t clip, int32_t format,
+                                        int32_t quality_or_compression, double *angles, int32_t *scan_rc, uint8_t **out,
+                                        int64_t *out_len)
+{
+    return streams_form(hough_detector(min_line_length, max_line_gap), streams, len, n, channels, flags, border_mode, border_value, clip,
+                        format, quality_or_compression, angles, scan_rc, out, out_len);
+}
+
+int omr_deskew_with_fft_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                      double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                                      double max_line_gap, int32_t flags, int32_t border_mode, const uint8_t border_value[4],
+                                      int32_t clip, int32_t format, int32_t quality_or_compression, double *angles,
+                                      int32_t *scan_rc, uint8_t **out, int64_t *out_len)
+{
+    return streams_form(fft_detector(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams, len, n, channels,
+                        flags, border_mode, border_value, clip, format, quality_or_compression, angles, scan_rc, out, out_len);
+}
+
+}  // extern "C"

@@ -169,6 +169,10 @@ hipError_t launch_threshold(const uint8_t *d_src, int64_t sstep, int rows, int c
                             int thresh, int maxval, hipStream_t s);
 hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int cols, int cn, uint8_t *d_dst,
                            int64_t dstep, hipStream_t s);
+// the same for n scans of one shape (cn = 3 or 4), scan i at d_src + i * sstride, its gray image at d_dst + i * dstride:
+// one launch, any alignment and pitch on either side, nothing outside a row read or written
+hipError_t launch_rgb2gray_batch(const uint8_t *d_src, int64_t sstride, int64_t sstep, int rows, int cols, int cn, int n,
+                                 uint8_t *d_dst, int64_t dstride, int64_t dstep, hipStream_t s);
 // erode(3x3 cross) x 3 iterations fused (omr.rs:98-112)
 hipError_t launch_erode3x_cross(const uint8_t *d_src, int64_t sstep, int rows, int cols, uint8_t *d_dst, int64_t dstep,
                                 hipStream_t s);

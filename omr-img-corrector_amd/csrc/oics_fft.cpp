@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
+#include "detector_deskew.hpp"
 #include "engine.hpp"
 #include "fft.hpp"
 #include "hough.hpp"
@@ -646,6 +647,21 @@ int omr_fft_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_
     return fft_angles_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols,
                              fft_hough_params(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), angles,
                              n_lines, d_lined, lined_stride_bytes, lined_step, (hipStream_t)stream);
+}
+
+// the FFT leg of the reference's benchmark on device-resident scans: gray, this file's batch detector, rotate_mat of the
+// originals (detector_deskew.cpp)
+int omr_fft_deskew_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
+                                int32_t channels, int64_t step_bytes, double canny_threshold_1, double canny_threshold_2,
+                                double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                const uint8_t border_value[4], int32_t clip, uint8_t *d_out, int64_t out_stride_bytes,
+                                int64_t out_step_bytes, int32_t *out_size, double *angles, int32_t *rc, int32_t *n_lines, void *stream)
+{
+    Detector d;
+    d.fft = true, d.canny_1 = canny_threshold_1, d.canny_2 = canny_threshold_2;
+    d.min_line_length = min_line_length, d.max_line_gap = max_line_gap;
+    return detector_deskew_device(d, d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, flags, border_mode, border_value,
+                                  clip, d_out, out_stride_bytes, out_step_bytes, out_size, angles, rc, n_lines, (hipStream_t)stream);
 }
 
 int omr_get_angles_with_fft_batch(const omr_image *grays, int32_t n, double canny_threshold_1, double canny_threshold_2,

@@ -830,6 +830,30 @@ int omr_rgb_to_gray_device(const uint8_t *d_src, int64_t src_step, int32_t rows,
     return gray_ptr(d_src, src_step, rows, cols, channels, d_dst, dst_step, (hipStream_t)stream);
 }
 
+int omr_rgb_to_gray_batch_device(const uint8_t *d_src, int32_t n, int64_t src_stride_bytes, int64_t src_step, int32_t rows,
+                                 int32_t cols, int32_t channels, uint8_t *d_dst, int64_t dst_stride_bytes, int64_t dst_step,
+                                 void *stream)
+{
+    clear_error();
+    if (!d_src || !d_dst) return fail(OMR_ERR_BADARG, "null device pointer");
+    if (n <= 0) return fail(OMR_ERR_BADARG, "batch of %d scans", n);
+    int rc = check_image_shape(rows, cols);
+    if (rc) return rc;
+    if (channels != 3 && channels != 4) return fail(OMR_ERR_ASSERT, "RGB2GRAY needs 3 or 4 channels, got %d", channels);
+    if (src_step < (int64_t)cols * channels || dst_step < cols) return fail(OMR_ERR_BADARG, "step too small");
+    // (by division: rows x pitch of an absurd pitch would leave 64 bits)
+    if (src_stride_bytes / rows < src_step || dst_stride_bytes / rows < dst_step)
+        return fail(OMR_ERR_BADARG, "scan stride smaller than a scan");
+    // [first byte, last byte) of everything the call reads and writes
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uint64_t)(n - 1) * src_stride_bytes + (uint64_t)(rows - 1) * src_step + (uint64_t)cols * channels;
+    const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uint64_t)(n - 1) * dst_stride_bytes + (uint64_t)(rows - 1) * dst_step + (uint64_t)cols;
+    if (s0 < t1 && t0 < s1) return fail(OMR_ERR_BADARG, "source and destination overlap");
+    if ((rc = have_device())) return rc;
+    OMR_HIP(launch_rgb2gray_batch(d_src, src_stride_bytes, src_step, rows, cols, channels, n, d_dst, dst_stride_bytes, dst_step,
+                                  (hipStream_t)stream));
+    return OMR_OK;
+}
+
 int omr_erode3_device(const uint8_t *d_src, int64_t src_step, int32_t rows, int32_t cols, uint8_t *d_dst,
                       int64_t dst_step, void *stream)
 {

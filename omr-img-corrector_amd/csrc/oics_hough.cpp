@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
+#include "detector_deskew.hpp"
 #include "engine.hpp"
 #include "hough.hpp"
 #include "hough_host.hpp"
@@ -710,6 +711,20 @@ int omr_hough_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t sca
     hp.max_line_gap = max_line_gap;
     return hough_angles_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels, hp, angles, rc, n_lines, d_lined,
                                lined_stride_bytes, lined_step, (hipStream_t)stream);
+}
+
+// the Hough leg of the reference's benchmark on device-resident scans: gray, this file's batch detector, rotate_mat of the
+// originals (detector_deskew.cpp)
+int omr_hough_deskew_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
+                                  int32_t channels, int64_t step_bytes, double min_line_length, double max_line_gap, int32_t flags,
+                                  int32_t border_mode, const uint8_t border_value[4], int32_t clip, uint8_t *d_out,
+                                  int64_t out_stride_bytes, int64_t out_step_bytes, int32_t *out_size, double *angles, int32_t *rc,
+                                  int32_t *n_lines, void *stream)
+{
+    Detector d;
+    d.min_line_length = min_line_length, d.max_line_gap = max_line_gap;
+    return detector_deskew_device(d, d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, flags, border_mode, border_value,
+                                  clip, d_out, out_stride_bytes, out_step_bytes, out_size, angles, rc, n_lines, (hipStream_t)stream);
 }
 
 int omr_hough_vote_select_device(const float *d_angles, const int32_t *d_offsets, int32_t n, int32_t *d_winner, void *stream)

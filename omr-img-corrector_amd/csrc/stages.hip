@@ -61,6 +61,108 @@ hipError_t launch_rgb2gray(const uint8_t *d_src, int64_t sstep, int rows, int co
 }
 
 // ------------------------------------------------------------------------------------------
+// The same conversion for a batch (omr_rgb_to_gray_batch_device): n scans of one shape, 3 or 4 channels, in one launch,
+// grid (tile, scan).  Any base address and any row pitch on either side: a lane owns the four destination pixels of one
+// ALIGNED destination dword of a row -- group g of a row starts at pixel 4 g - (row address & 3) -- and reads the CN + 1
+// aligned source dwords that cover their 4 CN bytes whatever the source's alignment, all of them issued before the first
+// is used (4 or 5 dwords in flight per lane, consecutive lanes on consecutive groups: a wave reads one contiguous piece of a
+// row), then shifts them into place with v_alignbyte_b32.  A covering dword that does not lie wholly inside the row's
+// cols x CN bytes -- only the first and the last groups of a row can have one -- is put together from the bytes that do,
+// and a group that is not wholly inside the row is done pixel by pixel: nothing outside a row is read or written.
+#define GB_GROUPS 64  // groups (destination dwords) across a tile: one wave per row of a tile
+#define GB_ROWS 16    // rows of a tile: four per lane
+
+// the aligned dword at byte `off` of a row of `len` bytes, of which only the bytes inside the row are read
+__device__ __forceinline__ uint32_t gb_load_inside(const uint8_t *__restrict__ row, int off, int len)
+{
+    if (off >= 0 && off + 4 <= len) return *(const uint32_t *)(row + off);
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (off + k >= 0 && off + k < len) v |= (uint32_t)row[off + k] << (8 * k);
+    return v;
+}
+
+template <int CN>
+__global__ __launch_bounds__(256) void rgb2gray_batch_kernel(const uint8_t *__restrict__ src, int64_t sstride, int64_t sstep,
+                                                             int rows, int cols, uint8_t *__restrict__ dst, int64_t dstride,
+                                                             int64_t dstep, int tiles_x)
+{
+    constexpr int ND = CN + 1;  // aligned dwords that cover 4 CN bytes at any alignment
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int g = tx * GB_GROUPS + (int)(threadIdx.x & (GB_GROUPS - 1));
+    const int r0 = ty * GB_ROWS + (int)(threadIdx.x / GB_GROUPS);
+    const uint8_t *S0 = src + (int64_t)blockIdx.y * sstride;
+    uint8_t *D0 = dst + (int64_t)blockIdx.y * dstride;
+#pragma unroll
+    for (int k = 0; k < GB_ROWS / 4; k++) {
+        const int y = r0 + 4 * k;
+        if (y >= rows) break;
+        const uint8_t *srow = S0 + (int64_t)y * sstep;
+        uint8_t *drow = D0 + (int64_t)y * dstep;
+        const int x0 = 4 * g - (int)((uintptr_t)drow & 3u);
+        if (x0 >= cols) continue;
+        if (x0 >= 0 && x0 + 4 <= cols) {
+            const int len = cols * CN;  // (cols < 32767: no overflow)
+            const uint32_t sh = ((uint32_t)(uintptr_t)srow + (uint32_t)(x0 * CN)) & 3u;
+            const int a0 = x0 * CN - (int)sh;  // the first covering dword, as a byte offset in the row: -3 at the least
+            uint32_t w[ND];
+            if (a0 >= 0 && a0 + 4 * ND <= len) {
+#pragma unroll
+                for (int j = 0; j < ND; j++) w[j] = *(const uint32_t *)(srow + a0 + 4 * j);
+            } else {
+#pragma unroll
+                for (int j = 0; j < ND; j++) w[j] = gb_load_inside(srow, a0 + 4 * j, len);
+            }
+            uint32_t b[CN];  // the group's 4 CN bytes, in order
+#pragma unroll
+            for (int j = 0; j < CN; j++) b[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
+            uint32_t g0, g1, g2, g3;
+            if (CN == 3) {  // p0.c0 p0.c1 p0.c2 p1.c0 | p1.c1 p1.c2 p2.c0 p2.c1 | p2.c2 p3.c0 p3.c1 p3.c2
+                g0 = bgr_gray(b[0] & 255u, (b[0] >> 8) & 255u, (b[0] >> 16) & 255u);
+                g1 = bgr_gray(b[0] >> 24, b[1] & 255u, (b[1] >> 8) & 255u);
+                g2 = bgr_gray((b[1] >> 16) & 255u, b[1] >> 24, b[2] & 255u);
+                g3 = bgr_gray((b[2] >> 8) & 255u, (b[2] >> 16) & 255u, b[2] >> 24);
+            } else {
+                g0 = bgr_gray(b[0] & 255u, (b[0] >> 8) & 255u, (b[0] >> 16) & 255u);
+                g1 = bgr_gray(b[1] & 255u, (b[1] >> 8) & 255u, (b[1] >> 16) & 255u);
+                g2 = bgr_gray(b[2] & 255u, (b[2] >> 8) & 255u, (b[2] >> 16) & 255u);
+                g3 = bgr_gray(b[CN - 1] & 255u, (b[CN - 1] >> 8) & 255u, (b[CN - 1] >> 16) & 255u);
+            }
+            *(uint32_t *)(drow + x0) = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+        } else {  // the row begins or ends inside this group
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int x = x0 + j;
+                if (x >= 0 && x < cols) {
+                    const uint8_t *P = srow + (int64_t)x * CN;
+                    drow[x] = (uint8_t)bgr_gray(P[0], P[1], P[2]);
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_rgb2gray_batch(const uint8_t *d_src, int64_t sstride, int64_t sstep, int rows, int cols, int cn, int n,
+                                 uint8_t *d_dst, int64_t dstride, int64_t dstep, hipStream_t s)
+{
+    // a row's first group may start up to 3 pixels before the row: (cols + 3) pixels in groups of 4
+    const int tiles_x = ((cols + 6) / 4 + GB_GROUPS - 1) / GB_GROUPS, tiles_y = (rows + GB_ROWS - 1) / GB_ROWS;
+    for (int i0 = 0; i0 < n; i0 += 65535) {  // (one launch for any batch a grid's y takes)
+        const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(n - i0 < 65535 ? n - i0 : 65535));
+        const uint8_t *S = d_src + (int64_t)i0 * sstride;
+        uint8_t *D = d_dst + (int64_t)i0 * dstride;
+        if (cn == 3)
+            hipLaunchKernelGGL(rgb2gray_batch_kernel<3>, grid, dim3(256), 0, s, S, sstride, sstep, rows, cols, D, dstride, dstep, tiles_x);
+        else
+            hipLaunchKernelGGL(rgb2gray_batch_kernel<4>, grid, dim3(256), 0, s, S, sstride, sstep, rows, cols, D, dstride, dstep, tiles_x);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------
 // erode(3x3 cross, iterations = 3, border = +inf), the three passes fused in LDS: a 64 x 16 output
 // tile with a halo of 3; positions outside the image stay +inf (255) in every pass, exactly as
 // three separate cv::erode calls would treat them.

@@ -121,6 +121,8 @@ SYMBOLS = {
     "omr_get_projection_standard_deviations": (C.c_int, [C.POINTER(OmrImage), f64p, f64p]),
     "omr_rgb_to_gray_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                          C.c_void_p]),
+    "omr_rgb_to_gray_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "omr_erode3_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "omr_resize_area_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                          C.c_int32, C.c_int32, C.c_void_p]),
@@ -270,6 +272,24 @@ SYMBOLS = {
                                                                 C.c_int32, C.c_uint16, C.c_double, C.c_double, C.c_int32, u8p,
                                                                 C.c_int32, f64p, i32p, i32p, C.POINTER(u8p),
                                                                 C.POINTER(C.c_int64)]),
+    "omr_detector_deskew_canvas": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, i32p, i32p]),
+    "omr_hough_deskew_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                                C.c_double, C.c_double, C.c_int32, C.c_int32, u8p, C.c_int32, C.c_void_p,
+                                                C.c_int64, C.c_int64, i32p, f64p, i32p, i32p, C.c_void_p]),
+    "omr_fft_deskew_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                              C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, u8p,
+                                              C.c_int32, C.c_void_p, C.c_int64, C.c_int64, i32p, f64p, i32p, i32p, C.c_void_p]),
+    "omr_deskew_with_hough_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, u8p,
+                                              C.c_int32, f64p, i32p, C.POINTER(OmrImageOwned)]),
+    "omr_deskew_with_fft_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.c_int32, C.c_int32, u8p, C.c_int32, f64p, i32p, C.POINTER(OmrImageOwned)]),
+    "omr_deskew_with_hough_batch_streams": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                                      C.c_double, C.c_double, C.c_int32, C.c_int32, u8p, C.c_int32, C.c_int32,
+                                                      C.c_int32, f64p, i32p, C.POINTER(u8p), C.POINTER(C.c_int64)]),
+    "omr_deskew_with_fft_batch_streams": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                                    C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, u8p,
+                                                    C.c_int32, C.c_int32, C.c_int32, f64p, i32p, C.POINTER(u8p),
+                                                    C.POINTER(C.c_int64)]),
     "omr_scale": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.POINTER(OmrImageOwned)]),
     "omr_shrink_to": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_resize": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.POINTER(OmrImageOwned)]),

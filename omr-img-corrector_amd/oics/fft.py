@@ -5,6 +5,7 @@ import numpy as np
 
 from ._lib import OmrImage, OmrImageOwned, check, f64p, i32p, lib
 from .hough import LINED_COLOR, _take, lined_picture as _lined_picture, lined_picture_batch_device as _lined_batch
+from . import transfer as _transfer
 from .transfer import _mat, as_image
 
 
@@ -78,3 +79,40 @@ def get_angles_with_fft(grays, canny_threshold_1, canny_threshold_2, min_line_le
     if not want_pictures:
         return angles
     return angles, [_take(owned[i]) for i in range(n)]
+
+
+def deskew_device(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, canny_threshold_1, canny_threshold_2,
+                  min_line_length, max_line_gap, flags, border_mode, border_value, clip_strategy, d_out, out_stride_bytes,
+                  out_step_bytes, stream=None):
+    """omr_fft_deskew_batch_device: the FFT leg of the reference's benchmark on n same-shape device-resident scans of 1 or 3
+    channels (d_scans, d_out: device addresses as ints) -- gray, get_angle_with_fft, rotate_mat of the ORIGINAL scan by its
+    angle into the top left of its slot (every slot holds transfer.detector_deskew_canvas's answer).  Returns (angles, rc,
+    n_lines, sizes): angles[i] has the per-call detector's bits (0.0 without a segment), rc is all 0, sizes[i] the
+    canvas's (rows, cols).  Synchronises `stream`."""
+    return _transfer._detector_deskew_device("omr_fft_deskew_batch_device",
+                                             (canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), d_scans, n,
+                                             scan_stride_bytes, rows, cols, channels, step_bytes, flags, border_mode, border_value,
+                                             clip_strategy, d_out, out_stride_bytes, out_step_bytes, stream)
+
+
+def deskew(srcs, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, flags=1, border_mode=0,
+           border_value=(255, 255, 255, 0), clip_strategy=1):
+    """omr_deskew_with_fft_batch: the same for host images of any mix of shapes, 1 or 3 channels each.  Returns (angles,
+    images): images[i] is what transfer.rotate_mat gives for srcs[i] and angles[i] (an array).  An invalid image fails the
+    whole call."""
+    ang, _, images = _transfer._detector_deskew("omr_deskew_with_fft_batch",
+                                                (canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), srcs, flags,
+                                                border_mode, border_value, clip_strategy)
+    return ang, images
+
+
+def deskew_streams(streams, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, flags=1, border_mode=0,
+                   border_value=(255, 255, 255, 0), clip_strategy=1, channels=3, png=False, level=100, want_out=True):
+    """omr_deskew_with_fft_batch_streams: the same from file contents (baseline JPEG or PNG, mixed, read as imread reads
+    them) to file contents (JPEG at quality `level`, or png=True: PNG at compression `level`), decoded and encoded on the
+    device.  Returns (angles, scan_rc, outputs): outputs[i] bytes, None where scan_rc[i] != 0 (a refused or damaged file);
+    want_out=False: the angles alone, outputs is None."""
+    return _transfer._detector_deskew_streams("omr_deskew_with_fft_batch_streams",
+                                              (canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams,
+                                              channels, flags, border_mode, border_value, clip_strategy, 1 if png else 0, level,
+                                              want_out)

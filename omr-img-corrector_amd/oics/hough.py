@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import OmrImage, OmrImageOwned, check, f64p, i32p, lib, u8p
+from . import transfer as _transfer
 from .transfer import _mat, as_image
 
 
@@ -124,3 +125,34 @@ def get_angles_with_hough(grays, min_line_length, max_line_gap, want_pictures=Fa
     if not want_pictures:
         return angles, rc
     return angles, rc, [_take(owned[i]) if owned[i].data else None for i in range(n)]
+
+
+def deskew_device(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, min_line_length, max_line_gap, flags,
+                  border_mode, border_value, clip_strategy, d_out, out_stride_bytes, out_step_bytes, stream=None):
+    """omr_hough_deskew_batch_device: the Hough leg of the reference's benchmark on n same-shape device-resident scans of 1
+    or 3 channels (d_scans, d_out: device addresses as ints) -- gray, get_angle_with_hough, rotate_mat of the ORIGINAL scan
+    by its angle into the top left of its slot (every slot holds transfer.detector_deskew_canvas's answer).  Returns
+    (angles, rc, n_lines, sizes): angles[i] has the per-call detector's bits, sizes[i] the canvas's (rows, cols); a scan
+    without a segment has rc -215, angle 0.0, size (0, 0) and an untouched slot.  Synchronises `stream`."""
+    return _transfer._detector_deskew_device("omr_hough_deskew_batch_device", (min_line_length, max_line_gap), d_scans, n,
+                                             scan_stride_bytes, rows, cols, channels, step_bytes, flags, border_mode, border_value,
+                                             clip_strategy, d_out, out_stride_bytes, out_step_bytes, stream)
+
+
+def deskew(srcs, min_line_length, max_line_gap, flags=1, border_mode=0, border_value=(255, 255, 255, 0), clip_strategy=1):
+    """omr_deskew_with_hough_batch: the same for host images of any mix of shapes, 1 or 3 channels each.  Returns
+    (angles, rc, images): images[i] is what transfer.rotate_mat gives for srcs[i] and angles[i] (an array), None where
+    rc[i] != 0.  An invalid image fails the whole call."""
+    return _transfer._detector_deskew("omr_deskew_with_hough_batch", (min_line_length, max_line_gap), srcs, flags, border_mode,
+                                      border_value, clip_strategy)
+
+
+def deskew_streams(streams, min_line_length, max_line_gap, flags=1, border_mode=0, border_value=(255, 255, 255, 0),
+                   clip_strategy=1, channels=3, png=False, level=100, want_out=True):
+    """omr_deskew_with_hough_batch_streams: the same from file contents (baseline JPEG or PNG, mixed, read as imread reads
+    them) to file contents (JPEG at quality `level`, or png=True: PNG at compression `level`), decoded and encoded on the
+    device.  Returns (angles, scan_rc, outputs): outputs[i] bytes, None where scan_rc[i] != 0 (a refused or damaged file,
+    or a scan without a segment); want_out=False: the angles alone, outputs is None."""
+    return _transfer._detector_deskew_streams("omr_deskew_with_hough_batch_streams", (min_line_length, max_line_gap), streams,
+                                              channels, flags, border_mode, border_value, clip_strategy, 1 if png else 0, level,
+                                              want_out)

@@ -146,6 +146,83 @@ def transfer_rgb_image_to_gray_image(src):
     return TransformableMatrix(out)
 
 
+def rgb_to_gray_batch(d_src, n, src_stride_bytes, src_step, rows, cols, channels, d_dst, dst_stride_bytes, dst_step, stream=None):
+    """omr_rgb_to_gray_batch_device: transfer_rgb_image_to_gray_image of n same-shape device-resident scans of 3 or 4
+    channels (d_src, d_dst: device addresses as ints) in one launch, scan i at d_src + i * src_stride_bytes, its gray image
+    at d_dst + i * dst_stride_bytes; byte for byte the per-call conversion, any alignment and pitch.  Enqueues only."""
+    check(lib().omr_rgb_to_gray_batch_device(C.c_void_p(int(d_src)) if d_src else None, int(n), int(src_stride_bytes), int(src_step),
+                                             int(rows), int(cols), int(channels), C.c_void_p(int(d_dst)) if d_dst else None,
+                                             int(dst_stride_bytes), int(dst_step), C.c_void_p(int(stream)) if stream else None))
+
+
+def detector_deskew_canvas(rows, cols, clip_strategy=RotateClipStrategy.CONTAIN):
+    """omr_detector_deskew_canvas (host only): (max_rows, max_cols), the slot that holds rotate_mat's canvas of a rows x
+    cols image at any angle -- what hough.deskew_device / fft.deskew_device ask of every output slot."""
+    mr, mc = C.c_int32(), C.c_int32()
+    check(lib().omr_detector_deskew_canvas(int(rows), int(cols), int(clip_strategy), C.byref(mr), C.byref(mc)))
+    return mr.value, mc.value
+
+
+def _detector_deskew_device(symbol, detector_args, d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, flags,
+                            border_mode, border_value, clip_strategy, d_out, out_stride_bytes, out_step_bytes, stream):
+    """omr_hough_deskew_batch_device / omr_fft_deskew_batch_device -> (angles, rc, n_lines, sizes)"""
+    n = int(n)
+    angles = np.zeros(max(n, 1), np.float64)
+    rc = np.zeros(max(n, 1), np.int32)
+    n_lines = np.zeros(max(n, 1), np.int32)
+    sizes = np.zeros((max(n, 1), 2), np.int32)
+    b = np.array([int(v) for v in border_value], np.uint8)
+    check(getattr(lib(), symbol)(C.c_void_p(int(d_scans)) if d_scans else None, n, int(scan_stride_bytes), int(rows), int(cols),
+                                 int(channels), int(step_bytes), *[float(v) for v in detector_args], int(flags), int(border_mode),
+                                 b.ctypes.data_as(u8p), int(clip_strategy), C.c_void_p(int(d_out)) if d_out else None,
+                                 int(out_stride_bytes), int(out_step_bytes), sizes.ctypes.data_as(_lib.i32p),
+                                 angles.ctypes.data_as(f64p), rc.ctypes.data_as(_lib.i32p), n_lines.ctypes.data_as(_lib.i32p),
+                                 C.c_void_p(int(stream)) if stream else None))
+    return angles[:n], rc[:n], n_lines[:n], sizes[:n]
+
+
+def _detector_deskew(symbol, detector_args, srcs, flags, border_mode, border_value, clip_strategy):
+    """omr_deskew_with_hough_batch / omr_deskew_with_fft_batch -> (angles, rc, [image or None])"""
+    views = [as_image(_mat(s)) for s in srcs]
+    n = len(views)
+    ims = (OmrImage * max(n, 1))(*[v[1] for v in views])
+    angles = np.zeros(max(n, 1), np.float64)
+    rc = np.zeros(max(n, 1), np.int32)
+    outs = (OmrImageOwned * max(n, 1))()
+    b = np.array([int(v) for v in border_value], np.uint8)
+    check(getattr(lib(), symbol)(ims, n, *[float(v) for v in detector_args], int(flags), int(border_mode), b.ctypes.data_as(u8p),
+                                 int(clip_strategy), angles.ctypes.data_as(f64p), rc.ctypes.data_as(_lib.i32p), outs))
+    return angles[:n], rc[:n], [_take_owned(outs[i]) if outs[i].data else None for i in range(n)]
+
+
+def _detector_deskew_streams(symbol, detector_args, streams, channels, flags, border_mode, border_value, clip_strategy, fmt,
+                             level, want_out):
+    """omr_deskew_with_hough_batch_streams / omr_deskew_with_fft_batch_streams -> (angles, scan_rc, [bytes or None] or None)"""
+    bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
+            for s in streams]
+    bufs = [b if b.size else np.zeros(1, np.uint8) for b in bufs]
+    n = len(bufs)
+    sp = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    sl = np.array([len(s) for s in streams] + [0], np.int64)
+    angles = np.zeros(max(n, 1), np.float64)
+    rc = np.zeros(max(n, 1), np.int32)
+    ptrs = (u8p * max(n, 1))()
+    lens = np.zeros(max(n, 1), np.int64)
+    b = np.array([int(v) for v in border_value], np.uint8)
+    check(getattr(lib(), symbol)(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), *[float(v) for v in detector_args],
+                                 int(flags), int(border_mode), b.ctypes.data_as(u8p), int(clip_strategy), int(fmt), int(level),
+                                 angles.ctypes.data_as(f64p), rc.ctypes.data_as(_lib.i32p), ptrs if want_out else None,
+                                 lens.ctypes.data_as(C.POINTER(C.c_int64)) if want_out else None))
+    out = None
+    if want_out:
+        out = [None] * n
+        for i in range(n):
+            if ptrs[i]:
+                out[i] = C.string_at(ptrs[i], int(lens[i]))
+                lib().omr_bytes_free(ptrs[i])
+    return angles[:n], rc[:n], out
+
+
 def transfer_gray_image_to_thresh_binary(src):
     """transfer.rs:294-301"""
     a, im = as_image(_mat(src))

@@ -1,9 +1,11 @@
 //! `oics::fft` (reference: packages/lib/src/fft.rs) -> omr_get_fft_image / omr_get_angle_with_fft / _ex,
 //! and the batch form omr_get_angles_with_fft_batch.
-use crate::bridge::{check, into_mat, view};
+use crate::bridge::{border_bytes, check, into_mat, view};
 use crate::ffi;
+use crate::projection::files_through;
 use crate::transfer::TransformableMatrix;
-use opencv::core::{Mat, Vector};
+use crate::types::RotateClipStrategy;
+use opencv::core::{Mat, Scalar, Vector};
 use opencv::imgcodecs;
 use opencv::prelude::*;
 use std::path::Path;
@@ -94,4 +96,56 @@ pub fn get_angles_with_fft_with_pictures(
     // every picture is taken over (and so released) even when an earlier one fails to convert
     let mats: Vec<opencv::Result<Mat>> = lined.into_iter().map(into_mat).collect();
     mats.into_iter().enumerate().map(|(i, m)| Ok((angles[i], m?))).collect()
+}
+
+/// The FFT leg of the reference's benchmark (core/src/main.rs:133-170) for a batch: `get_angle_with_fft` on
+/// `transfer_rgb_image_to_gray_image` of every image, then `rotate_mat` of the ORIGINAL by its angle
+/// (omr_deskew_with_fft_batch).  Images of any mix of shapes, 1 or 3 channels each; result i belongs to image i: the
+/// angle the per-call function returns (same f64 bits; 0.0 for a scan without a segment) with what `rotate_mat` gives
+/// for it.  Not in the reference crate.
+pub fn deskew_with_fft(
+    srcs: &[&TransformableMatrix],
+    canny_threshold_1: f64,
+    canny_threshold_2: f64,
+    min_line_length: f64,
+    max_line_gap: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+) -> opencv::Result<Vec<(f64, Mat)>> {
+    let n = srcs.len();
+    let views: Vec<ffi::OmrImage> = srcs.iter().map(|s| view(s.get_mat())).collect::<opencv::Result<_>>()?;
+    let border = border_bytes(border_value);
+    let mut angles = vec![0.0f64; n];
+    let mut outs: Vec<ffi::OmrImageOwned> = (0..n).map(|_| ffi::OmrImageOwned::empty()).collect();
+    check(unsafe {
+        ffi::omr_deskew_with_fft_batch(views.as_ptr(), n as i32, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), angles.as_mut_ptr(), std::ptr::null_mut(), outs.as_mut_ptr())
+    })?;
+    // every image is taken over (and so released) even when an earlier one fails to convert
+    let mats: Vec<opencv::Result<Mat>> = outs.into_iter().map(into_mat).collect();
+    mats.into_iter().enumerate().map(|(i, m)| Ok((angles[i], m?))).collect()
+}
+
+/// The same from files to files (omr_deskew_with_fft_batch_streams): baseline JPEG or PNG files in, read as imread reads
+/// them (an EXIF-tagged JPEG is turned), JPEG files at `quality` out, with nothing but file contents crossing to the GPU
+/// and back.  Returns the angle per file.  A file its decoder refuses or cannot decode fails the call with that scan's
+/// code and names it, and no output file is written.  Not in the reference crate.
+pub fn deskew_files_with_fft(
+    inputs: &[&str],
+    outputs: &[&str],
+    canny_threshold_1: f64,
+    canny_threshold_2: f64,
+    min_line_length: f64,
+    max_line_gap: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+    quality: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, jpeg, jpeg_len| unsafe {
+        ffi::omr_deskew_with_fft_batch_streams(streams, len, n, 3, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), 0, quality, angles, scan_rc, jpeg, jpeg_len)
+    })
 }

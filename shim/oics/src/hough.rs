@@ -1,9 +1,11 @@
 //! `oics::hough` (reference: packages/lib/src/hough.rs:17-100) -> omr_get_angle_with_hough / _ex,
 //! and its batch form omr_get_angles_with_hough_batch.
-use crate::bridge::{check, into_mat, view};
+use crate::bridge::{border_bytes, check, into_mat, view};
 use crate::ffi;
+use crate::projection::files_through;
 use crate::transfer::TransformableMatrix;
-use opencv::core::{Mat, Vector};
+use crate::types::RotateClipStrategy;
+use opencv::core::{Mat, Scalar, Vector};
 use opencv::imgcodecs;
 use std::path::Path;
 
@@ -100,4 +102,65 @@ pub fn get_angles_with_hough_with_pictures(
             Ok((angle, into_mat(pic)?))
         })
         .collect()
+}
+
+/// The Hough leg of the reference's benchmark (core/src/main.rs:96-132) for a batch: `get_angle_with_hough` on
+/// `transfer_rgb_image_to_gray_image` of every image, then `rotate_mat` of the ORIGINAL by its angle
+/// (omr_deskew_with_hough_batch).  Images of any mix of shapes, 1 or 3 channels each; one result per image at the image's
+/// own position: the angle the per-call function returns (same f64 bits) with what `rotate_mat` gives for it, or the
+/// per-call error for a scan without any segment.  An invalid image fails the whole batch: every entry then carries
+/// that error.  Not in the reference crate.
+pub fn deskew_with_hough(
+    srcs: &[&TransformableMatrix],
+    min_line_length: f64,
+    max_line_gap: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+) -> Vec<opencv::Result<(f64, Mat)>> {
+    let n = srcs.len();
+    let views: opencv::Result<Vec<ffi::OmrImage>> = srcs.iter().map(|s| view(s.get_mat())).collect();
+    let views = match views {
+        Ok(v) => v,
+        Err(e) => return (0..n).map(|_| Err(opencv::Error::new(e.code, e.message.clone()))).collect(),
+    };
+    let border = border_bytes(border_value);
+    let mut angles = vec![0.0f64; n];
+    let mut rc = vec![0i32; n];
+    let mut outs: Vec<ffi::OmrImageOwned> = (0..n).map(|_| ffi::OmrImageOwned::empty()).collect();
+    let call = check(unsafe {
+        ffi::omr_deskew_with_hough_batch(views.as_ptr(), n as i32, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), angles.as_mut_ptr(), rc.as_mut_ptr(), outs.as_mut_ptr())
+    });
+    if let Err(e) = call {
+        return (0..n).map(|_| Err(opencv::Error::new(e.code, e.message.clone()))).collect();
+    }
+    outs.into_iter()
+        .enumerate()
+        .map(|(i, img)| {
+            let angle = scan_result(rc[i], angles[i])?;
+            Ok((angle, into_mat(img)?))
+        })
+        .collect()
+}
+
+/// The same from files to files (omr_deskew_with_hough_batch_streams): baseline JPEG or PNG files in, read as imread reads
+/// them (an EXIF-tagged JPEG is turned), JPEG files at `quality` out, with nothing but file contents crossing to the GPU
+/// and back.  Returns the angle per file.  A file its decoder refuses or cannot decode, or a scan without any segment,
+/// fails the call with that scan's code and names it, and no output file is written.  Not in the reference crate.
+pub fn deskew_files_with_hough(
+    inputs: &[&str],
+    outputs: &[&str],
+    min_line_length: f64,
+    max_line_gap: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+    quality: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, jpeg, jpeg_len| unsafe {
+        ffi::omr_deskew_with_hough_batch_streams(streams, len, n, 3, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), 0, quality, angles, scan_rc, jpeg, jpeg_len)
+    })
 }

@@ -77,7 +77,7 @@ pub fn deskew_with_projections(
 /// `std::fs::read` per input, the one batch call `run` (streams in, streams out), then `std::fs::write` per output.  All or
 /// nothing: no file is written unless every scan was decoded and deskewed; every stream is released with omr_bytes_free
 /// on every path.
-fn files_through<F>(inputs: &[&str], outputs: &[&str], run: F) -> opencv::Result<Vec<f64>>
+pub(crate) fn files_through<F>(inputs: &[&str], outputs: &[&str], run: F) -> opencv::Result<Vec<f64>>
 where
     F: FnOnce(*mut *const u8, *const i64, i32, *mut f64, *mut i32, *mut *mut u8, *mut i64) -> i32,
 {
@@ -97,7 +97,7 @@ where
     let mut stream_len = vec![0i64; n];
     check(run(ptrs.as_mut_ptr(), lens.as_ptr(), n as i32, angles.as_mut_ptr(), scan_rc.as_mut_ptr(), streams.as_mut_ptr(), stream_len.as_mut_ptr()))?;
     let mut result: opencv::Result<()> = match (0..n).find(|&i| scan_rc[i] != 0) {
-        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("deskew_with_projections failed on {} (scan {}): the JPEG / PNG decoder or the deskew answered {}; no output file was written", inputs[i], i, scan_rc[i]))),
+        Some(i) => Err(opencv::Error::new(scan_rc[i], format!("the batch deskew failed on {} (scan {}): the JPEG / PNG decoder or the deskew answered {}; no output file was written", inputs[i], i, scan_rc[i]))),
         None => Ok(()),
     };
     for i in 0..n {

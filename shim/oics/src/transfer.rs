@@ -122,6 +122,29 @@ pub fn transfer_rgb_image_to_gray_image(src: &TransformableMatrix) -> Result<Tra
     Ok(TransformableMatrix { matrix: dst })
 }
 
+/// `transfer_rgb_image_to_gray_image` for `n` same-shape scans of 3 or 4 channels that already live in device memory
+/// (omr_rgb_to_gray_batch_device): scan i at `d_src + i * src_stride_bytes`, its gray image at `d_dst + i *
+/// dst_stride_bytes`, one launch, enqueued on `stream` (a hipStream_t, null for the default one).  Byte for byte the
+/// per-image conversion.  Not in the reference crate.
+///
+/// # Safety
+/// `d_src` and `d_dst` are device pointers that span the strides and steps given.
+pub unsafe fn rgb_images_to_gray(
+    d_src: *const u8,
+    n: i32,
+    src_stride_bytes: i64,
+    src_step: i64,
+    rows: i32,
+    cols: i32,
+    channels: i32,
+    d_dst: *mut u8,
+    dst_stride_bytes: i64,
+    dst_step: i64,
+    stream: *mut std::os::raw::c_void,
+) -> opencv::Result<()> {
+    check(ffi::omr_rgb_to_gray_batch_device(d_src, n, src_stride_bytes, src_step, rows, cols, channels, d_dst, dst_stride_bytes, dst_step, stream))
+}
+
 /// transfer.rs:294-301: threshold(127, 255, BINARY) -> omr_threshold_binary.
 pub fn transfer_gray_image_to_thresh_binary(src: &TransformableMatrix) -> Result<TransformableMatrix, opencv::Error> {
     let v = view(&src.matrix)?;
