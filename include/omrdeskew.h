@@ -1061,7 +1061,51 @@ int omr_png_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_ima
  * group records five events; results do not change.  Any output pointer may be NULL. */
 int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
 
-/* ---- imread: EXIF orientation and the two decoders behind one door -----------------------------
+/* ---- Bilevel TIFF decoding on the device --------------------------------------------------------
+ * What sheet-fed scanners write: 1-bit TIFF, CCITT Group 4 (T.6) above all.  The result is what libtiff makes of the file,
+ * byte for byte: 255 for a white pixel and 0 for a black one, replicated for 3 channels (B = G = R).
+ * Streams taken: classic TIFF in either byte order, the first IFD (imread returns page 0); BitsPerSample 1 and
+ * SamplesPerPixel 1 (either tag may be absent); Compression 1 (none), 32773 (PackBits) and 4 (T.6: pass, horizontal and
+ * every vertical mode, make-up codes up to 2560 and their repetition, an optional EOFB); Photometric 0 and 1; FillOrder 1
+ * and 2; strips with any RowsPerStrip and a short last strip, StripOffsets / StripByteCounts as SHORT or LONG, inline or
+ * out of line; T6Options 0.  channels = 1 or 3 from any of them.
+ * OMR_ERR_NOTIMPL, never a wrong picture: BigTIFF, tiles, any other depth, sample count, compression (3 / T.4 and 5 / LZW
+ * included) or photometric interpretation (a missing Photometric tag too), T6Options bit 1 (uncompressed mode), an
+ * Orientation tag other than 1 (what OpenCV 4.6 does with it is not established, as for PNG's eXIf), a T.6 image wider
+ * than 12288 columns (its lines' change positions live in LDS).
+ * OMR_ERR_BADARG, malformed structure: a stream too short for its header, an IFD, tag value or strip outside the stream, a
+ * tag of another type than SHORT or LONG, a size or RowsPerStrip of 0, an empty strip, strip counts that disagree with
+ * rows / RowsPerStrip, StripOffsets or StripByteCounts missing, a Compression 1 strip shorter than its rows, a FillOrder
+ * other than 1 or 2, T6Options bits other than bit 1.
+ * OMR_ERR_ASSERT, damaged data (the image's content is then unspecified): an invalid or an extension code, a run past the
+ * row's end or a run of 0 inside a row (T.6), a run past the strip's rows (PackBits), input that ends before the strip's
+ * rows do; a size above imread's own limits (2^20 rows or columns, 2^30 pixels), a strip of 2^28 bytes or more.  This
+ * refuses a little more than libtiff, which warns and carries on for some of these; a refused file goes to the host codec.
+ * Speed: see README.md and profiles/r24_tiff_decode.md.
+ *
+ * What the first IFD says.  Returns 0, OMR_ERR_NOTIMPL, OMR_ERR_BADARG or OMR_ERR_ASSERT by the rules above, as far as the
+ * tags decide them; the fields are filled in as far as the tags were readable (*photometric = -1: no such tag; *strips = 0
+ * unless the stream is accepted).  Any output pointer may be NULL.  Host only. */
+int omr_tiff_info(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *compression, int32_t *photometric,
+                  int32_t *fill_order, int32_t *strips);
+/* The run-length codes of ITU-T T.4 (Tables 2 and 3) as the decoder holds them, for white (black = 0) or black (1) runs:
+ * OMR_TIFF_CODES entries each of run[] (0 .. 63, the make-up runs 64 .. 1728, the extended make-up runs 1792 .. 2560),
+ * code[] (the code word as a number, its first bit the most significant of bits[] bits).  A test aid.  Host only. */
+#define OMR_TIFF_CODES 104
+int omr_tiff_code_tables(int32_t black, int32_t *run, int32_t *code, int32_t *bits);
+/* The TIFF twin of omr_png_decode_batch_device: every argument, out_size, rc and the OMR_ERR_BADARG rules for the call as
+ * there, rc[i] by the rules above. */
+int omr_tiff_decode_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                 uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
+                                 int32_t *out_size, int32_t *rc);
+/* imread of one buffer: the stream -> a packed host image of `channels` channels (release with omr_image_free). */
+int omr_tiff_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_image_owned *dst);
+/* Measurement aid, as omr_png_decode_stats: *groups = the groups of launches, stage_ms[0 .. 3] = device time summed over
+ * the groups of the upload, the PackBits kernel, the T.6 kernel, the unpack kernel.  While on, every group records five
+ * events; results do not change.  Any output pointer may be NULL. */
+int omr_tiff_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
+
+/* ---- imread: EXIF orientation and the three decoders behind one door -----------------------------
  * imread(IMREAD_COLOR) -- the first line of correct_default and of TransformableMatrix::new -- turns a JPEG by the
  * orientation its EXIF block carries; phones and sheet-fed scanners write such files for every portrait capture.  The
  * codes mean what OpenCV's ExifTransform (and Pillow's ImageOps.exif_transpose) does:
@@ -1096,8 +1140,11 @@ int omr_orient(const omr_image *src, int32_t orientation, omr_image_owned *dst);
 #define OMR_IMREAD_IGNORE_ORIENTATION 128 /* imgcodecs::IMREAD_IGNORE_ORIENTATION: decode a JPEG as stored */
 #define OMR_IMREAD_KIND_JPEG 0
 #define OMR_IMREAD_KIND_PNG 1
+#define OMR_IMREAD_KIND_TIFF 2
 /* What imread would return for this stream.  A stream that begins with PNG's eight signature bytes is a PNG
- * (*kind = OMR_IMREAD_KIND_PNG) and goes by omr_png_info's rules, every other one by omr_jpeg_info's, with one difference:
+ * (*kind = OMR_IMREAD_KIND_PNG) and goes by omr_png_info's rules, one that begins "II*\0" or "MM\0*" is a TIFF
+ * (OMR_IMREAD_KIND_TIFF: omr_tiff_info's rules, *components = 1, *orientation = its Orientation tag), every other one goes
+ * by omr_jpeg_info's, with one difference:
  * a JPEG whose EXIF orientation is 2..8 is accepted.  *rows, *cols: the size AFTER the turn (as stored with
  * OMR_IMREAD_IGNORE_ORIENTATION, or when the stream is refused); *components: 1 or 3 as stored (a PNG: 1 for colour types
  * 0 and 4, else 3); *orientation: the code found (1: none), whatever `flags` says.  flags: 0 or
@@ -1107,7 +1154,8 @@ int omr_orient(const omr_image *src, int32_t orientation, omr_image_owned *dst);
  * established: its EXIF reader is fed from JPEG markers, and eXIf support in its PNG reader may be later than 4.6. */
 int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *rows, int32_t *cols, int32_t *components,
                     int32_t *orientation, int32_t *kind);
-/* imread for a batch: omr_jpeg_decode_batch_device / omr_png_decode_batch_device (JPEG and PNG may be mixed, told apart
+/* imread for a batch: omr_jpeg_decode_batch_device / omr_png_decode_batch_device / omr_tiff_decode_batch_device (JPEG, PNG
+ * and TIFF may be mixed, told apart
  * as above; every argument, out_size, rc and the OMR_ERR_BADARG rules as theirs, plus `flags` as above), each stream by its
  * decoder's rules, except that a JPEG whose orientation is 2..8 is decoded and turned: "fits the slot" is judged on the
  * turned size, out_size holds the turned size.  Streams that need no turn are decoded straight into their slots; the
@@ -1116,7 +1164,7 @@ int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *
 int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
                             uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
                             int32_t *out_size, int32_t *rc);
-/* imread of one buffer, JPEG or PNG: the stream -> a packed host image of `channels` channels (release with
+/* imread of one buffer, JPEG, PNG or bilevel TIFF: the stream -> a packed host image of `channels` channels (release with
  * omr_image_free), turned by its EXIF orientation unless `flags` says otherwise. */
 int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t flags, omr_image_owned *dst);
 

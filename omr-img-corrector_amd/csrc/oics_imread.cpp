@@ -1,5 +1,5 @@
-// oics_imread.cpp -- host side of the orientation transforms (orient.hip) and the imread layer above the two decoders
-// (DESIGN.md section 4.23): omr_orient*, omr_imread*.  imread(IMREAD_COLOR) turns a JPEG by its EXIF orientation; the
+// oics_imread.cpp -- host side of the orientation transforms (orient.hip) and the imread layer above the three decoders
+// (DESIGN.md sections 4.23 and 4.25): omr_orient*, omr_imread*.  imread(IMREAD_COLOR) turns a JPEG by its EXIF orientation; the
 // decoders' own entry points refuse such a stream, this layer decodes it into a scratch buffer and turns it on the device.
 #include <stdlib.h>
 #include <string.h>
@@ -54,23 +54,32 @@ int check_slots(const void *p, int64_t stride, int64_t step, int rows, int cols,
     return OMR_OK;
 }
 
-// one parsed stream of the imread entry points
-struct Parsed {
-    bool png = false;
-    int rc = OMR_OK;
-    int rows = 0, cols = 0;  // as imread returns it: after the turn
-    int components = 0, orient = 1;
-};
+}  // namespace
 
-// header, kind and the turned size; h / ph: where the kind's header goes
-Parsed parse_stream(const uint8_t *s, int64_t len, bool ignore, JdecHeader *h, PdecHeader *ph)
+int omr::imread_turn_of(const JdecHeader &h, bool ignore)
 {
-    Parsed p;
-    p.png = pdec_is_png(s, len);
-    if (p.png) {
+    if (ignore || h.orient == 1) return 0;
+    if (h.orient < 1 || h.orient > 8)
+        return fail(OMR_ERR_NOTIMPL, "EXIF orientation %d is outside 1..8: what imread does with it is not established", h.orient);
+    return 1;
+}
+
+ImreadParsed omr::imread_parse(const uint8_t *s, int64_t len, int channels, bool ignore, JdecHeader *h, PdecHeader *ph, TdecHeader *th)
+{
+    ImreadParsed p;
+    if (pdec_is_png(s, len)) {
+        p.kind = IMREAD_PNG;
         p.rc = pdec_parse(s, len, ph);
         p.rows = ph->rows, p.cols = ph->cols, p.orient = ph->orient;
         p.components = ph->rows ? (ph->color_type == 0 || ph->color_type == 4 ? 1 : 3) : 0;
+        if (!p.rc && channels) p.rc = pdec_check_channels(*ph, channels);
+        return p;
+    }
+    if (tdec_is_tiff(s, len)) {
+        p.kind = IMREAD_TIFF;
+        p.rc = tdec_parse(s, len, th);
+        p.rows = th->rows, p.cols = th->cols, p.orient = th->orient;
+        p.components = th->rows ? 1 : 0;
         return p;
     }
     p.rc = jdec_parse(s, len, h, false);
@@ -80,16 +89,6 @@ Parsed parse_stream(const uint8_t *s, int64_t len, bool ignore, JdecHeader *h, P
     if (turn < 0) p.rc = turn;
     else if (turn && orient_transposes(h->orient)) std::swap(p.rows, p.cols);
     return p;
-}
-
-}  // namespace
-
-int omr::imread_turn_of(const JdecHeader &h, bool ignore)
-{
-    if (ignore || h.orient == 1) return 0;
-    if (h.orient < 1 || h.orient > 8)
-        return fail(OMR_ERR_NOTIMPL, "EXIF orientation %d is outside 1..8: what imread does with it is not established", h.orient);
-    return 1;
 }
 
 int omr::orient_device(const uint8_t *d_src, int64_t sstep, uint8_t *d_dst, int64_t dstep, int cn, std::vector<OrientImg> *recs,
@@ -111,22 +110,24 @@ int omr::orient_device(const uint8_t *d_src, int64_t sstep, uint8_t *d_dst, int6
     return OMR_OK;
 }
 
-int omr::imread_decode_device(const uint8_t *const *streams, const int64_t *len, const JdecHeader *hdr, const PdecHeader *png_hdr,
-                              const uint8_t *is_png, const int32_t *skip, int n, int channels, bool ignore, uint8_t *d_out,
-                              int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s)
+int omr::imread_decode_device(const uint8_t *const *streams, const int64_t *len, const ImreadHeaders &hd, const int32_t *skip, int n,
+                              int channels, bool ignore, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s)
 {
-    std::vector<int32_t> skip_jpeg((size_t)n, 1), skip_png((size_t)n, 1);
+    const JdecHeader *hdr = hd.jpeg;
+    std::vector<int32_t> skip_jpeg((size_t)n, 1), skip_png((size_t)n, 1), skip_tiff((size_t)n, 1);
     std::vector<int> turn;
-    int pngs = 0, direct = 0;
+    int pngs = 0, tiffs = 0, direct = 0;
     for (int i = 0; i < n; i++) {
         if (skip && skip[i]) continue;
-        if (is_png[i]) skip_png[(size_t)i] = 0, pngs++;
+        if (hd.kind[i] == IMREAD_PNG) skip_png[(size_t)i] = 0, pngs++;
+        else if (hd.kind[i] == IMREAD_TIFF) skip_tiff[(size_t)i] = 0, tiffs++;
         else if (!ignore && hdr[i].orient != 1) turn.push_back(i);
         else skip_jpeg[(size_t)i] = 0, direct++;
     }
     int r = OMR_OK;
     if (direct && (r = jpeg_decode_device(streams, len, hdr, skip_jpeg.data(), n, channels, d_out, out_stride, step, rc, s))) return r;
-    if (pngs && (r = png_decode_device(streams, len, png_hdr, skip_png.data(), n, channels, d_out, out_stride, step, rc, s))) return r;
+    if (pngs && (r = png_decode_device(streams, len, hd.png, skip_png.data(), n, channels, d_out, out_stride, step, rc, s))) return r;
+    if (tiffs && (r = tiff_decode_device(streams, len, hd.tiff, skip_tiff.data(), n, channels, d_out, out_stride, step, rc, s))) return r;
     if (turn.empty()) return OMR_OK;
 
     // the members to turn, as a run of their own: decoded as stored into scratch slots that hold the largest of them
@@ -238,12 +239,13 @@ int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *
     if (int r = check_flags(flags)) return r;
     std::vector<JdecHeader> h(1);
     PdecHeader ph;
-    const Parsed p = parse_stream(stream, len, (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0, &h[0], &ph);
+    TdecHeader th;
+    const ImreadParsed p = imread_parse(stream, len, 0, (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0, &h[0], &ph, &th);
     if (rows) *rows = p.rows;
     if (cols) *cols = p.cols;
     if (components) *components = p.components;
     if (orientation) *orientation = p.orient;
-    if (kind) *kind = p.png ? OMR_IMREAD_KIND_PNG : OMR_IMREAD_KIND_JPEG;
+    if (kind) *kind = p.kind;
     return p.rc;
 }
 
@@ -265,14 +267,14 @@ int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, i
     const bool ignore = (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0;
     std::vector<JdecHeader> hdr((size_t)n);
     std::vector<PdecHeader> png_hdr((size_t)n);
-    std::vector<uint8_t> is_png((size_t)n, 0);
+    std::vector<TdecHeader> tiff_hdr((size_t)n);
+    std::vector<uint8_t> kind((size_t)n, 0);
     std::vector<int32_t> skip((size_t)n, 0);
     int good = 0;
     for (int i = 0; i < n; i++) {
-        const Parsed p = parse_stream(streams[i], len[i], ignore, &hdr[(size_t)i], &png_hdr[(size_t)i]);
-        is_png[(size_t)i] = p.png;
+        const ImreadParsed p = imread_parse(streams[i], len[i], channels, ignore, &hdr[(size_t)i], &png_hdr[(size_t)i], &tiff_hdr[(size_t)i]);
+        kind[(size_t)i] = (uint8_t)p.kind;
         rc[i] = p.rc;
-        if (rc[i] == OMR_OK && p.png) rc[i] = pdec_check_channels(png_hdr[(size_t)i], channels);
         if (rc[i] == OMR_OK && (p.rows > rows || p.cols > cols))
             rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d as imread returns it, the slot %d x %d", i, p.rows, p.cols, rows, cols);
         skip[(size_t)i] = rc[i] != OMR_OK;
@@ -285,8 +287,8 @@ int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, i
     if (int r = have_device()) return r;
     LeasedStream st;
     if (int r = st.create()) return r;
-    const int r = imread_decode_device(streams, len, hdr.data(), png_hdr.data(), is_png.data(), skip.data(), n, channels, ignore, d_out,
-                                       out_stride_bytes, step_bytes, rc, st.s);
+    const ImreadHeaders hd{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()};
+    const int r = imread_decode_device(streams, len, hd, skip.data(), n, channels, ignore, d_out, out_stride_bytes, step_bytes, rc, st.s);
     for (int i = 0; r == OMR_OK && i < n; i++)
         if (rc[i]) out_size[2 * (size_t)i] = out_size[2 * (size_t)i + 1] = 0;
     return r;
@@ -301,9 +303,9 @@ int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t fla
     const bool ignore = (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0;
     std::vector<JdecHeader> h(1);
     std::vector<PdecHeader> ph(1);
-    const Parsed p = parse_stream(stream, len, ignore, &h[0], &ph[0]);
+    std::vector<TdecHeader> th(1);
+    const ImreadParsed p = imread_parse(stream, len, channels, ignore, &h[0], &ph[0], &th[0]);
     int r = p.rc;
-    if (!r && p.png) r = pdec_check_channels(ph[0], channels);
     if (r) return r;
     if ((r = have_device())) return r;
     LeasedStream st;
@@ -312,12 +314,12 @@ int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t fla
     DrainOnExit drain{st.s};
     DevBuf out;
     OMR_HIP(out.alloc((size_t)bytes));
-    const uint8_t is_png = p.png;
+    const uint8_t kind = (uint8_t)p.kind;
+    const ImreadHeaders hd{h.data(), ph.data(), th.data(), &kind};
     int32_t rc1 = 0;
-    if ((r = imread_decode_device(&stream, &len, h.data(), ph.data(), &is_png, nullptr, 1, channels, ignore, out.as<uint8_t>(), bytes, step,
-                                  &rc1, st.s)))
-        return r;
-    if (rc1) return fail(rc1, "the image data is damaged (what its decoder, omr_jpeg_decode or omr_png_decode, reports as OMR_ERR_ASSERT)");
+    if ((r = imread_decode_device(&stream, &len, hd, nullptr, 1, channels, ignore, out.as<uint8_t>(), bytes, step, &rc1, st.s))) return r;
+    if (rc1)
+        return fail(rc1, "the image data is damaged (what its decoder, omr_jpeg_decode, omr_png_decode or omr_tiff_decode, reports as OMR_ERR_ASSERT)");
     *dst = omr_image_owned{nullptr, p.rows, p.cols, channels, step};
     dst->data = (uint8_t *)malloc((size_t)bytes);
     if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");

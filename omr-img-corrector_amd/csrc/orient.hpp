@@ -8,6 +8,7 @@
 
 #include "jpeg_dec.hpp"
 #include "png_dec.hpp"
+#include "tiff_dec.hpp"
 
 namespace omr {
 
@@ -41,14 +42,34 @@ int orient_device(const uint8_t *d_src, int64_t sstep, uint8_t *d_dst, int64_t d
 // (2..8), OMR_ERR_NOTIMPL for a value outside 1..8.
 int imread_turn_of(const JdecHeader &h, bool ignore);
 
-// The decode of one run of parsed streams into the slots d_out + i * out_stride (rows `step` apart): PNG members
-// (is_png[i] != 0, png_hdr[i] holds) and JPEG members that need no turn (hdr[i].orient == 1, or `ignore`) go straight into
-// their slots through their decoders; JPEG members with an orientation 2..8 are decoded into a scratch buffer of the run
-// and turned into their slots by one launch of orient.hip -- no scratch and no launch when the run has none.  skip (may be
-// null): members left alone.  Every member's turned image fits its slot (checked by the caller).  rc[i] as the decoders'.
-// Synchronises `s`.
-int imread_decode_device(const uint8_t *const *streams, const int64_t *len, const JdecHeader *hdr, const PdecHeader *png_hdr,
-                         const uint8_t *is_png, const int32_t *skip, int n, int channels, bool ignore, uint8_t *d_out,
-                         int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s);
+// A stream's kind, by its first bytes: PNG's eight signature bytes, "II*\0" / "MM\0*" for a TIFF, else a JPEG.  The values
+// are those of OMR_IMREAD_KIND_*.
+enum ImreadKind : uint8_t { IMREAD_JPEG = 0, IMREAD_PNG = 1, IMREAD_TIFF = 2 };
+// the parsed headers of a run of streams: member i's header stands in the array of kind[i], the other two entries are unused
+struct ImreadHeaders {
+    const JdecHeader *jpeg;
+    const PdecHeader *png;
+    const TdecHeader *tiff;
+    const uint8_t *kind;
+};
+// What the header step of every imread entry point and of the streams flows finds for one stream.
+struct ImreadParsed {
+    int kind = IMREAD_JPEG;
+    int rc = 0;
+    int rows = 0, cols = 0;  // as imread returns it: after the turn
+    int components = 0, orient = 1;
+};
+// The header of its kind is filled in; rc by its decoder's rules, with a JPEG's orientation 2..8 accepted (and the size
+// turned) unless `ignore`, a value outside 1..8 refused.  channels: 1 or 3 adds the PNG decoder's rule for that output
+// (pdec_check_channels), 0 leaves it out.
+ImreadParsed imread_parse(const uint8_t *stream, int64_t len, int channels, bool ignore, JdecHeader *jpeg, PdecHeader *png, TdecHeader *tiff);
+
+// The decode of one run of parsed streams into the slots d_out + i * out_stride (rows `step` apart): PNG and TIFF members
+// and JPEG members that need no turn (orient == 1, or `ignore`) go straight into their slots through their decoders; JPEG
+// members with an orientation 2..8 are decoded into a scratch buffer of the run and turned into their slots by one launch
+// of orient.hip -- no scratch and no launch when the run has none.  skip (may be null): members left alone.  Every
+// member's turned image fits its slot (checked by the caller).  rc[i] as the decoders'.  Synchronises `s`.
+int imread_decode_device(const uint8_t *const *streams, const int64_t *len, const ImreadHeaders &hd, const int32_t *skip, int n,
+                         int channels, bool ignore, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s);
 
 }  // namespace omr

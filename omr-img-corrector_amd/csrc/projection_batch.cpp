@@ -518,9 +518,7 @@ namespace {
 struct StreamArgs {
     const uint8_t *const *streams;
     const int64_t *len;
-    const JdecHeader *hdr;
-    const PdecHeader *png_hdr;  // sheet k is a PNG stream where is_png[k] != 0: png_hdr[k] holds, hdr[k] does not
-    const uint8_t *is_png;
+    ImreadHeaders hd;  // sheet k's header stands in the array of its kind, hd.kind[k]
     int cn;
     uint16_t max_angle;
     double step, scale;
@@ -600,6 +598,7 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
     std::vector<int64_t> zlen;
     std::vector<JdecHeader> zhdr;
     std::vector<PdecHeader> zpng;
+    std::vector<TdecHeader> ztiff;
     std::vector<uint8_t> zkind;
     std::vector<int32_t> zrc;
     for (int j0 = 0; j0 < m; j0 += zmax) {
@@ -608,16 +607,17 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
         // its own members' slots and skips the other's
         // (JPEG members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer of the
         // chunk, which one launch turns into their slots)
-        zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z);
+        zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z), ztiff.resize((size_t)z);
         zkind.resize((size_t)z), zrc.assign((size_t)z, 0);
         for (int j = 0; j < z; j++) {
             const int k = idx[(size_t)(j0 + j)];
-            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k], zkind[(size_t)j] = a.is_png[k];
-            if (a.is_png[k]) zpng[(size_t)j] = a.png_hdr[k];
-            else zhdr[(size_t)j] = a.hdr[k];
+            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k], zkind[(size_t)j] = a.hd.kind[k];
+            if (zkind[(size_t)j] == IMREAD_PNG) zpng[(size_t)j] = a.hd.png[k];
+            else if (zkind[(size_t)j] == IMREAD_TIFF) ztiff[(size_t)j] = a.hd.tiff[k];
+            else zhdr[(size_t)j] = a.hd.jpeg[k];
         }
-        if ((rc = imread_decode_device(zs.data(), zlen.data(), zhdr.data(), zpng.data(), zkind.data(), nullptr, z, cn, false,
-                                       din.as<uint8_t>(), in_stride, row, zrc.data(), st.s)))
+        const ImreadHeaders zhd{zhdr.data(), zpng.data(), ztiff.data(), zkind.data()};
+        if ((rc = imread_decode_device(zs.data(), zlen.data(), zhd, nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, zrc.data(), st.s)))
             return rc;
         rc = a.out ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
                                                         out_stride, out_step, size.data(), ang.data(), best.data())
@@ -665,28 +665,26 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
     std::vector<int32_t> code((size_t)n, OMR_OK);
     std::vector<JdecHeader> hdr;
     std::vector<PdecHeader> png_hdr;
-    std::vector<uint8_t> is_png;
+    std::vector<TdecHeader> tiff_hdr;
+    std::vector<uint8_t> kind;
     std::vector<int> at;
     std::vector<omr_image> views;
     std::vector<const uint8_t *> zs;
     std::vector<int64_t> zlen;
     hdr.reserve((size_t)n);
     for (int i = 0; i < n; i++) {
-        hdr.emplace_back(), png_hdr.emplace_back();
-        const bool png = pdec_is_png(streams[i], len[i]);
-        int rc = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back(), false);
-        if (!rc && png) rc = pdec_check_channels(png_hdr.back(), channels);
-        int turn = 0;  // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
-        if (!rc && !png && (turn = imread_turn_of(hdr.back(), false)) < 0) rc = turn;
-        int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
-        if (turn > 0 && orient_transposes(hdr.back().orient)) std::swap(rows, cols);
+        hdr.emplace_back(), png_hdr.emplace_back(), tiff_hdr.emplace_back();
+        // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
+        const ImreadParsed ps = imread_parse(streams[i], len[i], channels, false, &hdr.back(), &png_hdr.back(), &tiff_hdr.back());
+        int rc = ps.rc;
+        const int rows = ps.rows, cols = ps.cols;
         Working w;
         if (!rc) rc = working_size(rows, cols, scale, &w);
         if ((code[(size_t)i] = rc)) {
-            hdr.pop_back(), png_hdr.pop_back();
+            hdr.pop_back(), png_hdr.pop_back(), tiff_hdr.pop_back();
             continue;
         }
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), is_png.push_back(png);
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), kind.push_back((uint8_t)ps.kind);
         views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
     }
     clear_error();
@@ -716,7 +714,7 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
         if ((rc = have_device())) return rc;
         int dev = 0;
         OMR_HIP(hipGetDevice(&dev));
-        StreamArgs a{zs.data(), zlen.data(), hdr.data(), png_hdr.data(), is_png.data(), channels, max_angle, step, scale, N, interp,
+        StreamArgs a{zs.data(), zlen.data(), ImreadHeaders{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()}, channels, max_angle, step, scale, N, interp,
                      border, quality, png_out, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
                      out ? bytes_len.data() : nullptr, dev};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);

@@ -28,7 +28,8 @@ OMR_PROJECTION_FRONT_NONE, OMR_PROJECTION_FRONT_AREA_INT = 0, 1
 OMR_PROJECTION_FRONT_AREA_GENERAL, OMR_PROJECTION_FRONT_LINEAR = 2, 3
 # flags and stream kinds of omr_imread* (include/omrdeskew.h)
 OMR_IMREAD_IGNORE_ORIENTATION = 128
-OMR_IMREAD_KIND_JPEG, OMR_IMREAD_KIND_PNG = 0, 1
+OMR_IMREAD_KIND_JPEG, OMR_IMREAD_KIND_PNG, OMR_IMREAD_KIND_TIFF = 0, 1, 2
+OMR_TIFF_CODES = 104
 
 
 class OmrImage(C.Structure):
@@ -243,6 +244,12 @@ SYMBOLS = {
                                               C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
     "omr_png_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_png_decode_stats": (C.c_int, [C.c_int32, i32p, f64p]),
+    "omr_tiff_info": (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, i32p, i32p, i32p, i32p]),
+    "omr_tiff_code_tables": (C.c_int, [C.c_int32, i32p, i32p, i32p]),
+    "omr_tiff_decode_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
+                                               C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
+    "omr_tiff_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OmrImageOwned)]),
+    "omr_tiff_decode_stats": (C.c_int, [C.c_int32, i32p, f64p]),
     "omr_orient_batch_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                           C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, i32p]),
     "omr_orient": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.POINTER(OmrImageOwned)]),

@@ -1,10 +1,10 @@
-"""imread on the device (omr_imread_*): JPEG or PNG file contents -> what imread(IMREAD_COLOR) returns, a JPEG turned by
+"""imread on the device (omr_imread_*): JPEG, PNG or bilevel TIFF file contents -> what imread(IMREAD_COLOR) returns, a JPEG turned by
 its EXIF orientation as imread does."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import OMR_IMREAD_IGNORE_ORIENTATION, OMR_IMREAD_KIND_JPEG, OMR_IMREAD_KIND_PNG  # noqa: F401
+from ._lib import OMR_IMREAD_IGNORE_ORIENTATION, OMR_IMREAD_KIND_JPEG, OMR_IMREAD_KIND_PNG, OMR_IMREAD_KIND_TIFF  # noqa: F401
 from ._lib import OmrImageOwned, check, i32p, lib
 from .transfer import _take_owned
 
@@ -17,8 +17,8 @@ def _buf(stream):
 
 def info(stream, flags=0):
     """omr_imread_info -> (rows, cols, components, orientation, kind): the size imread returns (after the turn, unless
-    flags = IGNORE_ORIENTATION), the components as stored, the EXIF orientation found (1: none) and OMR_IMREAD_KIND_JPEG
-    or _PNG.  Raises OmrError for a stream its decoder refuses (-213) or a malformed header (-5)."""
+    flags = IGNORE_ORIENTATION), the components as stored, the EXIF orientation found (1: none) and OMR_IMREAD_KIND_JPEG,
+    _PNG or _TIFF.  Raises OmrError for a stream its decoder refuses (-213) or a malformed header (-5)."""
     b = _buf(stream)
     r, c, n, o, k = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
     check(lib().omr_imread_info(b.ctypes.data, b.size, int(flags), C.byref(r), C.byref(c), C.byref(n), C.byref(o), C.byref(k)))
@@ -34,7 +34,7 @@ def decode(stream, channels=3, flags=0):
 
 
 def decode_batch_device(streams, channels, d_out, out_stride_bytes, step_bytes, rows, cols, flags=0):
-    """omr_imread_batch_device: host streams (JPEG and PNG, mixed) -> device-resident images, image i at the top left of
+    """omr_imread_batch_device: host streams (JPEG, PNG and TIFF, mixed) -> device-resident images, image i at the top left of
     the slot at d_out + i * out_stride_bytes (d_out: a device address).  Returns (out_size int32 [n, 2], rc int32 [n]):
     the images' (rows, cols) as imread returns them, 0 x 0 where rc[i] != 0.  Synchronous."""
     bufs = [_buf(s) for s in streams]

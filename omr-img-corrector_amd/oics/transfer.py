@@ -59,6 +59,12 @@ class TransformableMatrix:
         from . import png
         return cls(png.decode(stream, channels))
 
+    @classmethod
+    def from_tiff_bytes(cls, stream, channels=3):
+        """What im_read gives for a bilevel TIFF file with these bytes, decoded on the GPU (omr_tiff_decode)."""
+        from . import tiff
+        return cls(tiff.decode(stream, channels))
+
     def encode_jpeg(self, quality=100):
         """The bytes im_write(.., JPEG, quality) puts into its file (transfer.rs:169-186), encoded on the GPU
         (omr_jpeg_encode): gray or BGR."""

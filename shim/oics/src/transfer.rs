@@ -306,6 +306,16 @@ pub fn decode_png(stream: &[u8], channels: i32) -> Result<TransformableMatrix, o
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
+/// What `im_read` gives for a bilevel TIFF file with these bytes, decoded on the GPU (omr_tiff_decode): libtiff's rows as
+/// 255 / 0, byte for byte.  1-bit strips, uncompressed, PackBits or CCITT Group 4; one the decoder refuses (BigTIFF, tiles,
+/// other depths or compressions, an Orientation tag) is an error with code OMR_ERR_NOTIMPL, so that the caller can hand
+/// the file to its host codec.  Not in the reference crate.
+pub fn decode_tiff(stream: &[u8], channels: i32) -> Result<TransformableMatrix, opencv::Error> {
+    let mut out = ffi::OmrImageOwned::empty();
+    check(unsafe { ffi::omr_tiff_decode(stream.as_ptr(), stream.len() as i64, channels, &mut out) })?;
+    Ok(TransformableMatrix { matrix: into_mat(out)? })
+}
+
 /// An image turned by an EXIF orientation code 1..8 (omr_orient), on the GPU: what `imread` does to a JPEG that carries
 /// one (OpenCV's ExifTransform).  Gray or BGR, 8-bit.  Not in the reference crate.
 pub fn orient(m: &TransformableMatrix, orientation: i32) -> Result<TransformableMatrix, opencv::Error> {
@@ -314,8 +324,8 @@ pub fn orient(m: &TransformableMatrix, orientation: i32) -> Result<Transformable
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
-/// What `im_read` gives for a file with these bytes, JPEG or PNG (told apart by PNG's signature), decoded on the GPU
-/// (omr_imread): `decode_jpeg` / `decode_png`, and a JPEG with an EXIF orientation 2..8 is turned as `imread` turns it.
+/// What `im_read` gives for a file with these bytes, JPEG, PNG or bilevel TIFF (told apart by PNG's signature and TIFF's
+/// byte-order mark), decoded on the GPU (omr_imread): `decode_jpeg` / `decode_png` / `decode_tiff`, and a JPEG with an EXIF orientation 2..8 is turned as `imread` turns it.
 /// `flags`: 0, or `ImReadFlags::from(ImReadFlags::IgnoreOrientation)` (= `ffi::OMR_IMREAD_IGNORE_ORIENTATION`) to decode
 /// as stored.  Not in the reference crate.
 pub fn imread(stream: &[u8], channels: i32, flags: i32) -> Result<TransformableMatrix, opencv::Error> {
