@@ -951,13 +951,14 @@ void omr_bytes_free(uint8_t *bytes);
 
 /* ---- baseline JPEG decoding on the device ---------------------------------------------------
  * What imread returns: byte for byte libjpeg's output with its defaults (JDCT_ISLOW, fancy up-sampling, no scaling).
- * Streams taken: SOF0, 8 bit, Huffman, one interleaved scan; 1 component at 1 x 1, or 3 components (YCbCr) with Y at
- * 1 x 1, 2 x 1 or 2 x 2 and chroma at 1 x 1 (4:4:4, 4:2:2, 4:2:0); any DHT / DQT tables, with or without a restart
- * interval, any APPn / COM segments.  channels = 1 gives the Y plane (of a gray or a colour stream), channels = 3 BGR in
- * memory (B = G = R for a gray stream).
+ * Streams taken: SOF0, 8 bit, Huffman, one scan; 1 component whatever sampling factors (1..4) it declares -- its scan is
+ * not interleaved, one MCU is one block (T.81 A.2.2) -- or 3 components (YCbCr) with Y at 1 x 1, 2 x 1 or 2 x 2 and
+ * chroma at 1 x 1 (4:4:4, 4:2:2, 4:2:0); any DHT / DQT tables under any ids, with or without a restart interval, any
+ * APPn / COM segments and fill bytes before markers, intervals padded with any bits.  channels = 1 gives the Y plane (of
+ * a gray or a colour stream), channels = 3 BGR in memory (B = G = R for a gray stream).
  * OMR_ERR_NOTIMPL, never a wrong picture: SOF1 / SOF2 and the other frame types, 12-bit samples, arithmetic coding, more
- * than one scan, 4 components, other sampling factors, an Adobe APP14 segment or component ids R G B, 16-bit
- * quantisation tables, DNL, an EXIF orientation other than 1 (imread would turn the image).
+ * than one scan, 4 components, other sampling factors of a 3-component frame, an Adobe APP14 segment or component ids
+ * R G B, 16-bit quantisation tables, DNL, an EXIF orientation other than 1 (imread would turn the image).
  * OMR_ERR_BADARG: a malformed header -- no SOI, a segment running past the end, a table that SOS names but nobody
  * defined, a size of 0.  OMR_ERR_ASSERT: entropy data that ends early, runs into an invalid code, has other restart
  * markers than DRI predicts or leaves blocks over (the image's content is then unspecified); entropy data of 2^32 bits
@@ -969,7 +970,8 @@ void omr_bytes_free(uint8_t *bytes);
  * and 140 A4 sheets/s, 2.2 x and 2.3 x omr_correct_default_batch_jpeg with Pillow's decode of its inputs on 16 threads
  * inside the timed region (585 and 62).
  *
- * What a stream's header says: its size, components (1 or 3) and Y's sampling factors as in SOF (0x11, 0x21, 0x22).
+ * What a stream's header says: its size, components (1 or 3) and Y's sampling factors as in SOF (0x11, 0x21, 0x22;
+ * 0x11 for 1 component, whatever SOF declares).
  * Returns 0, OMR_ERR_NOTIMPL or OMR_ERR_BADARG by the rules above; the size is filled in whenever SOF was readable
  * (else 0).  Any output pointer may be NULL.  Host only. */
 int omr_jpeg_info(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *components, int32_t *sampling);

@@ -281,7 +281,10 @@ __device__ inline bool run_lane(const JdecHuff *tabs, const Span &s, int ny, int
 {
     bool bad = false;
     while (l.p < q.lim) {
-        const int c = l.slot < ny ? 0 : l.slot - ny + 1;
+        // the interval's blocks are done: what is left is its padding, which is not read as codes (libjpeg discards it at
+        // the marker; 0-bits or mixed bits there would otherwise decode as the start of a block that does not exist)
+        if (WRITE && b0 + cnt[0] >= nb) break;
+        const int c =l.slot < ny ? 0 : l.slot - ny + 1;
         const JdecHuff &t = tabs[l.zz == 0 ? c : 3 + c];
         const uint32_t w = peek(s, l.p);
         int len, sym;
@@ -440,8 +443,9 @@ __global__ __launch_bounds__(JDEC_LANES) void jdec_write_kernel(JdecPass p)
     uint32_t cnt[4] = {0, 0, 0, 0};
     const int ny = im.ncomp == 3 ? im.hs * im.vs : 1;
     bool bad = run_lane<true>(reinterpret_cast<const JdecHuff *>(s_tab), s, ny, im.bpm, q, l, cnt, coef, b0, nb, dcb);
-    // the interval must end between two MCUs with all its blocks and no more
-    if (q.last && (b0 + cnt[0] != nb || l.slot != 0 || l.zz != 0)) bad = true;
+    // the interval must end between two MCUs with all its blocks and no more: behind the last block less than a byte of
+    // padding, whatever its bits
+    if (q.last && (b0 + cnt[0] != nb || l.slot != 0 || l.zz != 0 || q.iend - l.p >= 8)) bad = true;
     if (bad) p.dyn[blockIdx.y].err = 1;
 }
 

@@ -319,8 +319,10 @@ int omr::jdec_parse(const uint8_t *s, int64_t len, JdecHeader *h, bool refuse_or
         return fail(OMR_ERR_NOTIMPL, "component ids R G B (not YCbCr) are not implemented");
     h->orient = orient;
     if (orient != 1 && refuse_orientation) return fail(OMR_ERR_NOTIMPL, "EXIF orientation %d is not implemented (imread would turn the image)", orient);
+    // a one-component scan is not interleaved: its MCU is one block whatever factors SOF declares (T.81 A.2.2)
+    if (nf == 1 && frame[0][1] >= 1 && frame[0][1] <= 4 && frame[0][2] >= 1 && frame[0][2] <= 4) frame[0][1] = frame[0][2] = 1;
     for (int i = 0; i < nf; i++) {
-        const bool ok = i == 0 ? (frame[0][1] == 1 && frame[0][2] == 1) || (nf == 3 && frame[0][1] == 2 && frame[0][2] <= 2 && frame[0][2] >= 1)
+        const bool ok = i == 0 ? (frame[0][1] == 1 && frame[0][2] == 1) || (frame[0][1] == 2 && frame[0][2] <= 2 && frame[0][2] >= 1)
                                : frame[i][1] == 1 && frame[i][2] == 1;
         if (!ok) return fail(OMR_ERR_NOTIMPL, "these sampling factors are not implemented (4:4:4, 4:2:2, 4:2:0)");
     }

@@ -181,8 +181,8 @@ def _parse(s, h):
     if orient != 1:
         raise Refused(NOTIMPL, "EXIF orientation %d" % orient)
     if nf == 1:
-        hs = vs = 1   # a single-component scan is not interleaved: its MCU is one block whatever SOF says
-        if (frame[0][1], frame[0][2]) != (1, 1):
+        hs = vs = 1   # a single-component scan is not interleaved: its MCU is one block whatever SOF says (T.81 A.2.2)
+        if not (1 <= frame[0][1] <= 4 and 1 <= frame[0][2] <= 4):
             raise Refused(NOTIMPL, "sampling factors")
     else:
         hs, vs = frame[0][1], frame[0][2]
@@ -345,7 +345,8 @@ def selfsync(h, data, ivals, sub_bits):
     where the lane of subsequence i stands when it crosses its end: round 0 starts every lane at its own first bit in state
     (0, 0), except an interval's first, which is right from the start; each later round restarts lane i from state[i - 1]
     where that changed in the round before, until a round changes nothing.  Then the blocks finished and the DC differences
-    summed per subsequence are scanned, and a last decode from the known states writes the coefficients.
+    summed per subsequence are scanned, and a last decode from the known states writes the coefficients; it reads no code
+    behind the interval's last block (the padding, whatever its bits), and a byte or more left there is an error.
     -> (coef, code, rounds)"""
     luts, comp, bpm = _tables(h)
     _, _, _, nm, nint = geometry(h)
@@ -366,6 +367,8 @@ def selfsync(h, data, ivals, sub_bits):
             lim = min((i + 1) * sub_bits, end)
             nblk, dsum, bad = 0, [0, 0, 0], False
             while p < lim:
+                if write is not None and write[0] + nblk >= nb:
+                    break       # the interval's blocks are done: the padding behind them is not read as codes
                 p2, slot2, zz2, done, (kind, idx, v), ok = _step(bits, luts, comp, bpm, p, slot, zz)
                 if p2 > end:        # the code runs past the interval (the padding, or a cut stream): the lane stops
                     p = end     # there, and the count of blocks and the state at the end tell which it was
@@ -407,12 +410,12 @@ def selfsync(h, data, ivals, sub_bits):
         for i in range(nsub):
             entry = (0, 0, 0) if i == 0 else state[i - 1]
             st, nblk, dsum, bad = run(i, *entry, write=(b, list(dcb)))
-            assert st == state[i] and (nblk, dsum) == info[i]
+            assert i == nsub - 1 or b + info[i][0] >= nb or (st == state[i] and (nblk, dsum) == info[i])
             if bad:
                 code = ASSERT
-            b += nblk
-            dcb = [x + y for x, y in zip(dcb, dsum)]
-        if b != nb or state[-1][1:] != (0, 0) or end - state[-1][0] >= 8:
+            b += info[i][0] if i < nsub - 1 else nblk     # the scan of the counts the rounds left
+            dcb = [x + y for x, y in zip(dcb, info[i][1])]
+        if b != nb or st[1:] != (0, 0) or end - st[0] >= 8:
             code = ASSERT
     return coef, code, rounds_max
 
