@@ -1071,18 +1071,25 @@ int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
  * every vertical mode, make-up codes up to 2560 and their repetition, an optional EOFB); Photometric 0 and 1; FillOrder 1
  * and 2; strips with any RowsPerStrip and a short last strip, StripOffsets / StripByteCounts as SHORT or LONG, inline or
  * out of line; T6Options 0.  channels = 1 or 3 from any of them.
+ * StripByteCounts may be absent (old writers): strip k then runs from its offset to the smallest strip offset greater
+ * than its own, or to the stream's end where there is none, and every check on a strip holds for that length; the decoders
+ * stop at the strip's rows, so the surplus is never read as codes.  A present tag is taken at its word: a wrong number of
+ * counts or a count of 0 stays OMR_ERR_BADARG.  A T.6 code that begins inside its strip and ends behind it is read with
+ * zeros for the missing bits, as libtiff reads it (a writer may drop a last byte that held only trailing zeros).
  * OMR_ERR_NOTIMPL, never a wrong picture: BigTIFF, tiles, any other depth, sample count, compression (3 / T.4 and 5 / LZW
  * included) or photometric interpretation (a missing Photometric tag too), T6Options bit 1 (uncompressed mode), an
  * Orientation tag other than 1 (what OpenCV 4.6 does with it is not established, as for PNG's eXIf), a T.6 image wider
  * than 12288 columns (its lines' change positions live in LDS).
  * OMR_ERR_BADARG, malformed structure: a stream too short for its header, an IFD, tag value or strip outside the stream, a
  * tag of another type than SHORT or LONG, a size or RowsPerStrip of 0, an empty strip, strip counts that disagree with
- * rows / RowsPerStrip, StripOffsets or StripByteCounts missing, a Compression 1 strip shorter than its rows, a FillOrder
+ * rows / RowsPerStrip, StripOffsets missing, a Compression 1 strip shorter than its rows, a FillOrder
  * other than 1 or 2, T6Options bits other than bit 1.
  * OMR_ERR_ASSERT, damaged data (the image's content is then unspecified): an invalid or an extension code, a run past the
  * row's end or a run of 0 inside a row (T.6), a run past the strip's rows (PackBits), input that ends before the strip's
  * rows do; a size above imread's own limits (2^20 rows or columns, 2^30 pixels), a strip of 2^28 bytes or more.  This
  * refuses a little more than libtiff, which warns and carries on for some of these; a refused file goes to the host codec.
+ * Two of these are chosen differences, streams libtiff reads without a warning: a run of 0 inside a T.6 row, and a PackBits
+ * run that passes the strip's rows (libtiff clips it).
  * Speed: see README.md and profiles/r24_tiff_decode.md.
  *
  * What the first IFD says.  Returns 0, OMR_ERR_NOTIMPL, OMR_ERR_BADARG or OMR_ERR_ASSERT by the rules above, as far as the

@@ -190,14 +190,30 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
     if (rps < 1) return fail(OMR_ERR_BADARG, "RowsPerStrip 0");
     h->rows_per_strip = (int32_t)std::min<int64_t>(rps, h->rows);
     const int64_t nstrips = ((int64_t)h->rows + h->rows_per_strip - 1) / h->rows_per_strip;
-    if (arr_at[0] < 0 || arr_at[1] < 0) return fail(OMR_ERR_BADARG, "StripOffsets or StripByteCounts missing");
-    if (arr_n[0] != nstrips || arr_n[1] != nstrips)
+    if (arr_at[0] < 0) return fail(OMR_ERR_BADARG, "StripOffsets missing");
+    // StripByteCounts may be missing (old writers): a strip then runs to the next strip offset above its own, the last
+    // one in the file to the stream's end, as libtiff estimates it.  A present tag is taken at its word.
+    const bool have_counts = arr_at[1] >= 0;
+    if (arr_n[0] != nstrips || (have_counts && arr_n[1] != nstrips))
         return fail(OMR_ERR_BADARG, "%lld strip offsets and %lld byte counts for %lld strips of %d rows", (long long)arr_n[0],
                     (long long)arr_n[1], (long long)nstrips, h->rows_per_strip);
+    auto offset_of = [&](int64_t k) -> int64_t { return arr_size[0] == 2 ? rd16(s + arr_at[0] + 2 * k, be) : rd32(s + arr_at[0] + 4 * k, be); };
+    std::vector<int64_t> sorted;
+    if (!have_counts) {
+        sorted.resize((size_t)nstrips);
+        for (int64_t k = 0; k < nstrips; k++) sorted[(size_t)k] = offset_of(k);
+        std::sort(sorted.begin(), sorted.end());
+    }
     h->strips.resize((size_t)nstrips);
     for (int64_t k = 0; k < nstrips; k++) {
-        const int64_t off = arr_size[0] == 2 ? rd16(s + arr_at[0] + 2 * k, be) : rd32(s + arr_at[0] + 4 * k, be);
-        const int64_t cnt = arr_size[1] == 2 ? rd16(s + arr_at[1] + 2 * k, be) : rd32(s + arr_at[1] + 4 * k, be);
+        const int64_t off = offset_of(k);
+        int64_t cnt;
+        if (have_counts) {
+            cnt = arr_size[1] == 2 ? rd16(s + arr_at[1] + 2 * k, be) : rd32(s + arr_at[1] + 4 * k, be);
+        } else {
+            const auto next = std::upper_bound(sorted.begin(), sorted.end(), off);
+            cnt = (next == sorted.end() ? len : *next) - off;  // < 1 or past the end where off is: refused below
+        }
         if (cnt < 1 || off < 8 || off > len || cnt > len - off)
             return fail(OMR_ERR_BADARG, "strip %lld (byte %lld, %lld bytes) lies outside the stream", (long long)k, (long long)off, (long long)cnt);
         if (cnt >= ((int64_t)1 << 28)) return fail(OMR_ERR_ASSERT, "a strip of 2^28 bytes or more: not supported");

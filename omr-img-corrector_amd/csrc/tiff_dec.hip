@@ -2,9 +2,9 @@
 // PackBits, one lane per strip; and the unpack kernel that turns packed rows into bytes of 0 / 255 in the output slots.
 //
 // Bounds.  Everything a kernel loops over is fixed on the host: a strip's byte length, its rows, the image's cols.  The
-// T.6 code reader consumes at least one bit per code and stops at the strip's bit length; a line's change positions are
-// strictly increasing and below cols, so a line holds at most cols of them (cols <= TDEC_T6_MAX_COLS, checked by the
-// parser); the PackBits loop consumes at least one input byte a turn.  Writes go to the workspace rows of the strip
+// T.6 code reader consumes at least one bit per code and takes none that begins behind the strip's bit length; a line's
+// change positions are strictly increasing and below cols, so a line holds at most cols of them (cols <=
+// TDEC_T6_MAX_COLS, checked by the parser); the PackBits loop consumes at least one input byte a turn.  Writes go to the workspace rows of the strip
 // (rows x pitch from dst_off) and, in the unpack kernel, to cols x channels bytes of rows `step` apart in the slot.
 #include <hip/hip_runtime.h>
 
@@ -93,11 +93,14 @@ struct T6Reader {
         const uint32_t v = byte(i) << 16 | byte(i + 1) << 8 | byte(i + 2);
         return (v >> (11 - (pos & 7))) & 0x1fffu;
     }
-    // false: the code reaches past the strip's end
+    // false: the code begins behind the strip's end.  One that begins inside it and ends behind it was matched with zeros
+    // for the missing bits, as libtiff reads it: a writer may drop a last byte that held only a code's trailing zeros
+    // (three at the most; no code is all zeros, so the next one finds nothing).
     __device__ bool skip(uint32_t bits)
     {
+        if (pos >= len * 8) return false;
         pos += bits;
-        return pos <= len * 8;
+        return true;
     }
 };
 

@@ -51,7 +51,7 @@ def test_accepted_variants_report_what_the_restatement_reports():
     assert len(seen) == 3 * 2 * 2 * 2
     base = _base()
     for kw in (dict(drop=(258,)), dict(drop=(277,)), dict(drop=(258, 277)), dict(drop=(278,), rps=20), dict(offsets_type=3, counts_type=3),
-               dict(drop=(293,)), dict(drop=(266,)), dict(extra=[(284, 3, [2])]), dict(extra=[(274, 3, [1])])):
+               dict(drop=(293,)), dict(drop=(266,)), dict(drop=(279,)), dict(drop=(279,), reverse=True, gap=3), dict(drop=(279,), ifd_first=True), dict(extra=[(284, 3, [2])]), dict(extra=[(274, 3, [1])])):
         h = tiff_ref.parse(base)
         strips = tiff_ref.strips_of(base) if "rps" not in kw else [b"".join(tiff_ref.strips_of(tiff_ref.pillow_tiff(
             tiff_cases.content("text", 20, 100, seed=1), "group4", 20)))]
@@ -76,7 +76,8 @@ REFUSALS = [
     ("no width", dict(drop=(256,)), -5),
     ("RowsPerStrip 0", dict(extra=[(278, 4, [0])]), -5),
     ("RowsPerStrip that disagrees with the strips", dict(extra=[(278, 4, [5])]), -5),
-    ("no StripByteCounts", dict(drop=(279,)), -5),
+    ("no StripOffsets", dict(drop=(273,)), -5),
+    ("one byte count for three strips", dict(extra=[(279, 4, [10])]), -5),
     ("an empty strip", dict(extra=[(279, 4, [0, 10, 10])]), -5),
     ("a strip offset beyond len", dict(extra=[(273, 4, [8, 1 << 20, 30])]), -5),
     ("a strip that runs past the end", dict(extra=[(279, 4, [10, 10, 1 << 20])]), -5),

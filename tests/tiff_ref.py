@@ -116,15 +116,22 @@ def parse(s):
         raise Refused(BADARG, "RowsPerStrip 0")
     rps = min(v[278], rows)
     ns = (rows + rps - 1) // rps
-    if 273 not in arr or 279 not in arr:
+    if 273 not in arr:
         raise Refused(BADARG, "no strips")
-    if arr[273][1] != ns or arr[279][1] != ns:
+    if arr[273][1] != ns or (279 in arr and arr[279][1] != ns):
         raise Refused(BADARG, "strip count")
+
+    def value(t, k):
+        return struct.unpack(e + {2: "H", 4: "I"}[arr[t][2]], s[arr[t][0] + arr[t][2] * k:arr[t][0] + arr[t][2] * (k + 1)])[0]
+    offs = [value(273, k) for k in range(ns)]
     strips = []
     rb = (cols + 7) // 8
     for k in range(ns):
-        off, ln = (struct.unpack(e + {2: "H", 4: "I"}[arr[t][2]], s[arr[t][0] + arr[t][2] * k:arr[t][0] + arr[t][2] * (k + 1)])[0]
-                   for t in (273, 279))
+        off = offs[k]
+        if 279 in arr:
+            ln = value(279, k)
+        else:  # no StripByteCounts: up to the next strip offset above this one, or to the stream's end
+            ln = min([o for o in offs if o > off] or [n]) - off
         if ln < 1 or off < 8 or off > n or ln > n - off:
             raise Refused(BADARG, "strip outside")
         if ln >= 1 << 28:
@@ -152,9 +159,10 @@ class _Bits:
         return (w >> (24 - k - (self.pos & 7))) & ((1 << k) - 1)
 
     def skip(self, k):
-        self.pos += k
-        if self.pos > self.n:
+        """a code that begins inside the data may end behind it: its missing bits were read as zeros, as libtiff does"""
+        if self.pos >= self.n:
             raise Damaged("input ends")
+        self.pos += k
 
 
 def _run(rd, colour, limit):
@@ -303,46 +311,95 @@ def decode(stream):
 
 
 # ---- the assembler ---------------------------------------------------------------------------------------------------
-def assemble(rows, cols, strips, compression, photometric=0, fill_order=1, rps=None, order="<", offsets_type=4, counts_type=4,
-             extra=(), drop=(), big=False):
-    """Strips (bytes each) -> a TIFF stream.  extra: [(tag, type, [values])] added or replacing; drop: tags left out;
-    fill_order 2 stores the strips bit-reversed (they are given in FillOrder 1)."""
-    e = order
-    if fill_order == 2:
-        strips = [bytes(s).translate(_REV) for s in strips]
-    body = b"".join(strips)
-    at = 8
-    offs = []
-    for s in strips:
-        offs.append(at)
-        at += len(s)
-    tags = {256: (4, [cols]), 257: (4, [rows]), 258: (3, [1]), 259: (3, [compression]), 262: (3, [photometric]),
-            266: (3, [fill_order]), 273: (offsets_type, offs), 277: (3, [1]), 278: (4, [rps if rps is not None else rows]),
-            279: (counts_type, [len(s) for s in strips])}
-    if compression == 4:
-        tags[293] = (4, [0])
-    for tag, typ, vals in extra:
-        tags[tag] = (typ, list(vals))
-    for tag in drop:
-        tags.pop(tag, None)
-    if len(body) & 1:
-        body += b"\0"
-    ifd = 8 + len(body)
-    ext_at = ifd + 2 + 12 * len(tags) + 4
+def _layout(strips, reverse, gap, share, odd):
+    """-> (each strip's offset in the blob, the blob): file order, gaps of 0xa5 bytes, equal strips stored once"""
+    n = len(strips)
+    rel, blob, seen = [0] * n, b"", {}
+    for k in (range(n - 1, -1, -1) if reverse else range(n)):
+        if share and strips[k] in seen:
+            rel[k] = seen[strips[k]]
+            continue
+        if odd and len(blob) & 1:  # the blob stands at an odd offset: even offsets in it are odd in the file
+            blob += b"\xa5"
+        rel[k] = seen[strips[k]] = len(blob)
+        blob += strips[k] + b"\xa5" * gap
+    return rel, blob
+
+
+def _ifd(e, at, tags, next_ifd, shuffle):
+    """the IFD that stands at `at`: count, entries, the next IFD's offset, then the values that do not fit an entry"""
+    ext_at = at + 2 + 12 * len(tags) + 4
     ext = b""
     ent = b""
-    for tag in sorted(tags):
+    order = sorted(tags)
+    if shuffle is not None:
+        np.random.RandomState(shuffle).shuffle(order)
+    for tag in order:
         typ, vals = tags[tag]
-        fmt = {1: "B", 2: "B", 3: "H", 4: "I"}[typ]  # 2: ASCII, a byte a value
-        data = struct.pack(e + fmt * len(vals), *vals)
+        if typ in (5, 10):  # RATIONAL: two LONGs a value
+            data, count = struct.pack(e + "I" * len(vals), *vals), len(vals) // 2
+        elif typ in (1, 2, 3, 4, 7):  # 2: ASCII, 7: UNDEFINED, a byte a value
+            data, count = struct.pack(e + {1: "B", 2: "B", 3: "H", 4: "I", 7: "B"}[typ] * len(vals), *vals), len(vals)
+        else:  # a type number no one knows: its value field is four bytes of something
+            data, count = struct.pack(e + "I", vals[0]), 1
         if len(data) <= 4:
             field = data.ljust(4, b"\0")
         else:
             field = struct.pack(e + "I", ext_at + len(ext))
             ext += data + (b"\0" if len(data) & 1 else b"")
-        ent += struct.pack(e + "HHI", tag, typ, len(vals)) + field
-    head = (b"II" if e == "<" else b"MM") + struct.pack(e + "HI", 43 if big else 42, ifd)
-    return head + body + struct.pack(e + "H", len(tags)) + ent + struct.pack(e + "I", 0) + ext
+        ent += struct.pack(e + "HHI", tag, typ, count) + field
+    return struct.pack(e + "H", len(tags)) + ent + struct.pack(e + "I", next_ifd) + ext
+
+
+def _page(base, next_ifd, rows, cols, strips, compression, photometric=0, fill_order=1, rps=None, order="<", offsets_type=4,
+          counts_type=4, extra=(), drop=(), ifd_first=False, odd=False, shuffle=None, reverse=False, gap=0, share=False, over=0):
+    """one picture's strips and IFD as they stand from file offset `base` (even) on -> (the IFD's offset, the bytes)"""
+    e = order
+    strips = [bytes(s) for s in strips]
+    if fill_order == 2:
+        strips = [s.translate(_REV) for s in strips]
+    rel, body = _layout(strips, reverse, gap, share, odd)
+    body += bytes(over)
+
+    def tags_for(data_at):
+        tags = {256: (4, [cols]), 257: (4, [rows]), 258: (3, [1]), 259: (3, [compression]), 262: (3, [photometric]),
+                266: (3, [fill_order]), 273: (offsets_type, [data_at + r for r in rel]), 277: (3, [1]),
+                278: (4, [rps if rps is not None else rows]), 279: (counts_type, [len(s) + over for s in strips])}
+        if compression == 4:
+            tags[293] = (4, [0])
+        for tag, typ, vals in extra:
+            tags[tag] = (typ, list(vals))
+        for tag in drop:
+            tags.pop(tag, None)
+        return tags
+
+    start = base + (1 if odd else 0)
+    if ifd_first:
+        data_at = start + len(_ifd(e, start, tags_for(0), 0, shuffle))
+        data_at += 1 if odd and not data_at & 1 else 0
+        ifd = _ifd(e, start, tags_for(data_at), next_ifd, shuffle)
+        return start, bytes(start - base) + ifd + bytes(data_at - start - len(ifd)) + body
+    data = body + (b"\0" if (start + len(body)) & 1 != (1 if odd else 0) else b"")
+    return start + len(data), bytes(start - base) + data + _ifd(e, start + len(data), tags_for(start), next_ifd, shuffle)
+
+
+def assemble(rows, cols, strips, compression, big=False, chain=None, **kw):
+    """Strips (bytes each) -> a TIFF stream.  Keywords: photometric, fill_order (2 stores the strips bit-reversed; they are
+    given in FillOrder 1), rps, order, offsets_type, counts_type; extra: [(tag, type, [values])] added or replacing; drop:
+    tags left out.  The forms a foreign writer may choose: ifd_first: the IFD in front of the strip data; odd: the IFD
+    and every strip at an odd offset; shuffle (a seed): the entries in a shuffled order; reverse: the strips in reverse
+    file order; gap: bytes between them; share: strips with equal bytes stored once; over: every byte count that much
+    larger than its strip; chain: the arguments (a dict) of a second picture, whose IFD the first one's points to."""
+    e = kw.get("order", "<")
+    ifd_at, first = _page(8, 0, rows, cols, strips, compression, **kw)
+    tail = b""
+    if chain is not None:  # the first page's length does not depend on the pointer it holds
+        first += bytes(len(first) & 1)
+        ifd2, tail = _page(8 + len(first), 0, **dict(chain, order=e))
+        ifd_at, first = _page(8, ifd2, rows, cols, strips, compression, **kw)
+        first += bytes(len(first) & 1)
+    head = (b"II" if e == "<" else b"MM") + struct.pack(e + "HI", 43 if big else 42, ifd_at)
+    return head + first + tail
 
 
 def strips_of(stream):
