@@ -36,9 +36,15 @@
 //                                   issued SL_AHEAD rows earlier belong -- an EVEN ring register: one v_mov_b64 with DST_REL
 //                                   moves a pair (an odd index is rounded down by the hardware, tools/mov64_probe.hip);
 //                                   register SL_DUMMY = 66 swallows a dummy pair; 0x8000 = M0's DST_REL bit --, then 1 dword
-//                                   = the TURN HEADER: the most segments any word of the 16 rows from this record on needs
-//                                   (1 .. 8; the kernel reads it at the first record of a turn and executes exactly that
-//                                   many slots per word).  One s_load_dwordx4 per row
+//                                   = the TURN HEADER (1 .. 8): how many slots per word the kernel executes.  The first record
+//                                   of a turn of SL_TURN rows holds the most segments any word of the turn needs (what
+//                                   oracle/slane_interp.c reads and holds every word of the turn against).  The kernel decides
+//                                   every SL_QUARTER rows: the records at rows 4, 8 and 12 of a turn hold the most segments any
+//                                   word of THEIR four rows needs, and the turn's SECOND record holds that of rows 0 .. 3 (it
+//                                   has landed at the top of a turn as the first has, and the first keeps the turn's).  Every
+//                                   other record holds the turn's maximum and is not read (slane_turn_header).  The slots
+//                                   past a word's own count are no-op pads, so any value >= the rows' own need gives the same
+//                                   words.  One s_load_dwordx4 per row
 //                  segment stream, SL_K words x S dwords per row.  A word is assembled from its segments in
 //                                   increasing bit order by funnel shifts, no masks (format v4):
 //                                     first segment : D = (ring[i] : ring[i - 1]) >> sh   read straight into the word so that
@@ -74,7 +80,8 @@ constexpr int SL_AHEAD = 4;                             // rows between a load a
 constexpr int SL_ZERO = SL_RING_ROWS * SL_RING_COLS;   // ring register that holds 0 (white runs read it)
 constexpr int SL_DUMMY = SL_ZERO + 2;                   // (even) register pair that swallows dummy fetch pairs
 constexpr int SL_PAIRS = 2;                             // fetch pairs per row
-constexpr int SL_TURN = 16;                             // rows per turn of the kernel's loop: one header per turn
+constexpr int SL_TURN = 16;                             // rows per turn of the kernel's loop
+constexpr int SL_QUARTER = 4;                           // rows between two decisions on the executed slots (slane_turn_header)
 constexpr uint32_t SL_PK_MODE = 0x60000u;               // pk >> 5 -> M0[13:12]: SRC0_REL | SRC1_REL
 constexpr uint32_t SL_COMMIT_MODE = 0x8000u;            // M0[15]: DST_REL
 constexpr int SL_PRE = 24;                              // virtual rows ahead of row 0
@@ -184,6 +191,14 @@ SL_HD inline void slane_first_segment(uint32_t &idx, uint32_t &sh, int len)
 // the records before it -- they would be virtual rows that fetch nothing -- had been swept already.
 inline int slane_records(int rows) { return (SL_PRE + rows + 63) & ~63; }
 inline int slane_exec_records(int rows) { return (SL_PRE + rows + SL_TURN - 1) & ~(SL_TURN - 1); }
+// The turn header of the record at row `row` (0 .. SL_TURN - 1) of a turn whose quarters need most[0 .. 3] slots per word: the
+// first record the turn's maximum, the second quarter 0's, rows 4 / 8 / 12 their own quarter's, the others the turn's.
+SL_HD inline uint32_t slane_turn_header(int row, const uint32_t most[SL_TURN / SL_QUARTER])
+{
+    uint32_t turn = most[0];
+    for (int i = 1; i < SL_TURN / SL_QUARTER; i++) turn = most[i] > turn ? most[i] : turn;
+    return row == 1 ? most[0] : (row > 0 && row % SL_QUARTER == 0) ? most[row / SL_QUARTER] : turn;
+}
 
 // warpAffine's integer tables of one candidate on the host (the expressions of tables_kernel, kernels.hip;
 // built -ffp-contract=off): adelta / bdelta per column, (X0, Y0) per row with round_delta = 512

@@ -157,21 +157,26 @@ __global__ __launch_bounds__(64) void slane_sched_kernel(SlaneBuild b, int ntask
     }
 }
 
-// thread = (task, turn): the turn header -- the most segments any word of the turn's SL_TURN records needs -- read back from the
-// encoded segment words (after slane_words_kernel)
+// thread = (task, turn): the turn headers -- the most segments any word of each quarter of the turn's SL_TURN records needs,
+// laid out over the records by slane_turn_header (slane_plan.cpp) -- read back from the encoded segment words (after
+// slane_words_kernel; nrec is whole turns: slane_exec_records)
 __global__ __launch_bounds__(256) void slane_turns_kernel(SlaneBuild b, int ntasks)
 {
-    const int nturns = (b.nrec + SL_TURN - 1) / SL_TURN;
+    const int nturns = b.nrec / SL_TURN;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)ntasks * nturns) return;
     const int task = (int)(i / nturns), q0 = (int)(i - (int64_t)task * nturns) * SL_TURN;
     const int S = slane_slots(b.cls[task]), RD = SL_K * S;
     const uint32_t *seg = b.prog + b.seg_off[task];
     uint32_t *fet = b.prog + b.fet_off[task];
-    uint32_t most = 1;
-    for (int q = q0; q < q0 + SL_TURN && q < b.nrec; q++)
-        for (int k = 0; k < SL_K; k++) most = max(most, (seg[(int64_t)q * RD + k * S] >> SL_NSHIFT) & 15u);
-    for (int q = q0; q < q0 + SL_TURN && q < b.nrec; q++) fet[(int64_t)q * SL_FREC + 3] = most;
+    uint32_t most[SL_TURN / SL_QUARTER];
+    for (int i4 = 0; i4 < SL_TURN / SL_QUARTER; i4++) {
+        uint32_t m = 1;
+        for (int q = q0 + i4 * SL_QUARTER; q < q0 + (i4 + 1) * SL_QUARTER; q++)
+            for (int k = 0; k < SL_K; k++) m = max(m, (seg[(int64_t)q * RD + k * S] >> SL_NSHIFT) & 15u);
+        most[i4] = m;
+    }
+    for (int q = q0; q < q0 + SL_TURN; q++) fet[(int64_t)q * SL_FREC + 3] = slane_turn_header(q - q0, most);
 }
 
 // grid (tasks, ceil(rows / 128))

@@ -218,12 +218,17 @@ bool slane_strip_program(const SlaneGeom &g, const int32_t *ad, const int32_t *b
             }
             w[0] |= (uint32_t)n << SL_NSHIFT;
         }
-    // ---- turn headers: the most segments any word of a turn of SL_TURN records needs (virtual rows: one white run)
+    // ---- turn headers: the most segments any word of a quarter of a turn needs (virtual rows: one white run), laid out over
+    // the turn's records by slane_turn_header (NREC is whole turns)
     for (int q0 = 0; q0 < NREC; q0 += SL_TURN) {
-        uint32_t most = 1;
-        for (int q = q0; q < q0 + SL_TURN && q < NREC; q++)
-            for (int k = 0; k < SL_K; k++) most = std::max(most, (seg[(size_t)q * RD + (size_t)k * S] >> SL_NSHIFT) & 15u);
-        for (int q = q0; q < q0 + SL_TURN && q < NREC; q++) fet[(size_t)q * SL_FREC + 3] = most;
+        uint32_t most[SL_TURN / SL_QUARTER];
+        for (int i = 0; i < SL_TURN / SL_QUARTER; i++) most[i] = 1;
+        for (int q = q0; q < q0 + SL_TURN; q++)
+            for (int k = 0; k < SL_K; k++) {
+                uint32_t &m = most[(q - q0) / SL_QUARTER];
+                m = std::max(m, (seg[(size_t)q * RD + (size_t)k * S] >> SL_NSHIFT) & 15u);
+            }
+        for (int q = q0; q < q0 + SL_TURN; q++) fet[(size_t)q * SL_FREC + 3] = slane_turn_header(q - q0, most);
     }
     return true;
 }

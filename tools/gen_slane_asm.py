@@ -1,6 +1,7 @@
 """Generates omr-img-corrector_amd/csrc/slane_asm.inc: the scan-lane sweep's wave program as
 gfx950 assembly text; ONE asm statement that dispatches on the strip's segment-slot class (2 / 4 / 8 slots per word laid out) and,
-once per turn of 16 rows, on the turn's header (1 .. S slots executed: 2 + 4 + 8 loop bodies; program format v3, round 5).
+every FOUR rows, on a header of the fetch record (1 .. S slots executed: 2 + 4 + 8 loop bodies of a turn of 16 rows each, with an
+entry at rows 0, 4, 8 and 12; program format v3, round 5; the quarters: round 25, slane_turn_header in slane.hpp).
 A null task -- a place of the workgroup without work -- takes a body of its own that only meets the workgroup and flushes its
 share of the row counts (null_body).
 
@@ -49,6 +50,13 @@ of round 4 -- profiles/r04_lanes_ablation.md -- was a violation of the second on
     nothing in flight -- and then requests rows r + 2, r + 3 into sets (r + 2) % 4, (r + 3) % 4, which rows r, r + 1 do not
     touch.  The flush ends on its own lgkmcnt(0).  After the last turn A, B are still in flight (two records past the
     stream's end: the program buffer has slack for them): the epilogue waits before it loads the dump pointer into s[16:17];
+  * quarter entries: a wave may leave body E at row 4, 8 or 12 for the same row of body E' (the compare with E behind that row's
+    lgkmcnt(0) and record requests -- two scalar instructions when the count stays --, else a dispatch stub behind the bodies), and
+    enters the bodies at the top of a turn through the same kind of stub on set B's header (the turn's second record: quarter 0).
+    So (a) at the entries L<cls>_e<E>_q<k> of one quarter the SAME loads are in flight on every edge, in every body: sets C, D --
+    the lint asserts equality there, not inclusion --; (b) everything a row does apart from its words (the counted wait, commit,
+    fetch, LDS slot, carry-save level) is the same instruction for instruction in every body of a class: body() asserts it; (c) the
+    words leave nothing behind but the word itself and M0 = 0, whatever E;
   * vector loads (the ring's fetches, the prefetch) return IN ORDER, four fetches per row into landing set r % 4, committed
     four rows later behind a COUNTED wait, vmcnt(12); extra loads among the younger ones (the prefetch: two per turn of the
     strip's first scan group) only make that wait stricter.  Row-count atomics are stores: they may retire out of order with
@@ -90,6 +98,7 @@ FOFF = (80, 84, 88, 92)        # fetch records of sets A..D: two pair offsets, t
 NLOAD = 4                      # loads per row
 RSRC = 96                      # s[96:99]: the image's descriptor, its base moved to the pair being loaded (num_records = the pair)
 AHEAD = 4
+QUARTER = 4                    # rows between two decisions on the executed slots (SL_QUARTER, slane.hpp)
 NULL_CLS = 7                   # SlaneTask::cls of a null task (SL_CLS_NULL, slane.hpp): a place of the workgroup without work
 
 
@@ -296,6 +305,25 @@ def rec_loads(out, x, S, row, force=False):
     out.append("s_load_dwordx4 s[%d:%d], s[2:3], %d" % (FOFF[x], FOFF[x] + 3, row * 16))
 
 
+def dispatch_stub(o, hdr, lo, hi, target, L, falls_into_last=False):
+    """branch to the label target(E) for the header E = s<hdr> in lo .. hi: a tree of compares, log2(S) deep (the linear chain it
+    replaces was up to 2 (S - 1) instructions at the top of every turn).  falls_into_last: target(hi) follows right behind."""
+    def tree(lo, hi):
+        if lo == hi:
+            o.append("s_branch " + target(lo))
+        elif hi == lo + 1:
+            o.extend(["s_cmp_eq_u32 s%d, %d" % (hdr, lo), "s_cbranch_scc1 " + target(lo), "s_branch " + target(hi)])
+        else:
+            mid = (lo + hi + 1) // 2
+            o.extend(["s_cmp_ge_u32 s%d, %d" % (hdr, mid), "s_cbranch_scc1 %s_ge%d" % (L, mid)])
+            tree(lo, mid - 1)
+            o.append("%s_ge%d:" % (L, mid))
+            tree(mid, hi)
+    tree(lo, hi)
+    if falls_into_last:
+        assert o.pop() == "s_branch " + target(hi)
+
+
 def body(o, S, L):
     """the row loop of the strips laid out with S slots per word.  A turn = TURN rows; the turn's header (the fetch record of its
     first row, second dword of the commit pair: set A) says how many slots per word its busiest word needs, and the turn
@@ -336,27 +364,43 @@ def body(o, S, L):
     o.append("s_waitcnt lgkmcnt(0)")
     rec_loads(o, 2, S, 2)
     rec_loads(o, 3, S, 3)
-    hdr = FOFF[0] + 3
-    for E in range(1, S):
-        o += ["s_cmp_eq_u32 s%d, %d" % (hdr, E), "s_cbranch_scc1 L%s_e%d" % (L, E)]
+    # quarter 0 runs on set B's header: the turn's first record keeps the turn's maximum (slane.hpp)
+    dispatch_stub(o, FOFF[1] + 3, 1, S, lambda E: "L%s_e%d_q0" % (L, E), "L%s_d0" % L, True)
+    frames = {}  # row of the turn -> what it executes apart from its words
     for E in range(S, 0, -1):
         Ex = max(1, E - 1) if "lessE" in ABLATE else E  # timing probe: what one executed slot per word costs
-        o.append("L%s_e%d:" % (L, E))
+        o.append("L%s_e%d_q0:" % (L, E))
         for r in range(TURN):
+            pre, disp, head, words, rest = [], [], [], [], []
             if r % 2 == 0 and r > 0:  # a batch of two rows: everything requested two rows ago is here; request the next two rows
-                o.append("s_waitcnt lgkmcnt(0)")
-                rec_loads(o, (r + 2) % 4, S, r + 2)
-                rec_loads(o, (r + 3) % 4, S, r + 3)
+                pre.append("s_waitcnt lgkmcnt(0)")
+                rec_loads(pre, (r + 2) % 4, S, r + 2)
+                rec_loads(pre, (r + 3) % 4, S, r + 3)
+            if r % QUARTER == 0 and r > 0:
+                # a quarter of the turn starts: its header rides in this row's record (set A: QUARTER is a multiple of four).
+                # Behind the wait and the requests, so that the same sets are in flight at this label in every body; the common
+                # case -- the count has not changed -- is a compare and a branch not taken.
+                assert r % 4 == 0
+                disp = ["s_cmp_lg_u32 s%d, %d" % (FOFF[0] + 3, E), "s_cbranch_scc1 L%s_d%d" % (L, r // QUARTER),
+                        "L%s_e%d_q%d:" % (L, E, r // QUARTER)]
             odd = r & 1
-            commit(o, r % 4, r % 4)
+            commit(head, r % 4, r % 4)
             d = (ST[0], ST[1]) if not odd else DODD
-            words2(o, SEG[r % 4], S, d[0], d[1], Ex, T0 + 4 * (r % 4))
-            fetch(o, r % 4, r % 4)
-            row_count(o, d[0], d[1], odd == 1, r // 2)
+            words2(words, SEG[r % 4], S, d[0], d[1], Ex, T0 + 4 * (r % 4))
+            fetch(rest, r % 4, r % 4)
+            row_count(rest, d[0], d[1], odd == 1, r // 2)
             if odd:
-                carry_save(o, "L%s_e%d_cs%d" % (L, E, r), (r & 2) != 0, r // 4)
-        if E > 1:
-            o.append("s_branch L%s_tail" % L)
+                carry_save(rest, "L%s_eX_cs%d" % (L, r), (r & 2) != 0, r // 4)
+            # carry-save phases, the LDS slot, the commit and fetch schedule and the counted wait belong to the row's place in the
+            # turn, not to E: a wave may enter any body at any quarter
+            frame = pre + ["<dispatch>"] * bool(disp) + head + ["<words>"] + rest
+            assert frames.setdefault(r, frame) == frame, "row %d of the turn differs between the bodies of %d slots" % (r, S)
+            o += pre + disp + head + words + [x.replace("L%s_eX_" % L, "L%s_e%d_" % (L, E)) for x in rest]
+        o.append("s_branch L%s_tail" % L)
+    # the dispatch stubs of quarters 1 ..: only a wave whose count changed comes here
+    for qt in range(1, TURN // QUARTER):
+        o.append("L%s_d%d:" % (L, qt))
+        dispatch_stub(o, FOFF[0] + 3, 1, S, lambda E: "L%s_e%d_q%d" % (L, E, qt), "L%s_d%d" % (L, qt))
     o.append("L%s_tail:" % L)
     flush(o, "L%s" % L)
     # (hotrec, a timing probe: the stream pointers stand still, every turn re-reads the first turn's records out of the scalar
@@ -438,6 +482,9 @@ def lint_scalar_loads(ins):
     the label was first entered with).  It runs for every variant the generator can emit, probes included."""
     import re
     fly, at_label, pending = set(), {}, {}
+    live = True  # is this point reached by falling through?
+    quarter = re.compile(r"_e\d+_q\d+$")  # entry labels of the bodies: reached from the dispatch stubs, out of any other body
+    want = {}  # (slot class, quarter) -> the SGPRs in flight at its entries
 
     def regs(txt):
         out = set()
@@ -448,12 +495,21 @@ def lint_scalar_loads(ins):
             out.add(int(a))
         return out
 
+    def same_at_quarter(lab, n, line):  # every edge into the entries of one quarter carries exactly the same loads in flight
+        if quarter.search(lab):
+            key = re.sub(r"_e\d+_q", "_q", lab)
+            assert want.setdefault(key, set(fly)) == fly, "instruction %d (%s): the loads in flight differ from the other edges into this quarter: %s" % (
+                n, line, sorted(fly ^ want[key]))
+
     for n, line in enumerate(ins):
         line = line.strip()
         if line.endswith(":"):
             lab = line[:-1]
+            if live:
+                same_at_quarter(lab, n, line)
             fly |= pending.pop(lab, set())
             at_label[lab] = set(fly)
+            live = True
             continue
         op, _, rest = line.partition(" ")
         if op == "s_waitcnt":
@@ -471,13 +527,14 @@ def lint_scalar_loads(ins):
         assert not (used & fly), "instruction %d (%s) touches SGPRs with a scalar load in flight: %s" % (n, line, sorted(used & fly))
         if op in ("s_branch",) or op.startswith("s_cbranch"):
             lab = rest.strip()
+            same_at_quarter(lab, n, line)
             if lab in at_label:  # backward
                 assert fly <= at_label[lab], "instruction %d (%s): the back edge carries loads in flight the label did not start with: %s" % (
                     n, line, sorted(fly - at_label[lab]))
             else:
                 pending[lab] = pending.get(lab, set()) | set(fly)
             if op == "s_branch":
-                fly = set()  # unreachable until the next label
+                fly, live = set(), False  # unreachable until the next label
     assert not pending, "branches to labels that never came: %s" % sorted(pending)
 
 
@@ -497,6 +554,17 @@ try:
     raise SystemExit("lint_scalar_loads did not notice a load into s[16:17] under records in flight")
 except AssertionError:
     pass
+# ... and a quarter entry that one body places in FRONT of the row's record requests: a wave that arrives there out of another
+# body has them in flight, a wave that falls through has not
+_q = [i for i, x in enumerate(_k) if x.endswith(":") and "_q" in x and not x.endswith("_q0:")]
+if _q and "norec" not in ABLATE:
+    _i = _q[0]
+    assert all(x.startswith("s_load_dword") for x in _k[_i - 6:_i - 2]) and _k[_i - 2].startswith("s_cmp_lg_u32")
+    try:
+        lint_scalar_loads(_k[:_i - 6] + _k[_i - 2:_i + 1] + _k[_i - 6:_i - 2] + _k[_i + 1:])
+        raise SystemExit("lint_scalar_loads did not notice a quarter entry with other loads in flight than its siblings")
+    except AssertionError:
+        pass
 body_txt = "\\n\\t\"\n    \"".join(kernel())
 out.append("#define SLANE_ASM \\\n    \"%s\\n\\t\"\n" % body_txt.replace("\n", " \\\n"))
 out.append("#define SLANE_ASM_CLOBBERS %s\n" % ", ".join(CLOB))
