@@ -1240,6 +1240,49 @@ int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const i
                                           double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **png,
                                           int64_t *png_len);
 
+/* ---- Group 4 TIFF encoding on the device ----------------------------------------------------------
+ * The bilevel exit for device-resident images: a 1-bit TIFF, CCITT Group 4 (T.6), whose strips are byte for byte what
+ * libtiff writes for the thresholded picture.  A pixel is white iff its gray value is greater than `threshold` (0 .. 254);
+ * for 3 channels (BGR in memory) the gray value is omr_rgb_to_gray_batch_device's.  A 0 / 255 image -- the TIFF decoder's
+ * output -- encodes to itself at any threshold.  Deterministic: the file is a function of the pixels, the shape, threshold,
+ * rows_per_strip and dpi alone -- not of its place in the batch, n, the other images, the base address, the pitch or the run.
+ * The file: little-endian classic TIFF, the IFD at offset 8 with its tags in ascending order -- 256 ImageWidth and 257
+ * ImageLength (LONG), 258 BitsPerSample 1, 259 Compression 4, 262 Photometric 0 (WhiteIsZero: white paper is coded as
+ * white runs), 273 StripOffsets (LONG), 277 SamplesPerPixel 1, 278 RowsPerStrip (LONG), 279 StripByteCounts (LONG), 282 and
+ * 283 X and YResolution dpi / 1 (only when dpi > 0), 293 T6Options 0, 296 ResolutionUnit 2 (inch, only when dpi > 0) -- then
+ * the resolutions, the two strip arrays (inside their entries when there is one strip), then the strips, FillOrder 1, each
+ * at an even offset.  rows_per_strip = 0 means one strip; a value above the rows is taken as the rows.  Every strip is coded
+ * under an imaginary white line by libtiff's rule (Fax3Encode2DRow: pass, vertical within 3, else horizontal), ends with
+ * EOFB (000000000001 twice) and is padded with zeros to a byte.
+ * Sizes above imread's own limits (2^20 rows or columns, 2^30 pixels) are refused with OMR_ERR_ASSERT, and so is a strip
+ * that could pass 2^31 - 1 bits (rows of a strip x (7 x cols + 32) + 31): bit offsets inside a strip are 32 bits wide.
+ * Speed: see README.md and profiles/r26_tiff_encode.md.
+ *
+ * An upper bound of the file's length for a rows x cols image of any content: 186 bytes of header, IFD and resolutions,
+ * 8 a strip for the arrays, and per strip ceil((its rows x (7 x cols + 32) + 24) / 8) rounded up to even -- a row's code
+ * takes at most 7 bits a pixel and 28 more (csrc/oics_tiff_enc.cpp has the argument; alternating pixels take 6 a pixel).
+ * OMR_ERR_ASSERT by the rules above, OMR_ERR_BADARG for a null bytes or a negative rows_per_strip.  Host only. */
+int omr_tiff_bound(int32_t rows, int32_t cols, int32_t rows_per_strip, int64_t *bytes);
+/* n device-resident images -> n files.  Slots, sizes (NULL allowed, 0 x 0 entries, an image at its slot's top left),
+ * d_out / out_stride_bytes (>= omr_tiff_bound of the slot) / out_len and the OMR_ERR_BADARG rules are exactly
+ * omr_png_encode_batch_device's: nothing is written at or behind out_len[i], a 0 x 0 entry leaves its slot untouched.
+ * Also OMR_ERR_BADARG: channels other than 1 or 3, a threshold outside 0 .. 254, a negative rows_per_strip or dpi.
+ * Every argument is checked before any device work.  Synchronous, on a stream of its own, which has drained on every
+ * return path. */
+int omr_tiff_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes, int64_t step_bytes, int32_t rows,
+                                 int32_t cols, int32_t channels, const int32_t *sizes, int32_t n, int32_t threshold,
+                                 int32_t rows_per_strip, int32_t dpi, uint8_t *d_out, int64_t out_stride_bytes,
+                                 int64_t *out_len);
+/* A host image -> its file in `out` (cap bytes), *len = the file's length.  cap too small (out may be NULL when cap is 0):
+ * OMR_ERR_NOMEM with *len = the length needed, nothing written. */
+int omr_tiff_encode(const omr_image *src, int32_t threshold, int32_t rows_per_strip, int32_t dpi, uint8_t *out, int64_t cap,
+                    int64_t *len);
+/* Measurement aid, as omr_png_encode_stats: *groups = the groups of launches, stage_ms[0 .. 3] = device time summed over
+ * the groups of threshold and pack, the row coder, the placement scans, and head + bit merge (which includes the host's
+ * placing of the files).  While on, every group records five events; results do not change.  Any output pointer may be
+ * NULL. */
+int omr_tiff_encode_stats(int32_t enable, int32_t *groups, double *stage_ms);
+
 /* ---- deskew with projections from file contents to file contents ------------------------------
  * The reference's benchmark flow, core/src/main.rs:68-95 -- imread, get_angle_with_projections, rotate_mat of the
  * original (CONTAIN, scale 1, BORDER_CONSTANT), imwrite -- for batches: omr_deskew_with_projections_batch with the scans
@@ -1290,6 +1333,14 @@ int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams,
                                                   int32_t interp, const uint8_t border_value[4], int32_t compression,
                                                   double *angles, int32_t *best_idx, int32_t *scan_rc, uint8_t **png,
                                                   int64_t *png_len);
+/* The same with Group 4 TIFF files as its outputs: tiff[i] is byte for byte omr_tiff_encode(canvas, threshold,
+ * rows_per_strip, dpi) of the deskewed canvas.  OMR_ERR_BADARG for the call also: a threshold outside 0 .. 254, a negative
+ * rows_per_strip or dpi.  The call-level OMR_ERR_ASSERT is omr_tiff_bound's refusal of the canvas. */
+int omr_deskew_with_projections_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                                   int32_t channels, uint16_t max_angle, double step, double resize_scale,
+                                                   int32_t interp, const uint8_t border_value[4], int32_t threshold,
+                                                   int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *best_idx,
+                                                   int32_t *scan_rc, uint8_t **tiff, int64_t *tiff_len);
 
 /* ---- deskew with the Hough and FFT detectors for batches ----------------------------------------
  * The other two legs of the reference's benchmark, core/src/main.rs:96-170: get_angle_with_hough / get_angle_with_fft on
@@ -1370,6 +1421,21 @@ int omr_deskew_with_fft_batch_streams(const uint8_t *const *streams, const int64
                                       double max_line_gap, int32_t flags, int32_t border_mode, const uint8_t border_value[4],
                                       int32_t clip, int32_t format, int32_t quality_or_compression, double *angles,
                                       int32_t *scan_rc, uint8_t **out, int64_t *out_len);
+/* The two with Group 4 TIFF files as their outputs (the format argument above keeps refusing any value but 0 and 1):
+ * out[i] is byte for byte omr_tiff_encode(canvas, threshold, rows_per_strip, dpi).  Everything else as above; OMR_ERR_BADARG
+ * for the call also: a threshold outside 0 .. 254, a negative rows_per_strip or dpi; the call-level OMR_ERR_ASSERT is
+ * omr_tiff_bound's refusal of the canvas slot. */
+int omr_deskew_with_hough_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                             double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                             const uint8_t border_value[4], int32_t clip, int32_t threshold,
+                                             int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *scan_rc,
+                                             uint8_t **out, int64_t *out_len);
+int omr_deskew_with_fft_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                           double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                                           double max_line_gap, int32_t flags, int32_t border_mode,
+                                           const uint8_t border_value[4], int32_t clip, int32_t threshold,
+                                           int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *scan_rc,
+                                           uint8_t **out, int64_t *out_len);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

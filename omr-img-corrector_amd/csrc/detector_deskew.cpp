@@ -28,6 +28,7 @@
 #include "orient.hpp"
 #include "png_dec.hpp"
 #include "png_enc.hpp"
+#include "tiff_enc.hpp"
 #include "stream_sink.hpp"
 
 using namespace omr;
@@ -197,13 +198,17 @@ struct StreamArgs {
     ImreadHeaders hd;  // sheet k's header stands in the array of its kind, hd.kind[k]
     int cn, flags, border_mode;
     const uint8_t *border;
-    int clip, level;
-    bool png_out;
+    int clip, level;  // level: quality, compression level or (TIFF) threshold
+    int out_kind;     // FORMAT_JPEG, FORMAT_PNG or FORMAT_TIFF
+    int rows_per_strip, dpi;  // the TIFF form's
     double *angles;
     int32_t *scan_rc;
     uint8_t **out;  // null (with out_len): the angles alone
     int64_t *out_len;
 };
+
+// the public format values, and the one only the _tiff entry points pass (the public argument refuses it)
+enum { FORMAT_JPEG = 0, FORMAT_PNG = 1, FORMAT_TIFF = -26 };
 
 int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<int> &idx)
 {
@@ -259,8 +264,10 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
         if (!a.out) continue;
         // the canvases stay on the device: encoded there, only the streams come down (a 0 x 0 canvas has none)
         StreamSink sink(a.out, a.out_len, idx, j0);
-        rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s)
-                       : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s);
+        rc = a.out_kind == FORMAT_TIFF  ? tiff_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level,
+                                                             a.rows_per_strip, a.dpi, sink, st.s)
+             : a.out_kind == FORMAT_PNG ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s)
+                                        : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s);
         if (rc) return rc;
     }
     return OMR_OK;
@@ -268,19 +275,20 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
 
 int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
                  int32_t border_mode, const uint8_t *border, int32_t clip, int32_t format, int32_t level, double *angles,
-                 int32_t *scan_rc, uint8_t **out, int64_t *out_len)
+                 int32_t *scan_rc, uint8_t **out, int64_t *out_len, int32_t rows_per_strip = 0, int32_t dpi = 0)
 {
     clear_error();
     if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
     if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
     if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "channels must be 1 or 3, got %d", channels);
-    if (format != 0 && format != 1) return fail(OMR_ERR_BADARG, "format %d (0 = JPEG, 1 = PNG)", format);
+    if (format != FORMAT_JPEG && format != FORMAT_PNG && format != FORMAT_TIFF) return fail(OMR_ERR_BADARG, "format %d (0 = JPEG, 1 = PNG)", format);
+    if (format == FORMAT_TIFF)
+        if (int r = tenc_check_params(channels, level, rows_per_strip, dpi)) return r;
     for (int i = 0; i < n; i++)
         if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
     int rc = check_rotate_args(flags, border_mode, clip);
     if (rc) return rc;
-    const bool png_out = format == 1;
     // the headers, on the host: a sheet its decoder refuses, or whose canvas slot leaves the image limit, keeps its code and
     // leaves the batch here
     std::vector<int32_t> code((size_t)n, OMR_OK);
@@ -322,12 +330,15 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
             for (const ImageShape &sh : b.shapes) {
                 int mr, mc;
                 if ((rc = detector_canvas(sh.rows, sh.cols, clip, &mr, &mc))) return rc;
-                if ((rc = png_out ? penc_check_shape(mr, mc, sh.cn) : jpeg_check_scan_bits(mr, mc, sh.cn))) return rc;
+                if ((rc = format == FORMAT_TIFF  ? tenc_check_shape(mr, mc, rows_per_strip, nullptr)
+                          : format == FORMAT_PNG ? penc_check_shape(mr, mc, sh.cn)
+                                                 : jpeg_check_scan_bits(mr, mc, sh.cn)))
+                    return rc;
             }
         }
         if ((rc = have_device())) return rc;
         const StreamArgs a{d, zs.data(), zlen.data(), ImreadHeaders{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()}, channels, flags, border_mode, border,
-                           clip, level, png_out, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
+                           clip, level, format, rows_per_strip, dpi, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
         if (rc) {
             for (uint8_t *p : bytes) free(p);
@@ -346,6 +357,9 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
     }
     return OMR_OK;
 }
+
+// a caller's format: anything but JPEG and PNG becomes a value streams_form refuses, the private one included
+int public_format(int format) { return format == FORMAT_TIFF ? FORMAT_TIFF - 1 : format; }
 
 Detector hough_detector(double min_line_length, double max_line_gap)
 {
@@ -446,7 +460,7 @@ int omr_deskew_with_hough_batch_streams(const uint8_t *const *streams, const int
                                         int64_t *out_len)
 {
     return streams_form(hough_detector(min_line_length, max_line_gap), streams, len, n, channels, flags, border_mode, border_value, clip,
-                        format, quality_or_compression, angles, scan_rc, out, out_len);
+                        public_format(format), quality_or_compression, angles, scan_rc, out, out_len);
 }
 
 int omr_deskew_with_fft_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
@@ -456,7 +470,28 @@ int omr_deskew_with_fft_batch_streams(const uint8_t *const *streams, const int64
                                       int32_t *scan_rc, uint8_t **out, int64_t *out_len)
 {
     return streams_form(fft_detector(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams, len, n, channels,
-                        flags, border_mode, border_value, clip, format, quality_or_compression, angles, scan_rc, out, out_len);
+                        flags, border_mode, border_value, clip, public_format(format), quality_or_compression, angles, scan_rc, out, out_len);
+}
+
+int omr_deskew_with_hough_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                             double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                             const uint8_t border_value[4], int32_t clip, int32_t threshold,
+                                             int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *scan_rc,
+                                             uint8_t **out, int64_t *out_len)
+{
+    return streams_form(hough_detector(min_line_length, max_line_gap), streams, len, n, channels, flags, border_mode, border_value, clip,
+                        FORMAT_TIFF, threshold, angles, scan_rc, out, out_len, rows_per_strip, dpi);
+}
+
+int omr_deskew_with_fft_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                           double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                                           double max_line_gap, int32_t flags, int32_t border_mode,
+                                           const uint8_t border_value[4], int32_t clip, int32_t threshold,
+                                           int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *scan_rc,
+                                           uint8_t **out, int64_t *out_len)
+{
+    return streams_form(fft_detector(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams, len, n, channels,
+                        flags, border_mode, border_value, clip, FORMAT_TIFF, threshold, angles, scan_rc, out, out_len, rows_per_strip, dpi);
 }
 
 }  // extern "C"

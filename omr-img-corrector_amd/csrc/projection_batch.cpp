@@ -31,6 +31,7 @@
 #include "orient.hpp"
 #include "png_dec.hpp"
 #include "png_enc.hpp"
+#include "tiff_enc.hpp"
 #include "stream_sink.hpp"
 
 using namespace omr;
@@ -525,14 +526,17 @@ struct StreamArgs {
     int N;
     int interp;
     const uint8_t *border;
-    int quality;  // the PNG form: the compression level
-    bool png_out;
+    int quality;  // the PNG form: the compression level; the TIFF form: the threshold
+    int out_kind;  // OUT_JPEG, OUT_PNG or OUT_TIFF
+    int rows_per_strip, dpi;  // the TIFF form's
     double *angles;
     int32_t *best_idx, *scan_rc;
     uint8_t **out;  // null (with out_len): the angles alone
     int64_t *out_len;
     int device;
 };
+
+enum { OUT_JPEG = 0, OUT_PNG = 1, OUT_TIFF = 2 };
 
 // a code of the per-call chain that belongs to its sheet (any other ends the call)
 bool sheet_code(int rc) { return rc == OMR_ERR_ASSERT || rc == OMR_ERR_BADARG || rc == OMR_ERR_NOTIMPL; }
@@ -549,10 +553,16 @@ int streams_per_call(const StreamArgs &a, const std::vector<int> &idx)
         if (!rc) rc = omr_get_angle_with_projections(&view, a.max_angle, a.step, a.scale, 1, &a.angles[k]);
         if (!rc && a.out) {
             rc = omr_rotate(&view, a.angles[k], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &rot);
-            if (!rc) rc = a.png_out ? omr_png_bound(rot.rows, rot.cols, rot.channels, &cap) : omr_jpeg_bound(rot.rows, rot.cols, rot.channels, &cap);
+            if (!rc)
+                rc = a.out_kind == OUT_TIFF  ? omr_tiff_bound(rot.rows, rot.cols, a.rows_per_strip, &cap)
+                     : a.out_kind == OUT_PNG ? omr_png_bound(rot.rows, rot.cols, rot.channels, &cap)
+                                             : omr_jpeg_bound(rot.rows, rot.cols, rot.channels, &cap);
             if (!rc && !(bytes = (uint8_t *)malloc((size_t)cap))) rc = fail(OMR_ERR_NOMEM, "out of host memory");
             const omr_image canvas{rot.data, rot.rows, rot.cols, rot.channels, rot.step_bytes};
-            if (!rc) rc = a.png_out ? omr_png_encode(&canvas, a.quality, bytes, cap, &used) : omr_jpeg_encode(&canvas, a.quality, bytes, cap, &used);
+            if (!rc)
+                rc = a.out_kind == OUT_TIFF  ? omr_tiff_encode(&canvas, a.quality, a.rows_per_strip, a.dpi, bytes, cap, &used)
+                     : a.out_kind == OUT_PNG ? omr_png_encode(&canvas, a.quality, bytes, cap, &used)
+                                             : omr_jpeg_encode(&canvas, a.quality, bytes, cap, &used);
         }
         omr_image_free(&img);
         omr_image_free(&rot);
@@ -635,19 +645,23 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
         if (!a.out) continue;
         // the canvases stay on the device: encoded there, only the streams come down
         StreamSink sink(a.out, a.out_len, idx, j0);
-        rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
-                       : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
+        rc = a.out_kind == OUT_TIFF  ? tiff_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality,
+                                                          a.rows_per_strip, a.dpi, sink, st.s)
+             : a.out_kind == OUT_PNG ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
+                                     : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
         if (rc) return rc;
     }
     return OMR_OK;
 }
 
-// omr_deskew_with_projections_batch_streams and its PNG form: `out` receives the streams of either kind
+// omr_deskew_with_projections_batch_streams and its PNG and TIFF forms: `out` receives the streams of any kind
 int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, uint16_t max_angle, double step,
                    double scale, int32_t interp, const uint8_t *border, int32_t quality, double *angles, int32_t *best_idx,
-                   int32_t *scan_rc, uint8_t **out, int64_t *out_len, bool png_out)
+                   int32_t *scan_rc, uint8_t **out, int64_t *out_len, int out_kind, int32_t rows_per_strip = 0, int32_t dpi = 0)
 {
     clear_error();
+    if (out_kind == OUT_TIFF)
+        if (int r = tenc_check_params(channels == 1 ? 1 : 3, quality, rows_per_strip, dpi)) return r;
     if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
     if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
@@ -708,14 +722,17 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
                     clear_error();
                     continue;
                 }
-                if ((rc = png_out ? penc_check_shape(dk.rows, dk.cols, sh.cn) : jpeg_check_scan_bits(dk.rows, dk.cols, sh.cn))) return rc;
+                if ((rc = out_kind == OUT_TIFF  ? tenc_check_shape(dk.rows, dk.cols, rows_per_strip, nullptr)
+                          : out_kind == OUT_PNG ? penc_check_shape(dk.rows, dk.cols, sh.cn)
+                                                : jpeg_check_scan_bits(dk.rows, dk.cols, sh.cn)))
+                    return rc;
             }
         }
         if ((rc = have_device())) return rc;
         int dev = 0;
         OMR_HIP(hipGetDevice(&dev));
         StreamArgs a{zs.data(), zlen.data(), ImreadHeaders{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()}, channels, max_angle, step, scale, N, interp,
-                     border, quality, png_out, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
+                     border, quality, out_kind, rows_per_strip, dpi, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
                      out ? bytes_len.data() : nullptr, dev};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
         if (rc) {
@@ -748,7 +765,7 @@ int omr_deskew_with_projections_batch_streams(const uint8_t *const *streams, con
                                               int32_t *best_idx, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len)
 {
     return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, quality, angles, best_idx,
-                          scan_rc, jpeg, jpeg_len, false);
+                          scan_rc, jpeg, jpeg_len, OUT_JPEG);
 }
 
 int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -758,7 +775,17 @@ int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams,
                                                   int64_t *png_len)
 {
     return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, compression, angles,
-                          best_idx, scan_rc, png, png_len, true);
+                          best_idx, scan_rc, png, png_len, OUT_PNG);
+}
+
+int omr_deskew_with_projections_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                                   int32_t channels, uint16_t max_angle, double step, double resize_scale,
+                                                   int32_t interp, const uint8_t border_value[4], int32_t threshold,
+                                                   int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *best_idx,
+                                                   int32_t *scan_rc, uint8_t **tiff, int64_t *tiff_len)
+{
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, threshold, angles,
+                          best_idx, scan_rc, tiff, tiff_len, OUT_TIFF, rows_per_strip, dpi);
 }
 
 }  // extern "C"

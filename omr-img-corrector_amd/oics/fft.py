@@ -116,3 +116,14 @@ def deskew_streams(streams, canny_threshold_1, canny_threshold_2, min_line_lengt
                                               (canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams,
                                               channels, flags, border_mode, border_value, clip_strategy, 1 if png else 0, level,
                                               want_out)
+
+
+def deskew_streams_tiff(streams, canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap, flags=1, border_mode=0,
+                        border_value=(255, 255, 255, 0), clip_strategy=1, channels=3, threshold=127, rows_per_strip=0, dpi=0,
+                        want_out=True):
+    """omr_deskew_with_fft_batch_streams_tiff: deskew_streams with Group 4 TIFF files as its outputs, outputs[i] byte for
+    byte oics.tiff.encode(canvas, threshold, rows_per_strip, dpi)."""
+    return _transfer._detector_deskew_streams("omr_deskew_with_fft_batch_streams_tiff",
+                                              (canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams,
+                                              channels, flags, border_mode, border_value, clip_strategy, 0, threshold, want_out,
+                                              tiff=(rows_per_strip, dpi))

@@ -156,3 +156,12 @@ def deskew_streams(streams, min_line_length, max_line_gap, flags=1, border_mode=
     return _transfer._detector_deskew_streams("omr_deskew_with_hough_batch_streams", (min_line_length, max_line_gap), streams,
                                               channels, flags, border_mode, border_value, clip_strategy, 1 if png else 0, level,
                                               want_out)
+
+
+def deskew_streams_tiff(streams, min_line_length, max_line_gap, flags=1, border_mode=0, border_value=(255, 255, 255, 0),
+                        clip_strategy=1, channels=3, threshold=127, rows_per_strip=0, dpi=0, want_out=True):
+    """omr_deskew_with_hough_batch_streams_tiff: deskew_streams with Group 4 TIFF files as its outputs, outputs[i] byte for
+    byte oics.tiff.encode(canvas, threshold, rows_per_strip, dpi)."""
+    return _transfer._detector_deskew_streams("omr_deskew_with_hough_batch_streams_tiff", (min_line_length, max_line_gap), streams,
+                                              channels, flags, border_mode, border_value, clip_strategy, 0, threshold, want_out,
+                                              tiff=(rows_per_strip, dpi))

@@ -60,8 +60,9 @@ def get_angles_and_deskew(srcs, max_angle, step, resize_scale, interp=1, border=
     return (ang[:n], idx[:n], images) if want_idx else (ang[:n], images)
 
 
-def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, level, channels, png, want_out):
-    """omr_deskew_with_projections_batch_streams / _png -> (angles, best_idx, scan_rc, [bytes or None] or None)"""
+def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, level, channels, png, want_out, tiff=None):
+    """omr_deskew_with_projections_batch_streams / _png / _tiff (tiff = (rows_per_strip, dpi), level = the threshold) ->
+    (angles, best_idx, scan_rc, [bytes or None] or None)"""
     from ._lib import u8p
     bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
             for s in streams]
@@ -75,8 +76,11 @@ def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, leve
     ptrs = (u8p * max(n, 1))()
     lens = np.zeros(max(n, 1), np.int64)
     fn = lib().omr_deskew_with_projections_batch_streams_png if png else lib().omr_deskew_with_projections_batch_streams
+    how = (int(level),)
+    if tiff is not None:
+        fn, how = lib().omr_deskew_with_projections_batch_streams_tiff, (int(level), int(tiff[0]), int(tiff[1]))
     check(fn(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), int(max_angle), float(step), float(resize_scale),
-             int(interp), _border4(border), int(level), ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p),
+             int(interp), _border4(border), *how, ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p),
              rc.ctypes.data_as(i32p), ptrs if want_out else None,
              lens.ctypes.data_as(C.POINTER(C.c_int64)) if want_out else None))
     out = None
@@ -99,6 +103,15 @@ def deskew_streams(streams, max_angle, step, resize_scale, interp=1, border=(255
     f64 bits), scan_rc[i] 0 or the code of a sheet that was refused or damaged, outputs[i] the encoded canvas as bytes
     (None where scan_rc[i] != 0).  want_idx: (angles, best_idx, scan_rc, outputs)."""
     ang, idx, rc, out = _deskew_streams(streams, max_angle, step, resize_scale, interp, border, quality, channels, png, True)
+    return (ang, idx, rc, out) if want_idx else (ang, rc, out)
+
+
+def deskew_streams_tiff(streams, max_angle, step, resize_scale, interp=1, border=(255, 255, 255), threshold=127,
+                        rows_per_strip=0, dpi=0, channels=3, want_idx=False):
+    """deskew_streams with Group 4 TIFF files as its outputs (omr_deskew_with_projections_batch_streams_tiff): outputs[i]
+    is oics.tiff.encode(canvas, threshold, rows_per_strip, dpi) of the deskewed canvas, byte for byte."""
+    ang, idx, rc, out = _deskew_streams(streams, max_angle, step, resize_scale, interp, border, threshold, channels, False, True,
+                                        tiff=(rows_per_strip, dpi))
     return (ang, idx, rc, out) if want_idx else (ang, rc, out)
 
 

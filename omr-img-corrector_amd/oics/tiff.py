@@ -1,11 +1,11 @@
 """Bilevel TIFF on the device (omr_tiff_*): uncompressed, PackBits and CCITT Group 4 strips decoded byte for byte to what
-libtiff gives, as 255 / 0."""
+libtiff gives, as 255 / 0, and a Group 4 encoder whose strips are byte for byte what libtiff writes."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import OMR_TIFF_CODES, OmrImageOwned, check, i32p, lib
-from .transfer import _take_owned
+from ._lib import OMR_TIFF_CODES, OmrImageOwned, check, i32p, lib, u8p
+from .transfer import _mat, _take_owned, as_image
 
 
 def _buf(stream):
@@ -60,4 +60,55 @@ def stats(enable=True):
     groups = C.c_int32()
     ms = np.zeros(len(STAGES), np.float64)
     check(lib().omr_tiff_decode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
+    return groups.value, [float(v) for v in ms]
+
+
+def bound(rows, cols, rows_per_strip=0):
+    """omr_tiff_bound: an upper bound of the encoded file's length in bytes"""
+    out = C.c_int64()
+    check(lib().omr_tiff_bound(int(rows), int(cols), int(rows_per_strip), C.byref(out)))
+    return out.value
+
+
+def encode_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, channels, sizes, n, d_out, out_stride_bytes,
+                        threshold=127, rows_per_strip=0, dpi=0):
+    """omr_tiff_encode_batch_device: n device-resident images in slots of rows x cols x channels (d_imgs, d_out: device
+    addresses; sizes: None or int32 [n, 2] of (rows, cols) per image) -> Group 4 TIFF files; a pixel is white iff its gray
+    value is above `threshold`.  Returns out_len int64 [n]: file i is out_len[i] bytes at d_out + i * out_stride_bytes
+    (0: a 0 x 0 entry, slot untouched).  Synchronous."""
+    n = int(n)
+    out_len = np.zeros(max(n, 0), np.int64)
+    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
+    check(lib().omr_tiff_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
+                                             int(channels), None if sz is None else sz.ctypes.data_as(i32p), n,
+                                             int(threshold), int(rows_per_strip), int(dpi), d_out, int(out_stride_bytes),
+                                             out_len.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out_len
+
+
+def encode(mat, threshold=127, rows_per_strip=0, dpi=0):
+    """omr_tiff_encode: a host image (gray or BGR) -> a Group 4 TIFF file as bytes, its strips libtiff's for the picture
+    thresholded at `threshold`.  One call in the usual case: the first buffer holds an eighth of the pixels, which pages
+    stay far below; a file that does not fit answers -4 with its length, and a second call encodes into that."""
+    a, im = as_image(_mat(mat))
+    n = C.c_int64()
+    L = lib()
+    buf = np.empty(min(im.rows * im.cols // 8 + 4096, bound(im.rows, im.cols, rows_per_strip)), np.uint8)
+    rc = L.omr_tiff_encode(C.byref(im), int(threshold), int(rows_per_strip), int(dpi), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
+    if rc == -4:
+        buf = np.empty(n.value, np.uint8)
+        rc = L.omr_tiff_encode(C.byref(im), int(threshold), int(rows_per_strip), int(dpi), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
+    check(rc)
+    return buf[: n.value].tobytes()
+
+
+STAGES_ENC = ("threshold and pack", "row coder", "placement", "head and bit merge")
+
+
+def encode_stats(enable=True):
+    """omr_tiff_encode_stats (measurement aid): what this thread's last encode took -> (groups, [ms per stage of
+    STAGES_ENC]); then switches the collection on or off for the thread's next encodes."""
+    groups = C.c_int32()
+    ms = np.zeros(len(STAGES_ENC), np.float64)
+    check(lib().omr_tiff_encode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
     return groups.value, [float(v) for v in ms]

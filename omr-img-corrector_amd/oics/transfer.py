@@ -77,6 +77,12 @@ class TransformableMatrix:
         from . import png
         return png.encode(self.matrix, compression)
 
+    def encode_tiff(self, threshold=127, rows_per_strip=0, dpi=0):
+        """A Group 4 TIFF file of the matrix thresholded at `threshold` (white above it), encoded on the GPU
+        (omr_tiff_encode): gray or BGR.  The strips are byte for byte what libtiff writes for that picture."""
+        from . import tiff
+        return tiff.encode(self.matrix, threshold, rows_per_strip, dpi)
+
     def get_mat(self):
         return self.matrix
 
@@ -202,8 +208,10 @@ def _detector_deskew(symbol, detector_args, srcs, flags, border_mode, border_val
 
 
 def _detector_deskew_streams(symbol, detector_args, streams, channels, flags, border_mode, border_value, clip_strategy, fmt,
-                             level, want_out):
-    """omr_deskew_with_hough_batch_streams / omr_deskew_with_fft_batch_streams -> (angles, scan_rc, [bytes or None] or None)"""
+                             level, want_out, tiff=None):
+    """omr_deskew_with_hough_batch_streams / omr_deskew_with_fft_batch_streams -> (angles, scan_rc, [bytes or None] or None).
+    tiff = (rows_per_strip, dpi): the _tiff symbol, which takes (threshold = level, rows_per_strip, dpi) for (fmt, level)"""
+    how = (int(fmt), int(level)) if tiff is None else (int(level), int(tiff[0]), int(tiff[1]))
     bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
             for s in streams]
     bufs = [b if b.size else np.zeros(1, np.uint8) for b in bufs]
@@ -216,7 +224,7 @@ def _detector_deskew_streams(symbol, detector_args, streams, channels, flags, bo
     lens = np.zeros(max(n, 1), np.int64)
     b = np.array([int(v) for v in border_value], np.uint8)
     check(getattr(lib(), symbol)(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), *[float(v) for v in detector_args],
-                                 int(flags), int(border_mode), b.ctypes.data_as(u8p), int(clip_strategy), int(fmt), int(level),
+                                 int(flags), int(border_mode), b.ctypes.data_as(u8p), int(clip_strategy), *how,
                                  angles.ctypes.data_as(f64p), rc.ctypes.data_as(_lib.i32p), ptrs if want_out else None,
                                  lens.ctypes.data_as(C.POINTER(C.c_int64)) if want_out else None))
     out = None

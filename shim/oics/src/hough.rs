@@ -164,3 +164,25 @@ pub fn deskew_files_with_hough(
         ffi::omr_deskew_with_hough_batch_streams(streams, len, n, 3, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), 0, quality, angles, scan_rc, jpeg, jpeg_len)
     })
 }
+
+/// `deskew_files_with_hough` with CCITT Group 4 TIFF files as its outputs (omr_deskew_with_hough_batch_streams_tiff): a
+/// pixel is white iff its gray value is above `threshold` (0 .. 254); `rows_per_strip` 0: one strip a page; `dpi` 0: no
+/// resolution tags.  Not in the reference crate.
+pub fn deskew_files_with_hough_tiff(
+    inputs: &[&str],
+    outputs: &[&str],
+    min_line_length: f64,
+    max_line_gap: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+    threshold: i32,
+    rows_per_strip: i32,
+    dpi: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, tiff, tiff_len| unsafe {
+        ffi::omr_deskew_with_hough_batch_streams_tiff(streams, len, n, 3, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), threshold, rows_per_strip, dpi, angles, scan_rc, tiff, tiff_len)
+    })
+}

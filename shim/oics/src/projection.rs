@@ -158,3 +158,25 @@ pub fn deskew_files_with_projections_png(
         ffi::omr_deskew_with_projections_batch_streams_png(streams, len, n, 3, max_angle, angle_step, resize_scale, flags, border.as_ptr(), compression, angles, std::ptr::null_mut(), scan_rc, png, png_len)
     })
 }
+
+/// `deskew_files_with_projections` with bilevel outputs (omr_deskew_with_projections_batch_streams_tiff): JPEG, PNG or
+/// TIFF files in, CCITT Group 4 TIFF files out, a pixel white iff its gray value is above `threshold` (0 .. 254), the
+/// strips byte for byte libtiff's.  `rows_per_strip` 0: one strip a page; `dpi` 0: no resolution tags.  Not in the
+/// reference crate.
+pub fn deskew_files_with_projections_tiff(
+    inputs: &[&str],
+    outputs: &[&str],
+    max_angle: u16,
+    angle_step: f64,
+    resize_scale: f64,
+    flags: i32,
+    border_value: Scalar,
+    threshold: i32,
+    rows_per_strip: i32,
+    dpi: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, tiff, tiff_len| unsafe {
+        ffi::omr_deskew_with_projections_batch_streams_tiff(streams, len, n, 3, max_angle, angle_step, resize_scale, flags, border.as_ptr(), threshold, rows_per_strip, dpi, angles, std::ptr::null_mut(), scan_rc, tiff, tiff_len)
+    })
+}

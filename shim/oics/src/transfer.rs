@@ -285,6 +285,26 @@ pub fn encode_png(m: &TransformableMatrix, compression: i32) -> Result<Vec<u8>, 
     Ok(out)
 }
 
+/// A CCITT Group 4 TIFF file of the Mat thresholded at `threshold` (0 .. 254; a pixel is white iff its gray value is
+/// above it), encoded on the GPU (omr_tiff_encode): gray or BGR, 8-bit.  The strips are byte for byte what libtiff writes
+/// for that picture.  `rows_per_strip` 0: one strip; `dpi` 0: no resolution tags.  Not in the reference crate.
+pub fn encode_tiff(m: &TransformableMatrix, threshold: i32, rows_per_strip: i32, dpi: i32) -> Result<Vec<u8>, opencv::Error> {
+    let v = view(&m.matrix)?;
+    let mut bound = 0i64;
+    check(unsafe { ffi::omr_tiff_bound(v.rows, v.cols, rows_per_strip, &mut bound) })?;
+    let first = v.rows as i64 * v.cols as i64 / 8 + 4096;
+    let mut out = vec![0u8; first.min(bound) as usize];
+    let mut len = 0i64;
+    let mut rc = unsafe { ffi::omr_tiff_encode(&v, threshold, rows_per_strip, dpi, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    if rc == ffi::OMR_ERR_NOMEM {
+        out = vec![0u8; len as usize];
+        rc = unsafe { ffi::omr_tiff_encode(&v, threshold, rows_per_strip, dpi, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    }
+    check(rc)?;
+    out.truncate(len as usize);
+    Ok(out)
+}
+
 /// What `im_read` gives for a file with these bytes (`imread(.., IMREAD_COLOR)` for `channels` = 3, `IMREAD_GRAYSCALE`
 /// for 1), decoded on the GPU (omr_jpeg_decode): libjpeg's output with its defaults, byte for byte.  Baseline streams;
 /// one the decoder refuses (progressive, CMYK, an EXIF orientation, ..) is an error with code OMR_ERR_NOTIMPL, so that
