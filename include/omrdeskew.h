@@ -1076,8 +1076,8 @@ int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
  * stop at the strip's rows, so the surplus is never read as codes.  A present tag is taken at its word: a wrong number of
  * counts or a count of 0 stays OMR_ERR_BADARG.  A T.6 code that begins inside its strip and ends behind it is read with
  * zeros for the missing bits, as libtiff reads it (a writer may drop a last byte that held only trailing zeros).
- * OMR_ERR_NOTIMPL, never a wrong picture: BigTIFF, tiles, any other depth, sample count, compression (3 / T.4 and 5 / LZW
- * included) or photometric interpretation (a missing Photometric tag too), T6Options bit 1 (uncompressed mode), an
+ * OMR_ERR_NOTIMPL, never a wrong picture: BigTIFF, tiles, any other depth, sample count, compression (3 / T.4 and, at 1
+ * bit, 5 / LZW included) or photometric interpretation (a missing Photometric tag too), T6Options bit 1 (uncompressed mode), an
  * Orientation tag other than 1 (what OpenCV 4.6 does with it is not established, as for PNG's eXIf), a T.6 image wider
  * than 12288 columns (its lines' change positions live in LDS).
  * OMR_ERR_BADARG, malformed structure: a stream too short for its header, an IFD, tag value or strip outside the stream, a
@@ -1092,11 +1092,34 @@ int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
  * run that passes the strip's rows (libtiff clips it).
  * Speed: see README.md and profiles/r24_tiff_decode.md.
  *
+ * 8-bit gray and RGB, what a scanner writes in its gray and colour modes.  Taken besides the above,
+ * with the same rules for the file's structure: BitsPerSample 8 with SamplesPerPixel 1 and Photometric 0 or 1 (0 is
+ * inverted on reading, as libtiff does); BitsPerSample 8,8,8 with SamplesPerPixel 3, Photometric 2 and
+ * PlanarConfiguration 1; Compression 1, 32773 and 5 -- LZW in its TIFF 6.0 form: codes most significant bit first, Clear
+ * 256, EOI 257, widths 9 to 12 with the early change; Predictor 1 and, with LZW, 2 (horizontal differencing per sample).
+ * libtiff knows the Predictor tag with LZW and Deflate alone: a raw or PackBits file that carries it is read as if it did
+ * not, here as there.  A gray file gives gray (channels = 1) or B = G = R (3), an RGB file gives BGR (3); a gray image
+ * from an RGB file is OMR_ERR_NOTIMPL (omr_png_decode's rule).  A raw strip needs rows x cols x samples bytes.
+ * An LZW strip may lack its EOI, carry bytes behind it, hold more output than its rows and Clear codes anywhere: libtiff
+ * reads all of these, and so does the decoder, which stops at the strip's rows.
+ * OMR_ERR_NOTIMPL besides the above: LZW at 1 bit; Deflate (8, 32946) and JPEG (6, 7) in TIFF; palette images, ExtraSamples
+ * (alpha); 16 bits and every depth other than 1 and 8; PlanarConfiguration 2 with three samples; FillOrder 2 at 8 bits; a
+ * Predictor other than 1 and 2 with LZW; old-style LZW (a strip that begins 00 with the low bit of its next byte set).
+ * OMR_ERR_ASSERT, damaged LZW data: a strip that does not begin with Clear, a code above the next free entry, a first
+ * code after Clear that is no literal, a table pushed past entry 4095, input that ends (EOI, or no room for another
+ * code) before the strip's rows do; an LZW strip of 2^31 bytes of rows or more.
+ * Speed: see README.md and profiles/r27_tiff8_decode.md.
+ *
  * What the first IFD says.  Returns 0, OMR_ERR_NOTIMPL, OMR_ERR_BADARG or OMR_ERR_ASSERT by the rules above, as far as the
  * tags decide them; the fields are filled in as far as the tags were readable (*photometric = -1: no such tag; *strips = 0
  * unless the stream is accepted).  Any output pointer may be NULL.  Host only. */
 int omr_tiff_info(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *compression, int32_t *photometric,
                   int32_t *fill_order, int32_t *strips);
+/* The same with *bits_per_sample (1 or 8), *samples_per_pixel (1 or 3) and *predictor (1 or 2; 1 for every compression
+ * but LZW) of an accepted stream; 1, 1, 1 for a refused one. */
+int omr_tiff_info_ex(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *compression, int32_t *photometric,
+                     int32_t *fill_order, int32_t *strips, int32_t *bits_per_sample, int32_t *samples_per_pixel,
+                     int32_t *predictor);
 /* The run-length codes of ITU-T T.4 (Tables 2 and 3) as the decoder holds them, for white (black = 0) or black (1) runs:
  * OMR_TIFF_CODES entries each of run[] (0 .. 63, the make-up runs 64 .. 1728, the extended make-up runs 1792 .. 2560),
  * code[] (the code word as a number, its first bit the most significant of bits[] bits).  A test aid.  Host only. */
@@ -1113,6 +1136,11 @@ int omr_tiff_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_im
  * the groups of the upload, the PackBits kernel, the T.6 kernel, the unpack kernel.  While on, every group records five
  * events; results do not change.  Any output pointer may be NULL. */
 int omr_tiff_decode_stats(int32_t enable, int32_t *groups, double *stage_ms);
+/* The same for every stage: stage_ms[0 .. min(capacity, *stages) - 1] = the upload, the PackBits, T.6 and LZW kernels, the
+ * unpack kernel (1 bit) and the finishing kernel (8 bits); *stages = OMR_TIFF_DECODE_STAGES.  OMR_ERR_BADARG: a negative
+ * capacity, or a null stage_ms with a capacity above 0. */
+#define OMR_TIFF_DECODE_STAGES 6
+int omr_tiff_decode_stats_ex(int32_t enable, int32_t *groups, double *stage_ms, int32_t capacity, int32_t *stages);
 
 /* ---- imread: EXIF orientation and the three decoders behind one door -----------------------------
  * imread(IMREAD_COLOR) -- the first line of correct_default and of TransformableMatrix::new -- turns a JPEG by the
@@ -1152,7 +1180,7 @@ int omr_orient(const omr_image *src, int32_t orientation, omr_image_owned *dst);
 #define OMR_IMREAD_KIND_TIFF 2
 /* What imread would return for this stream.  A stream that begins with PNG's eight signature bytes is a PNG
  * (*kind = OMR_IMREAD_KIND_PNG) and goes by omr_png_info's rules, one that begins "II*\0" or "MM\0*" is a TIFF
- * (OMR_IMREAD_KIND_TIFF: omr_tiff_info's rules, *components = 1, *orientation = its Orientation tag), every other one goes
+ * (OMR_IMREAD_KIND_TIFF: omr_tiff_info's rules, *components = 1 or, for an RGB file, 3, *orientation = its Orientation tag), every other one goes
  * by omr_jpeg_info's, with one difference:
  * a JPEG whose EXIF orientation is 2..8 is accepted.  *rows, *cols: the size AFTER the turn (as stored with
  * OMR_IMREAD_IGNORE_ORIENTATION, or when the stream is refused); *components: 1 or 3 as stored (a PNG: 1 for colour types
@@ -1173,7 +1201,7 @@ int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *
 int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
                             uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
                             int32_t *out_size, int32_t *rc);
-/* imread of one buffer, JPEG, PNG or bilevel TIFF: the stream -> a packed host image of `channels` channels (release with
+/* imread of one buffer, JPEG, PNG or TIFF (bilevel, 8-bit gray or RGB): the stream -> a packed host image of `channels` channels (release with
  * omr_image_free), turned by its EXIF orientation unless `flags` says otherwise. */
 int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t flags, omr_image_owned *dst);
 

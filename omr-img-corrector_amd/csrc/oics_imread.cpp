@@ -79,7 +79,8 @@ ImreadParsed omr::imread_parse(const uint8_t *s, int64_t len, int channels, bool
         p.kind = IMREAD_TIFF;
         p.rc = tdec_parse(s, len, th);
         p.rows = th->rows, p.cols = th->cols, p.orient = th->orient;
-        p.components = th->rows ? 1 : 0;
+        p.components = th->rows ? th->samples : 0;
+        if (!p.rc && channels) p.rc = tdec_check_channels(*th, channels);
         return p;
     }
     p.rc = jdec_parse(s, len, h, false);

@@ -1,4 +1,5 @@
-// oics_tiff_dec.cpp -- host side of the bilevel TIFF decoder (tiff_dec.hip): the walk over the
+// oics_tiff_dec.cpp -- host side of the TIFF decoder (bilevel: tiff_dec.hip; 8-bit gray and RGB:
+// tiff_dec8.hip, section 4.27): the walk over the
 // first IFD with what it refuses, the run-length code tables of ITU-T T.4 and the lookup table the T.6 kernel reads, the
 // launches of a group and the entry points omr_tiff_info / omr_tiff_decode*.  The host visits the header and the tags
 // only; everything inside the strips is the device's.  Every offset read from the file is checked against the stream's
@@ -85,7 +86,7 @@ uint32_t rd32(const uint8_t *p, bool be)
               : (uint32_t)p[3] << 24 | (uint32_t)p[2] << 16 | (uint32_t)p[1] << 8 | p[0];
 }
 
-int64_t row_bytes_of(const TdecHeader &h) { return ((int64_t)h.cols + 7) / 8; }
+int64_t row_bytes_of(const TdecHeader &h) { return h.bits_per_sample == 8 ? (int64_t)h.cols * h.samples : ((int64_t)h.cols + 7) / 8; }
 
 }  // namespace
 
@@ -118,8 +119,8 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
     const int64_t entries = rd16(s + ifd, be);
     if (entries == 0 || ifd + 2 + 12 * entries > len) return fail(OMR_ERR_BADARG, "the first IFD's %lld entries run past the end", (long long)entries);
 
-    bool have_cols = false, have_rows = false, tiles = false;
-    int64_t bps = 1, spp = 1, planar = 1, t6opt = 0, rps = 0xffffffffll;
+    bool have_cols = false, have_rows = false, tiles = false, extra = false;
+    int64_t bps = 1, bps_count = 1, spp = 1, planar = 1, t6opt = 0, rps = 0xffffffffll, predictor = 1;
     // StripOffsets / StripByteCounts: where the values stand, their type and count
     int64_t arr_at[2] = {-1, -1}, arr_n[2] = {0, 0};
     int arr_size[2] = {0, 0};
@@ -131,8 +132,12 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
             tiles = true;
             continue;
         }
+        if (tag == 338) {  // ExtraSamples
+            extra = true;
+            continue;
+        }
         const bool known = tag == 256 || tag == 257 || tag == 258 || tag == 259 || tag == 262 || tag == 266 || tag == 273 ||
-                           tag == 274 || tag == 277 || tag == 278 || tag == 279 || tag == 284 || tag == 293;
+                           tag == 274 || tag == 277 || tag == 278 || tag == 279 || tag == 284 || tag == 293 || tag == 317;
         if (!known) continue;
         const int size = type == 3 ? 2 : type == 4 ? 4 : type == 1 ? 1 : 0;
         if (size == 0 || (size == 1 && tag != 258)) return fail(OMR_ERR_BADARG, "tag %u has type %u (SHORT or LONG expected)", tag, type);
@@ -150,9 +155,14 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
             continue;
         }
         if (tag == 258 || tag == 277) {  // one value per sample
-            if (tag == 258) bps = v;
+            if (tag == 258) bps = v, bps_count = count;
             else spp = v;
-            if (tag == 258 && count != 1) bps = -1;
+            if (tag == 258 && count == 3) {  // the three must agree
+                for (int k = 1; k < 3; k++)
+                    if ((size == 2 ? (int64_t)rd16(s + at + 2 * k, be) : size == 4 ? (int64_t)rd32(s + at + 4 * k, be) : (int64_t)s[at + k]) != v) bps = -1;
+            } else if (tag == 258 && count != 1) {
+                bps = -1;
+            }
             continue;
         }
         if (count != 1) return fail(OMR_ERR_BADARG, "tag %u has %lld values", tag, (long long)count);
@@ -166,17 +176,30 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
         case 278: rps = v; break;
         case 284: planar = v; break;
         case 293: t6opt = v; break;
+        case 317: predictor = v; break;
         }
     }
     if (tiles) return fail(OMR_ERR_NOTIMPL, "tiled TIFF is not implemented");
-    if (bps != 1) return fail(OMR_ERR_NOTIMPL, "BitsPerSample other than 1 is not implemented");
+    if (extra) return fail(OMR_ERR_NOTIMPL, "ExtraSamples (alpha or other extra samples) are not implemented");
+    if (bps != 1 && bps != 8) return fail(OMR_ERR_NOTIMPL, "BitsPerSample other than 1 and 8 (the same for every sample) is not implemented");
     if (planar != 1 && spp > 1) return fail(OMR_ERR_NOTIMPL, "PlanarConfiguration 2 with %lld samples is not implemented", (long long)spp);
-    if (spp != 1) return fail(OMR_ERR_NOTIMPL, "SamplesPerPixel %lld is not implemented", (long long)spp);
-    if (h->compression != TDEC_COMP_NONE && h->compression != TDEC_COMP_PACKBITS && h->compression != TDEC_COMP_T6)
-        return fail(OMR_ERR_NOTIMPL, "Compression %d is not implemented (1, 4 and 32773 are)", h->compression);
-    if (h->photometric != 0 && h->photometric != 1)
-        return fail(OMR_ERR_NOTIMPL, "Photometric %d is not implemented (0 and 1 are; -1: the tag is missing)", h->photometric);
+    if (spp != 1 && spp != 3) return fail(OMR_ERR_NOTIMPL, "SamplesPerPixel %lld is not implemented (1 and 3 are)", (long long)spp);
+    if (spp == 3 && (bps != 8 || bps_count != 3)) return fail(OMR_ERR_NOTIMPL, "three samples are implemented with BitsPerSample 8,8,8 alone");
+    if (spp == 1 && bps_count != 1) return fail(OMR_ERR_NOTIMPL, "%lld values of BitsPerSample for one sample", (long long)bps_count);
+    if (h->compression != TDEC_COMP_NONE && h->compression != TDEC_COMP_PACKBITS && h->compression != TDEC_COMP_T6 && h->compression != TDEC_COMP_LZW)
+        return fail(OMR_ERR_NOTIMPL, "Compression %d is not implemented (1, 4, 5 and 32773 are)", h->compression);
+    if (h->compression == TDEC_COMP_T6 && bps != 1) return fail(OMR_ERR_NOTIMPL, "Compression 4 (T.6) is implemented at 1 bit alone");
+    if (h->compression == TDEC_COMP_LZW && bps != 8) return fail(OMR_ERR_NOTIMPL, "Compression 5 (LZW) is implemented at 8 bits alone");
+    if (spp == 3 ? h->photometric != 2 : (h->photometric != 0 && h->photometric != 1))
+        return fail(OMR_ERR_NOTIMPL, "Photometric %d with %lld samples is not implemented (0 and 1 with one sample, 2 with three; -1: the tag is missing)",
+                    h->photometric, (long long)spp);
     if (h->fill_order != 1 && h->fill_order != 2) return fail(OMR_ERR_BADARG, "FillOrder %d (1 or 2)", h->fill_order);
+    if (h->fill_order == 2 && bps == 8) return fail(OMR_ERR_NOTIMPL, "FillOrder 2 at 8 bits is not implemented");
+    // libtiff knows the tag with LZW and Deflate alone and reads a raw or PackBits file that carries it as if it did not
+    if (h->compression == TDEC_COMP_LZW && predictor != 1 && predictor != 2)
+        return fail(OMR_ERR_NOTIMPL, "Predictor %lld is not implemented (1 and 2 are)", (long long)predictor);
+    h->bits_per_sample = (int32_t)bps, h->samples = (int32_t)spp;
+    h->predictor = h->compression == TDEC_COMP_LZW ? (int32_t)predictor : 1;
     if (h->compression == TDEC_COMP_T6 && (t6opt & 2)) return fail(OMR_ERR_NOTIMPL, "T6Options bit 1 (uncompressed mode) is not implemented");
     if (h->compression == TDEC_COMP_T6 && t6opt) return fail(OMR_ERR_BADARG, "T6Options %lld (0 expected)", (long long)t6opt);
     if (h->orient != 1)
@@ -218,6 +241,12 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
             return fail(OMR_ERR_BADARG, "strip %lld (byte %lld, %lld bytes) lies outside the stream", (long long)k, (long long)off, (long long)cnt);
         if (cnt >= ((int64_t)1 << 28)) return fail(OMR_ERR_ASSERT, "a strip of 2^28 bytes or more: not supported");
         const int64_t srows = std::min<int64_t>(h->rows_per_strip, h->rows - k * h->rows_per_strip);
+        if (h->compression == TDEC_COMP_LZW) {
+            // libtiff takes a strip that begins 00 with the low bit of the next byte set for the old LZW, least significant bit first
+            if (cnt >= 2 && s[off] == 0 && (s[off + 1] & 1)) return fail(OMR_ERR_NOTIMPL, "strip %lld is old-style LZW: not implemented", (long long)k);
+            if (srows * row_bytes_of(*h) >= ((int64_t)1 << 31))
+                return fail(OMR_ERR_ASSERT, "an LZW strip of 2^31 bytes of rows or more: not supported");
+        }
         if (h->compression == TDEC_COMP_NONE && cnt < srows * row_bytes_of(*h))
             return fail(OMR_ERR_BADARG, "strip %lld holds %lld bytes, its %lld rows need %lld", (long long)k, (long long)cnt, (long long)srows,
                         (long long)(srows * row_bytes_of(*h)));
@@ -303,7 +332,7 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
     // the host objects that asynchronous copies read or write stand before the drain
     std::vector<TdecImg> im((size_t)g);
     std::vector<TdecDyn> dyn((size_t)g);
-    std::vector<TdecStrip> strips[2];  // PackBits, T.6
+    std::vector<TdecStrip> strips[3];  // PackBits, T.6, LZW
     std::vector<uint8_t> host;
     DrainOnExit drain{s};
     TdecStats &stats = tdec_stats();
@@ -316,7 +345,7 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
     };
     // the uploaded bytes: the lookup table, then every strip at a multiple of 16 (a Compression 1 image: its rows in a row)
     size_t src_bytes = up16(kLutBytes), raw_bytes = 0;
-    int max_rows = 1;
+    int max_rows[2] = {0, 0};  // of the bilevel images, of the 8-bit ones
     std::vector<size_t> first((size_t)g);  // an image's first strip in the uploaded bytes
     for (int j = 0; j < g; j++) {
         const TdecHeader &h = hdr[idx[j]];
@@ -325,10 +354,11 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
         const int32_t rb = (int32_t)row_bytes_of(h);
         m.out_off = (int64_t)idx[j] * out_stride;
         m.rows = h.rows, m.cols = h.cols, m.invert = h.photometric == 0;
-        max_rows = std::max(max_rows, h.rows);
+        m.depth = h.bits_per_sample, m.samples = h.samples, m.predictor = h.predictor;
+        max_rows[h.bits_per_sample == 8] = std::max(max_rows[h.bits_per_sample == 8], h.rows);
         first[(size_t)j] = src_bytes;
         if (h.compression == TDEC_COMP_NONE) {
-            m.bits_off = (int64_t)src_bytes, m.pitch = rb, m.from_src = 1, m.lsb = h.fill_order == 2;
+            m.bits_off = (int64_t)src_bytes, m.pitch = rb, m.from_src = 1, m.lsb = h.fill_order == 2;  // 8 bits: FillOrder 1 (the parser)
             src_bytes += up16((size_t)rb * (size_t)h.rows);
             continue;
         }
@@ -342,7 +372,7 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
             st.dst_off = m.bits_off + (int64_t)row0 * m.pitch;
             st.img = j, st.rows = std::min(h.rows_per_strip, h.rows - row0), st.cols = h.cols, st.pitch = m.pitch;
             st.lsb = h.fill_order == 2;
-            strips[t6].push_back(st);
+            strips[t6 ? 1 : h.compression == TDEC_COMP_LZW ? 2 : 0].push_back(st);
             src_bytes += up16(st.src_len);
         }
         raw_bytes += up16((size_t)m.pitch * (size_t)h.rows);
@@ -367,9 +397,10 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
         return OMR_OK;
     });
     if (r) return r;
-    const size_t np = strips[0].size(), nt = strips[1].size();
+    const size_t np = strips[0].size(), nt = strips[1].size(), nl = strips[2].size();
     std::vector<TdecStrip> all(strips[0]);
     all.insert(all.end(), strips[1].begin(), strips[1].end());
+    all.insert(all.end(), strips[2].begin(), strips[2].end());
     DevBuf d_src, d_im, d_dyn, d_strips, raw;
     OMR_HIP(d_src.alloc(src_bytes));
     OMR_HIP(d_im.alloc(sizeof(TdecImg) * (size_t)g));
@@ -387,8 +418,9 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
     if (!all.empty()) OMR_HIP(hipMemcpyAsync(d_strips.p, all.data(), sizeof(TdecStrip) * all.size(), hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemsetAsync(d_dyn.p, 0, sizeof(TdecDyn) * (size_t)g, s));
     if ((r = mark(1)) || (r = tdec_launch_packbits(p, d_strips.as<TdecStrip>(), (int)np, s)) || (r = mark(2)) ||
-        (r = tdec_launch_t6(p, d_strips.as<TdecStrip>() + np, (int)nt, s)) || (r = mark(3)) || (r = tdec_launch_unpack(p, max_rows, s)) ||
-        (r = mark(4)))
+        (r = tdec_launch_t6(p, d_strips.as<TdecStrip>() + np, (int)nt, s)) || (r = mark(3)) ||
+        (r = tdec_launch_lzw(p, d_strips.as<TdecStrip>() + np + nt, (int)nl, s)) || (r = mark(4)) || (r = tdec_launch_unpack(p, max_rows[0], s)) ||
+        (r = mark(5)) || (r = tdec_launch_finish8(p, max_rows[1], s)) || (r = mark(6)))
         return r;
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(TdecDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
@@ -411,6 +443,13 @@ TdecStats &omr::tdec_stats()
 {
     static thread_local TdecStats st;
     return st;
+}
+
+int omr::tdec_check_channels(const TdecHeader &h, int channels)
+{
+    if (channels == 1 && h.samples == 3)
+        return fail(OMR_ERR_NOTIMPL, "a gray image from an RGB stream is not implemented (the gray weights of imread's TIFF reader are not established)");
+    return OMR_OK;
 }
 
 int omr::tiff_decode_device(const uint8_t *const *streams, const int64_t *, const TdecHeader *hdr, const int32_t *skip, int n,
@@ -457,6 +496,25 @@ int omr_tiff_info(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *co
     return rc;
 }
 
+int omr_tiff_info_ex(const uint8_t *stream, int64_t len, int32_t *rows, int32_t *cols, int32_t *compression, int32_t *photometric,
+                     int32_t *fill_order, int32_t *strips, int32_t *bits_per_sample, int32_t *samples_per_pixel, int32_t *predictor)
+{
+    clear_error();
+    if (!stream || len < 0) return fail(OMR_ERR_BADARG, "null stream");
+    TdecHeader h;
+    const int rc = tdec_parse(stream, len, &h);
+    if (rows) *rows = h.rows;
+    if (cols) *cols = h.cols;
+    if (compression) *compression = h.compression;
+    if (photometric) *photometric = h.photometric;
+    if (fill_order) *fill_order = h.fill_order;
+    if (strips) *strips = (int32_t)h.strips.size();
+    if (bits_per_sample) *bits_per_sample = h.bits_per_sample;
+    if (samples_per_pixel) *samples_per_pixel = h.samples;
+    if (predictor) *predictor = h.predictor;
+    return rc;
+}
+
 int omr_tiff_code_tables(int32_t black, int32_t *run, int32_t *code, int32_t *bits)
 {
     clear_error();
@@ -486,6 +544,7 @@ int omr_tiff_decode_batch_device(const uint8_t *const *streams, const int64_t *l
     for (int i = 0; i < n; i++) {
         TdecHeader &h = hdr[(size_t)i];
         rc[i] = tdec_parse(streams[i], len[i], &h);
+        if (rc[i] == OMR_OK) rc[i] = tdec_check_channels(h, channels);
         if (rc[i] == OMR_OK && (h.rows > rows || h.cols > cols))
             rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d, the slot %d x %d", i, h.rows, h.cols, rows, cols);
         skip[(size_t)i] = rc[i] != OMR_OK;
@@ -509,8 +568,21 @@ int omr_tiff_decode_stats(int32_t enable, int32_t *groups, double *stage_ms)
     clear_error();
     TdecStats &st = tdec_stats();
     if (groups) *groups = st.groups;
+    const int four[4] = {0, 1, 2, 4};  // upload, PackBits, T.6, unpack: the stages this call has always reported
     if (stage_ms)
-        for (int k = 0; k < TDEC_STAGES; k++) stage_ms[k] = st.ms[k];
+        for (int k = 0; k < 4; k++) stage_ms[k] = st.ms[four[k]];
+    st.on = enable != 0;
+    return OMR_OK;
+}
+
+int omr_tiff_decode_stats_ex(int32_t enable, int32_t *groups, double *stage_ms, int32_t capacity, int32_t *stages)
+{
+    clear_error();
+    if (capacity < 0 || (capacity > 0 && !stage_ms)) return fail(OMR_ERR_BADARG, "capacity %d with %s stage_ms", capacity, stage_ms ? "a" : "a null");
+    TdecStats &st = tdec_stats();
+    if (groups) *groups = st.groups;
+    for (int k = 0; k < TDEC_STAGES && k < capacity; k++) stage_ms[k] = st.ms[k];
+    if (stages) *stages = TDEC_STAGES;
     st.on = enable != 0;
     return OMR_OK;
 }
@@ -522,7 +594,7 @@ int omr_tiff_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_im
     if (int r = check_channels(channels)) return r;
     std::vector<TdecHeader> h(1);
     int r = tdec_parse(stream, len, &h[0]);
-    if (r) return r;
+    if (r || (r = tdec_check_channels(h[0], channels))) return r;
     if ((r = have_device())) return r;
     LeasedStream st;
     if ((r = st.create())) return r;
@@ -532,7 +604,7 @@ int omr_tiff_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_im
     const int32_t skip = 0;
     int32_t rc1 = 0;
     if ((r = tiff_decode_device(&stream, &len, h.data(), &skip, 1, channels, out.as<uint8_t>(), bytes, step, &rc1, st.s))) return r;
-    if (rc1) return fail(rc1, "the image data is damaged (an invalid code, a run past the row's or the strip's end, or input that ends early)");
+    if (rc1) return fail(rc1, "the image data is damaged (an invalid code, a run past the row's or the strip's end, a full LZW table, or input that ends early)");
     *dst = omr_image_owned{nullptr, h[0].rows, h[0].cols, channels, step};
     dst->data = (uint8_t *)malloc((size_t)bytes);
     if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");

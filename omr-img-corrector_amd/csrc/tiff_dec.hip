@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(256) tdec_unpack(TdecPass p)
 {
     const int i = (int)blockIdx.y, r = (int)blockIdx.x;
     const TdecImg im = p.imgs[i];
-    if (r >= im.rows || p.dyn[i].err) return;
+    if (im.depth != 1 || r >= im.rows || p.dyn[i].err) return;  // depth 8: tdec_finish8's (tiff_dec8.hip)
     const uint8_t *bits = (im.from_src ? p.src : p.raw) + im.bits_off + (int64_t)r * im.pitch;
     uint8_t *o = p.out + im.out_off + (int64_t)r * p.step;
     const int cn = p.channels;

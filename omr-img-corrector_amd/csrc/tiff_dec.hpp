@@ -1,4 +1,5 @@
-// tiff_dec.hpp -- the bilevel TIFF decoder's device side (tiff_dec.hip) as oics_tiff_dec.cpp sees it.
+// tiff_dec.hpp -- the TIFF decoder's device side (tiff_dec.hip: bilevel; tiff_dec8.hip: 8-bit gray
+// and RGB, section 4.27) as oics_tiff_dec.cpp sees it.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -15,7 +16,7 @@ constexpr int TDEC_WIN_BYTES = 8192;     // a strip's input window in LDS
 constexpr int TDEC_LUT_BITS = 13;        // the longest run-length code
 constexpr int TDEC_CODES = 104;          // per colour: 64 terminating, 27 make-up and 13 extended make-up codes
 
-constexpr int TDEC_COMP_NONE = 1, TDEC_COMP_T6 = 4, TDEC_COMP_PACKBITS = 32773;
+constexpr int TDEC_COMP_NONE = 1, TDEC_COMP_T6 = 4, TDEC_COMP_LZW = 5, TDEC_COMP_PACKBITS = 32773;
 
 // One image of a launch, filled on the host from its header.
 struct TdecImg {
@@ -25,10 +26,13 @@ struct TdecImg {
     int32_t pitch;     // bytes from one packed row to the next
     int32_t from_src;  // != 0: bits_off counts in the uploaded bytes
     int32_t lsb;       // != 0: the packed rows' first pixel is bit 0 of a byte (FillOrder 2 without a decoder in front)
-    int32_t invert;    // != 0: a set bit is black (Photometric 0)
+    int32_t invert;    // != 0: a set bit is black (Photometric 0); at depth 8: every sample is inverted
+    int32_t depth;     // 1: tdec_unpack's image; 8: tdec_finish8's, its rows `samples` bytes a pixel
+    int32_t samples;   // 1 or 3
+    int32_t predictor; // 2: a row's samples are differences to the pixel on the left
 };
 
-// One strip of a launch of the PackBits or the T.6 kernel.
+// One strip of a launch of the PackBits, the T.6 or the LZW kernel.
 struct TdecStrip {
     int64_t src_off;   // its bytes in the uploaded bytes
     int64_t dst_off;   // its first row in the workspace
@@ -63,8 +67,10 @@ struct TdecPass {
 
 int tdec_launch_packbits(const TdecPass &p, const TdecStrip *d_strips, int nstrips, hipStream_t s);
 int tdec_launch_t6(const TdecPass &p, const TdecStrip *d_strips, int nstrips, hipStream_t s);
-// max_rows: the tallest image's
+int tdec_launch_lzw(const TdecPass &p, const TdecStrip *d_strips, int nstrips, hipStream_t s);
+// max_rows: the tallest image's of the kernel's depth
 int tdec_launch_unpack(const TdecPass &p, int max_rows, hipStream_t s);
+int tdec_launch_finish8(const TdecPass &p, int max_rows, hipStream_t s);
 
 // ---- host side (oics_tiff_dec.cpp)
 struct TdecPiece {
@@ -78,10 +84,13 @@ struct TdecHeader {
     int32_t rows = 0, cols = 0;
     int32_t compression = 1, photometric = -1, fill_order = 1, orient = 1;
     int32_t rows_per_strip = 0;
+    int32_t bits_per_sample = 1, samples = 1, predictor = 1;
     std::vector<TdecPiece> strips;
 };
 bool tdec_is_tiff(const uint8_t *stream, int64_t len);
 int tdec_parse(const uint8_t *stream, int64_t len, TdecHeader *h);
+// OMR_ERR_NOTIMPL for a gray image asked of an RGB stream (the PNG decoder's rule, pdec_check_channels), else 0
+int tdec_check_channels(const TdecHeader &h, int channels);
 // the run-length codes of ITU-T T.4 (Tables 2 and 3) for one colour, TDEC_CODES entries each
 void tdec_code_tables(int black, int32_t *run, int32_t *code, int32_t *bits);
 // n parsed streams (hdr[i]; skip[i] != 0: not decoded) into slots d_out + i * out_stride of `channels` channels, rows
@@ -90,11 +99,11 @@ void tdec_code_tables(int black, int32_t *run, int32_t *code, int32_t *bits);
 int tiff_decode_device(const uint8_t *const *streams, const int64_t *len, const TdecHeader *hdr, const int32_t *skip, int n,
                        int channels, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s);
 
-constexpr int TDEC_STAGES = 4;  // upload, PackBits, T.6, unpack
+constexpr int TDEC_STAGES = 6;  // upload, PackBits, T.6, LZW, unpack, finish8
 struct TdecStats {
     bool on = false;
     int32_t groups = 0;
-    double ms[TDEC_STAGES] = {0, 0, 0, 0};
+    double ms[TDEC_STAGES] = {0, 0, 0, 0, 0, 0};
 };
 TdecStats &tdec_stats();
 

@@ -250,6 +250,8 @@ SYMBOLS = {
                                                C.c_int64, C.c_int64, C.c_int32, C.c_int32, i32p, i32p]),
     "omr_tiff_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OmrImageOwned)]),
     "omr_tiff_decode_stats": (C.c_int, [C.c_int32, i32p, f64p]),
+    "omr_tiff_info_ex": (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]),
+    "omr_tiff_decode_stats_ex": (C.c_int, [C.c_int32, i32p, f64p, C.c_int32, i32p]),
     "omr_orient_batch_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                           C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, i32p]),
     "omr_orient": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.POINTER(OmrImageOwned)]),

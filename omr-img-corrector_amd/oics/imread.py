@@ -1,4 +1,4 @@
-"""imread on the device (omr_imread_*): JPEG, PNG or bilevel TIFF file contents -> what imread(IMREAD_COLOR) returns, a JPEG turned by
+"""imread on the device (omr_imread_*): JPEG, PNG or TIFF (bilevel, 8-bit gray or RGB; see oics.tiff) file contents -> what imread(IMREAD_COLOR) returns, a JPEG turned by
 its EXIF orientation as imread does."""
 import ctypes as C
 

@@ -1,5 +1,6 @@
-"""Bilevel TIFF on the device (omr_tiff_*): uncompressed, PackBits and CCITT Group 4 strips decoded byte for byte to what
-libtiff gives, as 255 / 0, and a Group 4 encoder whose strips are byte for byte what libtiff writes."""
+"""TIFF on the device (omr_tiff_*): bilevel files (uncompressed, PackBits and CCITT Group 4 strips, as 255 / 0) and 8-bit
+gray and RGB files (uncompressed, PackBits and LZW strips, Predictor 1 and 2) decoded byte for byte to what libtiff gives,
+and a Group 4 encoder whose strips are byte for byte what libtiff writes."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +22,14 @@ def info(stream):
     return tuple(x.value for x in v)
 
 
+def info_ex(stream):
+    """omr_tiff_info_ex -> info's six values and (bits_per_sample, samples_per_pixel, predictor)"""
+    b = _buf(stream)
+    v = [C.c_int32() for _ in range(9)]
+    check(lib().omr_tiff_info_ex(b.ctypes.data, b.size, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
 def code_tables(black):
     """omr_tiff_code_tables -> [(run, code, bits)]: the T.4 run-length codes of one colour as the decoder holds them"""
     run, code, bits = (np.zeros(OMR_TIFF_CODES, np.int32) for _ in range(3))
@@ -29,7 +38,8 @@ def code_tables(black):
 
 
 def decode(stream, channels=3):
-    """omr_tiff_decode: imread of one buffer -> (rows, cols) for channels = 1, (rows, cols, 3) BGR for channels = 3."""
+    """omr_tiff_decode: imread of one buffer -> (rows, cols) for channels = 1, (rows, cols, 3) BGR for channels = 3.  An
+    RGB file asked for as gray raises OmrError (-213)."""
     b = _buf(stream)
     out = OmrImageOwned()
     check(lib().omr_tiff_decode(b.ctypes.data, b.size, int(channels), C.byref(out)))
@@ -60,6 +70,19 @@ def stats(enable=True):
     groups = C.c_int32()
     ms = np.zeros(len(STAGES), np.float64)
     check(lib().omr_tiff_decode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
+    return groups.value, [float(v) for v in ms]
+
+
+STAGES_EX = ("upload", "PackBits", "T.6", "LZW", "unpack", "finish8")
+
+
+def stats_ex(enable=True):
+    """omr_tiff_decode_stats_ex: stats with every stage -> (groups, [ms per stage of STAGES_EX])"""
+    groups, stages = C.c_int32(), C.c_int32()
+    ms = np.zeros(len(STAGES_EX), np.float64)
+    check(lib().omr_tiff_decode_stats_ex(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double)), ms.size,
+                                         C.byref(stages)))
+    assert stages.value == len(STAGES_EX)
     return groups.value, [float(v) for v in ms]
 
 

@@ -61,7 +61,7 @@ class TransformableMatrix:
 
     @classmethod
     def from_tiff_bytes(cls, stream, channels=3):
-        """What im_read gives for a bilevel TIFF file with these bytes, decoded on the GPU (omr_tiff_decode)."""
+        """What im_read gives for a TIFF file (bilevel, 8-bit gray or RGB) with these bytes, decoded on the GPU (omr_tiff_decode)."""
         from . import tiff
         return cls(tiff.decode(stream, channels))
 

@@ -326,10 +326,11 @@ pub fn decode_png(stream: &[u8], channels: i32) -> Result<TransformableMatrix, o
     Ok(TransformableMatrix { matrix: into_mat(out)? })
 }
 
-/// What `im_read` gives for a bilevel TIFF file with these bytes, decoded on the GPU (omr_tiff_decode): libtiff's rows as
-/// 255 / 0, byte for byte.  1-bit strips, uncompressed, PackBits or CCITT Group 4; one the decoder refuses (BigTIFF, tiles,
-/// other depths or compressions, an Orientation tag) is an error with code OMR_ERR_NOTIMPL, so that the caller can hand
-/// the file to its host codec.  Not in the reference crate.
+/// What `im_read` gives for a TIFF file with these bytes, decoded on the GPU (omr_tiff_decode): libtiff's rows, byte for
+/// byte.  1-bit strips (uncompressed, PackBits or CCITT Group 4) as 255 / 0; 8-bit gray and RGB strips (uncompressed,
+/// PackBits or LZW, Predictor 1 or 2), an RGB file as BGR.  One the decoder refuses (BigTIFF, tiles, other depths or
+/// compressions, palette, alpha, an Orientation tag, a gray image asked of an RGB file) is an error with code
+/// OMR_ERR_NOTIMPL, so that the caller can hand the file to its host codec.  Not in the reference crate.
 pub fn decode_tiff(stream: &[u8], channels: i32) -> Result<TransformableMatrix, opencv::Error> {
     let mut out = ffi::OmrImageOwned::empty();
     check(unsafe { ffi::omr_tiff_decode(stream.as_ptr(), stream.len() as i64, channels, &mut out) })?;
