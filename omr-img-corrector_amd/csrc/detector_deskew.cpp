@@ -38,11 +38,6 @@ namespace {
 const int kDeskewChunk = 32;  // scans of a shape per run when canvases are made: omr_deskew_with_projections_batch's bound
 const int kAnglesChunk = 64;  // ... when only the angles are asked for: the detectors' own host batches' bound
 
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 // the flow on checked arguments.  skip (may be null): scans that are neither detected on nor rotated (their angle 0.0,
 // their code left to the caller).  rc is never null here.  max_rows x max_cols: detector_canvas's answer; d_out may be
 // null: the angles alone.  Synchronises `s`.
@@ -224,41 +219,27 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
     OMR_HIP(din.alloc((size_t)zmax * in_stride));
     if (a.out) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
     std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> codes((size_t)zmax), size(2 * (size_t)zmax, 0), zrc;
-    std::vector<const uint8_t *> zs;
-    std::vector<int64_t> zlen;
-    std::vector<JdecHeader> zhdr;
-    std::vector<PdecHeader> zpng;
-    std::vector<TdecHeader> ztiff;
-    std::vector<uint8_t> zkind;
+    std::vector<int32_t> codes((size_t)zmax), size(2 * (size_t)zmax, 0);
+    ImreadChunk ck;
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
         // the chunk's streams -> the scan slots through the imread layer: each decoder fills its own members' slots, JPEG
         // members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer and orient.hip
-        zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z), ztiff.resize((size_t)z);
-        zkind.resize((size_t)z), zrc.assign((size_t)z, 0);
-        for (int j = 0; j < z; j++) {
-            const int k = idx[(size_t)(j0 + j)];
-            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k], zkind[(size_t)j] = a.hd.kind[k];
-            if (zkind[(size_t)j] == IMREAD_PNG) zpng[(size_t)j] = a.hd.png[k];
-            else if (zkind[(size_t)j] == IMREAD_TIFF) ztiff[(size_t)j] = a.hd.tiff[k];
-            else zhdr[(size_t)j] = a.hd.jpeg[k];
-        }
-        const ImreadHeaders zhd{zhdr.data(), zpng.data(), ztiff.data(), zkind.data()};
-        if ((rc = imread_decode_device(zs.data(), zlen.data(), zhd, nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, zrc.data(), st.s)))
+        ck.gather(a.hd, a.streams, a.len, idx, j0, z);
+        if ((rc = imread_decode_device(ck.zs.data(), ck.zlen.data(), ck.hd.view(), nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, ck.zrc.data(), st.s)))
             return rc;
         // damaged image data: the slot's content means nothing.  Cleared, so that the detector finds a blank scan there
         // whatever the slot held; its angle and canvas are not made
         for (int j = 0; j < z; j++)
-            if (zrc[(size_t)j]) OMR_HIP(hipMemsetAsync(din.as<uint8_t>() + (size_t)j * in_stride, 255, (size_t)in_stride, st.s));
+            if (ck.zrc[(size_t)j]) OMR_HIP(hipMemsetAsync(din.as<uint8_t>() + (size_t)j * in_stride, 255, (size_t)in_stride, st.s));
         if (a.out && a.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(dout.p, 0, (size_t)z * out_stride, st.s));
         if ((rc = deskew_run(a.d, din.as<uint8_t>(), z, in_stride, rows, cols, cn, row, a.flags, a.border_mode, a.border, a.clip, mr, mc,
                              a.out ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data(), ang.data(), codes.data(), nullptr,
-                             zrc.data(), st.s)))
+                             ck.zrc.data(), st.s)))
             return rc;
         for (int j = 0; j < z; j++) {
             const int k = idx[(size_t)(j0 + j)];
-            a.scan_rc[k] = zrc[(size_t)j] ? zrc[(size_t)j] : codes[(size_t)j];
+            a.scan_rc[k] = ck.zrc[(size_t)j] ? ck.zrc[(size_t)j] : codes[(size_t)j];
             a.angles[k] = a.scan_rc[k] ? 0.0 : ang[(size_t)j];
         }
         if (!a.out) continue;
@@ -292,28 +273,24 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
     // the headers, on the host: a sheet its decoder refuses, or whose canvas slot leaves the image limit, keeps its code and
     // leaves the batch here
     std::vector<int32_t> code((size_t)n, OMR_OK);
-    std::vector<JdecHeader> hdr;
-    std::vector<PdecHeader> png_hdr;
-    std::vector<TdecHeader> tiff_hdr;
-    std::vector<uint8_t> kind;
+    ImreadRun run;
     std::vector<int> at;
     std::vector<omr_image> views;
     std::vector<const uint8_t *> zs;
     std::vector<int64_t> zlen;
-    hdr.reserve((size_t)n);
+    run.reserve((size_t)n);
     for (int i = 0; i < n; i++) {
-        hdr.emplace_back(), png_hdr.emplace_back(), tiff_hdr.emplace_back();
         // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
-        const ImreadParsed ps = imread_parse(streams[i], len[i], channels, false, &hdr.back(), &png_hdr.back(), &tiff_hdr.back());
+        const ImreadParsed ps = run.append(streams[i], len[i], channels, false);
         int r = ps.rc;
         const int rows = ps.rows, cols = ps.cols;
         int mr, mc;
         if (!r) r = out ? detector_canvas(rows, cols, clip, &mr, &mc) : check_image_shape(rows, cols);
         if ((code[(size_t)i] = r)) {
-            hdr.pop_back(), png_hdr.pop_back(), tiff_hdr.pop_back();
+            run.drop_last();
             continue;
         }
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), kind.push_back((uint8_t)ps.kind);
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]);
         views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
     }
     clear_error();
@@ -337,7 +314,7 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
             }
         }
         if ((rc = have_device())) return rc;
-        const StreamArgs a{d, zs.data(), zlen.data(), ImreadHeaders{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()}, channels, flags, border_mode, border,
+        const StreamArgs a{d, zs.data(), zlen.data(), run.view(), channels, flags, border_mode, border,
                            clip, level, format, rows_per_strip, dpi, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
         if (rc) {

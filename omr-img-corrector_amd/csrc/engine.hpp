@@ -100,6 +100,14 @@ struct LeasedStream {
     std::unique_ptr<PoolScope> pool_;
 };
 
+// Synchronises `s` on every return path, the error ones included.  Declared behind the host objects that asynchronous
+// copies on `s` read or write, so that they go only once the stream has drained: whatever the function returns, nothing
+// it queued still runs.  (Declared behind a workspace or buffers too, it drains the stream before they go back.)
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
 // "is there a device" of every entry point (no CPU fallback: OMR_ERR_GPU), and the preamble of a *_create: the same,
 // then OMR_ERR_BADARG for a `device` at or above the count, then hipSetDevice
 int have_device(int *count = nullptr);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "codec_stats.hpp"
+
 namespace omr {
 
 // Bits of a subsequence (one lane of the Huffman kernels) and subsequences per workgroup.  -DOMR_JDEC_SUB_BITS /
@@ -119,10 +121,9 @@ int jpeg_decode_device(const uint8_t *const *streams, const int64_t *len, const 
 
 // What omr_jpeg_decode_stats reports: kept per thread, filled by jpeg_decode_device while `on`.
 constexpr int JDEC_STAGES = 6;  // upload and clearing, un-stuffing, synchronisation rounds, coefficients, inverse DCT, colour
-struct JdecStats {
-    bool on = false;
-    int32_t groups = 0, rounds = 0;  // rounds: the most any group took
-    double ms[JDEC_STAGES] = {0, 0, 0, 0, 0, 0};
+struct JdecStats : CodecStats<JDEC_STAGES> {
+    int32_t rounds = 0;  // the most any group took
+    void begin_call() { CodecStats::begin_call(), rounds = 0; }
 };
 JdecStats &jdec_stats();
 

@@ -463,13 +463,6 @@ int log_pictures(FftWork &w, const uint8_t *d_scans, int n, int64_t stride, int6
     return OMR_OK;
 }
 
-// The workspace and the buffers of a batch call go back when it returns, on every path: declared after them, this drains
-// the stream first
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 HoughParams fft_hough_params(double canny_threshold_1, double canny_threshold_2, double min_line_length, double max_line_gap)
 {
     HoughParams hp;

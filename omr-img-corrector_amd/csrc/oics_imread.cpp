@@ -8,23 +8,12 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
-#include "engine.hpp"
+#include "codec_host.hpp"
 #include "orient.hpp"
 
 using namespace omr;
 
 namespace {
-
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
-int check_channels(int channels)
-{
-    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "a decoded image has 1 or 3 channels, got %d", channels);
-    return OMR_OK;
-}
 
 int cn_orient(int cn)
 {
@@ -90,6 +79,27 @@ ImreadParsed omr::imread_parse(const uint8_t *s, int64_t len, int channels, bool
     if (turn < 0) p.rc = turn;
     else if (turn && orient_transposes(h->orient)) std::swap(p.rows, p.cols);
     return p;
+}
+
+ImreadParsed ImreadRun::append(const uint8_t *stream, int64_t len, int channels, bool ignore)
+{
+    jpeg.emplace_back(), png.emplace_back(), tiff.emplace_back();
+    const ImreadParsed p = imread_parse(stream, len, channels, ignore, &jpeg.back(), &png.back(), &tiff.back());
+    kind.push_back((uint8_t)p.kind);
+    return p;
+}
+
+void ImreadChunk::gather(const ImreadHeaders &src, const uint8_t *const *streams, const int64_t *len, const std::vector<int> &idx, int j0, int z)
+{
+    zs.resize((size_t)z), zlen.resize((size_t)z), zrc.assign((size_t)z, 0);
+    hd.jpeg.resize((size_t)z), hd.png.resize((size_t)z), hd.tiff.resize((size_t)z), hd.kind.resize((size_t)z);
+    for (int j = 0; j < z; j++) {
+        const int k = idx[(size_t)(j0 + j)];
+        zs[(size_t)j] = streams[k], zlen[(size_t)j] = len[k], hd.kind[(size_t)j] = src.kind[k];
+        if (src.kind[k] == IMREAD_PNG) hd.png[(size_t)j] = src.png[k];
+        else if (src.kind[k] == IMREAD_TIFF) hd.tiff[(size_t)j] = src.tiff[k];
+        else hd.jpeg[(size_t)j] = src.jpeg[k];
+    }
 }
 
 int omr::orient_device(const uint8_t *d_src, int64_t sstep, uint8_t *d_dst, int64_t dstep, int cn, std::vector<OrientImg> *recs,
@@ -171,7 +181,7 @@ int omr_orient_batch_device(const uint8_t *d_src, int64_t src_stride_bytes, int6
     clear_error();
     if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
     if (!orient || !out_size) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
+    if (int r = check_decoded_channels(channels)) return r;
     if (int r = check_slots(d_src, src_stride_bytes, src_step_bytes, rows, cols, channels, "source")) return r;
     if (int r = check_slots(d_dst, dst_stride_bytes, dst_step_bytes, dst_rows, dst_cols, channels, "destination")) return r;
     if (n == 0) return OMR_OK;
@@ -238,10 +248,8 @@ int omr_imread_info(const uint8_t *stream, int64_t len, int32_t flags, int32_t *
     clear_error();
     if (!stream || len < 0) return fail(OMR_ERR_BADARG, "null stream");
     if (int r = check_flags(flags)) return r;
-    std::vector<JdecHeader> h(1);
-    PdecHeader ph;
-    TdecHeader th;
-    const ImreadParsed p = imread_parse(stream, len, 0, (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0, &h[0], &ph, &th);
+    ImreadRun run;
+    const ImreadParsed p = run.append(stream, len, 0, (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0);
     if (rows) *rows = p.rows;
     if (cols) *cols = p.cols;
     if (components) *components = p.components;
@@ -254,79 +262,35 @@ int omr_imread_batch_device(const uint8_t *const *streams, const int64_t *len, i
                             uint8_t *d_out, int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols,
                             int32_t *out_size, int32_t *rc)
 {
-    clear_error();
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
-    if (!streams || !len || !d_out || !out_size || !rc) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    if (int r = check_flags(flags)) return r;
-    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "empty slot");
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (out_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "out_stride_bytes < rows x step_bytes");
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
-    if (n == 0) return OMR_OK;
     const bool ignore = (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0;
-    std::vector<JdecHeader> hdr((size_t)n);
-    std::vector<PdecHeader> png_hdr((size_t)n);
-    std::vector<TdecHeader> tiff_hdr((size_t)n);
-    std::vector<uint8_t> kind((size_t)n, 0);
-    std::vector<int32_t> skip((size_t)n, 0);
-    int good = 0;
-    for (int i = 0; i < n; i++) {
-        const ImreadParsed p = imread_parse(streams[i], len[i], channels, ignore, &hdr[(size_t)i], &png_hdr[(size_t)i], &tiff_hdr[(size_t)i]);
-        kind[(size_t)i] = (uint8_t)p.kind;
-        rc[i] = p.rc;
-        if (rc[i] == OMR_OK && (p.rows > rows || p.cols > cols))
-            rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d as imread returns it, the slot %d x %d", i, p.rows, p.cols, rows, cols);
-        skip[(size_t)i] = rc[i] != OMR_OK;
-        out_size[2 * (size_t)i] = skip[(size_t)i] ? 0 : p.rows;
-        out_size[2 * (size_t)i + 1] = skip[(size_t)i] ? 0 : p.cols;
-        good += !skip[(size_t)i];
-    }
-    if (good == 0) return OMR_OK;  // every stream refused: the codes are in rc, there is no device work
-    clear_error();
-    if (int r = have_device()) return r;
-    LeasedStream st;
-    if (int r = st.create()) return r;
-    const ImreadHeaders hd{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()};
-    const int r = imread_decode_device(streams, len, hd, skip.data(), n, channels, ignore, d_out, out_stride_bytes, step_bytes, rc, st.s);
-    for (int i = 0; r == OMR_OK && i < n; i++)
-        if (rc[i]) out_size[2 * (size_t)i] = out_size[2 * (size_t)i + 1] = 0;
-    return r;
+    ImreadRun run;
+    return decode_batch_entry(
+        BatchDecodeArgs{streams, len, n, channels, d_out, out_stride_bytes, step_bytes, rows, cols, out_size, rc},
+        "stream %d is %d x %d as imread returns it, the slot %d x %d", [&] { return check_flags(flags); }, [&](size_t cnt) { run.reserve(cnt); },
+        [&](int i) {
+            const ImreadParsed p = run.append(streams[i], len[i], channels, ignore);
+            return ParsedSize{p.rc, p.rows, p.cols};
+        },
+        [&](const int32_t *skip, hipStream_t s) {
+            return imread_decode_device(streams, len, run.view(), skip, n, channels, ignore, d_out, out_stride_bytes, step_bytes, rc, s);
+        });
 }
 
 int omr_imread(const uint8_t *stream, int64_t len, int32_t channels, int32_t flags, omr_image_owned *dst)
 {
-    clear_error();
-    if (!stream || len < 0 || !dst) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    if (int r = check_flags(flags)) return r;
     const bool ignore = (flags & OMR_IMREAD_IGNORE_ORIENTATION) != 0;
-    std::vector<JdecHeader> h(1);
-    std::vector<PdecHeader> ph(1);
-    std::vector<TdecHeader> th(1);
-    const ImreadParsed p = imread_parse(stream, len, channels, ignore, &h[0], &ph[0], &th[0]);
-    int r = p.rc;
-    if (r) return r;
-    if ((r = have_device())) return r;
-    LeasedStream st;
-    if ((r = st.create())) return r;
-    const int64_t step = (int64_t)p.cols * channels, bytes = step * p.rows;
-    DrainOnExit drain{st.s};
-    DevBuf out;
-    OMR_HIP(out.alloc((size_t)bytes));
-    const uint8_t kind = (uint8_t)p.kind;
-    const ImreadHeaders hd{h.data(), ph.data(), th.data(), &kind};
-    int32_t rc1 = 0;
-    if ((r = imread_decode_device(&stream, &len, hd, nullptr, 1, channels, ignore, out.as<uint8_t>(), bytes, step, &rc1, st.s))) return r;
-    if (rc1)
-        return fail(rc1, "the image data is damaged (what its decoder, omr_jpeg_decode, omr_png_decode or omr_tiff_decode, reports as OMR_ERR_ASSERT)");
-    *dst = omr_image_owned{nullptr, p.rows, p.cols, channels, step};
-    dst->data = (uint8_t *)malloc((size_t)bytes);
-    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    r = staged_d2h(dst->data, out.p, (size_t)bytes, st.s);
-    if (r) omr_image_free(dst);
-    return r;
+    ImreadRun run;
+    return decode_one_entry(
+        stream, len, channels, dst,
+        "the image data is damaged (what its decoder, omr_jpeg_decode, omr_png_decode or omr_tiff_decode, reports as OMR_ERR_ASSERT)",
+        [&] { return check_flags(flags); },
+        [&] {
+            const ImreadParsed p = run.append(stream, len, channels, ignore);
+            return ParsedSize{p.rc, p.rows, p.cols};
+        },
+        [&](uint8_t *d_out, int64_t stride, int64_t step, int32_t *rc, hipStream_t s) {
+            return imread_decode_device(&stream, &len, run.view(), nullptr, 1, channels, ignore, d_out, stride, step, rc, s);
+        });
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "../../include/omrdeskew.h"
 #include "engine.hpp"
 #include "jpeg.hpp"
+#include "stream_sink.hpp"
 
 using namespace omr;
 
@@ -147,11 +148,6 @@ int check_jpeg_shape(int rows, int cols, int cn)
     return OMR_OK;
 }
 
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 constexpr int64_t kGroupBlocks = 4 << 20;  // blocks of one group of launches: 512 MB of coefficients
 constexpr int kGroupImages = 4096;
 
@@ -244,41 +240,6 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     OMR_HIP(hipStreamSynchronize(s));
     return sink.done(i0, g, len.data());
 }
-
-// the public device form's sink: slot i of the caller's buffer, lengths into the caller's host array
-struct SlotSink : JpegSink {
-    uint8_t *d_out;
-    int64_t stride;
-    int64_t *out_len;
-    int place(int i0, int cnt, const int64_t *len, uint8_t **out, int64_t *off) override
-    {
-        *out = d_out;
-        for (int j = 0; j < cnt; j++) off[j] = (int64_t)(i0 + j) * stride, out_len[i0 + j] = len[j];
-        return OMR_OK;
-    }
-    int done(int, int, const int64_t *) override { return OMR_OK; }
-};
-
-// omr_jpeg_encode's sink: one stream, into the caller's host buffer when it fits
-struct HostSink : JpegSink {
-    uint8_t *out;
-    int64_t cap, len = 0;
-    hipStream_t s;
-    DevBuf buf;
-    bool fits = false;
-    int place(int, int, const int64_t *l, uint8_t **d_out, int64_t *off) override
-    {
-        len = l[0], off[0] = 0;
-        OMR_HIP(buf.alloc((size_t)len));
-        *d_out = buf.as<uint8_t>();
-        return OMR_OK;
-    }
-    int done(int, int, const int64_t *) override
-    {
-        fits = out && len <= cap;
-        return fits ? staged_d2h(out, buf.p, (size_t)len, s) : OMR_OK;
-    }
-};
 
 }  // namespace
 

@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
-#include "engine.hpp"
+#include "codec_host.hpp"
 #include "jpeg_dec.hpp"
 #include "png_dec.hpp"
 
@@ -48,17 +48,6 @@ int exif_orientation(const uint8_t *b, int64_t n)
     return exif_orientation_tiff(b + 6, n - 6);
 }
 
-int check_channels(int channels)
-{
-    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "a decoded image has 1 or 3 channels, got %d", channels);
-    return OMR_OK;
-}
-
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 constexpr int64_t kGroupBlocks = 4 << 20;     // blocks of one group of launches: 512 MB of coefficients
 constexpr int64_t kGroupBytes = 256 << 20;    // entropy data of one group
 constexpr int kGroupImages = 4096;
@@ -68,23 +57,6 @@ int64_t blocks_of(const JdecHeader &h)
     const int64_t mw = (h.cols + 8 * h.hs - 1) / (8 * h.hs), mh = (h.rows + 8 * h.vs - 1) / (8 * h.vs);
     return mw * mh * (h.hs * h.vs + (h.ncomp == 3 ? 2 : 0));
 }
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// the events between a group's stages, made only while the thread collects omr_jpeg_decode_stats
-struct StageEvents {
-    hipEvent_t e[JDEC_STAGES + 1] = {};
-    int n = 0;
-    int create()
-    {
-        for (; n <= JDEC_STAGES; n++) OMR_HIP(hipEventCreate(&e[n]));
-        return OMR_OK;
-    }
-    ~StageEvents()
-    {
-        for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]);
-    }
-};
 
 // one group: images idx[0 .. g)
 int decode_group(const uint8_t *const *streams, const int64_t *len, const JdecHeader *hdr, const int *idx, int g, int channels,
@@ -99,13 +71,8 @@ int decode_group(const uint8_t *const *streams, const int64_t *len, const JdecHe
     uint32_t h_changed = 0;
     DrainOnExit drain{s};
     JdecStats &stats = jdec_stats();
-    StageEvents ev;
-    if (stats.on)
-        if (int r = ev.create()) return r;
-    auto mark = [&](int k) -> int {
-        if (stats.on) OMR_HIP(hipEventRecord(ev.e[k], s));
-        return OMR_OK;
-    };
+    StageTimer<JDEC_STAGES> ev;
+    if (int r = ev.begin(stats.on)) return r;
     size_t src_bytes = 0, bit_bytes = 0, plane_bytes = 0;
     uint32_t blocks = 0, ivals = 0, subs = 0, chunks = 0, max_blocks = 1;
     int max_chunks = 1, max_groups = 1, max_rows = 1, max_cols = 1;
@@ -176,7 +143,7 @@ int decode_group(const uint8_t *const *streams, const int64_t *len, const JdecHe
     p.state = state.as<uint64_t>(), p.sub_cnt = scnt.as<uint32_t>(), p.sub_ex = sex.as<uint32_t>();
     p.chg = chg.as<uint8_t>(), p.sub_total = subs, p.changed = changed.as<uint32_t>();
     p.coef = coef.as<int16_t>(), p.planes = planes.as<uint8_t>(), p.out = d_out, p.step = step;
-    int r = mark(0);
+    int r = ev.mark(0, s);
     if (r) return r;
     OMR_HIP(hipMemcpyAsync(d_src.p, host.data(), src_bytes, hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(JdecImg) * (size_t)g, hipMemcpyHostToDevice, s));
@@ -185,7 +152,7 @@ int decode_group(const uint8_t *const *streams, const int64_t *len, const JdecHe
     OMR_HIP(hipMemsetAsync(bitbuf.p, 0, bit_bytes, s));
     OMR_HIP(hipMemsetAsync(coef.p, 0, (size_t)blocks * 128, s));
     OMR_HIP(hipMemsetAsync(chg.p, 0, (size_t)subs * 2, s));
-    if ((r = mark(1)) || (r = jdec_launch_unstuff(p, max_chunks, s)) || (r = mark(2))) return r;
+    if ((r = ev.mark(1, s)) || (r = jdec_launch_unstuff(p, max_chunks, s)) || (r = ev.mark(2, s))) return r;
     // rounds until one changes nothing: after round k the first k subsequences of every interval stand, so the number of
     // subsequences bounds the rounds
     uint32_t round = 0;
@@ -198,19 +165,12 @@ int decode_group(const uint8_t *const *streams, const int64_t *len, const JdecHe
         OMR_HIP(hipStreamSynchronize(s));
         if (h_changed == 0) break;
     }
-    if ((r = mark(3)) || (r = jdec_launch_finish(p, max_groups, max_blocks, max_rows, max_cols, s, stats.on ? &ev.e[4] : nullptr)) ||
-        (r = mark(6)))
+    if ((r = ev.mark(3, s)) || (r = jdec_launch_finish(p, max_groups, max_blocks, max_rows, max_cols, s, ev.from(4))) || (r = ev.mark(6, s)))
         return r;
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(JdecDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
-    if (stats.on) {
-        stats.groups++, stats.rounds = std::max(stats.rounds, (int32_t)round + 1);
-        for (int k = 0; k < JDEC_STAGES; k++) {
-            float ms = 0;
-            OMR_HIP(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-            stats.ms[k] += ms;
-        }
-    }
+    if (stats.on) stats.rounds = std::max(stats.rounds, (int32_t)round + 1);
+    if ((r = ev.finish(stats))) return r;
     for (int j = 0; j < g; j++)
         if (dyn[(size_t)j].err) rc[idx[j]] = OMR_ERR_ASSERT;
     return OMR_OK;
@@ -369,39 +329,21 @@ int omr::exif_orientation_tiff(const uint8_t *t, int64_t n)
     return 1;
 }
 
-JdecStats &omr::jdec_stats()
-{
-    static thread_local JdecStats st;
-    return st;
-}
+JdecStats &omr::jdec_stats() { return thread_stats<JdecStats>(); }
 
 int omr::jpeg_decode_device(const uint8_t *const *streams, const int64_t *len, const JdecHeader *hdr, const int32_t *skip, int n,
                             int channels, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s)
 {
-    JdecStats &stats = jdec_stats();
-    stats.groups = stats.rounds = 0;
-    for (double &v : stats.ms) v = 0;
-    DrainOnExit drain{s};  // declared before any buffer: they go back only behind a drained stream
-    std::vector<int> idx;
-    for (int i0 = 0; i0 < n;) {
-        idx.clear();
-        int64_t blocks = 0, bytes = 0;
-        int i = i0;
-        for (; i < n && (int)idx.size() < kGroupImages; i++) {
-            if (skip[i]) continue;
-            if (len[i] - hdr[i].data <= 0) {  // nothing behind SOS
-                rc[i] = OMR_ERR_ASSERT;
-                continue;
-            }
-            const int64_t b = blocks_of(hdr[i]), by = len[i] - hdr[i].data;
-            if (!idx.empty() && (blocks + b > kGroupBlocks || bytes + by > kGroupBytes)) break;
-            blocks += b, bytes += by, idx.push_back(i);
-        }
-        if (!idx.empty())
-            if (int r = decode_group(streams, len, hdr, idx.data(), (int)idx.size(), channels, d_out, out_stride, step, rc, s)) return r;
-        i0 = i;
-    }
-    return OMR_OK;
+    jdec_stats().begin_call();
+    DrainOnExit drain{s};
+    return for_each_group(
+        n, skip, kGroupImages, kGroupBlocks, kGroupBytes,
+        [&](int i) {
+            const int64_t bytes = len[i] - hdr[i].data;
+            if (bytes <= 0) rc[i] = OMR_ERR_ASSERT;  // nothing behind SOS
+            return GroupCost{blocks_of(hdr[i]), bytes, bytes > 0};
+        },
+        [&](const int *idx, int g) { return decode_group(streams, len, hdr, idx, g, channels, d_out, out_stride, step, rc, s); });
 }
 
 extern "C" {
@@ -423,73 +365,43 @@ int omr_jpeg_decode_batch_device(const uint8_t *const *streams, const int64_t *l
                                  int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols, int32_t *out_size,
                                  int32_t *rc)
 {
-    clear_error();
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
-    if (!streams || !len || !d_out || !out_size || !rc) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "empty slot");
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (out_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "out_stride_bytes < rows x step_bytes");
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
-    if (n == 0) return OMR_OK;
-    std::vector<JdecHeader> hdr((size_t)n);
-    std::vector<int32_t> skip((size_t)n, 0);
-    int good = 0;
-    for (int i = 0; i < n; i++) {
-        rc[i] = jdec_parse(streams[i], len[i], &hdr[(size_t)i]);
-        if (rc[i] == OMR_OK && (hdr[(size_t)i].rows > rows || hdr[(size_t)i].cols > cols))
-            rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d, the slot %d x %d", i, hdr[(size_t)i].rows, hdr[(size_t)i].cols, rows, cols);
-        skip[(size_t)i] = rc[i] != OMR_OK;
-        out_size[2 * (size_t)i] = skip[(size_t)i] ? 0 : hdr[(size_t)i].rows;
-        out_size[2 * (size_t)i + 1] = skip[(size_t)i] ? 0 : hdr[(size_t)i].cols;
-        good += !skip[(size_t)i];
-    }
-    if (good == 0) return OMR_OK;  // every stream refused: the codes are in rc, there is no device work
-    clear_error();
-    if (int r = have_device()) return r;
-    LeasedStream st;
-    if (int r = st.create()) return r;
-    return jpeg_decode_device(streams, len, hdr.data(), skip.data(), n, channels, d_out, out_stride_bytes, step_bytes, rc, st.s);
+    std::vector<JdecHeader> hdr;
+    return decode_batch_entry(
+        BatchDecodeArgs{streams, len, n, channels, d_out, out_stride_bytes, step_bytes, rows, cols, out_size, rc},
+        "stream %d is %d x %d, the slot %d x %d", no_extra_check, [&](size_t cnt) { hdr.reserve(cnt); },
+        [&](int i) {
+            hdr.emplace_back();
+            const int r = jdec_parse(streams[i], len[i], &hdr.back());
+            return ParsedSize{r, hdr.back().rows, hdr.back().cols};
+        },
+        [&](const int32_t *skip, hipStream_t s) {
+            return jpeg_decode_device(streams, len, hdr.data(), skip, n, channels, d_out, out_stride_bytes, step_bytes, rc, s);
+        });
 }
 
 int omr_jpeg_decode_stats(int32_t enable, int32_t *sub_bits, int32_t *groups, int32_t *rounds, double *stage_ms)
 {
     clear_error();
-    JdecStats &st = jdec_stats();
     if (sub_bits) *sub_bits = JDEC_SUB_BITS;
-    if (groups) *groups = st.groups;
-    if (rounds) *rounds = st.rounds;
-    if (stage_ms)
-        for (int k = 0; k < JDEC_STAGES; k++) stage_ms[k] = st.ms[k];
-    st.on = enable != 0;
+    if (rounds) *rounds = jdec_stats().rounds;
+    jdec_stats().report(enable, groups, stage_ms);
     return OMR_OK;
 }
 
 int omr_jpeg_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_image_owned *dst)
 {
-    clear_error();
-    if (!stream || len < 0 || !dst) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
     std::vector<JdecHeader> h(1);
-    int r = jdec_parse(stream, len, &h[0]);
-    if (r) return r;
-    if ((r = have_device())) return r;
-    LeasedStream st;
-    if ((r = st.create())) return r;
-    const int64_t step = (int64_t)h[0].cols * channels, bytes = step * h[0].rows;
-    DevBuf out;
-    OMR_HIP(out.alloc((size_t)bytes));
     const int32_t skip = 0;
-    int32_t rc1 = 0;
-    if ((r = jpeg_decode_device(&stream, &len, h.data(), &skip, 1, channels, out.as<uint8_t>(), bytes, step, &rc1, st.s))) return r;
-    if (rc1) return fail(rc1, "the entropy data is not a scan of its header (cut short, an invalid code, or blocks left over)");
-    *dst = omr_image_owned{nullptr, h[0].rows, h[0].cols, channels, step};
-    dst->data = (uint8_t *)malloc((size_t)bytes);
-    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    r = staged_d2h(dst->data, out.p, (size_t)bytes, st.s);
-    if (r) omr_image_free(dst);
-    return r;
+    return decode_one_entry(
+        stream, len, channels, dst, "the entropy data is not a scan of its header (cut short, an invalid code, or blocks left over)",
+        no_extra_check,
+        [&] {
+            const int r = jdec_parse(stream, len, &h[0]);
+            return ParsedSize{r, h[0].rows, h[0].cols};
+        },
+        [&](uint8_t *d_out, int64_t stride, int64_t step, int32_t *rc, hipStream_t s) {
+            return jpeg_decode_device(&stream, &len, h.data(), &skip, 1, channels, d_out, stride, step, rc, s);
+        });
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
-#include "engine.hpp"
+#include "codec_host.hpp"
 #include "host_threads.hpp"
 #include "png_dec.hpp"
 
@@ -58,36 +58,9 @@ int samples_of(int color_type) { return color_type == 0 ? 1 : color_type == 2 ? 
 
 int64_t row_bytes_of(const PdecHeader &h) { return ((int64_t)h.cols * samples_of(h.color_type) * h.depth + 7) / 8; }
 
-int check_channels(int channels)
-{
-    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "a decoded image has 1 or 3 channels, got %d", channels);
-    return OMR_OK;
-}
-
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 constexpr int64_t kGroupRaw = (int64_t)4 << 30;  // inflated bytes of one group of launches: 160 A4 colour images, an image per CU
 constexpr int64_t kGroupBytes = (int64_t)2 << 30;  // zlib streams of one group
 constexpr int kGroupImages = 4096;
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-struct StageEvents {
-    hipEvent_t e[PDEC_STAGES + 1] = {};
-    int n = 0;
-    int create()
-    {
-        for (; n <= PDEC_STAGES; n++) OMR_HIP(hipEventCreate(&e[n]));
-        return OMR_OK;
-    }
-    ~StageEvents()
-    {
-        for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]);
-    }
-};
 
 // one group: images idx[0 .. g)
 int decode_group(const uint8_t *const *streams, const PdecHeader *hdr, const int *idx, int g, int channels, uint8_t *d_out,
@@ -98,14 +71,8 @@ int decode_group(const uint8_t *const *streams, const PdecHeader *hdr, const int
     std::vector<PdecDyn> dyn((size_t)g);
     std::vector<uint8_t> host;
     DrainOnExit drain{s};
-    PdecStats &stats = pdec_stats();
-    StageEvents ev;
-    if (stats.on)
-        if (int r = ev.create()) return r;
-    auto mark = [&](int k) -> int {
-        if (stats.on) OMR_HIP(hipEventRecord(ev.e[k], s));
-        return OMR_OK;
-    };
+    StageTimer<PDEC_STAGES> ev;
+    if (int r = ev.begin(pdec_stats().on)) return r;
     size_t src_bytes = 0, raw_bytes = 0;
     int max_chunks = 1;
     for (int j = 0; j < g; j++) {
@@ -149,23 +116,16 @@ int decode_group(const uint8_t *const *streams, const PdecHeader *hdr, const int
     memset(&p, 0, sizeof p);
     p.src = d_src.as<uint8_t>(), p.imgs = d_im.as<PdecImg>(), p.dyn = d_dyn.as<PdecDyn>(), p.raw = raw.as<uint8_t>();
     p.n = g, p.channels = channels, p.out = d_out, p.step = step;
-    if ((r = mark(0))) return r;
+    if ((r = ev.mark(0, s))) return r;
     if (src_bytes) OMR_HIP(hipMemcpyAsync(d_src.p, host.data(), src_bytes, hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(PdecImg) * (size_t)g, hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemsetAsync(d_dyn.p, 0, sizeof(PdecDyn) * (size_t)g, s));
-    if ((r = mark(1)) || (r = pdec_launch_inflate(p, s)) || (r = mark(2)) || (r = pdec_launch_adler(p, max_chunks, s)) ||
-        (r = mark(3)) || (r = pdec_launch_unfilter(p, s)) || (r = mark(4)))
+    if ((r = ev.mark(1, s)) || (r = pdec_launch_inflate(p, s)) || (r = ev.mark(2, s)) || (r = pdec_launch_adler(p, max_chunks, s)) ||
+        (r = ev.mark(3, s)) || (r = pdec_launch_unfilter(p, s)) || (r = ev.mark(4, s)))
         return r;
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(PdecDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
-    if (stats.on) {
-        stats.groups++;
-        for (int k = 0; k < PDEC_STAGES; k++) {
-            float ms = 0;
-            OMR_HIP(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-            stats.ms[k] += ms;
-        }
-    }
+    if ((r = ev.finish(pdec_stats()))) return r;
     for (int j = 0; j < g; j++)
         if (im[(size_t)j].skip || dyn[(size_t)j].err) rc[idx[j]] = OMR_ERR_ASSERT;
     return OMR_OK;
@@ -259,35 +219,17 @@ int omr::pdec_check_channels(const PdecHeader &h, int channels)
     return OMR_OK;
 }
 
-PdecStats &omr::pdec_stats()
-{
-    static thread_local PdecStats st;
-    return st;
-}
+PdecStats &omr::pdec_stats() { return thread_stats<PdecStats>(); }
 
 int omr::png_decode_device(const uint8_t *const *streams, const int64_t *, const PdecHeader *hdr, const int32_t *skip, int n,
                            int channels, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s)
 {
-    PdecStats &stats = pdec_stats();
-    stats.groups = 0;
-    for (double &v : stats.ms) v = 0;
-    DrainOnExit drain{s};  // declared before any buffer: they go back only behind a drained stream
-    std::vector<int> idx;
-    for (int i0 = 0; i0 < n;) {
-        idx.clear();
-        int64_t raw = 0, bytes = 0;
-        int i = i0;
-        for (; i < n && (int)idx.size() < kGroupImages; i++) {
-            if (skip[i]) continue;
-            const int64_t rw = (int64_t)hdr[i].rows * (1 + row_bytes_of(hdr[i])), by = hdr[i].idat_bytes;
-            if (!idx.empty() && (raw + rw > kGroupRaw || bytes + by > kGroupBytes)) break;
-            raw += rw, bytes += by, idx.push_back(i);
-        }
-        if (!idx.empty())
-            if (int r = decode_group(streams, hdr, idx.data(), (int)idx.size(), channels, d_out, out_stride, step, rc, s)) return r;
-        i0 = i;
-    }
-    return OMR_OK;
+    pdec_stats().begin_call();
+    DrainOnExit drain{s};
+    return for_each_group(
+        n, skip, kGroupImages, kGroupRaw, kGroupBytes,
+        [&](int i) { return GroupCost{(int64_t)hdr[i].rows * (1 + row_bytes_of(hdr[i])), hdr[i].idat_bytes, true}; },
+        [&](const int *idx, int g) { return decode_group(streams, hdr, idx, g, channels, d_out, out_stride, step, rc, s); });
 }
 
 extern "C" {
@@ -309,76 +251,43 @@ int omr_png_decode_batch_device(const uint8_t *const *streams, const int64_t *le
                                 int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols, int32_t *out_size,
                                 int32_t *rc)
 {
-    clear_error();
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
-    if (!streams || !len || !d_out || !out_size || !rc) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "empty slot");
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (out_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "out_stride_bytes < rows x step_bytes");
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
-    if (n == 0) return OMR_OK;
-    std::vector<PdecHeader> hdr((size_t)n);
-    std::vector<int32_t> skip((size_t)n, 0);
-    int good = 0;
-    for (int i = 0; i < n; i++) {
-        PdecHeader &h = hdr[(size_t)i];
-        rc[i] = pdec_parse(streams[i], len[i], &h);
-        if (rc[i] == OMR_OK) rc[i] = pdec_check_channels(h, channels);
-        if (rc[i] == OMR_OK && (h.rows > rows || h.cols > cols))
-            rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d, the slot %d x %d", i, h.rows, h.cols, rows, cols);
-        skip[(size_t)i] = rc[i] != OMR_OK;
-        out_size[2 * (size_t)i] = skip[(size_t)i] ? 0 : h.rows;
-        out_size[2 * (size_t)i + 1] = skip[(size_t)i] ? 0 : h.cols;
-        good += !skip[(size_t)i];
-    }
-    if (good == 0) return OMR_OK;  // every stream refused: the codes are in rc, there is no device work
-    clear_error();
-    if (int r = have_device()) return r;
-    LeasedStream st;
-    if (int r = st.create()) return r;
-    const int r = png_decode_device(streams, len, hdr.data(), skip.data(), n, channels, d_out, out_stride_bytes, step_bytes, rc, st.s);
-    for (int i = 0; r == OMR_OK && i < n; i++)
-        if (rc[i]) out_size[2 * (size_t)i] = out_size[2 * (size_t)i + 1] = 0;
-    return r;
+    std::vector<PdecHeader> hdr;
+    return decode_batch_entry(
+        BatchDecodeArgs{streams, len, n, channels, d_out, out_stride_bytes, step_bytes, rows, cols, out_size, rc},
+        "stream %d is %d x %d, the slot %d x %d", no_extra_check, [&](size_t cnt) { hdr.reserve(cnt); },
+        [&](int i) {
+            hdr.emplace_back();
+            int r = pdec_parse(streams[i], len[i], &hdr.back());
+            if (r == OMR_OK) r = pdec_check_channels(hdr.back(), channels);
+            return ParsedSize{r, hdr.back().rows, hdr.back().cols};
+        },
+        [&](const int32_t *skip, hipStream_t s) {
+            return png_decode_device(streams, len, hdr.data(), skip, n, channels, d_out, out_stride_bytes, step_bytes, rc, s);
+        });
 }
 
 int omr_png_decode_stats(int32_t enable, int32_t *groups, double *stage_ms)
 {
     clear_error();
-    PdecStats &st = pdec_stats();
-    if (groups) *groups = st.groups;
-    if (stage_ms)
-        for (int k = 0; k < PDEC_STAGES; k++) stage_ms[k] = st.ms[k];
-    st.on = enable != 0;
+    pdec_stats().report(enable, groups, stage_ms);
     return OMR_OK;
 }
 
 int omr_png_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_image_owned *dst)
 {
-    clear_error();
-    if (!stream || len < 0 || !dst) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    std::vector<PdecHeader> h(1);
-    int r = pdec_parse(stream, len, &h[0]);
-    if (r || (r = pdec_check_channels(h[0], channels))) return r;
-    if ((r = have_device())) return r;
-    LeasedStream st;
-    if ((r = st.create())) return r;
-    const int64_t step = (int64_t)h[0].cols * channels, bytes = step * h[0].rows;
-    DevBuf out;
-    OMR_HIP(out.alloc((size_t)bytes));
+    PdecHeader h;
     const int32_t skip = 0;
-    int32_t rc1 = 0;
-    if ((r = png_decode_device(&stream, &len, h.data(), &skip, 1, channels, out.as<uint8_t>(), bytes, step, &rc1, st.s))) return r;
-    if (rc1) return fail(rc1, "the image data is damaged (a chunk's CRC, the deflate stream, its Adler-32 or size, a filter byte or a palette index)");
-    *dst = omr_image_owned{nullptr, h[0].rows, h[0].cols, channels, step};
-    dst->data = (uint8_t *)malloc((size_t)bytes);
-    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    r = staged_d2h(dst->data, out.p, (size_t)bytes, st.s);
-    if (r) omr_image_free(dst);
-    return r;
+    return decode_one_entry(
+        stream, len, channels, dst,
+        "the image data is damaged (a chunk's CRC, the deflate stream, its Adler-32 or size, a filter byte or a palette index)", no_extra_check,
+        [&] {
+            int r = pdec_parse(stream, len, &h);
+            if (r == OMR_OK) r = pdec_check_channels(h, channels);
+            return ParsedSize{r, h.rows, h.cols};
+        },
+        [&](uint8_t *d_out, int64_t stride, int64_t step, int32_t *rc, hipStream_t s) {
+            return png_decode_device(&stream, &len, &h, &skip, 1, channels, d_out, stride, step, rc, s);
+        });
 }
 
 }  // extern "C"

@@ -7,39 +7,20 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
-#include "engine.hpp"
+#include "codec_host.hpp"
 #include "png_enc.hpp"
+#include "stream_sink.hpp"
 
 using namespace omr;
 
 namespace {
-
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
 
 // raw bytes of one group of launches; the workspace is about five times that (raw, two bytes of match / token entry per
 // raw byte, the bit buffer, the code tables)
 constexpr int64_t kGroupRaw = (int64_t)512 << 20;
 constexpr int kGroupImages = 4096;
 
-int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 int64_t blocks_of(int64_t raw) { return (raw + PENC_BLOCK - 1) / PENC_BLOCK; }
-
-struct StageEvents {
-    hipEvent_t e[PENC_STAGES + 1] = {};
-    int n = 0;
-    int create()
-    {
-        for (; n <= PENC_STAGES; n++) OMR_HIP(hipEventCreate(&e[n]));
-        return OMR_OK;
-    }
-    ~StageEvents()
-    {
-        for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]);
-    }
-};
 
 // one group: images [i0, i0 + g)
 int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn, const int32_t *sizes, int i0, int g,
@@ -49,14 +30,8 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     std::vector<PencDyn> dyn((size_t)g);
     std::vector<int64_t> len((size_t)g, 0), off((size_t)g, 0);
     DrainOnExit drain{s};  // behind the host objects that asynchronous copies read or write, before the device buffers
-    PencStats &stats = penc_stats();
-    StageEvents ev;
-    if (stats.on)
-        if (int r = ev.create()) return r;
-    auto mark = [&](int k) -> int {
-        if (stats.on) OMR_HIP(hipEventRecord(ev.e[k], s));
-        return OMR_OK;
-    };
+    StageTimer<PENC_STAGES> ev;
+    if (int r = ev.begin(penc_stats().on)) return r;
     int64_t raw_bytes = 0, blocks = 0, max_raw = 0;
     int max_rows = 0;
     for (int j = 0; j < g; j++) {
@@ -100,16 +75,16 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     // 1. everything up to the blocks' sizes; the host learns every stream's length
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(PencImg) * (size_t)g, hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemsetAsync(d_dyn.p, 0, sizeof(PencDyn) * (size_t)g, s));
-    int rc = mark(0);
-    if (rc || (rc = penc_launch_filter(p, max_rows, s)) || (rc = mark(1)) || (rc = penc_launch_adler(p, max_raw, s)) || (rc = mark(2)))
+    int rc = ev.mark(0, s);
+    if (rc || (rc = penc_launch_filter(p, max_rows, s)) || (rc = ev.mark(1, s)) || (rc = penc_launch_adler(p, max_raw, s)) || (rc = ev.mark(2, s)))
         return rc;
     if (!stored_only && (rc = penc_launch_parse(p, max_raw, max_pieces, s))) return rc;
-    if ((rc = mark(3)) || (rc = penc_launch_blocks(p, max_blocks, s)) || (rc = mark(4))) return rc;
+    if ((rc = ev.mark(3, s)) || (rc = penc_launch_blocks(p, max_blocks, s)) || (rc = ev.mark(4, s))) return rc;
     if (!stored_only) {
         OMR_HIP(hipMemsetAsync(zbuf.p, 0, (size_t)blocks * PENC_ZBLOCK, s));
         if ((rc = penc_launch_bits(p, max_blocks, s))) return rc;
     }
-    if ((rc = mark(5))) return rc;
+    if ((rc = ev.mark(5, s))) return rc;
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(PencDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
     for (int j = 0; j < g; j++)
@@ -119,53 +94,11 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     for (int j = 0; j < g; j++) im[(size_t)j].out_off = off[(size_t)j];
     p.out = d_out;
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(PencImg) * (size_t)g, hipMemcpyHostToDevice, s));
-    if ((rc = penc_launch_streams(p, max_blocks, s)) || (rc = mark(6))) return rc;
+    if ((rc = penc_launch_streams(p, max_blocks, s)) || (rc = ev.mark(6, s))) return rc;
     OMR_HIP(hipStreamSynchronize(s));
-    if (stats.on) {
-        stats.groups++;
-        for (int k = 0; k < PENC_STAGES; k++) {
-            float ms = 0;
-            OMR_HIP(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-            stats.ms[k] += ms;
-        }
-    }
+    if ((rc = ev.finish(penc_stats()))) return rc;
     return sink.done(i0, g, len.data());
 }
-
-// the public device form's sink: slot i of the caller's buffer, lengths into the caller's host array
-struct SlotSink : JpegSink {
-    uint8_t *d_out;
-    int64_t stride;
-    int64_t *out_len;
-    int place(int i0, int cnt, const int64_t *len, uint8_t **out, int64_t *off) override
-    {
-        *out = d_out;
-        for (int j = 0; j < cnt; j++) off[j] = (int64_t)(i0 + j) * stride, out_len[i0 + j] = len[j];
-        return OMR_OK;
-    }
-    int done(int, int, const int64_t *) override { return OMR_OK; }
-};
-
-// omr_png_encode's sink: one stream, into the caller's host buffer when it fits
-struct HostSink : JpegSink {
-    uint8_t *out;
-    int64_t cap, len = 0;
-    hipStream_t s;
-    DevBuf buf;
-    bool fits = false;
-    int place(int, int, const int64_t *l, uint8_t **d_out, int64_t *off) override
-    {
-        len = l[0], off[0] = 0;
-        OMR_HIP(buf.alloc((size_t)len));
-        *d_out = buf.as<uint8_t>();
-        return OMR_OK;
-    }
-    int done(int, int, const int64_t *) override
-    {
-        fits = out && len <= cap;
-        return fits ? staged_d2h(out, buf.p, (size_t)len, s) : OMR_OK;
-    }
-};
 
 int check_batch_args(const void *d_imgs, const void *d_out, const void *out_len, int n)
 {
@@ -196,18 +129,12 @@ int omr::penc_check_shape(int rows, int cols, int cn)
     return OMR_OK;
 }
 
-PencStats &omr::penc_stats()
-{
-    static thread_local PencStats st;
-    return st;
-}
+PencStats &omr::penc_stats() { return thread_stats<PencStats>(); }
 
 int omr::png_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn, const int32_t *sizes, int n,
                            int compression, JpegSink &sink, hipStream_t s)
 {
-    PencStats &stats = penc_stats();
-    stats.groups = 0;
-    for (double &v : stats.ms) v = 0;
+    penc_stats().begin_call();
     compression = std::min(std::max(compression, 0), 9);
     for (int i = 0; i < n; i++)
         if (sizes[2 * (size_t)i] > 0)
@@ -293,11 +220,7 @@ int omr_png_encode(const omr_image *src, int32_t compression, uint8_t *out, int6
 int omr_png_encode_stats(int32_t enable, int32_t *groups, double *stage_ms)
 {
     clear_error();
-    PencStats &st = penc_stats();
-    if (groups) *groups = st.groups;
-    if (stage_ms)
-        for (int k = 0; k < PENC_STAGES; k++) stage_ms[k] = st.ms[k];
-    st.on = enable != 0;
+    penc_stats().report(enable, groups, stage_ms);
     return OMR_OK;
 }
 

@@ -16,7 +16,7 @@
 
 #include "../../include/omrdeskew.h"
 #ifndef TDEC_PARSER_ONLY
-#include "engine.hpp"
+#include "codec_host.hpp"
 #include "host_threads.hpp"
 #endif
 #include "tiff_dec.hpp"
@@ -259,22 +259,9 @@ int omr::tdec_parse(const uint8_t *s, int64_t len, TdecHeader *h)
 
 namespace {
 
-int check_channels(int channels)
-{
-    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "a decoded image has 1 or 3 channels, got %d", channels);
-    return OMR_OK;
-}
-
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 constexpr int64_t kGroupRaw = (int64_t)1 << 30;    // packed rows of one group of launches
 constexpr int64_t kGroupBytes = (int64_t)1 << 30;  // strips of one group
 constexpr int kGroupImages = 4096;                 // the unpack kernel's grid takes 65535
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 constexpr size_t kLutBytes = sizeof(uint16_t) * 2 * ((size_t)1 << TDEC_LUT_BITS);
 
@@ -296,20 +283,6 @@ const std::vector<uint16_t> &lut()
     }();
     return t;
 }
-
-struct StageEvents {
-    hipEvent_t e[TDEC_STAGES + 1] = {};
-    int n = 0;
-    int create()
-    {
-        for (; n <= TDEC_STAGES; n++) OMR_HIP(hipEventCreate(&e[n]));
-        return OMR_OK;
-    }
-    ~StageEvents()
-    {
-        for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]);
-    }
-};
 
 int64_t raw_bytes_of(const TdecHeader &h)
 {
@@ -335,14 +308,8 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
     std::vector<TdecStrip> strips[3];  // PackBits, T.6, LZW
     std::vector<uint8_t> host;
     DrainOnExit drain{s};
-    TdecStats &stats = tdec_stats();
-    StageEvents ev;
-    if (stats.on)
-        if (int r = ev.create()) return r;
-    auto mark = [&](int k) -> int {
-        if (stats.on) OMR_HIP(hipEventRecord(ev.e[k], s));
-        return OMR_OK;
-    };
+    StageTimer<TDEC_STAGES> ev;
+    if (int r = ev.begin(tdec_stats().on)) return r;
     // the uploaded bytes: the lookup table, then every strip at a multiple of 16 (a Compression 1 image: its rows in a row)
     size_t src_bytes = up16(kLutBytes), raw_bytes = 0;
     int max_rows[2] = {0, 0};  // of the bilevel images, of the 8-bit ones
@@ -412,26 +379,19 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
     p.src = d_src.as<uint8_t>(), p.imgs = d_im.as<TdecImg>(), p.dyn = d_dyn.as<TdecDyn>(), p.raw = raw.as<uint8_t>();
     p.lut = d_src.as<uint16_t>();
     p.n = g, p.channels = channels, p.out = d_out, p.step = step;
-    if ((r = mark(0))) return r;
+    if ((r = ev.mark(0, s))) return r;
     OMR_HIP(hipMemcpyAsync(d_src.p, host.data(), src_bytes, hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(TdecImg) * (size_t)g, hipMemcpyHostToDevice, s));
     if (!all.empty()) OMR_HIP(hipMemcpyAsync(d_strips.p, all.data(), sizeof(TdecStrip) * all.size(), hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemsetAsync(d_dyn.p, 0, sizeof(TdecDyn) * (size_t)g, s));
-    if ((r = mark(1)) || (r = tdec_launch_packbits(p, d_strips.as<TdecStrip>(), (int)np, s)) || (r = mark(2)) ||
-        (r = tdec_launch_t6(p, d_strips.as<TdecStrip>() + np, (int)nt, s)) || (r = mark(3)) ||
-        (r = tdec_launch_lzw(p, d_strips.as<TdecStrip>() + np + nt, (int)nl, s)) || (r = mark(4)) || (r = tdec_launch_unpack(p, max_rows[0], s)) ||
-        (r = mark(5)) || (r = tdec_launch_finish8(p, max_rows[1], s)) || (r = mark(6)))
+    if ((r = ev.mark(1, s)) || (r = tdec_launch_packbits(p, d_strips.as<TdecStrip>(), (int)np, s)) || (r = ev.mark(2, s)) ||
+        (r = tdec_launch_t6(p, d_strips.as<TdecStrip>() + np, (int)nt, s)) || (r = ev.mark(3, s)) ||
+        (r = tdec_launch_lzw(p, d_strips.as<TdecStrip>() + np + nt, (int)nl, s)) || (r = ev.mark(4, s)) || (r = tdec_launch_unpack(p, max_rows[0], s)) ||
+        (r = ev.mark(5, s)) || (r = tdec_launch_finish8(p, max_rows[1], s)) || (r = ev.mark(6, s)))
         return r;
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(TdecDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
-    if (stats.on) {
-        stats.groups++;
-        for (int k = 0; k < TDEC_STAGES; k++) {
-            float ms = 0;
-            OMR_HIP(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-            stats.ms[k] += ms;
-        }
-    }
+    if ((r = ev.finish(tdec_stats()))) return r;
     for (int j = 0; j < g; j++)
         if (dyn[(size_t)j].err) rc[idx[j]] = OMR_ERR_ASSERT;
     return OMR_OK;
@@ -439,11 +399,7 @@ int decode_group(const uint8_t *const *streams, const TdecHeader *hdr, const int
 
 }  // namespace
 
-TdecStats &omr::tdec_stats()
-{
-    static thread_local TdecStats st;
-    return st;
-}
+TdecStats &omr::tdec_stats() { return thread_stats<TdecStats>(); }
 
 int omr::tdec_check_channels(const TdecHeader &h, int channels)
 {
@@ -455,27 +411,15 @@ int omr::tdec_check_channels(const TdecHeader &h, int channels)
 int omr::tiff_decode_device(const uint8_t *const *streams, const int64_t *, const TdecHeader *hdr, const int32_t *skip, int n,
                             int channels, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s)
 {
-    TdecStats &stats = tdec_stats();
-    stats.groups = 0;
-    for (double &v : stats.ms) v = 0;
-    DrainOnExit drain{s};  // declared before any buffer: they go back only behind a drained stream
-    std::vector<int> idx;
-    for (int i0 = 0; i0 < n;) {
-        idx.clear();
-        int64_t raw = 0, bytes = 0;
-        int i = i0;
-        for (; i < n && (int)idx.size() < kGroupImages; i++) {
-            if (skip[i]) continue;
-            const int64_t rw = raw_bytes_of(hdr[i]);
+    tdec_stats().begin_call();
+    DrainOnExit drain{s};
+    return for_each_group(
+        n, skip, kGroupImages, kGroupRaw, kGroupBytes,
+        [&](int i) {
             const int64_t by = hdr[i].compression == TDEC_COMP_NONE ? row_bytes_of(hdr[i]) * hdr[i].rows : src_bytes_of(hdr[i]);
-            if (!idx.empty() && (raw + rw > kGroupRaw || bytes + by > kGroupBytes)) break;
-            raw += rw, bytes += by, idx.push_back(i);
-        }
-        if (!idx.empty())
-            if (int r = decode_group(streams, hdr, idx.data(), (int)idx.size(), channels, d_out, out_stride, step, rc, s)) return r;
-        i0 = i;
-    }
-    return OMR_OK;
+            return GroupCost{raw_bytes_of(hdr[i]), by, true};
+        },
+        [&](const int *idx, int g) { return decode_group(streams, hdr, idx, g, channels, d_out, out_stride, step, rc, s); });
 }
 
 extern "C" {
@@ -528,39 +472,19 @@ int omr_tiff_decode_batch_device(const uint8_t *const *streams, const int64_t *l
                                  int64_t out_stride_bytes, int64_t step_bytes, int32_t rows, int32_t cols, int32_t *out_size,
                                  int32_t *rc)
 {
-    clear_error();
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
-    if (!streams || !len || !d_out || !out_size || !rc) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    if (rows <= 0 || cols <= 0) return fail(OMR_ERR_BADARG, "empty slot");
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (out_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "out_stride_bytes < rows x step_bytes");
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
-    if (n == 0) return OMR_OK;
-    std::vector<TdecHeader> hdr((size_t)n);
-    std::vector<int32_t> skip((size_t)n, 0);
-    int good = 0;
-    for (int i = 0; i < n; i++) {
-        TdecHeader &h = hdr[(size_t)i];
-        rc[i] = tdec_parse(streams[i], len[i], &h);
-        if (rc[i] == OMR_OK) rc[i] = tdec_check_channels(h, channels);
-        if (rc[i] == OMR_OK && (h.rows > rows || h.cols > cols))
-            rc[i] = fail(OMR_ERR_BADARG, "stream %d is %d x %d, the slot %d x %d", i, h.rows, h.cols, rows, cols);
-        skip[(size_t)i] = rc[i] != OMR_OK;
-        out_size[2 * (size_t)i] = skip[(size_t)i] ? 0 : h.rows;
-        out_size[2 * (size_t)i + 1] = skip[(size_t)i] ? 0 : h.cols;
-        good += !skip[(size_t)i];
-    }
-    if (good == 0) return OMR_OK;  // every stream refused: the codes are in rc, there is no device work
-    clear_error();
-    if (int r = have_device()) return r;
-    LeasedStream st;
-    if (int r = st.create()) return r;
-    const int r = tiff_decode_device(streams, len, hdr.data(), skip.data(), n, channels, d_out, out_stride_bytes, step_bytes, rc, st.s);
-    for (int i = 0; r == OMR_OK && i < n; i++)
-        if (rc[i]) out_size[2 * (size_t)i] = out_size[2 * (size_t)i + 1] = 0;
-    return r;
+    std::vector<TdecHeader> hdr;
+    return decode_batch_entry(
+        BatchDecodeArgs{streams, len, n, channels, d_out, out_stride_bytes, step_bytes, rows, cols, out_size, rc},
+        "stream %d is %d x %d, the slot %d x %d", no_extra_check, [&](size_t cnt) { hdr.reserve(cnt); },
+        [&](int i) {
+            hdr.emplace_back();
+            int r = tdec_parse(streams[i], len[i], &hdr.back());
+            if (r == OMR_OK) r = tdec_check_channels(hdr.back(), channels);
+            return ParsedSize{r, hdr.back().rows, hdr.back().cols};
+        },
+        [&](const int32_t *skip, hipStream_t s) {
+            return tiff_decode_device(streams, len, hdr.data(), skip, n, channels, d_out, out_stride_bytes, step_bytes, rc, s);
+        });
 }
 
 int omr_tiff_decode_stats(int32_t enable, int32_t *groups, double *stage_ms)
@@ -579,38 +503,27 @@ int omr_tiff_decode_stats_ex(int32_t enable, int32_t *groups, double *stage_ms, 
 {
     clear_error();
     if (capacity < 0 || (capacity > 0 && !stage_ms)) return fail(OMR_ERR_BADARG, "capacity %d with %s stage_ms", capacity, stage_ms ? "a" : "a null");
-    TdecStats &st = tdec_stats();
-    if (groups) *groups = st.groups;
-    for (int k = 0; k < TDEC_STAGES && k < capacity; k++) stage_ms[k] = st.ms[k];
+    tdec_stats().report(enable, groups, stage_ms, std::min<int>(capacity, TDEC_STAGES));
     if (stages) *stages = TDEC_STAGES;
-    st.on = enable != 0;
     return OMR_OK;
 }
 
 int omr_tiff_decode(const uint8_t *stream, int64_t len, int32_t channels, omr_image_owned *dst)
 {
-    clear_error();
-    if (!stream || len < 0 || !dst) return fail(OMR_ERR_BADARG, "null argument");
-    if (int r = check_channels(channels)) return r;
-    std::vector<TdecHeader> h(1);
-    int r = tdec_parse(stream, len, &h[0]);
-    if (r || (r = tdec_check_channels(h[0], channels))) return r;
-    if ((r = have_device())) return r;
-    LeasedStream st;
-    if ((r = st.create())) return r;
-    const int64_t step = (int64_t)h[0].cols * channels, bytes = step * h[0].rows;
-    DevBuf out;
-    OMR_HIP(out.alloc((size_t)bytes));
+    TdecHeader h;
     const int32_t skip = 0;
-    int32_t rc1 = 0;
-    if ((r = tiff_decode_device(&stream, &len, h.data(), &skip, 1, channels, out.as<uint8_t>(), bytes, step, &rc1, st.s))) return r;
-    if (rc1) return fail(rc1, "the image data is damaged (an invalid code, a run past the row's or the strip's end, a full LZW table, or input that ends early)");
-    *dst = omr_image_owned{nullptr, h[0].rows, h[0].cols, channels, step};
-    dst->data = (uint8_t *)malloc((size_t)bytes);
-    if (!dst->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    r = staged_d2h(dst->data, out.p, (size_t)bytes, st.s);
-    if (r) omr_image_free(dst);
-    return r;
+    return decode_one_entry(
+        stream, len, channels, dst,
+        "the image data is damaged (an invalid code, a run past the row's or the strip's end, a full LZW table, or input that ends early)",
+        no_extra_check,
+        [&] {
+            int r = tdec_parse(stream, len, &h);
+            if (r == OMR_OK) r = tdec_check_channels(h, channels);
+            return ParsedSize{r, h.rows, h.cols};
+        },
+        [&](uint8_t *d_out, int64_t stride, int64_t step, int32_t *rc, hipStream_t s) {
+            return tiff_decode_device(&stream, &len, &h, &skip, 1, channels, d_out, stride, step, rc, s);
+        });
 }
 
 }  // extern "C"

@@ -8,7 +8,8 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
-#include "engine.hpp"
+#include "codec_host.hpp"
+#include "stream_sink.hpp"
 #include "tiff_dec.hpp"  // tdec_code_tables: the one set of T.4 codes
 #include "tiff_enc.hpp"
 
@@ -16,28 +17,9 @@ using namespace omr;
 
 namespace {
 
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 // bytes of row code segments in one group of launches (the largest part of the workspace)
 constexpr int64_t kGroupCode = (int64_t)1 << 30;
 constexpr int kGroupImages = 4096;
-
-struct StageEvents {
-    hipEvent_t e[TENC_STAGES + 1] = {};
-    int n = 0;
-    int create()
-    {
-        for (; n <= TENC_STAGES; n++) OMR_HIP(hipEventCreate(&e[n]));
-        return OMR_OK;
-    }
-    ~StageEvents()
-    {
-        for (int i = 0; i < n; i++) (void)hipEventDestroy(e[i]);
-    }
-};
 
 int pack_w_of(int cols) { return (cols + 31) / 32 + 1; }
 int seg_w_of(int cols) { return (int)((tenc_row_bits(cols) + 31) / 32) + 1; }
@@ -104,14 +86,8 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     std::vector<TencDyn> dyn((size_t)g);
     std::vector<int64_t> len((size_t)g, 0), off((size_t)g, 0);
     DrainOnExit drain{s};  // behind the host objects that asynchronous copies read or write, before the device buffers
-    TencStats &stats = tenc_stats();
-    StageEvents ev;
-    if (stats.on)
-        if (int r = ev.create()) return r;
-    auto mark = [&](int k) -> int {
-        if (stats.on) OMR_HIP(hipEventRecord(ev.e[k], s));
-        return OMR_OK;
-    };
+    StageTimer<TENC_STAGES> ev;
+    if (int r = ev.begin(tenc_stats().on)) return r;
     int64_t pack_words = 0, code_words = 0, rows_all = 0, strips_all = 0, max_pack_bytes = 0;
     int max_rows = 0, max_cols = 0, max_strips = 0, max_rps = 0;
     for (int j = 0; j < g; j++) {
@@ -163,9 +139,9 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     // 1. everything up to the strips' sizes; the host learns every file's length
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(TencImg) * (size_t)g, hipMemcpyHostToDevice, s));
     OMR_HIP(hipMemcpyAsync(d_codes.p, codes, sizeof codes, hipMemcpyHostToDevice, s));
-    int rc = mark(0);
-    if (rc || (rc = tenc_launch_pack(p, max_pack_bytes, s)) || (rc = mark(1)) || (rc = tenc_launch_rows(p, max_rows, s)) || (rc = mark(2)) ||
-        (rc = tenc_launch_place(p, max_strips, max_rps, s)) || (rc = mark(3)))
+    int rc = ev.mark(0, s);
+    if (rc || (rc = tenc_launch_pack(p, max_pack_bytes, s)) || (rc = ev.mark(1, s)) || (rc = tenc_launch_rows(p, max_rows, s)) || (rc = ev.mark(2, s)) ||
+        (rc = tenc_launch_place(p, max_strips, max_rps, s)) || (rc = ev.mark(3, s)))
         return rc;
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(TencDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
@@ -180,53 +156,11 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     for (int j = 0; j < g; j++) im[(size_t)j].out_off = off[(size_t)j];
     p.out = d_out;
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(TencImg) * (size_t)g, hipMemcpyHostToDevice, s));
-    if ((rc = tenc_launch_merge(p, max_data, max_strips, s)) || (rc = mark(4))) return rc;
+    if ((rc = tenc_launch_merge(p, max_data, max_strips, s)) || (rc = ev.mark(4, s))) return rc;
     OMR_HIP(hipStreamSynchronize(s));
-    if (stats.on) {
-        stats.groups++;
-        for (int k = 0; k < TENC_STAGES; k++) {
-            float ms = 0;
-            OMR_HIP(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-            stats.ms[k] += ms;
-        }
-    }
+    if ((rc = ev.finish(tenc_stats()))) return rc;
     return sink.done(i0, g, len.data());
 }
-
-// the public device form's sink: slot i of the caller's buffer, lengths into the caller's host array
-struct SlotSink : JpegSink {
-    uint8_t *d_out;
-    int64_t stride;
-    int64_t *out_len;
-    int place(int i0, int cnt, const int64_t *len, uint8_t **out, int64_t *off) override
-    {
-        *out = d_out;
-        for (int j = 0; j < cnt; j++) off[j] = (int64_t)(i0 + j) * stride, out_len[i0 + j] = len[j];
-        return OMR_OK;
-    }
-    int done(int, int, const int64_t *) override { return OMR_OK; }
-};
-
-// omr_tiff_encode's sink: one file, into the caller's host buffer when it fits
-struct HostSink : JpegSink {
-    uint8_t *out;
-    int64_t cap, len = 0;
-    hipStream_t s;
-    DevBuf buf;
-    bool fits = false;
-    int place(int, int, const int64_t *l, uint8_t **d_out, int64_t *off) override
-    {
-        len = l[0], off[0] = 0;
-        OMR_HIP(buf.alloc((size_t)len));
-        *d_out = buf.as<uint8_t>();
-        return OMR_OK;
-    }
-    int done(int, int, const int64_t *) override
-    {
-        fits = out && len <= cap;
-        return fits ? staged_d2h(out, buf.p, (size_t)len, s) : OMR_OK;
-    }
-};
 
 }  // namespace
 
@@ -277,18 +211,12 @@ int omr::tenc_check_params(int cn, int threshold, int rows_per_strip, int dpi)
     return OMR_OK;
 }
 
-TencStats &omr::tenc_stats()
-{
-    static thread_local TencStats st;
-    return st;
-}
+TencStats &omr::tenc_stats() { return thread_stats<TencStats>(); }
 
 int omr::tiff_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn, const int32_t *sizes, int n, int threshold,
                             int rows_per_strip, int dpi, JpegSink &sink, hipStream_t s)
 {
-    TencStats &stats = tenc_stats();
-    stats.groups = 0;
-    for (double &v : stats.ms) v = 0;
+    tenc_stats().begin_call();
     int rc = tenc_check_params(cn, threshold, rows_per_strip, dpi);
     if (rc) return rc;
     for (int i = 0; i < n; i++)
@@ -380,11 +308,7 @@ int omr_tiff_encode(const omr_image *src, int32_t threshold, int32_t rows_per_st
 int omr_tiff_encode_stats(int32_t enable, int32_t *groups, double *stage_ms)
 {
     clear_error();
-    TencStats &st = tenc_stats();
-    if (groups) *groups = st.groups;
-    if (stage_ms)
-        for (int k = 0; k < TENC_STAGES; k++) stage_ms[k] = st.ms[k];
-    st.on = enable != 0;
+    tenc_stats().report(enable, groups, stage_ms);
     return OMR_OK;
 }
 

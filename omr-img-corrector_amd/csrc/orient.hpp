@@ -64,6 +64,31 @@ struct ImreadParsed {
 // (pdec_check_channels), 0 leaves it out.
 ImreadParsed imread_parse(const uint8_t *stream, int64_t len, int channels, bool ignore, JdecHeader *jpeg, PdecHeader *png, TdecHeader *tiff);
 
+#pragma GCC visibility push(hidden)  // the library's own: not in the dynamic symbol table
+// The owner of a run's parsed headers: the three parallel header vectors and the kind bytes behind an ImreadHeaders.
+struct ImreadRun {
+    std::vector<JdecHeader> jpeg;
+    std::vector<PdecHeader> png;
+    std::vector<TdecHeader> tiff;
+    std::vector<uint8_t> kind;
+    void reserve(size_t n) { jpeg.reserve(n), png.reserve(n), tiff.reserve(n), kind.reserve(n); }
+    // imread_parse of one more stream, as the run's last member; a caller that does not accept it drops it again
+    ImreadParsed append(const uint8_t *stream, int64_t len, int channels, bool ignore);
+    void drop_last() { jpeg.pop_back(), png.pop_back(), tiff.pop_back(), kind.pop_back(); }
+    ImreadHeaders view() const { return ImreadHeaders{jpeg.data(), png.data(), tiff.data(), kind.data()}; }
+};
+
+// One chunk of a streams flow's bucket, reused from chunk to chunk: what imread_decode_device takes for members
+// idx[j0 .. j0 + z) of the run `src` (with the run's streams and their lengths), and their codes.
+struct ImreadChunk {
+    std::vector<const uint8_t *> zs;
+    std::vector<int64_t> zlen;
+    ImreadRun hd;
+    std::vector<int32_t> zrc;
+    void gather(const ImreadHeaders &src, const uint8_t *const *streams, const int64_t *len, const std::vector<int> &idx, int j0, int z);
+};
+#pragma GCC visibility pop
+
 // The decode of one run of parsed streams into the slots d_out + i * out_stride (rows `step` apart): PNG and TIFF members
 // and JPEG members that need no turn (orient == 1, or `ignore`) go straight into their slots through their decoders; JPEG
 // members with an orientation 2..8 are decoded into a scratch buffer of the run and turned into their slots by one launch

@@ -5,6 +5,8 @@
 
 #include <vector>
 
+#include "codec_stats.hpp"
+
 namespace omr {
 
 constexpr int PDEC_WIN_WORDS = 1024;    // an image's input window in LDS, 32-bit words
@@ -93,11 +95,7 @@ int png_decode_device(const uint8_t *const *streams, const int64_t *len, const P
 int exif_orientation_tiff(const uint8_t *tiff, int64_t n);
 
 constexpr int PDEC_STAGES = 4;  // upload, inflate, Adler-32, unfilter and convert
-struct PdecStats {
-    bool on = false;
-    int32_t groups = 0;
-    double ms[PDEC_STAGES] = {0, 0, 0, 0};
-};
+struct PdecStats : CodecStats<PDEC_STAGES> {};
 PdecStats &pdec_stats();
 
 }  // namespace omr

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "codec_stats.hpp"
 #include "jpeg.hpp"  // JpegSink: where a group's streams go (the protocol is the JPEG encoder's: place, then done)
 
 namespace omr {
@@ -95,11 +96,7 @@ int png_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t step, i
                       int compression, JpegSink &sink, hipStream_t s);
 
 constexpr int PENC_STAGES = 6;  // filter, Adler-32, matches and parse, code sets and placement, bit writer, copy + CRC-32 + wrap
-struct PencStats {
-    bool on = false;
-    int32_t groups = 0;
-    double ms[PENC_STAGES] = {0, 0, 0, 0, 0, 0};
-};
+struct PencStats : CodecStats<PENC_STAGES> {};
 PencStats &penc_stats();
 
 }  // namespace omr

@@ -604,30 +604,15 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
     if (a.out) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
     std::vector<double> ang((size_t)zmax);
     std::vector<int32_t> best((size_t)zmax), size(2 * (size_t)zmax);
-    std::vector<const uint8_t *> zs;
-    std::vector<int64_t> zlen;
-    std::vector<JdecHeader> zhdr;
-    std::vector<PdecHeader> zpng;
-    std::vector<TdecHeader> ztiff;
-    std::vector<uint8_t> zkind;
-    std::vector<int32_t> zrc;
+    ImreadChunk ck;
     for (int j0 = 0; j0 < m; j0 += zmax) {
         const int z = std::min(zmax, m - j0);
         // the chunk's streams -> the scan slots, decoded on the device; a bucket may hold both kinds: each decoder fills
         // its own members' slots and skips the other's
         // (JPEG members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer of the
         // chunk, which one launch turns into their slots)
-        zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z), ztiff.resize((size_t)z);
-        zkind.resize((size_t)z), zrc.assign((size_t)z, 0);
-        for (int j = 0; j < z; j++) {
-            const int k = idx[(size_t)(j0 + j)];
-            zs[(size_t)j] = a.streams[k], zlen[(size_t)j] = a.len[k], zkind[(size_t)j] = a.hd.kind[k];
-            if (zkind[(size_t)j] == IMREAD_PNG) zpng[(size_t)j] = a.hd.png[k];
-            else if (zkind[(size_t)j] == IMREAD_TIFF) ztiff[(size_t)j] = a.hd.tiff[k];
-            else zhdr[(size_t)j] = a.hd.jpeg[k];
-        }
-        const ImreadHeaders zhd{zhdr.data(), zpng.data(), ztiff.data(), zkind.data()};
-        if ((rc = imread_decode_device(zs.data(), zlen.data(), zhd, nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, zrc.data(), st.s)))
+        ck.gather(a.hd, a.streams, a.len, idx, j0, z);
+        if ((rc = imread_decode_device(ck.zs.data(), ck.zlen.data(), ck.hd.view(), nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, ck.zrc.data(), st.s)))
             return rc;
         rc = a.out ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
                                                         out_stride, out_step, size.data(), ang.data(), best.data())
@@ -635,8 +620,8 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
         if (rc) return rc;
         for (int j = 0; j < z; j++) {
             const int k = idx[(size_t)(j0 + j)];
-            if (zrc[(size_t)j]) {  // damaged image data: the slot's content means nothing; its code and no output
-                a.scan_rc[k] = zrc[(size_t)j], a.angles[k] = 0.0, a.best_idx[k] = -1;
+            if (ck.zrc[(size_t)j]) {  // damaged image data: the slot's content means nothing; its code and no output
+                a.scan_rc[k] = ck.zrc[(size_t)j], a.angles[k] = 0.0, a.best_idx[k] = -1;
                 size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
             } else {
                 a.angles[k] = ang[(size_t)j], a.best_idx[k] = best[(size_t)j];
@@ -677,28 +662,24 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
     // the headers, on the host: a sheet its decoder refuses, or for which the per-call function would fail, keeps its
     // code and leaves the batch here
     std::vector<int32_t> code((size_t)n, OMR_OK);
-    std::vector<JdecHeader> hdr;
-    std::vector<PdecHeader> png_hdr;
-    std::vector<TdecHeader> tiff_hdr;
-    std::vector<uint8_t> kind;
+    ImreadRun run;
     std::vector<int> at;
     std::vector<omr_image> views;
     std::vector<const uint8_t *> zs;
     std::vector<int64_t> zlen;
-    hdr.reserve((size_t)n);
+    run.reserve((size_t)n);
     for (int i = 0; i < n; i++) {
-        hdr.emplace_back(), png_hdr.emplace_back(), tiff_hdr.emplace_back();
         // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
-        const ImreadParsed ps = imread_parse(streams[i], len[i], channels, false, &hdr.back(), &png_hdr.back(), &tiff_hdr.back());
+        const ImreadParsed ps = run.append(streams[i], len[i], channels, false);
         int rc = ps.rc;
         const int rows = ps.rows, cols = ps.cols;
         Working w;
         if (!rc) rc = working_size(rows, cols, scale, &w);
         if ((code[(size_t)i] = rc)) {
-            hdr.pop_back(), png_hdr.pop_back(), tiff_hdr.pop_back();
+            run.drop_last();
             continue;
         }
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), kind.push_back((uint8_t)ps.kind);
+        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]);
         views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
     }
     clear_error();
@@ -731,7 +712,7 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
         if ((rc = have_device())) return rc;
         int dev = 0;
         OMR_HIP(hipGetDevice(&dev));
-        StreamArgs a{zs.data(), zlen.data(), ImreadHeaders{hdr.data(), png_hdr.data(), tiff_hdr.data(), kind.data()}, channels, max_angle, step, scale, N, interp,
+        StreamArgs a{zs.data(), zlen.data(), run.view(), channels, max_angle, step, scale, N, interp,
                      border, quality, out_kind, rows_per_strip, dpi, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
                      out ? bytes_len.data() : nullptr, dev};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);

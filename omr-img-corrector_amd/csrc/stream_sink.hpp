@@ -1,5 +1,6 @@
-// stream_sink.hpp -- where the files-to-files batch forms (correct_batch.cpp, projection_batch.cpp) let the device
-// encoders put a chunk's streams: fresh host buffers, so that only the streams cross the link.
+// stream_sink.hpp -- where the device encoders put a group's streams (the JpegSink protocol, jpeg.hpp: place, then done):
+// SlotSink and HostSink for the encoders' own entry points, StreamSink for the files-to-files batch forms
+// (correct_batch.cpp, projection_batch.cpp, detector_deskew.cpp): fresh host buffers, so that only the streams cross the link.
 #pragma once
 #include <stdlib.h>
 
@@ -11,6 +12,43 @@
 #include "jpeg.hpp"
 
 namespace omr {
+
+#pragma GCC visibility push(hidden)  // the library's own: not in the dynamic symbol table
+// an omr_*_encode_batch_device's sink: slot i of the caller's buffer, lengths into the caller's host array
+struct SlotSink : JpegSink {
+    uint8_t *d_out;
+    int64_t stride;
+    int64_t *out_len;
+    int place(int i0, int cnt, const int64_t *len, uint8_t **out, int64_t *off) override
+    {
+        *out = d_out;
+        for (int j = 0; j < cnt; j++) off[j] = (int64_t)(i0 + j) * stride, out_len[i0 + j] = len[j];
+        return OMR_OK;
+    }
+    int done(int, int, const int64_t *) override { return OMR_OK; }
+};
+
+// an omr_*_encode's sink: one stream, into the caller's host buffer when it fits
+struct HostSink : JpegSink {
+    uint8_t *out;
+    int64_t cap, len = 0;
+    hipStream_t s;
+    DevBuf buf;
+    bool fits = false;
+    int place(int, int, const int64_t *l, uint8_t **d_out, int64_t *off) override
+    {
+        len = l[0], off[0] = 0;
+        OMR_HIP(buf.alloc((size_t)len));
+        *d_out = buf.as<uint8_t>();
+        return OMR_OK;
+    }
+    int done(int, int, const int64_t *) override
+    {
+        fits = out && len <= cap;
+        return fits ? staged_d2h(out, buf.p, (size_t)len, s) : OMR_OK;
+    }
+};
+#pragma GCC visibility pop
 
 // The streams of a chunk's canvases -> fresh host buffers: a device buffer of exactly the streams' size per group of the
 // encoder, then one staged copy per stream from several threads.  Stream j belongs to sheet idx[j0 + j]: out[that]

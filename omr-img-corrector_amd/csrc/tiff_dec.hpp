@@ -6,6 +6,8 @@
 
 #include <vector>
 
+#include "codec_stats.hpp"
+
 namespace omr {
 
 constexpr int TDEC_MAX_SIDE = 1 << 20;  // rows and cols tdec_parse takes: imread's own limits
@@ -100,11 +102,7 @@ int tiff_decode_device(const uint8_t *const *streams, const int64_t *len, const 
                        int channels, uint8_t *d_out, int64_t out_stride, int64_t step, int32_t *rc, hipStream_t s);
 
 constexpr int TDEC_STAGES = 6;  // upload, PackBits, T.6, LZW, unpack, finish8
-struct TdecStats {
-    bool on = false;
-    int32_t groups = 0;
-    double ms[TDEC_STAGES] = {0, 0, 0, 0, 0, 0};
-};
+struct TdecStats : CodecStats<TDEC_STAGES> {};
 TdecStats &tdec_stats();
 
 }  // namespace omr

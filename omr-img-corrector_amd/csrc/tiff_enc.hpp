@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "codec_stats.hpp"
 #include "jpeg.hpp"  // JpegSink: where a group's streams go (the protocol is the JPEG encoder's: place, then done)
 
 namespace omr {
@@ -83,11 +84,7 @@ int tiff_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t step, 
                        int rows_per_strip, int dpi, JpegSink &sink, hipStream_t s);
 
 constexpr int TENC_STAGES = 4;  // threshold and pack, row coder, placement, head + bit merge
-struct TencStats {
-    bool on = false;
-    int32_t groups = 0;
-    double ms[TENC_STAGES] = {0, 0, 0, 0};
-};
+struct TencStats : CodecStats<TENC_STAGES> {};
 TencStats &tenc_stats();
 
 }  // namespace omr

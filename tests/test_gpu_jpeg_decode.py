@@ -186,6 +186,55 @@ def test_fill_bytes_before_a_stuffed_ff_are_refused():
     _same(imgs[2], imgs[0], "trailing")
 
 
+def _three_small_streams():
+    """24 x 40: a good 4:2:0 stream, a copy cut in the middle of its entropy data (its header still parses: only the device
+    can refuse it), a good gray one"""
+    img = _content(24, 40, "ruled")
+    good = fz.make_stream(img, 90, subsampling=2)
+    sos = good.index(b"\xff\xda")
+    cut = good[:sos + (len(good) - sos) // 2]
+    assert jpeg.info(cut)[:2] == (24, 40)
+    return [good, cut, fz.make_stream(img, 90, gray=True)]
+
+
+def test_out_size_is_zero_where_the_device_finds_the_damage():
+    """the header's promise ("0 x 0 where rc[i] != 0") for a refusal that comes from the device, not from the parser"""
+    streams = _three_small_streams()
+    imgs, size, rc = fz.decode_on_device(streams, 24, 40, 3, pitch_pad=3)
+    assert list(rc) == [0, -215, 0]
+    assert list(size[1]) == [0, 0]
+    assert list(size[0]) == [24, 40] and list(size[2]) == [24, 40]
+    for i in (0, 2):
+        _same(imgs[i], fz.pillow_decode(streams[i], 3), i)
+
+
+def test_decode_stats_on_a_fresh_thread_report_the_last_call_alone():
+    """the statistics are per thread and per call: on, one group with its rounds and stage times; off again, the next
+    decode reports no group"""
+    import math
+    import threading
+    streams = _three_small_streams()
+    seen = {}
+
+    def work():
+        jpeg.decode_stats(True)
+        try:
+            fz.decode_on_device(streams, 24, 40, 3, pitch_pad=3)
+            seen["on"] = jpeg.decode_stats(False)
+        finally:
+            jpeg.decode_stats(False)
+        fz.decode_on_device(streams, 24, 40, 3, pitch_pad=3)
+        seen["off"] = jpeg.decode_stats(False)
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    _, groups, rounds, ms = seen["on"]
+    assert groups == 1 and rounds >= 1
+    assert all(math.isfinite(v) and v >= 0 for v in ms) and sum(ms) > 0, ms
+    assert seen["off"][1] == 0
+
+
 def test_zz_damaged_entropy_data_between_two_good_streams():
     """Last in the file.  A stream cut in the middle of its entropy data, and one with a byte of it changed: rc = -215, or a
     full decode equal to Pillow's where the change happens to leave a valid stream.  The neighbours stay exact."""

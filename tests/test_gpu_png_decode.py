@@ -234,6 +234,33 @@ def test_stats_count_groups_and_stages():
     assert png.stats(False) == (0, [0.0] * 4)
 
 
+def test_decode_stats_are_not_the_tiff_encoders():
+    """the two codecs have as many stages; their statistics are still two objects: with the PNG decoder's collection on,
+    a TIFF encode on the same thread collects nothing and leaves the decoder's figures alone"""
+    import threading
+    from oics import tiff
+    s = P.write(_noise(64, 96, 9), 2, 8, filters=4)
+    seen = {}
+
+    def work():
+        png.stats(True)
+        try:
+            imgs, _, rc = fz.decode_on_device([s], 64, 96, 3)
+            seen["before"] = png.stats(True)
+            tiff.encode(imgs[0])
+            seen["tiff"] = tiff.encode_stats(False)
+            seen["after"] = png.stats(False)
+        finally:
+            png.stats(False), tiff.encode_stats(False)
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    assert seen["before"][0] == 1 and sum(seen["before"][1]) > 0
+    assert seen["tiff"] == (0, [0.0] * len(tiff.STAGES_ENC))
+    assert seen["after"] == seen["before"]
+
+
 def test_zz_damaged_data_between_two_good_streams():
     """Last in the file.  Each damaged stream sits between two good ones and answers -215; the good ones stay exact.  None
     of them asks the kernels for anything outside their bounds checks: a flipped bit in a stored block's LEN, a zlib stream

@@ -158,6 +158,58 @@ def test_single_decode_and_stats():
     assert groups == 1 and len(ms) == 4 and all(v >= 0 for v in ms) and sum(ms) > 0
 
 
+def test_stats_on_a_fresh_thread_report_the_last_call_alone():
+    """per thread and per call: on, one group with its stage times; off again, the next decode reports no group"""
+    import math
+    import threading
+    _, s = tiff_cases.small_cases()[700]
+    seen = {}
+
+    def work():
+        tiff.stats(True)
+        try:
+            tiff.decode(s, 1)
+            seen["on"] = tiff.stats(False)
+        finally:
+            tiff.stats(False)
+        tiff.decode(s, 1)
+        seen["off"] = tiff.stats(False)
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    groups, ms = seen["on"]
+    assert groups == 1 and all(math.isfinite(v) and v >= 0 for v in ms) and sum(ms) > 0, ms
+    assert seen["off"][0] == 0
+
+
+def test_decode_stats_are_not_the_png_encoders():
+    """the two codecs have as many stages; their statistics are still two objects: with the TIFF decoder's collection on,
+    a PNG encode on the same thread collects nothing and leaves the decoder's figures alone"""
+    import threading
+    from oics import png
+    _, s = tiff_cases.small_cases()[700]
+    seen = {}
+
+    def work():
+        tiff.stats_ex(True)
+        try:
+            img = tiff.decode(s, 1)
+            seen["before"] = tiff.stats_ex(True)
+            png.encode(img)
+            seen["png"] = png.encode_stats(False)
+            seen["after"] = tiff.stats_ex(False)
+        finally:
+            tiff.stats_ex(False), png.encode_stats(False)
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    assert seen["before"][0] == 1 and sum(seen["before"][1]) > 0
+    assert seen["png"] == (0, [0.0] * len(png.STAGES_ENC))
+    assert seen["after"] == seen["before"]
+
+
 def test_imread_mixes_the_three_kinds():
     import fuzz_jpeg_decode as fz
     import orient_ref as O
