@@ -825,6 +825,22 @@ int omr_deskew_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t
 int omr_get_fft_image(const omr_image *gray_u8c1, omr_image_owned *magnitude_image,
                       omr_image_owned *magnitude_log_image);
 
+/* Inspection hook (like omr_hough_vote_select_device and omr_correct_batch_front_device: for the tests, not part of the
+ * reference's surface): omr_get_fft_image's run -- the same two passes and picture kernel, one execution -- which also
+ * hands back the float arrays the pictures are made from.  R = rows, C = cols, H = C / 2 + 1 (the input is real: the
+ * columns beyond C / 2 are mirror images and are never computed).  All arrays are HOST memory, packed, column index major:
+ *   row_pass   2 * H * R floats, (re, im) pairs: [c * R + r] = sum_x img(r, x) exp(-2 pi i c x / C), img = u8 * (1 / 255),
+ *              the row pass's complex half spectrum, unscaled
+ *   magnitude  H * R floats: [c * R + k] = |F(k, c)|, F = DFT2(img) / (R C), exactly as the column pass left it:
+ *              UNSHIFTED (DC at [0]); fft_shift (fft.rs:67-86) and the mirror |F(k, c)| = |F((R - k) % R, C - c)| for
+ *              c > C / 2 are applied by the picture kernel alone
+ *   extrema    2 floats: min |F| and max |F| over the H * R points, as the picture kernel reads them
+ *   magnitude_image, magnitude_log_image: the two pictures of the SAME run, as omr_get_fft_image returns them
+ * Every output may be NULL (all of them NULL: OMR_ERR_BADARG).  Argument checks as omr_get_fft_image; a refused or
+ * failed call writes nothing. */
+int omr_fft_spectrum_raw(const omr_image *gray_u8c1, float *row_pass, float *magnitude, float *extrema,
+                         omr_image_owned *magnitude_image, omr_image_owned *magnitude_log_image);
+
 /* The magnitude_log pictures of n device-resident scans of one shape (BASELINE config 5):
  * d_magnitude_log: n x rows x cols bytes, packed. */
 int omr_fft_image_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,

@@ -275,8 +275,7 @@ __global__ __launch_bounds__(NT) void fft_pass_kernel(FftPass p)
     }
     cfloat *Q = P == A ? B : A;
     cfloat *dst = p.dst + line * dls;
-    // spectrum-picture mode (column pass): point k of this line is F(k, line); it lands at the quadrant-swapped
-    // position of the |F| image
+    // spectrum-picture mode (column pass): point k of this line is F(k, line); |F| stays at that place
     const bool mag_mode = !pairs;
     const int sc = (int)line;
     float lo = __builtin_inff(), hi = -__builtin_inff();
@@ -380,7 +379,8 @@ hipError_t launch_fft_pass(const FftPass &p, hipStream_t s)
 {
     if (p.lines <= 0) return hipSuccess;
     if (p.m > OMR_FFT_MAX_M || (1 << p.log2m) != p.m) return hipErrorInvalidValue;
-    const size_t lds = (p.m > OMR_FFT_MAX_PINGPONG ? 1 : 2) * sizeof(cfloat) * (size_t)FFT_LDS_ELEMS(p.m);
+    size_t lds = (p.m > OMR_FFT_MAX_PINGPONG ? 1 : 2) * sizeof(cfloat) * (size_t)FFT_LDS_ELEMS(p.m);
+    if (lds < 2 * sizeof(float) * 16) lds = 2 * sizeof(float) * 16;  // the extrema of up to 16 waves pass through it too (m <= 4)
     if (p.m > OMR_FFT_MAX_PINGPONG && !p.Wfull) return hipErrorInvalidValue;
     // Transforms of more than 4096 points hold the CU alone (> 80 KB of LDS): 1024 threads (4 waves per SIMD, one
     // radix-8 butterfly of a stage each) instead of 512 with two each.

@@ -35,9 +35,14 @@ struct FftPass {
     int64_t dst_line_stride, dst_elem_stride;
     int32_t xcd_blocked;    // workgroups of one XCD take consecutive lines (their partial cache lines of a
                             // transposed / strided array then meet in that XCD's L2)
-    // Column pass of the spectrum pictures: when mag_dst is set the pass writes |F| (float) instead of F,
-    // already quadrant-swapped (fft_shift, fft.rs:67-86: an odd last row / column stays put), and the
-    // per-workgroup extrema of |F| to part[2 * line .. + 1] -- no complex spectrum is ever written.
+    // Column pass of the spectrum pictures: when mag_dst is set the pass writes |F| (float) instead of F, each point
+    // at its OWN place (no quadrant swap, no mirrored copy), and the per-workgroup extrema of |F| to
+    // part[2 * line .. + 1] -- no complex spectrum is ever written.  Layout of the two arrays between the passes
+    // (what omr_fft_spectrum_raw hands out with the pitches removed), R x C the image, c = 0 .. C/2, k = 0 .. R - 1:
+    //   row pass     dst[c * pitch + k]         = sum_x img(k, x) exp(-2 pi i c x / C)   (complex, unscaled; line = column c)
+    //   column pass  mag_dst[c * mag_pitch + k] = |F(k, c)|, F = DFT2(img) / (R C)       (float, DFT_SCALE applied)
+    // spec_pictures_kernel alone applies fft_shift (fft.rs:67-86: an odd last row / column stays put) and takes the
+    // columns C/2 + 1 .. C - 1 from the conjugate-symmetric points, |F(k, c)| = |F((R - k) % R, C - c)|.
     float *mag_dst;         // TRANSPOSED |F| of the half spectrum: lines (= columns 0 .. C/2) of mag_pitch floats, |F(k, c)| at
                             // [c * mag_pitch + k], unshifted (the picture kernel shifts and mirrors), or NULL
     int32_t mag_pitch, img_rows, img_cols;
@@ -47,8 +52,8 @@ struct FftPass {
     //   imaginary part of one complex line and separates the two spectra by Hermitian symmetry,
     //   A[k] = (Z[k] + conj Z[n-k]) / 2, B[k] = (Z[k] - conj Z[n-k]) / 2i; only columns 0 .. n/2 are written
     //   (the rest is their mirror image).  src_rows = number of rows (an odd last row goes alone).
-    // half_mirror (column pass in picture mode): lines = img_cols / 2 + 1; |F(k, c)| is also stored at the
-    //   mirrored point ((R - k) % R, (C - c) % C), F(-k, -c) = conj F(k, c), unless the column is its own mirror.
+    // half_mirror (column pass in picture mode): lines = img_cols / 2 + 1, the other columns being mirror images,
+    //   F(-k, -c) = conj F(k, c).  The pass stores no mirrored copy: the picture kernel reads the mirror.
     int32_t real_pairs, src_rows, half_mirror;
     // several scans per launch (blockIdx.y = scan): strides of the per-scan arrays; 0 / 1 scan by default
     const cfloat *Wfull;    // in-place path (m > OMR_FFT_MAX_PINGPONG): m / 2 twiddles exp(-2 pi i t / m)

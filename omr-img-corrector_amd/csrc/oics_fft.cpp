@@ -209,6 +209,9 @@ struct AxisTables {
             m <<= 1;
             log2m++;
         }
+        // a 1-point axis (an image of one row or one column): fft_forward_lds has no stage for m = 1 and would hand back a
+        // buffer nothing was loaded into.  Two points, the second one zero (the kernels read 0 beyond n and emit k < n only)
+        if (n == 1) m = 2, log2m = 1;
         if (m > OMR_FFT_BIG_MAX_M)
             return fail(OMR_ERR_NOTIMPL, "DFT length %d needs a transform of %d points; at most %d are supported", n, m,
                         OMR_FFT_BIG_MAX_M);
@@ -395,7 +398,7 @@ struct FftWork {
         q.mag_scan_stride = (int64_t)(cols / 2 + 1) * mag_pitch;
         q.part_scan_stride = 2 * (int64_t)cols;
         q.src_c = c0.as<cfloat>();
-        q.dst = nullptr;  // spectrum-picture mode: |F|, quadrant-swapped, straight from the column pass
+        q.dst = nullptr;  // spectrum-picture mode: |F| straight from the column pass, unshifted (fft.hpp)
         q.mag_dst = mag.as<float>();
         q.mag_pitch = mag_pitch;
         q.img_rows = rows;
@@ -563,6 +566,59 @@ int omr_get_fft_image(const omr_image *gray, omr_image_owned *magnitude_image, o
         if (magnitude_image) omr_image_free(magnitude_image);
         return rc;
     }
+    return OMR_OK;
+}
+
+// Inspection hook: omr_get_fft_image's run (the same FftWork::run, one scan) with the workspace's float arrays handed
+// back beside the two pictures -- the row pass's half spectrum, the column pass's |F| and the extrema the picture kernel
+// reads -- packed, the pitches removed.  Host code only; everything is staged in host memory first, so that a call that
+// fails has written nothing.
+int omr_fft_spectrum_raw(const omr_image *gray, float *row_pass, float *magnitude, float *extrema,
+                         omr_image_owned *magnitude_image, omr_image_owned *magnitude_log_image)
+{
+    clear_error();
+    int rc = check_gray(gray);
+    if (rc) return rc;
+    if (!row_pass && !magnitude && !extrema && !magnitude_image && !magnitude_log_image) return fail(OMR_ERR_BADARG, "null output");
+    if ((rc = have_device())) return rc;
+    LeasedStream st;
+    if ((rc = st.create())) return rc;
+    const int rows = gray->rows, cols = gray->cols, half = cols / 2 + 1;
+    DevBuf in, m8, l8;
+    if ((rc = upload(gray, &in, st.s))) return rc;
+    FftWork w;
+    if ((rc = w.create(rows, cols, st.s))) return rc;
+    const size_t px = (size_t)rows * cols;
+    OMR_HIP(m8.alloc(px));
+    OMR_HIP(l8.alloc(px));
+    if ((rc = w.run(in.as<uint8_t>(), cols, m8.as<uint8_t>(), l8.as<uint8_t>(), st.s))) return rc;
+    std::vector<cfloat> c0;
+    std::vector<float> mg;
+    uint32_t mm[4] = {0, 0, 0, 0};
+    if (row_pass) {
+        c0.resize((size_t)half * w.pitch);
+        if ((rc = staged_d2h(c0.data(), w.c0.p, sizeof(cfloat) * c0.size(), st.s))) return rc;
+    }
+    if (magnitude) {
+        mg.resize((size_t)half * w.mag_pitch);
+        if ((rc = staged_d2h(mg.data(), w.mag.p, sizeof(float) * mg.size(), st.s))) return rc;
+    }
+    if (extrema && (rc = staged_d2h(mm, w.mm.p, sizeof(mm), st.s))) return rc;
+    omr_image_owned mi{}, li{};
+    if (magnitude_image && (rc = download_owned(m8.as<uint8_t>(), rows, cols, &mi, st.s))) return rc;
+    if (magnitude_log_image && (rc = download_owned(l8.as<uint8_t>(), rows, cols, &li, st.s))) {
+        omr_image_free(&mi);
+        return rc;
+    }
+    // every copy has succeeded: now the caller's memory
+    for (int c = 0; row_pass && c < half; c++) memcpy(row_pass + 2 * (size_t)c * rows, &c0[(size_t)c * w.pitch], sizeof(cfloat) * rows);
+    for (int c = 0; magnitude && c < half; c++) memcpy(magnitude + (size_t)c * rows, &mg[(size_t)c * w.mag_pitch], sizeof(float) * rows);
+    for (int i = 0; extrema && i < 2; i++) {  // fft.hip's f2key undone: keys that order like the floats
+        const uint32_t k = mm[i], b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+        memcpy(extrema + i, &b, sizeof(b));
+    }
+    if (magnitude_image) *magnitude_image = mi;
+    if (magnitude_log_image) *magnitude_log_image = li;
     return OMR_OK;
 }
 

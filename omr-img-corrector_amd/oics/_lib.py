@@ -14,6 +14,7 @@ u8p = C.POINTER(C.c_uint8)
 i32p = C.POINTER(C.c_int32)
 u32p = C.POINTER(C.c_uint32)
 f64p = C.POINTER(C.c_double)
+f32p = C.POINTER(C.c_float)
 
 # warpAffine flags and border modes of omr_rotate_ex / omr_rotate_device_ex (include/omrdeskew.h)
 OMR_INTER_NEAREST, OMR_INTER_LINEAR, OMR_INTER_CUBIC, OMR_INTER_AREA, OMR_INTER_LANCZOS4 = 0, 1, 2, 3, 4
@@ -210,6 +211,7 @@ SYMBOLS = {
     "omr_deskew_with_projections_batch": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_uint16, C.c_double, C.c_double,
                                                     C.c_int32, u8p, f64p, i32p, C.POINTER(OmrImageOwned)]),
     "omr_get_fft_image": (C.c_int, [C.POINTER(OmrImage), C.POINTER(OmrImageOwned), C.POINTER(OmrImageOwned)]),
+    "omr_fft_spectrum_raw": (C.c_int, [C.POINTER(OmrImage), f32p, f32p, f32p, C.POINTER(OmrImageOwned), C.POINTER(OmrImageOwned)]),
     "omr_fft_image_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                              C.c_void_p, C.c_void_p]),
     "omr_get_angle_with_fft": (C.c_int, [C.POINTER(OmrImage), C.c_double, C.c_double, C.c_double, C.c_double, f64p]),

@@ -17,6 +17,25 @@ def get_fft_image(gray_tm):
     return _take(m), _take(lg)
 
 
+def spectrum_raw(gray_tm):
+    """omr_fft_spectrum_raw, the inspection hook behind the spectrum tests: get_fft_image's run with the float arrays
+    the pictures are made from.  Returns (row_pass, magnitude, (min, max), magnitude_image, magnitude_log_image) for a
+    [R, C] scan, H = C // 2 + 1: row_pass complex64 [H, R], the row pass's half spectrum, [c, r] = sum_x img[r, x]
+    exp(-2 pi i c x / C) (unscaled); magnitude float32 [H, R], [c, k] = |F(k, c)| with DFT_SCALE, unshifted; the extrema
+    of magnitude as float32, as the picture kernel reads them; the two uint8 pictures of the same run."""
+    from ._lib import f32p
+    a, im = as_image(_mat(gray_tm))
+    rows, cols = a.shape[:2]
+    half = cols // 2 + 1
+    row = np.zeros((half, rows), np.complex64)
+    mag = np.zeros((half, rows), np.float32)
+    ext = np.zeros(2, np.float32)
+    m, lg = OmrImageOwned(), OmrImageOwned()
+    check(lib().omr_fft_spectrum_raw(C.byref(im), row.ctypes.data_as(f32p), mag.ctypes.data_as(f32p), ext.ctypes.data_as(f32p),
+                                     C.byref(m), C.byref(lg)))
+    return row, mag, (ext[0], ext[1]), _take(m), _take(lg)
+
+
 def fft_image_batch_device(d_scans_ptr, n, scan_stride, rows, cols, step, d_out_ptr, stream=None):
     """magnitude_log pictures of n device-resident scans (config 5)"""
     check(lib().omr_fft_image_batch_device(d_scans_ptr, n, scan_stride, rows, cols, step, d_out_ptr, stream))
