@@ -1327,6 +1327,52 @@ int omr_tiff_encode(const omr_image *src, int32_t threshold, int32_t rows_per_st
  * NULL. */
 int omr_tiff_encode_stats(int32_t enable, int32_t *groups, double *stage_ms);
 
+/* ---- 8-bit gray and RGB TIFF encoding on the device --------------------------------------------
+ * The exit that keeps the gray levels: an 8-bit TIFF of 1 sample (gray) or 3 (BGR in memory, written R, G, B), uncompressed
+ * (compression 1) or LZW (5), with Predictor 1, or 2 (horizontal differencing, per sample, mod 256) with LZW only.  The
+ * contract is omr_png_encode's: the file is valid, it decodes to the image exactly (libtiff, omr_tiff_decode), and it is
+ * deterministic -- a function of the pixels, the shape, compression, predictor, rows_per_strip and dpi alone, not of its
+ * place in the batch, n, the other images, the base address, the pitch or the run.  It is NOT libtiff's byte stream.
+ * The file: little-endian classic TIFF, the IFD at offset 8 with its tags in ascending order -- 256 ImageWidth and 257
+ * ImageLength (LONG), 258 BitsPerSample 8 or 8,8,8, 259 Compression, 262 Photometric 1 (BlackIsZero) or 2 (RGB), 273
+ * StripOffsets (LONG), 277 SamplesPerPixel, 278 RowsPerStrip (LONG), 279 StripByteCounts (LONG), 282 and 283 X and
+ * YResolution dpi / 1 (only when dpi > 0), 284 PlanarConfiguration 1 (colour only), 296 ResolutionUnit 2 (only when
+ * dpi > 0), 317 Predictor 2 (only then) -- then the resolutions, BitsPerSample's three values and a zero SHORT (colour),
+ * the two strip arrays (inside their entries when there is one strip), then the strips, each at an even offset with a zero
+ * in front where the one before is odd.  rows_per_strip = 0 means libtiff's default, the most rows whose raw strip is at
+ * most 8192 bytes and at least one -- not one strip as for Group 4: the strips are coded in parallel, one strip a page is
+ * one wave a page.  A value above the rows is taken as the rows.
+ * An LZW strip is TIFF 6.0's: codes most significant bit first, Clear (256) first, the longest matches, EOI (257), zeros
+ * to a byte; a code's width follows the count of codes since the last Clear (9 bits below 254, 10 below 766, 11 below 1790,
+ * then 12: the early change).  Clear is sent when the table is full and only then: it is the code with index 3836 since
+ * the last Clear (libtiff's writer's point), so no reader adds an entry above 4092.
+ * Refused with OMR_ERR_ASSERT: an empty image, sizes above imread's limits (2^20 rows or columns, 2^30 pixels), a strip
+ * that could pass 2^31 - 1 bits, a file that could pass 2^32 - 1 bytes.  Speed: README.md, profiles/r28_tiff8_encode.md.
+ *
+ * An upper bound of the file's length for any content: 206 bytes of head, 8 a strip for the arrays, and per strip of n raw
+ * bytes (its rows x cols x channels), rounded up to even: n uncompressed; ceil(12 x (n + n / 3836 + 2) / 8) for LZW (every
+ * code but Clear and EOI takes a byte of input or more, Clear stands in front and behind every 3836 of them, no code is
+ * wider than 12 bits).  OMR_ERR_BADARG for a null bytes, channels other than 1 or 3, a compression other than 1 or 5, a
+ * negative rows_per_strip.  Host only. */
+int omr_tiff8_bound(int32_t rows, int32_t cols, int32_t channels, int32_t compression, int32_t rows_per_strip, int64_t *bytes);
+/* n device-resident images -> n files.  Slots, sizes (NULL allowed, 0 x 0 entries, an image at its slot's top left),
+ * d_out / out_stride_bytes / out_len and the OMR_ERR_BADARG rules are omr_tiff_encode_batch_device's: nothing is written at
+ * or behind out_len[i], a 0 x 0 entry leaves its slot untouched.  out_stride_bytes holds omr_tiff8_bound of the slot and of
+ * every image (with rows_per_strip 0 an image narrower than its slot has strips of its own).  Also OMR_ERR_BADARG: a
+ * compression other than 1 or 5, a predictor other than 1 or 2, predictor 2 with compression 1, a negative dpi.  Every
+ * argument is checked before any device work.  Synchronous, on a stream of its own, which has drained on every return. */
+int omr_tiff8_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes, int64_t step_bytes, int32_t rows,
+                                  int32_t cols, int32_t channels, const int32_t *sizes, int32_t n, int32_t compression,
+                                  int32_t predictor, int32_t rows_per_strip, int32_t dpi, uint8_t *d_out,
+                                  int64_t out_stride_bytes, int64_t *out_len);
+/* A host image -> its file in `out` (cap bytes), *len = the file's length.  cap too small (out may be NULL when cap is 0):
+ * OMR_ERR_NOMEM with *len = the length needed, nothing written. */
+int omr_tiff8_encode(const omr_image *src, int32_t compression, int32_t predictor, int32_t rows_per_strip, int32_t dpi,
+                     uint8_t *out, int64_t cap, int64_t *len);
+/* Measurement aid, as omr_tiff_encode_stats: stage_ms[0 .. 3] = staging (LZW), the LZW coder (uncompressed: the strips'
+ * lengths), the placement scan, and head + strips into the file (which includes the host's placing of the files). */
+int omr_tiff8_encode_stats(int32_t enable, int32_t *groups, double *stage_ms);
+
 /* ---- deskew with projections from file contents to file contents ------------------------------
  * The reference's benchmark flow, core/src/main.rs:68-95 -- imread, get_angle_with_projections, rotate_mat of the
  * original (CONTAIN, scale 1, BORDER_CONSTANT), imwrite -- for batches: omr_deskew_with_projections_batch with the scans
@@ -1385,6 +1431,14 @@ int omr_deskew_with_projections_batch_streams_tiff(const uint8_t *const *streams
                                                    int32_t interp, const uint8_t border_value[4], int32_t threshold,
                                                    int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *best_idx,
                                                    int32_t *scan_rc, uint8_t **tiff, int64_t *tiff_len);
+/* The same with 8-bit TIFF files as its outputs: tiff[i] is byte for byte omr_tiff8_encode(canvas, compression, predictor,
+ * rows_per_strip, dpi) of the deskewed canvas, gray or colour as `channels` says.  OMR_ERR_BADARG for the call also:
+ * omr_tiff8_encode_batch_device's parameter rules.  The call-level OMR_ERR_ASSERT is omr_tiff8_bound's refusal of the canvas. */
+int omr_deskew_with_projections_batch_streams_tiff8(const uint8_t *const *streams, const int64_t *len, int32_t n,
+                                                    int32_t channels, uint16_t max_angle, double step, double resize_scale,
+                                                    int32_t interp, const uint8_t border_value[4], int32_t compression,
+                                                    int32_t predictor, int32_t rows_per_strip, int32_t dpi, double *angles,
+                                                    int32_t *best_idx, int32_t *scan_rc, uint8_t **tiff, int64_t *tiff_len);
 
 /* ---- deskew with the Hough and FFT detectors for batches ----------------------------------------
  * The other two legs of the reference's benchmark, core/src/main.rs:96-170: get_angle_with_hough / get_angle_with_fft on
@@ -1480,6 +1534,20 @@ int omr_deskew_with_fft_batch_streams_tiff(const uint8_t *const *streams, const 
                                            const uint8_t border_value[4], int32_t clip, int32_t threshold,
                                            int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *scan_rc,
                                            uint8_t **out, int64_t *out_len);
+/* The two with 8-bit TIFF files as their outputs: out[i] is byte for byte omr_tiff8_encode(canvas, compression, predictor,
+ * rows_per_strip, dpi).  Everything else as above; OMR_ERR_BADARG for the call also: omr_tiff8_encode_batch_device's
+ * parameter rules; the call-level OMR_ERR_ASSERT is omr_tiff8_bound's refusal of the canvas slot. */
+int omr_deskew_with_hough_batch_streams_tiff8(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                              double min_line_length, double max_line_gap, int32_t flags, int32_t border_mode,
+                                              const uint8_t border_value[4], int32_t clip, int32_t compression,
+                                              int32_t predictor, int32_t rows_per_strip, int32_t dpi, double *angles,
+                                              int32_t *scan_rc, uint8_t **out, int64_t *out_len);
+int omr_deskew_with_fft_batch_streams_tiff8(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
+                                            double canny_threshold_1, double canny_threshold_2, double min_line_length,
+                                            double max_line_gap, int32_t flags, int32_t border_mode,
+                                            const uint8_t border_value[4], int32_t clip, int32_t compression,
+                                            int32_t predictor, int32_t rows_per_strip, int32_t dpi, double *angles,
+                                            int32_t *scan_rc, uint8_t **out, int64_t *out_len);
 
 /* calculate::get_arithmetic_mean / get_standard_deviation (calculate.rs:2-10, :13-23) */
 int omr_get_arithmetic_mean(const double *v, size_t n, double *out);

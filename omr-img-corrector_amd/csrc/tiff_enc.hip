@@ -14,46 +14,13 @@
 
 #include "bgr.hpp"
 #include "engine.hpp"
+#include "row_bytes.hpp"
 #include "tiff_enc.hpp"
 
 namespace omr {
 namespace {
 
 // ---- pack.
-// Bytes [sb, sb + nbytes) of a row (row .. row + row_len) -> v[k] = bytes 4 k .. 4 k + 3 of them, little-endian.  Aligned
-// dword loads where the dword lies inside the ROW (neighbouring threads' bytes included), byte loads of the row's own bytes
-// where it straddles an end: nothing outside the row is read, at any base address and pitch.
-template <int NW>
-__device__ __forceinline__ void load_segment(const uint8_t *row, int row_len, int sb, int nbytes, uint32_t (&v)[NW])
-{
-    const uintptr_t r0 = (uintptr_t)row, r1 = r0 + (uintptr_t)row_len, p = r0 + (uintptr_t)sb;
-    const uint32_t a = (uint32_t)(p & 3);
-    const uintptr_t q = p - a;
-    uint32_t w[NW + 1];
-#pragma unroll
-    for (int k = 0; k <= NW; k++) {
-        const uintptr_t d = q + 4 * (uintptr_t)k;
-        uint32_t x = 0;
-        if (d < p + (uintptr_t)nbytes) {
-            if (d >= r0 && d + 4 <= r1) {
-                x = *(const uint32_t *)d;
-            } else {
-                for (int b = 0; b < 4; b++)
-                    if (d + b >= r0 && d + b < r1) x |= (uint32_t)*(const uint8_t *)(d + b) << (8 * b);
-            }
-        }
-        w[k] = x;
-    }
-#pragma unroll
-    for (int k = 0; k < NW; k++) v[k] = a ? (w[k] >> (8 * a)) | (w[k + 1] << (32 - 8 * a)) : w[k];
-}
-
-template <int NW>
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&v)[NW], int b)
-{
-    return (v[b >> 2] >> (8 * (b & 3))) & 255u;
-}
-
 // Packed row y of an image (y = 0: a line of zeros, the white line above a strip; y >= 1: image row y - 1) is pack_w dwords;
 // thread idx writes its byte idx % (4 pack_w).  Bounds: y <= rows, so the source row y - 1 < rows; pixels x0 .. x0 + npx - 1
 // < cols; the byte written has an index below (rows + 1) x 4 pack_w, the image's share of the workspace.
@@ -368,14 +335,24 @@ int tenc_launch_place(const TencPass &p, int max_strips, int max_rps, hipStream_
 {
     tenc_rowscan_kernel<<<dim3(up_div(max_strips, 4), (unsigned)p.n), 256, 0, s>>>(p, (max_rps + 63) / 64);
     if (int rc = launched("tenc_rowscan_kernel")) return rc;
+    return tenc_launch_stripscan(p, max_strips, s);
+}
+
+int tenc_launch_stripscan(const TencPass &p, int max_strips, hipStream_t s)
+{
     tenc_stripscan_kernel<<<(unsigned)p.n, 64, 0, s>>>(p, (max_strips + 63) / 64);
     return launched("tenc_stripscan_kernel");
 }
 
-int tenc_launch_merge(const TencPass &p, int64_t max_data_len, int max_strips, hipStream_t s)
+int tenc_launch_head(const TencPass &p, int max_strips, hipStream_t s)
 {
     tenc_head_kernel<<<(unsigned)p.n, 256, 0, s>>>(p, (max_strips + 255) / 256);
-    if (int rc = launched("tenc_head_kernel")) return rc;
+    return launched("tenc_head_kernel");
+}
+
+int tenc_launch_merge(const TencPass &p, int64_t max_data_len, int max_strips, hipStream_t s)
+{
+    if (int rc = tenc_launch_head(p, max_strips, s)) return rc;
     if (max_data_len <= 0) return OMR_OK;
     tenc_merge_kernel<<<dim3(up_div((max_data_len + 1) / 2, 256), (unsigned)p.n), 256, 0, s>>>(p);
     return launched("tenc_merge_kernel");

@@ -13,6 +13,7 @@ constexpr int64_t TENC_MAX_PIXELS = (int64_t)1 << 30;
 constexpr int TENC_CODES = 104;         // per colour, in tdec_code_tables' order: entry r for a run r < 64, 63 + m / 64 for a make-up run m
 constexpr int TENC_EOFB_BITS = 24;
 constexpr int TENC_HEAD_MAX = 8 + 2 + 12 * 13 + 4 + 16;  // header, the IFD with every tag, the two resolutions
+constexpr int TENC_HEAD_CAP = 208;      // room of TencImg::head: the 8-bit writer's head too (TENC8_HEAD_MAX, tiff_enc8.hpp)
 constexpr int64_t TENC_MAX_STRIP_BITS = ((int64_t)1 << 31) - 1;  // bit offsets inside a strip are 32 bits wide
 constexpr int64_t TENC_MAX_FILE = ((int64_t)1 << 32) - 1;        // classic TIFF's offsets
 
@@ -32,7 +33,7 @@ struct TencImg {
     int32_t head_len;  // bytes of head[]
     int32_t off_pos, cnt_pos;  // where StripOffsets' and StripByteCounts' values stand in the file
     int32_t data_at;   // the file offset of the first strip
-    uint8_t head[TENC_HEAD_MAX];  // header, IFD and resolutions as the file begins, the two strip arrays' values left out
+    uint8_t head[TENC_HEAD_CAP];  // header, IFD and resolutions as the file begins, the two strip arrays' values left out
 };
 
 // what the device learns about an image
@@ -67,6 +68,10 @@ int tenc_launch_pack(const TencPass &p, int64_t max_pack_bytes, hipStream_t s);
 int tenc_launch_rows(const TencPass &p, int max_rows, hipStream_t s);
 int tenc_launch_place(const TencPass &p, int max_strips, int max_rps, hipStream_t s);  // row offsets, then strip offsets and lengths
 int tenc_launch_merge(const TencPass &p, int64_t max_data_len, int max_strips, hipStream_t s);  // head and strip arrays, then the strips' bits
+// the halves of place and merge that know nothing of Group 4, for the 8-bit writer (tiff_enc8.hpp) as well: sbytes[] ->
+// soff[] and dyn[] (imgs, dyn, n, sbytes, soff of p are read); head[], soff[] and sbytes[] -> the file's first data_at bytes
+int tenc_launch_stripscan(const TencPass &p, int max_strips, hipStream_t s);
+int tenc_launch_head(const TencPass &p, int max_strips, hipStream_t s);
 
 // ---- host side (oics_tiff_enc.cpp)
 // bits of one row's code at most, and the bound of the file's length (rps: 1 .. rows)

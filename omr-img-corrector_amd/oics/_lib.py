@@ -282,6 +282,25 @@ SYMBOLS = {
                                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                                          u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f64p, i32p,
                                                          C.POINTER(u8p), C.POINTER(C.c_int64)]),
+    "omr_tiff8_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "omr_tiff8_encode_batch_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                C.POINTER(C.c_int64)]),
+    "omr_tiff8_encode": (C.c_int, [C.POINTER(OmrImage), C.c_int32, C.c_int32, C.c_int32, C.c_int32, u8p, C.c_int64,
+                                   C.POINTER(C.c_int64)]),
+    "omr_tiff8_encode_stats": (C.c_int, [C.c_int32, i32p, f64p]),
+    "omr_deskew_with_projections_batch_streams_tiff8": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
+                                                                  C.c_int32, C.c_uint16, C.c_double, C.c_double, C.c_int32, u8p,
+                                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, f64p, i32p, i32p,
+                                                                  C.POINTER(u8p), C.POINTER(C.c_int64)]),
+    "omr_deskew_with_hough_batch_streams_tiff8": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                                            C.c_double, C.c_double, C.c_int32, C.c_int32, u8p, C.c_int32,
+                                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, f64p, i32p,
+                                                            C.POINTER(u8p), C.POINTER(C.c_int64)]),
+    "omr_deskew_with_fft_batch_streams_tiff8": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                          u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f64p, i32p,
+                                                          C.POINTER(u8p), C.POINTER(C.c_int64)]),
     "omr_png_bound": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "omr_png_encode_batch_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p,
                                               C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),

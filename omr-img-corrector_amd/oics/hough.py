@@ -165,3 +165,12 @@ def deskew_streams_tiff(streams, min_line_length, max_line_gap, flags=1, border_
     return _transfer._detector_deskew_streams("omr_deskew_with_hough_batch_streams_tiff", (min_line_length, max_line_gap), streams,
                                               channels, flags, border_mode, border_value, clip_strategy, 0, threshold, want_out,
                                               tiff=(rows_per_strip, dpi))
+
+
+def deskew_streams_tiff8(streams, min_line_length, max_line_gap, flags=1, border_mode=0, border_value=(255, 255, 255, 0),
+                         clip_strategy=1, channels=3, compression=5, predictor=1, rows_per_strip=0, dpi=0, want_out=True):
+    """omr_deskew_with_hough_batch_streams_tiff8: deskew_streams with 8-bit TIFF files as its outputs, outputs[i] byte for
+    byte oics.tiff.encode8(canvas, compression, predictor, rows_per_strip, dpi)."""
+    return _transfer._detector_deskew_streams("omr_deskew_with_hough_batch_streams_tiff8", (min_line_length, max_line_gap), streams,
+                                              channels, flags, border_mode, border_value, clip_strategy, 0, compression, want_out,
+                                              tiff=(predictor, rows_per_strip, dpi))

@@ -60,8 +60,10 @@ def get_angles_and_deskew(srcs, max_angle, step, resize_scale, interp=1, border=
     return (ang[:n], idx[:n], images) if want_idx else (ang[:n], images)
 
 
-def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, level, channels, png, want_out, tiff=None):
-    """omr_deskew_with_projections_batch_streams / _png / _tiff (tiff = (rows_per_strip, dpi), level = the threshold) ->
+def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, level, channels, png, want_out, tiff=None,
+                    tiff8=None):
+    """omr_deskew_with_projections_batch_streams / _png / _tiff (tiff = (rows_per_strip, dpi), level = the threshold) /
+    _tiff8 (tiff8 = (predictor, rows_per_strip, dpi), level = the compression) ->
     (angles, best_idx, scan_rc, [bytes or None] or None)"""
     from ._lib import u8p
     bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
@@ -79,6 +81,8 @@ def _deskew_streams(streams, max_angle, step, resize_scale, interp, border, leve
     how = (int(level),)
     if tiff is not None:
         fn, how = lib().omr_deskew_with_projections_batch_streams_tiff, (int(level), int(tiff[0]), int(tiff[1]))
+    if tiff8 is not None:
+        fn, how = lib().omr_deskew_with_projections_batch_streams_tiff8, (int(level),) + tuple(int(v) for v in tiff8)
     check(fn(sp, sl.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), int(max_angle), float(step), float(resize_scale),
              int(interp), _border4(border), *how, ang.ctypes.data_as(f64p), idx.ctypes.data_as(i32p),
              rc.ctypes.data_as(i32p), ptrs if want_out else None,
@@ -112,6 +116,16 @@ def deskew_streams_tiff(streams, max_angle, step, resize_scale, interp=1, border
     is oics.tiff.encode(canvas, threshold, rows_per_strip, dpi) of the deskewed canvas, byte for byte."""
     ang, idx, rc, out = _deskew_streams(streams, max_angle, step, resize_scale, interp, border, threshold, channels, False, True,
                                         tiff=(rows_per_strip, dpi))
+    return (ang, idx, rc, out) if want_idx else (ang, rc, out)
+
+
+def deskew_streams_tiff8(streams, max_angle, step, resize_scale, interp=1, border=(255, 255, 255), compression=5, predictor=1,
+                         rows_per_strip=0, dpi=0, channels=3, want_idx=False):
+    """deskew_streams with 8-bit TIFF files as its outputs (omr_deskew_with_projections_batch_streams_tiff8): outputs[i] is
+    oics.tiff.encode8(canvas, compression, predictor, rows_per_strip, dpi) of the deskewed canvas, byte for byte -- gray
+    for channels = 1, RGB for 3, the gray levels kept."""
+    ang, idx, rc, out = _deskew_streams(streams, max_angle, step, resize_scale, interp, border, compression, channels, False, True,
+                                        tiff8=(predictor, rows_per_strip, dpi))
     return (ang, idx, rc, out) if want_idx else (ang, rc, out)
 
 

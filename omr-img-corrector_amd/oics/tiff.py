@@ -1,6 +1,7 @@
 """TIFF on the device (omr_tiff_*): bilevel files (uncompressed, PackBits and CCITT Group 4 strips, as 255 / 0) and 8-bit
 gray and RGB files (uncompressed, PackBits and LZW strips, Predictor 1 and 2) decoded byte for byte to what libtiff gives,
-and a Group 4 encoder whose strips are byte for byte what libtiff writes."""
+a Group 4 encoder whose strips are byte for byte what libtiff writes, and an 8-bit gray and RGB encoder (uncompressed or
+LZW, Predictor 1 and 2) whose files decode to the image exactly."""
 import ctypes as C
 
 import numpy as np
@@ -134,4 +135,57 @@ def encode_stats(enable=True):
     groups = C.c_int32()
     ms = np.zeros(len(STAGES_ENC), np.float64)
     check(lib().omr_tiff_encode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
+    return groups.value, [float(v) for v in ms]
+
+
+def bound8(rows, cols, channels=1, compression=5, rows_per_strip=0):
+    """omr_tiff8_bound: an upper bound of the 8-bit file's length in bytes"""
+    out = C.c_int64()
+    check(lib().omr_tiff8_bound(int(rows), int(cols), int(channels), int(compression), int(rows_per_strip), C.byref(out)))
+    return out.value
+
+
+def encode8_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, channels, sizes, n, d_out, out_stride_bytes,
+                         compression=5, predictor=1, rows_per_strip=0, dpi=0):
+    """omr_tiff8_encode_batch_device: n device-resident images in slots of rows x cols x channels (d_imgs, d_out: device
+    addresses; sizes: None or int32 [n, 2] of (rows, cols) per image) -> 8-bit TIFF files, gray or RGB, uncompressed
+    (compression 1) or LZW (5).  Returns out_len int64 [n]: file i is out_len[i] bytes at d_out + i * out_stride_bytes
+    (0: a 0 x 0 entry, slot untouched).  Synchronous."""
+    n = int(n)
+    out_len = np.zeros(max(n, 0), np.int64)
+    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
+    check(lib().omr_tiff8_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
+                                              int(channels), None if sz is None else sz.ctypes.data_as(i32p), n,
+                                              int(compression), int(predictor), int(rows_per_strip), int(dpi), d_out,
+                                              int(out_stride_bytes), out_len.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out_len
+
+
+def encode8(mat, compression=5, predictor=1, rows_per_strip=0, dpi=0):
+    """omr_tiff8_encode: a host image (gray or BGR) -> an 8-bit TIFF file as bytes that decodes to the image exactly.  One
+    call in the usual case: the first buffer holds the raw pixels and a page of head, which LZW passes only on noise; a file
+    that does not fit answers -4 with its length, and a second call encodes into that."""
+    a, im = as_image(_mat(mat))
+    n = C.c_int64()
+    L = lib()
+    args = (int(compression), int(predictor), int(rows_per_strip), int(dpi))
+    raw = im.rows * im.cols * im.channels
+    buf = np.empty(raw + 4096 + 8 * im.rows, np.uint8)
+    rc = L.omr_tiff8_encode(C.byref(im), *args, buf.ctypes.data_as(u8p), buf.size, C.byref(n))
+    if rc == -4:
+        buf = np.empty(n.value, np.uint8)
+        rc = L.omr_tiff8_encode(C.byref(im), *args, buf.ctypes.data_as(u8p), buf.size, C.byref(n))
+    check(rc)
+    return buf[: n.value].tobytes()
+
+
+STAGES_ENC8 = ("staging", "LZW", "placement", "head and strips")
+
+
+def encode8_stats(enable=True):
+    """omr_tiff8_encode_stats (measurement aid): what this thread's last 8-bit encode took -> (groups, [ms per stage of
+    STAGES_ENC8]); then switches the collection on or off for the thread's next encodes."""
+    groups = C.c_int32()
+    ms = np.zeros(len(STAGES_ENC8), np.float64)
+    check(lib().omr_tiff8_encode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
     return groups.value, [float(v) for v in ms]

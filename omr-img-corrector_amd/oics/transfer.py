@@ -83,6 +83,12 @@ class TransformableMatrix:
         from . import tiff
         return tiff.encode(self.matrix, threshold, rows_per_strip, dpi)
 
+    def encode_tiff8(self, compression=5, predictor=1, rows_per_strip=0, dpi=0):
+        """The image as an 8-bit TIFF file, gray or RGB, uncompressed (1) or LZW (5), encoded on the GPU (omr_tiff8_encode).
+        It decodes to the image exactly."""
+        from . import tiff
+        return tiff.encode8(self.matrix, compression, predictor, rows_per_strip, dpi)
+
     def get_mat(self):
         return self.matrix
 
@@ -210,8 +216,9 @@ def _detector_deskew(symbol, detector_args, srcs, flags, border_mode, border_val
 def _detector_deskew_streams(symbol, detector_args, streams, channels, flags, border_mode, border_value, clip_strategy, fmt,
                              level, want_out, tiff=None):
     """omr_deskew_with_hough_batch_streams / omr_deskew_with_fft_batch_streams -> (angles, scan_rc, [bytes or None] or None).
-    tiff = (rows_per_strip, dpi): the _tiff symbol, which takes (threshold = level, rows_per_strip, dpi) for (fmt, level)"""
-    how = (int(fmt), int(level)) if tiff is None else (int(level), int(tiff[0]), int(tiff[1]))
+    tiff = (rows_per_strip, dpi): the _tiff symbol, which takes (threshold = level, rows_per_strip, dpi) for (fmt, level);
+    tiff = (predictor, rows_per_strip, dpi): the _tiff8 symbol, level = the compression"""
+    how = (int(fmt), int(level)) if tiff is None else (int(level),) + tuple(int(v) for v in tiff)
     bufs = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else np.ascontiguousarray(s, np.uint8)
             for s in streams]
     bufs = [b if b.size else np.zeros(1, np.uint8) for b in bufs]

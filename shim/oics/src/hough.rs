@@ -186,3 +186,26 @@ pub fn deskew_files_with_hough_tiff(
         ffi::omr_deskew_with_hough_batch_streams_tiff(streams, len, n, 3, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), threshold, rows_per_strip, dpi, angles, scan_rc, tiff, tiff_len)
     })
 }
+
+/// `deskew_files_with_hough` with 8-bit RGB TIFF files as its outputs (omr_deskew_with_hough_batch_streams_tiff8):
+/// `compression` 1 (none) or 5 (LZW), `predictor` 1, or 2 with LZW; `rows_per_strip` 0: strips of at most 8192 raw bytes;
+/// `dpi` 0: no resolution tags.  Not in the reference crate.
+pub fn deskew_files_with_hough_tiff8(
+    inputs: &[&str],
+    outputs: &[&str],
+    min_line_length: f64,
+    max_line_gap: f64,
+    flags: i32,
+    border_mode: i32,
+    border_value: Scalar,
+    clip_strategy: RotateClipStrategy,
+    compression: i32,
+    predictor: i32,
+    rows_per_strip: i32,
+    dpi: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, tiff, tiff_len| unsafe {
+        ffi::omr_deskew_with_hough_batch_streams_tiff8(streams, len, n, 3, min_line_length, max_line_gap, flags, border_mode, border.as_ptr(), clip_strategy.to_abi(), compression, predictor, rows_per_strip, dpi, angles, scan_rc, tiff, tiff_len)
+    })
+}

@@ -180,3 +180,26 @@ pub fn deskew_files_with_projections_tiff(
         ffi::omr_deskew_with_projections_batch_streams_tiff(streams, len, n, 3, max_angle, angle_step, resize_scale, flags, border.as_ptr(), threshold, rows_per_strip, dpi, angles, std::ptr::null_mut(), scan_rc, tiff, tiff_len)
     })
 }
+
+/// `deskew_files_with_projections` with 8-bit RGB TIFF files as its outputs
+/// (omr_deskew_with_projections_batch_streams_tiff8): the canvases with their levels intact, `compression` 1 (none) or 5
+/// (LZW), `predictor` 1, or 2 with LZW.  `rows_per_strip` 0: strips of at most 8192 raw bytes; `dpi` 0: no resolution
+/// tags.  Not in the reference crate.
+pub fn deskew_files_with_projections_tiff8(
+    inputs: &[&str],
+    outputs: &[&str],
+    max_angle: u16,
+    angle_step: f64,
+    resize_scale: f64,
+    flags: i32,
+    border_value: Scalar,
+    compression: i32,
+    predictor: i32,
+    rows_per_strip: i32,
+    dpi: i32,
+) -> opencv::Result<Vec<f64>> {
+    let border = border_bytes(border_value);
+    files_through(inputs, outputs, |streams, len, n, angles, scan_rc, tiff, tiff_len| unsafe {
+        ffi::omr_deskew_with_projections_batch_streams_tiff8(streams, len, n, 3, max_angle, angle_step, resize_scale, flags, border.as_ptr(), compression, predictor, rows_per_strip, dpi, angles, std::ptr::null_mut(), scan_rc, tiff, tiff_len)
+    })
+}

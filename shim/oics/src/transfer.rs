@@ -305,6 +305,26 @@ pub fn encode_tiff(m: &TransformableMatrix, threshold: i32, rows_per_strip: i32,
     Ok(out)
 }
 
+/// An 8-bit TIFF file of the Mat, gray or RGB, encoded on the GPU (omr_tiff8_encode): `compression` 1 (none) or 5 (LZW),
+/// `predictor` 1, or 2 with LZW.  The file decodes to the Mat exactly.  `rows_per_strip` 0: libtiff's default, strips of
+/// at most 8192 raw bytes; `dpi` 0: no resolution tags.  Not in the reference crate.
+pub fn encode_tiff8(m: &TransformableMatrix, compression: i32, predictor: i32, rows_per_strip: i32, dpi: i32) -> Result<Vec<u8>, opencv::Error> {
+    let v = view(&m.matrix)?;
+    let mut bound = 0i64;
+    check(unsafe { ffi::omr_tiff8_bound(v.rows, v.cols, v.channels, compression, rows_per_strip, &mut bound) })?;
+    let first = v.rows as i64 * v.cols as i64 * v.channels as i64 + 8 * v.rows as i64 + 4096;
+    let mut out = vec![0u8; first.min(bound) as usize];
+    let mut len = 0i64;
+    let mut rc = unsafe { ffi::omr_tiff8_encode(&v, compression, predictor, rows_per_strip, dpi, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    if rc == ffi::OMR_ERR_NOMEM {
+        out = vec![0u8; len as usize];
+        rc = unsafe { ffi::omr_tiff8_encode(&v, compression, predictor, rows_per_strip, dpi, out.as_mut_ptr(), out.len() as i64, &mut len) };
+    }
+    check(rc)?;
+    out.truncate(len as usize);
+    Ok(out)
+}
+
 /// What `im_read` gives for a file with these bytes (`imread(.., IMREAD_COLOR)` for `channels` = 3, `IMREAD_GRAYSCALE`
 /// for 1), decoded on the GPU (omr_jpeg_decode): libjpeg's output with its defaults, byte for byte.  Baseline streams;
 /// one the decoder refuses (progressive, CMYK, an EXIF orientation, ..) is an error with code OMR_ERR_NOTIMPL, so that
