@@ -3,7 +3,11 @@ random shapes (1..90 per side), channels 1..4, interpolations 0..4, border modes
 WARP_FILL_OUTLIERS, clip, angles in [-180, 180] (a third of them on the 90-degree grid) and scales in [0.2, 3]
 (LDS-staged and global-fallback tiles), random per-channel border values, odd buffer offsets and pitches over a
 sentinel canvas.  Every byte of the canvas is compared; bytes past each canvas row must stay untouched.
-Usage: python tests/fuzz/fuzz_rotate_ex.py [cases] [seed]"""
+With a third argument `float64` (off by default: the cases and their checks are then exactly as without it) the cases
+that interpolate (LINEAR, CUBIC, LANCZOS4) and write every pixel (not BORDER_TRANSPARENT) run on smooth content of the
+drawn shape instead of the drawn noise, and the canvas is also held to tests/geom_exact.py's float64 warp within its
+general bound.
+Usage: python tests/fuzz/fuzz_rotate_ex.py [cases] [seed] [float64]"""
 import ctypes as C
 import os
 import sys
@@ -22,7 +26,7 @@ from oics import _lib
 SENTINEL = 0x5A
 
 
-def run_case(rng):
+def run_case(rng, float64=False):
     rows, cols, cn = int(rng.integers(1, 91)), int(rng.integers(1, 91)), int(rng.integers(1, 5))
     interp, mode, clip = int(rng.choice([0, 1, 2, 3, 4])), int(rng.integers(0, 6)), int(rng.integers(0, 2))
     flags = interp | (16 if rng.random() < 0.3 else 0) | (8 if rng.random() < 0.2 else 0)
@@ -32,6 +36,10 @@ def run_case(rng):
     a = rng.integers(0, 256, (rows, cols, cn), dtype=np.uint8)
     if rng.random() < 0.5:
         a[(np.add.outer(np.arange(rows), np.arange(cols)) % 2).astype(bool)] = 255
+    float64 = float64 and interp != 0 and mode != wr.TRANSPARENT
+    if float64:  # after every draw, so the stream of cases is the same with and without the option
+        import geom_cases
+        a = geom_cases.smooth(rows, cols, cn, seed=rows * 91 + cols)
     dr, dc = C.c_int32(), C.c_int32()
     assert _lib.lib().omr_rotate_size(rows, cols, angle, clip, C.byref(dr), C.byref(dc)) == 0
     dr, dc = dr.value, dc.value
@@ -57,15 +65,24 @@ def run_case(rng):
     exp = wr.rotate_ex(a, angle, scale, flags, mode, border, clip, init=np.full((dr, dc, cn), SENTINEL, np.uint8))
     if not np.array_equal(got, exp):
         return case, "%d bytes differ" % int((got != exp).sum())
+    if float64:
+        import geom_exact as gx
+        M, er, ec = gx.rotate_geometry(rows, cols, angle, scale, clip, bool(flags & wr.INVERSE_MAP))
+        if (er, ec) != (dr, dc):
+            return case, "canvas %r, float64 geometry %r" % ((dr, dc), (er, ec))
+        bad, at, _ = gx.worst(got, gx.warp(a, M, dr, dc, interp, mode, border), gx.general_warp_bound(interp, a, mode, border))
+        if bad:
+            return case, "%d pixels over the float64 bound, worst (index, got, exact, bound) %r" % (bad, at)
     return case, None
 
 
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 500
     rng = np.random.Generator(np.random.PCG64(int(sys.argv[2]) if len(sys.argv) > 2 else 1))
+    float64 = len(sys.argv) > 3 and sys.argv[3] == "float64"
     bad = []
     for _ in range(cases):
-        case, err = run_case(rng)
+        case, err = run_case(rng, float64)
         if err:
             bad.append((case, err))
     print("cases", cases, "mismatches", len(bad), bad[:5])
