@@ -26,13 +26,12 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
+#include "encode_any.hpp"
 #include "engine.hpp"
 #include "hough_host.hpp"
 #include "host_threads.hpp"
-#include "jpeg.hpp"
 #include "jpeg_dec.hpp"
 #include "png_dec.hpp"
-#include "png_enc.hpp"
 #include "stream_sink.hpp"
 
 using namespace omr;
@@ -339,8 +338,7 @@ struct HostArgs {
     // the JPEG form (omr_correct_default_batch_jpeg): streams instead of canvases
     uint8_t **jpeg = nullptr;
     int64_t *jpeg_len = nullptr;
-    int32_t quality = 0;
-    bool png_out = false;  // the PNG forms: the streams are PNG, `quality` is the compression level
+    OutFormat fmt{OUT_JPEG, 0};  // the PNG forms: OUT_PNG with the compression level
     // the streams form (omr_correct_default_batch_streams): srcs carries the shapes only, the sheets are decoded on the device
     const uint8_t *const *streams = nullptr;
     const int64_t *stream_len = nullptr;
@@ -458,9 +456,7 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
             for (int j = 0; j < z; j++)
                 if (src[(size_t)j] != OMR_OK) size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
             StreamSink sink(a.jpeg, a.jpeg_len, idx, j0);
-            rc = a.png_out ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
-                           : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
-            if (rc) return rc;
+            if ((rc = a.fmt.encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, sink, st.s))) return rc;
             t_down += now_ms() - t3;
             continue;
         }
@@ -482,10 +478,9 @@ int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector
 int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
                          int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
                          double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
-                         omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, int32_t quality,
+                         omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, const OutFormat &fmt,
                          const uint8_t *const *streams = nullptr, const int64_t *stream_len = nullptr,
-                         const JdecHeader *hdr = nullptr, const PdecHeader *png_hdr = nullptr, const uint8_t *is_png = nullptr,
-                         bool png_out = false)
+                         const JdecHeader *hdr = nullptr, const PdecHeader *png_hdr = nullptr, const uint8_t *is_png = nullptr)
 {
     if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     ShapeBuckets b;
@@ -499,7 +494,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
         for (const ImageShape &sh : b.shapes) {
             int R, C;
             canvas_of(sh.rows, sh.cols, &R, &C);
-            if ((rc = png_out ? penc_check_shape(R, C, sh.cn) : jpeg_check_scan_bits(R, C, sh.cn))) return rc;
+            if ((rc = fmt.check_canvas(R, C, sh.cn))) return rc;
         }
     }
     if ((rc = have_device())) return rc;
@@ -507,7 +502,7 @@ int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_m
     OMR_HIP(hipGetDevice(&dev));
     HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
-    a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.quality = quality, a.png_out = png_out;
+    a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.fmt = fmt;
     a.streams = streams, a.stream_len = stream_len, a.hdr = hdr, a.png_hdr = png_hdr, a.is_png = is_png;
     for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
         rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
@@ -647,7 +642,7 @@ int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t project
     clear_error();
     return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                                 hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, nullptr,
-                                nullptr, 0);
+                                nullptr, OutFormat{OUT_JPEG, 0});
 }
 
 int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
@@ -659,7 +654,7 @@ int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t pr
     if (!jpeg || !jpeg_len) return fail(OMR_ERR_BADARG, "bad batch arguments");
     return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                                 hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, jpeg,
-                                jpeg_len, quality);
+                                jpeg_len, OutFormat{OUT_JPEG, quality});
 }
 
 int omr_correct_default_batch_png(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
@@ -671,7 +666,7 @@ int omr_correct_default_batch_png(const omr_image *srcs, int32_t n, uint16_t pro
     if (!png || !png_len) return fail(OMR_ERR_BADARG, "bad batch arguments");
     return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
                                 hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, png,
-                                png_len, compression, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+                                png_len, OutFormat{OUT_PNG, compression});
 }
 
 }  // extern "C"
@@ -681,8 +676,8 @@ namespace {
 // omr_correct_default_batch_streams and its PNG form: `jpeg` receives the streams of either kind
 int correct_default_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
                             double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
-                            double hough_min_line_length, double hough_max_line_gap, int32_t quality, double *rotate_angle,
-                            int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len, bool png_out)
+                            double hough_min_line_length, double hough_max_line_gap, const OutFormat &fmt, double *rotate_angle,
+                            int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len)
 {
     clear_error();
     if (!streams || !len || n < 1 || !rotate_angle || !need_check || !scan_rc || !jpeg || !jpeg_len)
@@ -720,8 +715,8 @@ int correct_default_streams(const uint8_t *const *streams, const int64_t *len, i
     std::vector<int64_t> out_len((size_t)g);
     const int rc = correct_default_host(views.data(), g, projection_max_angle, projection_angle_step, projection_max_width,
                                         projection_max_height, hough_min_line_length, hough_max_line_gap, ang.data(), chk.data(),
-                                        src.data(), nullptr, out.data(), out_len.data(), quality, zs.data(), zlen.data(),
-                                        hdr.data(), png_hdr.data(), is_png.data(), png_out);
+                                        src.data(), nullptr, out.data(), out_len.data(), fmt, zs.data(), zlen.data(),
+                                        hdr.data(), png_hdr.data(), is_png.data());
     if (rc) return rc;
     for (int k = 0; k < g; k++) {
         const int i = at[(size_t)k];
@@ -742,8 +737,8 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
                                       int64_t *jpeg_len)
 {
     return correct_default_streams(streams, len, n, projection_max_angle, projection_angle_step, projection_max_width,
-                                   projection_max_height, hough_min_line_length, hough_max_line_gap, quality, rotate_angle,
-                                   need_check, scan_rc, jpeg, jpeg_len, false);
+                                   projection_max_height, hough_min_line_length, hough_max_line_gap, OutFormat{OUT_JPEG, quality},
+                                   rotate_angle, need_check, scan_rc, jpeg, jpeg_len);
 }
 
 int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -754,8 +749,8 @@ int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const i
                                           int64_t *png_len)
 {
     return correct_default_streams(streams, len, n, projection_max_angle, projection_angle_step, projection_max_width,
-                                   projection_max_height, hough_min_line_length, hough_max_line_gap, compression, rotate_angle,
-                                   need_check, scan_rc, png, png_len, true);
+                                   projection_max_height, hough_min_line_length, hough_max_line_gap, OutFormat{OUT_PNG, compression},
+                                   rotate_angle, need_check, scan_rc, png, png_len);
 }
 
 }  // extern "C"

@@ -21,15 +21,12 @@
 
 #include "../../include/omrdeskew.h"
 #include "detector_deskew.hpp"
+#include "encode_any.hpp"
 #include "engine.hpp"
 #include "host_threads.hpp"
-#include "jpeg.hpp"
 #include "jpeg_dec.hpp"
 #include "orient.hpp"
 #include "png_dec.hpp"
-#include "png_enc.hpp"
-#include "tiff_enc.hpp"
-#include "tiff_enc8.hpp"
 #include "stream_sink.hpp"
 
 using namespace omr;
@@ -194,18 +191,13 @@ struct StreamArgs {
     ImreadHeaders hd;  // sheet k's header stands in the array of its kind, hd.kind[k]
     int cn, flags, border_mode;
     const uint8_t *border;
-    int clip, level;  // level: quality, compression level, (TIFF) threshold or (8-bit TIFF) Compression
-    int out_kind;     // FORMAT_JPEG, FORMAT_PNG, FORMAT_TIFF or FORMAT_TIFF8
-    int rows_per_strip, dpi;  // the TIFF forms'
-    int predictor;    // the 8-bit TIFF form's
+    int clip;
+    OutFormat fmt;  // what writes the canvases
     double *angles;
     int32_t *scan_rc;
     uint8_t **out;  // null (with out_len): the angles alone
     int64_t *out_len;
 };
-
-// the public format values, and the ones only the _tiff and _tiff8 entry points pass (the public argument refuses them)
-enum { FORMAT_JPEG = 0, FORMAT_PNG = 1, FORMAT_TIFF = -26, FORMAT_TIFF8 = -29 };
 
 int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<int> &idx)
 {
@@ -247,13 +239,7 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
         if (!a.out) continue;
         // the canvases stay on the device: encoded there, only the streams come down (a 0 x 0 canvas has none)
         StreamSink sink(a.out, a.out_len, idx, j0);
-        rc = a.out_kind == FORMAT_TIFF8 ? tiff8_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level,
-                                                              a.predictor, a.rows_per_strip, a.dpi, sink, st.s)
-             : a.out_kind == FORMAT_TIFF ? tiff_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level,
-                                                             a.rows_per_strip, a.dpi, sink, st.s)
-             : a.out_kind == FORMAT_PNG ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s)
-                                        : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.level, sink, st.s);
-        if (rc) return rc;
+        if ((rc = a.fmt.encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, sink, st.s))) return rc;
     }
     return OMR_OK;
 }
@@ -267,11 +253,9 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
     if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
     if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
     if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "channels must be 1 or 3, got %d", channels);
-    if (format != FORMAT_JPEG && format != FORMAT_PNG && format != FORMAT_TIFF && format != FORMAT_TIFF8) return fail(OMR_ERR_BADARG, "format %d (0 = JPEG, 1 = PNG)", format);
-    if (format == FORMAT_TIFF)
-        if (int r = tenc_check_params(channels, level, rows_per_strip, dpi)) return r;
-    if (format == FORMAT_TIFF8)
-        if (int r = tenc8_check_params(channels, level, predictor, rows_per_strip, dpi)) return r;
+    if (format != OUT_JPEG && format != OUT_PNG && format != OUT_TIFF && format != OUT_TIFF8) return fail(OMR_ERR_BADARG, "format %d (0 = JPEG, 1 = PNG)", format);
+    const OutFormat fmt{(OutKind)format, level, predictor, rows_per_strip, dpi};
+    if (int r = fmt.check_params(channels)) return r;
     for (int i = 0; i < n; i++)
         if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
     int rc = check_rotate_args(flags, border_mode, clip);
@@ -313,16 +297,12 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
             for (const ImageShape &sh : b.shapes) {
                 int mr, mc;
                 if ((rc = detector_canvas(sh.rows, sh.cols, clip, &mr, &mc))) return rc;
-                if ((rc = format == FORMAT_TIFF8 ? tenc8_check_shape(mr, mc, sh.cn, level, rows_per_strip, nullptr)
-                          : format == FORMAT_TIFF ? tenc_check_shape(mr, mc, rows_per_strip, nullptr)
-                          : format == FORMAT_PNG ? penc_check_shape(mr, mc, sh.cn)
-                                                 : jpeg_check_scan_bits(mr, mc, sh.cn)))
-                    return rc;
+                if ((rc = fmt.check_canvas(mr, mc, sh.cn))) return rc;
             }
         }
         if ((rc = have_device())) return rc;
         const StreamArgs a{d, zs.data(), zlen.data(), run.view(), channels, flags, border_mode, border,
-                           clip, level, format, rows_per_strip, dpi, predictor, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
+                           clip, fmt, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
         if (rc) {
             for (uint8_t *p : bytes) free(p);
@@ -343,7 +323,7 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
 }
 
 // a caller's format: anything but JPEG and PNG becomes a value streams_form refuses, the private one included
-int public_format(int format) { return format == FORMAT_TIFF || format == FORMAT_TIFF8 ? FORMAT_TIFF - 1 : format; }
+int public_format(int format) { return format == OUT_TIFF || format == OUT_TIFF8 ? OUT_TIFF - 1 : format; }
 
 Detector hough_detector(double min_line_length, double max_line_gap)
 {
@@ -464,7 +444,7 @@ int omr_deskew_with_hough_batch_streams_tiff(const uint8_t *const *streams, cons
                                              uint8_t **out, int64_t *out_len)
 {
     return streams_form(hough_detector(min_line_length, max_line_gap), streams, len, n, channels, flags, border_mode, border_value, clip,
-                        FORMAT_TIFF, threshold, angles, scan_rc, out, out_len, rows_per_strip, dpi);
+                        OUT_TIFF, threshold, angles, scan_rc, out, out_len, rows_per_strip, dpi);
 }
 
 int omr_deskew_with_fft_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
@@ -475,7 +455,7 @@ int omr_deskew_with_fft_batch_streams_tiff(const uint8_t *const *streams, const 
                                            uint8_t **out, int64_t *out_len)
 {
     return streams_form(fft_detector(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams, len, n, channels,
-                        flags, border_mode, border_value, clip, FORMAT_TIFF, threshold, angles, scan_rc, out, out_len, rows_per_strip, dpi);
+                        flags, border_mode, border_value, clip, OUT_TIFF, threshold, angles, scan_rc, out, out_len, rows_per_strip, dpi);
 }
 
 int omr_deskew_with_hough_batch_streams_tiff8(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
@@ -485,7 +465,7 @@ int omr_deskew_with_hough_batch_streams_tiff8(const uint8_t *const *streams, con
                                               int32_t *scan_rc, uint8_t **out, int64_t *out_len)
 {
     return streams_form(hough_detector(min_line_length, max_line_gap), streams, len, n, channels, flags, border_mode, border_value, clip,
-                        FORMAT_TIFF8, compression, angles, scan_rc, out, out_len, rows_per_strip, dpi, predictor);
+                        OUT_TIFF8, compression, angles, scan_rc, out, out_len, rows_per_strip, dpi, predictor);
 }
 
 int omr_deskew_with_fft_batch_streams_tiff8(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
@@ -496,7 +476,7 @@ int omr_deskew_with_fft_batch_streams_tiff8(const uint8_t *const *streams, const
                                             int32_t *scan_rc, uint8_t **out, int64_t *out_len)
 {
     return streams_form(fft_detector(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), streams, len, n, channels,
-                        flags, border_mode, border_value, clip, FORMAT_TIFF8, compression, angles, scan_rc, out, out_len, rows_per_strip, dpi,
+                        flags, border_mode, border_value, clip, OUT_TIFF8, compression, angles, scan_rc, out, out_len, rows_per_strip, dpi,
                         predictor);
 }
 

@@ -1,5 +1,6 @@
 // oics_jpeg.cpp -- host side of the JPEG encoder (jpeg.hip): libjpeg's default tables and header,
-// the bound of a stream's length, the launches of a batch and the entry points omr_jpeg_*.
+// the bound of a stream's length, the shapes it refuses, a group's layout and launches, and the cost that closes a group.
+// The entry points omr_jpeg_encode* are the shared frame's (codec_host.hpp, section 4.28) with these handed in.
 #include <stdlib.h>
 #include <string.h>
 
@@ -7,9 +8,8 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
-#include "engine.hpp"
+#include "codec_host.hpp"
 #include "jpeg.hpp"
-#include "stream_sink.hpp"
 
 using namespace omr;
 
@@ -156,6 +156,10 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
                  const JpegTables *d_tab, const uint8_t *d_header, int header_len, int sof_off, JpegSink &sink, hipStream_t s)
 {
     std::vector<JpegImg> im((size_t)g);
+    GroupStreams out(sink, i0, g);
+    std::vector<uint32_t> h_bits((size_t)g), h_ff((size_t)g);
+    DrainOnExit drain{s};  // behind the host objects that asynchronous copies read or write, before the device buffers
+    DevBuf d_im, coef, aclen, dcdiff, local, csum, coff, ibits, iff, bitbuf, fsum, foff;
     uint32_t blocks = 0, chunks = 0;
     int max_tx = 1, max_ty = 1, max_chunks = 1;
     for (int j = 0; j < g; j++) {
@@ -173,14 +177,7 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
         max_ty = std::max(max_ty, (r + JPEG_TILE_H - 1) / JPEG_TILE_H);
         max_chunks = std::max(max_chunks, (int)m.nchunk);
     }
-    std::vector<int64_t> len((size_t)g, 0);
-    if (blocks == 0) {  // nothing but 0 x 0 entries
-        uint8_t *d_out = nullptr;
-        std::vector<int64_t> off((size_t)g, 0);
-        if (int rc = sink.place(i0, g, len.data(), &d_out, off.data())) return rc;
-        return sink.done(i0, g, len.data());
-    }
-    DevBuf d_im, coef, aclen, dcdiff, local, csum, coff, ibits, bitbuf, fsum, foff, iff;
+    if (blocks == 0) return out.all_empty();
     OMR_HIP(d_im.alloc(sizeof(JpegImg) * (size_t)g));
     OMR_HIP(coef.alloc((size_t)blocks * 128));
     OMR_HIP(aclen.alloc((size_t)blocks * 2));
@@ -201,7 +198,6 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(JpegImg) * (size_t)g, hipMemcpyHostToDevice, s));
     int rc = jpeg_launch_blocks(p, max_tx, max_ty, s);
     if (rc || (rc = jpeg_launch_lengths(p, max_chunks, s))) return rc;
-    std::vector<uint32_t> h_bits((size_t)g), h_ff((size_t)g);
     OMR_HIP(hipMemcpyAsync(h_bits.data(), ibits.p, (size_t)g * 4, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
     int64_t words = 0;
@@ -228,17 +224,12 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     OMR_HIP(hipMemcpyAsync(h_ff.data(), iff.p, (size_t)g * 4, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
     for (int j = 0; j < g; j++)
-        if (im[(size_t)j].nblk) len[(size_t)j] = (int64_t)header_len + im[(size_t)j].nbytes + h_ff[(size_t)j] + 2;
+        if (im[(size_t)j].nblk) out.len[(size_t)j] = (int64_t)header_len + im[(size_t)j].nbytes + h_ff[(size_t)j] + 2;
     // 3. the streams, where the caller wants them
-    uint8_t *d_out = nullptr;
-    std::vector<int64_t> off((size_t)g, 0);
-    if ((rc = sink.place(i0, g, len.data(), &d_out, off.data()))) return rc;
-    for (int j = 0; j < g; j++) im[(size_t)j].out_off = off[(size_t)j];
-    p.out = d_out;
-    OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(JpegImg) * (size_t)g, hipMemcpyHostToDevice, s));
+    if ((rc = out.place(im, d_im, s, &p.out))) return rc;
     if ((rc = jpeg_launch_streams(p, max_bchunks, s))) return rc;
     OMR_HIP(hipStreamSynchronize(s));
-    return sink.done(i0, g, len.data());
+    return out.done();
 }
 
 }  // namespace
@@ -257,7 +248,6 @@ int omr::jpeg_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t s
     for (int i = 0; i < n; i++)
         if (sizes[2 * (size_t)i] > 0)
             if (int rc = jpeg_check_scan_bits(sizes[2 * (size_t)i], sizes[2 * (size_t)i + 1], cn)) return rc;
-    DrainOnExit drain{s};  // declared before the buffers below: they go back only behind a drained stream
     JpegTables tab;
     uint16_t ql[64], qc[64];
     quant_tables(quality, ql, qc);
@@ -266,24 +256,17 @@ int omr::jpeg_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t s
     derive(kAcLuma, tab.ac[0], 256), derive(kAcChroma, tab.ac[1], 256);
     int sof_off = 0;
     const std::vector<uint8_t> header = build_header(cn, ql, qc, &sof_off);
+    DrainOnExit drain{s};  // behind the tables and the header, which asynchronous copies read, before the device buffers
     DevBuf d_tab, d_header;
-    int rc = upload_table(&d_tab, &tab, sizeof tab, s);
-    if (rc || (rc = upload_table(&d_header, header.data(), header.size(), s))) return rc;
-    for (int i0 = 0; i0 < n;) {
-        int g = 0;
-        int64_t blocks = 0;
-        while (i0 + g < n && g < kGroupImages) {
-            const int r = sizes[2 * (size_t)(i0 + g)], c = sizes[2 * (size_t)(i0 + g) + 1];
-            const int64_t b = r > 0 ? scan_blocks(r, c, cn) : 0;
-            if (g > 0 && blocks + b > kGroupBlocks) break;
-            blocks += b, g++;
-        }
-        if ((rc = encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, d_tab.as<JpegTables>(), d_header.as<uint8_t>(),
-                               (int)header.size(), sof_off, sink, s)))
-            return rc;
-        i0 += g;
-    }
-    return OMR_OK;
+    if (int rc = upload_table(&d_tab, &tab, sizeof tab, s)) return rc;
+    if (int rc = upload_table(&d_header, header.data(), header.size(), s)) return rc;
+    return for_each_run(
+        sizes, n, kGroupImages, [&](int r, int c) { return GroupCost{scan_blocks(r, c, cn), 0}; },
+        [](const GroupCost &sum, const GroupCost &m) { return sum.a + m.a <= kGroupBlocks; },
+        [&](int i0, int g) {
+            return encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, d_tab.as<JpegTables>(), d_header.as<uint8_t>(), (int)header.size(),
+                                sof_off, sink, s);
+        });
 }
 
 extern "C" {
@@ -309,55 +292,23 @@ int omr_jpeg_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes
                                  int32_t channels, const int32_t *sizes, int32_t n, int32_t quality, uint8_t *d_out,
                                  int64_t out_stride_bytes, int64_t *out_len)
 {
-    clear_error();
-    if (!d_imgs || !d_out || !out_len) return fail(OMR_ERR_BADARG, "null argument");
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
-    int rc = check_jpeg_shape(rows, cols, channels);
-    if (rc) return rc;
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (img_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "img_stride_bytes < rows x step_bytes");
-    std::vector<int32_t> sz(2 * (size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int r = sizes ? sizes[2 * (size_t)i] : rows, c = sizes ? sizes[2 * (size_t)i + 1] : cols;
-        if (r < 0 || c < 0 || r > rows || c > cols || ((r == 0) != (c == 0)))
-            return fail(OMR_ERR_BADARG, "sizes[%d] = %d x %d does not fit the %d x %d slot", i, r, c, rows, cols);
-        sz[2 * (size_t)i] = r, sz[2 * (size_t)i + 1] = c;
-    }
-    if (out_stride_bytes < stream_bound(rows, cols, channels))
-        return fail(OMR_ERR_BADARG, "out_stride_bytes below omr_jpeg_bound (%lld)", (long long)stream_bound(rows, cols, channels));
-    if ((rc = jpeg_check_scan_bits(rows, cols, channels))) return rc;
-    if (n == 0) return OMR_OK;
-    if ((rc = have_device())) return rc;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    SlotSink sink;
-    sink.d_out = d_out, sink.stride = out_stride_bytes, sink.out_len = out_len;
-    return jpeg_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz.data(), n, quality, sink, st.s);
+    const BatchEncodeArgs a{d_imgs, img_stride_bytes, step_bytes, rows, cols, channels, sizes, n, d_out, out_stride_bytes, out_len};
+    return encode_batch_entry(
+        a, "omr_jpeg_bound", [&] { return check_jpeg_shape(rows, cols, channels); }, [&] { return stream_bound(rows, cols, channels); },
+        no_image_check, [&] { return jpeg_check_scan_bits(rows, cols, channels); },
+        [&](const int32_t *sz, JpegSink &sink, hipStream_t s) {
+            return jpeg_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz, n, quality, sink, s);
+        });
 }
 
 int omr_jpeg_encode(const omr_image *src, int32_t quality, uint8_t *out, int64_t cap, int64_t *len)
 {
-    clear_error();
-    if (!src || !src->data || !len || cap < 0 || (!out && cap > 0)) return fail(OMR_ERR_BADARG, "null argument");
-    int rc = check_jpeg_shape(src->rows, src->cols, src->channels);
-    if (rc) return rc;
-    if (src->step_bytes < (int64_t)src->cols * src->channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
-    if ((rc = jpeg_check_scan_bits(src->rows, src->cols, src->channels))) return rc;
-    if ((rc = have_device())) return rc;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    const int64_t row = (int64_t)src->cols * src->channels;
-    DevBuf in;
-    OMR_HIP(in.alloc((size_t)(row * src->rows)));
-    if ((rc = upload_rows(in.p, (size_t)row, src->data, (size_t)src->step_bytes, (size_t)row, (size_t)src->rows, st.s))) return rc;
-    const int32_t size[2] = {src->rows, src->cols};
-    HostSink sink;
-    sink.out = out, sink.cap = cap, sink.s = st.s;
-    rc = jpeg_encode_device(in.as<uint8_t>(), row * src->rows, row, src->channels, size, 1, quality, sink, st.s);
-    if (rc) return rc;
-    *len = sink.len;
-    if (!sink.fits) return fail(OMR_ERR_NOMEM, "the stream takes %lld bytes, the buffer holds %lld", (long long)sink.len, (long long)cap);
-    return OMR_OK;
+    return encode_one_entry(
+        src, out, cap, len, "stream", [&] { return check_jpeg_shape(src->rows, src->cols, src->channels); },
+        [&] { return jpeg_check_scan_bits(src->rows, src->cols, src->channels); },
+        [&](const uint8_t *d_img, int64_t stride, int64_t step, const int32_t *size, JpegSink &sink, hipStream_t s) {
+            return jpeg_encode_device(d_img, stride, step, src->channels, size, 1, quality, sink, s);
+        });
 }
 
 void omr_bytes_free(uint8_t *p) { free(p); }

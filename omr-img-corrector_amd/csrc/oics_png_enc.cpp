@@ -1,5 +1,6 @@
 // oics_png_enc.cpp -- host side of the PNG encoder (png_enc.hip): the bound of a stream's length,
-// the shapes it refuses, the launches of a group and the entry points omr_png_bound / omr_png_encode*.
+// the shapes it refuses, a group's layout and launches, and the cost that closes a group.  The entry points
+// omr_png_encode* are the shared frame's (codec_host.hpp, section 4.28) with these handed in.
 #include <stdlib.h>
 #include <string.h>
 
@@ -9,7 +10,6 @@
 #include "../../include/omrdeskew.h"
 #include "codec_host.hpp"
 #include "png_enc.hpp"
-#include "stream_sink.hpp"
 
 using namespace omr;
 
@@ -28,7 +28,7 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
 {
     std::vector<PencImg> im((size_t)g);
     std::vector<PencDyn> dyn((size_t)g);
-    std::vector<int64_t> len((size_t)g, 0), off((size_t)g, 0);
+    GroupStreams out(sink, i0, g);
     DrainOnExit drain{s};  // behind the host objects that asynchronous copies read or write, before the device buffers
     StageTimer<PENC_STAGES> ev;
     if (int r = ev.begin(penc_stats().on)) return r;
@@ -46,11 +46,7 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
         raw_bytes += up16(raw), blocks += m.nblk;
         max_raw = std::max(max_raw, raw), max_rows = std::max(max_rows, r);
     }
-    uint8_t *d_out = nullptr;
-    if (blocks == 0) {  // nothing but 0 x 0 entries
-        if (int rc = sink.place(i0, g, len.data(), &d_out, off.data())) return rc;
-        return sink.done(i0, g, len.data());
-    }
+    if (blocks == 0) return out.all_empty();
     const int max_blocks = (int)blocks_of(max_raw), max_pieces = (int)((max_raw + PENC_PIECE - 1) / PENC_PIECE);
     const bool stored_only = compression == 0;
     DevBuf d_im, d_dyn, raw, mt, pcnt, pbit, blk, codes, hdr, zbuf;
@@ -88,23 +84,13 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     OMR_HIP(hipMemcpyAsync(dyn.data(), d_dyn.p, sizeof(PencDyn) * (size_t)g, hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
     for (int j = 0; j < g; j++)
-        if (im[(size_t)j].nblk) len[(size_t)j] = (int64_t)PENC_BEFORE + dyn[(size_t)j].deflate_len + PENC_AFTER;
+        if (im[(size_t)j].nblk) out.len[(size_t)j] = (int64_t)PENC_BEFORE + dyn[(size_t)j].deflate_len + PENC_AFTER;
     // 2. the streams, where the caller wants them
-    if ((rc = sink.place(i0, g, len.data(), &d_out, off.data()))) return rc;
-    for (int j = 0; j < g; j++) im[(size_t)j].out_off = off[(size_t)j];
-    p.out = d_out;
-    OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(PencImg) * (size_t)g, hipMemcpyHostToDevice, s));
+    if ((rc = out.place(im, d_im, s, &p.out))) return rc;
     if ((rc = penc_launch_streams(p, max_blocks, s)) || (rc = ev.mark(6, s))) return rc;
     OMR_HIP(hipStreamSynchronize(s));
     if ((rc = ev.finish(penc_stats()))) return rc;
-    return sink.done(i0, g, len.data());
-}
-
-int check_batch_args(const void *d_imgs, const void *d_out, const void *out_len, int n)
-{
-    if (!d_imgs || !d_out || !out_len) return fail(OMR_ERR_BADARG, "null argument");
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
-    return OMR_OK;
+    return out.done();
 }
 
 }  // namespace
@@ -140,19 +126,10 @@ int omr::png_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t st
         if (sizes[2 * (size_t)i] > 0)
             if (int rc = penc_check_shape(sizes[2 * (size_t)i], sizes[2 * (size_t)i + 1], cn)) return rc;
     DrainOnExit drain{s};
-    for (int i0 = 0; i0 < n;) {
-        int g = 0;
-        int64_t raw = 0;
-        while (i0 + g < n && g < kGroupImages) {
-            const int r = sizes[2 * (size_t)(i0 + g)], c = sizes[2 * (size_t)(i0 + g) + 1];
-            const int64_t b = r > 0 ? penc_raw_bytes(r, c, cn) : 0;
-            if (g > 0 && raw + b > kGroupRaw) break;
-            raw += b, g++;
-        }
-        if (int rc = encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, compression, sink, s)) return rc;
-        i0 += g;
-    }
-    return OMR_OK;
+    return for_each_run(
+        sizes, n, kGroupImages, [&](int r, int c) { return GroupCost{penc_raw_bytes(r, c, cn), 0}; },
+        [](const GroupCost &sum, const GroupCost &m) { return sum.a + m.a <= kGroupRaw; },
+        [&](int i0, int g) { return encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, compression, sink, s); });
 }
 
 extern "C" {
@@ -170,51 +147,22 @@ int omr_png_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes,
                                 int32_t channels, const int32_t *sizes, int32_t n, int32_t compression, uint8_t *d_out,
                                 int64_t out_stride_bytes, int64_t *out_len)
 {
-    clear_error();
-    int rc = check_batch_args(d_imgs, d_out, out_len, n);
-    if (rc || (rc = penc_check_shape(rows, cols, channels))) return rc;
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (img_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "img_stride_bytes < rows x step_bytes");
-    std::vector<int32_t> sz(2 * (size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int r = sizes ? sizes[2 * (size_t)i] : rows, c = sizes ? sizes[2 * (size_t)i + 1] : cols;
-        if (r < 0 || c < 0 || r > rows || c > cols || ((r == 0) != (c == 0)))
-            return fail(OMR_ERR_BADARG, "sizes[%d] = %d x %d does not fit the %d x %d slot", i, r, c, rows, cols);
-        sz[2 * (size_t)i] = r, sz[2 * (size_t)i + 1] = c;
-    }
-    if (out_stride_bytes < penc_bound(rows, cols, channels))
-        return fail(OMR_ERR_BADARG, "out_stride_bytes below omr_png_bound (%lld)", (long long)penc_bound(rows, cols, channels));
-    if (n == 0) return OMR_OK;
-    if ((rc = have_device())) return rc;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    SlotSink sink;
-    sink.d_out = d_out, sink.stride = out_stride_bytes, sink.out_len = out_len;
-    return png_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz.data(), n, compression, sink, st.s);
+    const BatchEncodeArgs a{d_imgs, img_stride_bytes, step_bytes, rows, cols, channels, sizes, n, d_out, out_stride_bytes, out_len};
+    return encode_batch_entry(
+        a, "omr_png_bound", [&] { return penc_check_shape(rows, cols, channels); }, [&] { return penc_bound(rows, cols, channels); },
+        no_image_check, no_extra_check,
+        [&](const int32_t *sz, JpegSink &sink, hipStream_t s) {
+            return png_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz, n, compression, sink, s);
+        });
 }
 
 int omr_png_encode(const omr_image *src, int32_t compression, uint8_t *out, int64_t cap, int64_t *len)
 {
-    clear_error();
-    if (!src || !src->data || !len || cap < 0 || (!out && cap > 0)) return fail(OMR_ERR_BADARG, "null argument");
-    int rc = penc_check_shape(src->rows, src->cols, src->channels);
-    if (rc) return rc;
-    if (src->step_bytes < (int64_t)src->cols * src->channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
-    if ((rc = have_device())) return rc;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    const int64_t row = (int64_t)src->cols * src->channels;
-    DevBuf in;
-    OMR_HIP(in.alloc((size_t)(row * src->rows)));
-    if ((rc = upload_rows(in.p, (size_t)row, src->data, (size_t)src->step_bytes, (size_t)row, (size_t)src->rows, st.s))) return rc;
-    const int32_t size[2] = {src->rows, src->cols};
-    HostSink sink;
-    sink.out = out, sink.cap = cap, sink.s = st.s;
-    rc = png_encode_device(in.as<uint8_t>(), row * src->rows, row, src->channels, size, 1, compression, sink, st.s);
-    if (rc) return rc;
-    *len = sink.len;
-    if (!sink.fits) return fail(OMR_ERR_NOMEM, "the stream takes %lld bytes, the buffer holds %lld", (long long)sink.len, (long long)cap);
-    return OMR_OK;
+    return encode_one_entry(
+        src, out, cap, len, "stream", [&] { return penc_check_shape(src->rows, src->cols, src->channels); }, no_extra_check,
+        [&](const uint8_t *d_img, int64_t stride, int64_t step, const int32_t *size, JpegSink &sink, hipStream_t s) {
+            return png_encode_device(d_img, stride, step, src->channels, size, 1, compression, sink, s);
+        });
 }
 
 int omr_png_encode_stats(int32_t enable, int32_t *groups, double *stage_ms)

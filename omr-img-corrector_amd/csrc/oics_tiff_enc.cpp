@@ -1,6 +1,7 @@
 // oics_tiff_enc.cpp -- host side of the Group 4 TIFF encoder (tiff_enc.hip): the bound of a file's
-// length, the shapes it refuses, the file's head, the launches of a group and the entry points omr_tiff_bound /
-// omr_tiff_encode*.
+// length, the parameters and shapes it refuses, a group's layout and launches, and the cost that closes a group.  The
+// file's head is tiff_head.hpp's from this writer's description; the entry points omr_tiff_encode* are the shared frame's
+// (codec_host.hpp, section 4.28) with these handed in.
 #include <stdlib.h>
 #include <string.h>
 
@@ -9,7 +10,6 @@
 
 #include "../../include/omrdeskew.h"
 #include "codec_host.hpp"
-#include "stream_sink.hpp"
 #include "tiff_dec.hpp"  // tdec_code_tables: the one set of T.4 codes
 #include "tiff_enc.hpp"
 
@@ -23,7 +23,6 @@ constexpr int kGroupImages = 4096;
 
 int pack_w_of(int cols) { return (cols + 31) / 32 + 1; }
 int seg_w_of(int cols) { return (int)((tenc_row_bits(cols) + 31) / 32) + 1; }
-int strips_of(int rows, int rps) { return (rows + rps - 1) / rps; }
 int64_t strip_bytes_max(int rows_of_strip, int cols) { return ((int64_t)rows_of_strip * tenc_row_bits(cols) + TENC_EOFB_BITS + 7) / 8; }
 // halvings that empty a range of v
 int halvings(int v)
@@ -33,58 +32,13 @@ int halvings(int v)
     return k + 1;
 }
 
-void le16(uint8_t *d, uint32_t v) { d[0] = (uint8_t)v, d[1] = (uint8_t)(v >> 8); }
-void le32(uint8_t *d, uint32_t v) { le16(d, v), le16(d + 2, v >> 16); }
-
-// The file's first bytes: "II" 42, the IFD at 8 with its tags in ascending order, the next-IFD pointer 0, the two
-// resolutions.  Behind them, for more than one strip, StripOffsets' and StripByteCounts' arrays (LONG), then the strips.
-void build_head(TencImg &m, int dpi)
-{
-    uint8_t *h = m.head;
-    memset(h, 0, sizeof m.head);
-    h[0] = h[1] = 'I', le16(h + 2, 42), le32(h + 4, 8);
-    const int nt = dpi > 0 ? 13 : 10;
-    const int ifd_end = 8 + 2 + 12 * nt + 4;
-    const int res_at = ifd_end;
-    m.head_len = ifd_end + (dpi > 0 ? 16 : 0);
-    le16(h + 8, (uint32_t)nt);
-    uint8_t *e = h + 10;
-    auto entry = [&](int tag, int type, uint32_t count, uint32_t value) {
-        le16(e, (uint32_t)tag), le16(e + 2, (uint32_t)type), le32(e + 4, count);
-        if (type == 3) le16(e + 8, value);
-        else le32(e + 8, value);
-        e += 12;
-        return (int)(e - 4 - h);  // where the value stands
-    };
-    const uint32_t ns = (uint32_t)m.ns;
-    const int arrays_at = m.head_len;
-    entry(256, 4, 1, (uint32_t)m.cols);
-    entry(257, 4, 1, (uint32_t)m.rows);
-    entry(258, 3, 1, 1);
-    entry(259, 3, 1, 4);
-    entry(262, 3, 1, 0);
-    const int off_in = entry(273, 4, ns, ns > 1 ? (uint32_t)arrays_at : 0);
-    entry(277, 3, 1, 1);
-    entry(278, 4, 1, (uint32_t)m.rps);
-    const int cnt_in = entry(279, 4, ns, ns > 1 ? (uint32_t)(arrays_at + 4 * ns) : 0);
-    if (dpi > 0) entry(282, 5, 1, (uint32_t)res_at), entry(283, 5, 1, (uint32_t)res_at + 8);
-    entry(293, 4, 1, 0);
-    if (dpi > 0) {
-        entry(296, 3, 1, 2);
-        le32(h + res_at, (uint32_t)dpi), le32(h + res_at + 4, 1), le32(h + res_at + 8, (uint32_t)dpi), le32(h + res_at + 12, 1);
-    }
-    m.off_pos = ns > 1 ? arrays_at : off_in;
-    m.cnt_pos = ns > 1 ? arrays_at + 4 * (int)ns : cnt_in;
-    m.data_at = arrays_at + (ns > 1 ? 8 * (int)ns : 0);
-}
-
 // one group: images [i0, i0 + g)
 int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn, const int32_t *sizes, int i0, int g, int threshold,
                  int rows_per_strip, int dpi, JpegSink &sink, hipStream_t s)
 {
     std::vector<TencImg> im((size_t)g);
     std::vector<TencDyn> dyn((size_t)g);
-    std::vector<int64_t> len((size_t)g, 0), off((size_t)g, 0);
+    GroupStreams out(sink, i0, g);
     DrainOnExit drain{s};  // behind the host objects that asynchronous copies read or write, before the device buffers
     StageTimer<TENC_STAGES> ev;
     if (int r = ev.begin(tenc_stats().on)) return r;
@@ -101,17 +55,13 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
         m.rps = rows_per_strip > 0 ? std::min(rows_per_strip, r) : r;
         m.ns = strips_of(r, m.rps);
         m.pack_w = pack_w_of(c), m.seg_w = seg_w_of(c);
-        build_head(m, dpi);
+        tenc_set_head(m, TiffHeadDesc{r, c, m.rps, m.ns, 1, 1, 4, 0, 1, true, dpi});  // bilevel, Group 4, white is zero, T6Options
         pack_words += ((int64_t)r + 1) * m.pack_w, code_words += (int64_t)r * m.seg_w, rows_all += r, strips_all += m.ns;
         max_pack_bytes = std::max(max_pack_bytes, ((int64_t)r + 1) * m.pack_w * 4);
         max_rows = std::max(max_rows, r), max_cols = std::max(max_cols, c);
         max_strips = std::max(max_strips, m.ns), max_rps = std::max(max_rps, m.rps);
     }
-    uint8_t *d_out = nullptr;
-    if (rows_all == 0) {  // nothing but 0 x 0 entries
-        if (int rc = sink.place(i0, g, len.data(), &d_out, off.data())) return rc;
-        return sink.done(i0, g, len.data());
-    }
+    if (rows_all == 0) return out.all_empty();
     uint32_t codes[2 * TENC_CODES];
     for (int k = 0; k < 2; k++) {
         int32_t run[TENC_CODES], code[TENC_CODES], bits[TENC_CODES];
@@ -148,18 +98,15 @@ int encode_group(const uint8_t *d_imgs, int64_t img_stride, int64_t step, int cn
     int64_t max_data = 0;
     for (int j = 0; j < g; j++)
         if (im[(size_t)j].rows) {
-            len[(size_t)j] = (int64_t)im[(size_t)j].data_at + dyn[(size_t)j].data_len;
+            out.len[(size_t)j] = (int64_t)im[(size_t)j].data_at + dyn[(size_t)j].data_len;
             max_data = std::max<int64_t>(max_data, dyn[(size_t)j].data_len);
         }
     // 2. the files, where the caller wants them
-    if ((rc = sink.place(i0, g, len.data(), &d_out, off.data()))) return rc;
-    for (int j = 0; j < g; j++) im[(size_t)j].out_off = off[(size_t)j];
-    p.out = d_out;
-    OMR_HIP(hipMemcpyAsync(d_im.p, im.data(), sizeof(TencImg) * (size_t)g, hipMemcpyHostToDevice, s));
+    if ((rc = out.place(im, d_im, s, &p.out))) return rc;
     if ((rc = tenc_launch_merge(p, max_data, max_strips, s)) || (rc = ev.mark(4, s))) return rc;
     OMR_HIP(hipStreamSynchronize(s));
     if ((rc = ev.finish(tenc_stats()))) return rc;
-    return sink.done(i0, g, len.data());
+    return out.done();
 }
 
 }  // namespace
@@ -182,8 +129,8 @@ int64_t omr::tenc_bound(int rows, int cols, int rps)
 {
     const int full = rows / rps, rest = rows % rps;
     int64_t b = TENC_HEAD_MAX + 8 * (int64_t)strips_of(rows, rps);
-    b += full * ((strip_bytes_max(rps, cols) + 1) & ~(int64_t)1);
-    if (rest) b += (strip_bytes_max(rest, cols) + 1) & ~(int64_t)1;
+    b += full * even_offset(strip_bytes_max(rps, cols));
+    if (rest) b += even_offset(strip_bytes_max(rest, cols));
     return b;
 }
 
@@ -223,19 +170,10 @@ int omr::tiff_encode_device(const uint8_t *d_imgs, int64_t img_stride, int64_t s
         if (sizes[2 * (size_t)i] > 0)
             if ((rc = tenc_check_shape(sizes[2 * (size_t)i], sizes[2 * (size_t)i + 1], rows_per_strip, nullptr))) return rc;
     DrainOnExit drain{s};
-    for (int i0 = 0; i0 < n;) {
-        int g = 0;
-        int64_t bytes = 0;
-        while (i0 + g < n && g < kGroupImages) {
-            const int r = sizes[2 * (size_t)(i0 + g)], c = sizes[2 * (size_t)(i0 + g) + 1];
-            const int64_t b = r > 0 ? (int64_t)r * seg_w_of(c) * 4 : 0;
-            if (g > 0 && bytes + b > kGroupCode) break;
-            bytes += b, g++;
-        }
-        if ((rc = encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, threshold, rows_per_strip, dpi, sink, s))) return rc;
-        i0 += g;
-    }
-    return OMR_OK;
+    return for_each_run(
+        sizes, n, kGroupImages, [](int r, int c) { return GroupCost{(int64_t)r * seg_w_of(c) * 4, 0}; },
+        [](const GroupCost &sum, const GroupCost &m) { return sum.a + m.a <= kGroupCode; },
+        [&](int i0, int g) { return encode_group(d_imgs, img_stride, step, cn, sizes, i0, g, threshold, rows_per_strip, dpi, sink, s); });
 }
 
 extern "C" {
@@ -254,55 +192,33 @@ int omr_tiff_encode_batch_device(const uint8_t *d_imgs, int64_t img_stride_bytes
                                  int32_t channels, const int32_t *sizes, int32_t n, int32_t threshold, int32_t rows_per_strip,
                                  int32_t dpi, uint8_t *d_out, int64_t out_stride_bytes, int64_t *out_len)
 {
-    clear_error();
-    if (!d_imgs || !d_out || !out_len) return fail(OMR_ERR_BADARG, "null argument");
-    if (n < 0) return fail(OMR_ERR_BADARG, "negative n");
+    const BatchEncodeArgs a{d_imgs, img_stride_bytes, step_bytes, rows, cols, channels, sizes, n, d_out, out_stride_bytes, out_len};
     int rps = 0;
-    int rc = tenc_check_params(channels, threshold, rows_per_strip, dpi);
-    if (rc || (rc = tenc_check_shape(rows, cols, rows_per_strip, &rps))) return rc;
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes < cols x channels");
-    if (img_stride_bytes < (int64_t)rows * step_bytes) return fail(OMR_ERR_BADARG, "img_stride_bytes < rows x step_bytes");
-    std::vector<int32_t> sz(2 * (size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int r = sizes ? sizes[2 * (size_t)i] : rows, c = sizes ? sizes[2 * (size_t)i + 1] : cols;
-        if (r < 0 || c < 0 || r > rows || c > cols || ((r == 0) != (c == 0)))
-            return fail(OMR_ERR_BADARG, "sizes[%d] = %d x %d does not fit the %d x %d slot", i, r, c, rows, cols);
-        sz[2 * (size_t)i] = r, sz[2 * (size_t)i + 1] = c;
-    }
-    if (out_stride_bytes < tenc_bound(rows, cols, rps))
-        return fail(OMR_ERR_BADARG, "out_stride_bytes below omr_tiff_bound (%lld)", (long long)tenc_bound(rows, cols, rps));
-    if (n == 0) return OMR_OK;
-    if ((rc = have_device())) return rc;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    SlotSink sink;
-    sink.d_out = d_out, sink.stride = out_stride_bytes, sink.out_len = out_len;
-    return tiff_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz.data(), n, threshold, rows_per_strip, dpi, sink, st.s);
+    return encode_batch_entry(
+        a, "omr_tiff_bound",
+        [&] {
+            const int rc = tenc_check_params(channels, threshold, rows_per_strip, dpi);
+            return rc ? rc : tenc_check_shape(rows, cols, rows_per_strip, &rps);
+        },
+        [&] { return tenc_bound(rows, cols, rps); }, no_image_check, no_extra_check,
+        [&](const int32_t *sz, JpegSink &sink, hipStream_t s) {
+            return tiff_encode_device(d_imgs, img_stride_bytes, step_bytes, channels, sz, n, threshold, rows_per_strip, dpi, sink, s);
+        });
 }
 
 int omr_tiff_encode(const omr_image *src, int32_t threshold, int32_t rows_per_strip, int32_t dpi, uint8_t *out, int64_t cap,
                     int64_t *len)
 {
-    clear_error();
-    if (!src || !src->data || !len || cap < 0 || (!out && cap > 0)) return fail(OMR_ERR_BADARG, "null argument");
-    int rc = tenc_check_params(src->channels, threshold, rows_per_strip, dpi);
-    if (rc || (rc = tenc_check_shape(src->rows, src->cols, rows_per_strip, nullptr))) return rc;
-    if (src->step_bytes < (int64_t)src->cols * src->channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
-    if ((rc = have_device())) return rc;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    const int64_t row = (int64_t)src->cols * src->channels;
-    DevBuf in;
-    OMR_HIP(in.alloc((size_t)(row * src->rows)));
-    if ((rc = upload_rows(in.p, (size_t)row, src->data, (size_t)src->step_bytes, (size_t)row, (size_t)src->rows, st.s))) return rc;
-    const int32_t size[2] = {src->rows, src->cols};
-    HostSink sink;
-    sink.out = out, sink.cap = cap, sink.s = st.s;
-    rc = tiff_encode_device(in.as<uint8_t>(), row * src->rows, row, src->channels, size, 1, threshold, rows_per_strip, dpi, sink, st.s);
-    if (rc) return rc;
-    *len = sink.len;
-    if (!sink.fits) return fail(OMR_ERR_NOMEM, "the file takes %lld bytes, the buffer holds %lld", (long long)sink.len, (long long)cap);
-    return OMR_OK;
+    return encode_one_entry(
+        src, out, cap, len, "file",
+        [&] {
+            const int rc = tenc_check_params(src->channels, threshold, rows_per_strip, dpi);
+            return rc ? rc : tenc_check_shape(src->rows, src->cols, rows_per_strip, nullptr);
+        },
+        no_extra_check,
+        [&](const uint8_t *d_img, int64_t stride, int64_t step, const int32_t *size, JpegSink &sink, hipStream_t s) {
+            return tiff_encode_device(d_img, stride, step, src->channels, size, 1, threshold, rows_per_strip, dpi, sink, s);
+        });
 }
 
 int omr_tiff_encode_stats(int32_t enable, int32_t *groups, double *stage_ms)

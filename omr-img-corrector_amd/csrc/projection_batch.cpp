@@ -23,16 +23,13 @@
 #include <vector>
 
 #include "../../include/omrdeskew.h"
+#include "encode_any.hpp"
 #include "engine.hpp"
 #include "host_threads.hpp"
 #include "hough_host.hpp"
-#include "jpeg.hpp"
 #include "jpeg_dec.hpp"
 #include "orient.hpp"
 #include "png_dec.hpp"
-#include "png_enc.hpp"
-#include "tiff_enc.hpp"
-#include "tiff_enc8.hpp"
 #include "stream_sink.hpp"
 
 using namespace omr;
@@ -527,18 +524,13 @@ struct StreamArgs {
     int N;
     int interp;
     const uint8_t *border;
-    int quality;  // the PNG form: the compression level; the TIFF form: the threshold; the 8-bit TIFF form: Compression
-    int out_kind;  // OUT_JPEG, OUT_PNG, OUT_TIFF or OUT_TIFF8
-    int rows_per_strip, dpi;  // the TIFF forms'
-    int predictor;  // the 8-bit TIFF form's
+    OutFormat fmt;  // what writes the canvases
     double *angles;
     int32_t *best_idx, *scan_rc;
     uint8_t **out;  // null (with out_len): the angles alone
     int64_t *out_len;
     int device;
 };
-
-enum { OUT_JPEG = 0, OUT_PNG = 1, OUT_TIFF = 2, OUT_TIFF8 = 3 };
 
 // a code of the per-call chain that belongs to its sheet (any other ends the call)
 bool sheet_code(int rc) { return rc == OMR_ERR_ASSERT || rc == OMR_ERR_BADARG || rc == OMR_ERR_NOTIMPL; }
@@ -555,18 +547,10 @@ int streams_per_call(const StreamArgs &a, const std::vector<int> &idx)
         if (!rc) rc = omr_get_angle_with_projections(&view, a.max_angle, a.step, a.scale, 1, &a.angles[k]);
         if (!rc && a.out) {
             rc = omr_rotate(&view, a.angles[k], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &rot);
-            if (!rc)
-                rc = a.out_kind == OUT_TIFF8 ? omr_tiff8_bound(rot.rows, rot.cols, rot.channels, a.quality, a.rows_per_strip, &cap)
-                     : a.out_kind == OUT_TIFF ? omr_tiff_bound(rot.rows, rot.cols, a.rows_per_strip, &cap)
-                     : a.out_kind == OUT_PNG ? omr_png_bound(rot.rows, rot.cols, rot.channels, &cap)
-                                             : omr_jpeg_bound(rot.rows, rot.cols, rot.channels, &cap);
+            if (!rc) rc = a.fmt.bound(rot.rows, rot.cols, rot.channels, &cap);
             if (!rc && !(bytes = (uint8_t *)malloc((size_t)cap))) rc = fail(OMR_ERR_NOMEM, "out of host memory");
             const omr_image canvas{rot.data, rot.rows, rot.cols, rot.channels, rot.step_bytes};
-            if (!rc)
-                rc = a.out_kind == OUT_TIFF8 ? omr_tiff8_encode(&canvas, a.quality, a.predictor, a.rows_per_strip, a.dpi, bytes, cap, &used)
-                     : a.out_kind == OUT_TIFF ? omr_tiff_encode(&canvas, a.quality, a.rows_per_strip, a.dpi, bytes, cap, &used)
-                     : a.out_kind == OUT_PNG ? omr_png_encode(&canvas, a.quality, bytes, cap, &used)
-                                             : omr_jpeg_encode(&canvas, a.quality, bytes, cap, &used);
+            if (!rc) rc = a.fmt.encode_host(&canvas, bytes, cap, &used);
         }
         omr_image_free(&img);
         omr_image_free(&rot);
@@ -634,28 +618,18 @@ int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<in
         if (!a.out) continue;
         // the canvases stay on the device: encoded there, only the streams come down
         StreamSink sink(a.out, a.out_len, idx, j0);
-        rc = a.out_kind == OUT_TIFF8 ? tiff8_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality,
-                                                           a.predictor, a.rows_per_strip, a.dpi, sink, st.s)
-             : a.out_kind == OUT_TIFF ? tiff_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality,
-                                                          a.rows_per_strip, a.dpi, sink, st.s)
-             : a.out_kind == OUT_PNG ? png_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s)
-                                     : jpeg_encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, a.quality, sink, st.s);
-        if (rc) return rc;
+        if ((rc = a.fmt.encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, sink, st.s))) return rc;
     }
     return OMR_OK;
 }
 
 // omr_deskew_with_projections_batch_streams and its PNG and TIFF forms: `out` receives the streams of any kind
 int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, uint16_t max_angle, double step,
-                   double scale, int32_t interp, const uint8_t *border, int32_t quality, double *angles, int32_t *best_idx,
-                   int32_t *scan_rc, uint8_t **out, int64_t *out_len, int out_kind, int32_t rows_per_strip = 0, int32_t dpi = 0,
-                   int32_t predictor = 1)
+                   double scale, int32_t interp, const uint8_t *border, const OutFormat &fmt, double *angles, int32_t *best_idx,
+                   int32_t *scan_rc, uint8_t **out, int64_t *out_len)
 {
     clear_error();
-    if (out_kind == OUT_TIFF8)
-        if (int r = tenc8_check_params(channels == 1 ? 1 : 3, quality, predictor, rows_per_strip, dpi)) return r;
-    if (out_kind == OUT_TIFF)
-        if (int r = tenc_check_params(channels == 1 ? 1 : 3, quality, rows_per_strip, dpi)) return r;
+    if (int r = fmt.check_params(channels == 1 ? 1 : 3)) return r;  // a bad channel count has its own refusal below
     if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
     if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
     if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
@@ -712,18 +686,14 @@ int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n,
                     clear_error();
                     continue;
                 }
-                if ((rc = out_kind == OUT_TIFF8 ? tenc8_check_shape(dk.rows, dk.cols, sh.cn, quality, rows_per_strip, nullptr)
-                          : out_kind == OUT_TIFF ? tenc_check_shape(dk.rows, dk.cols, rows_per_strip, nullptr)
-                          : out_kind == OUT_PNG ? penc_check_shape(dk.rows, dk.cols, sh.cn)
-                                                : jpeg_check_scan_bits(dk.rows, dk.cols, sh.cn)))
-                    return rc;
+                if ((rc = fmt.check_canvas(dk.rows, dk.cols, sh.cn))) return rc;
             }
         }
         if ((rc = have_device())) return rc;
         int dev = 0;
         OMR_HIP(hipGetDevice(&dev));
         StreamArgs a{zs.data(), zlen.data(), run.view(), channels, max_angle, step, scale, N, interp,
-                     border, quality, out_kind, rows_per_strip, dpi, predictor, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
+                     border, fmt, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
                      out ? bytes_len.data() : nullptr, dev};
         for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
         if (rc) {
@@ -755,8 +725,8 @@ int omr_deskew_with_projections_batch_streams(const uint8_t *const *streams, con
                                               const uint8_t border_value[4], int32_t quality, double *angles,
                                               int32_t *best_idx, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len)
 {
-    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, quality, angles, best_idx,
-                          scan_rc, jpeg, jpeg_len, OUT_JPEG);
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, OutFormat{OUT_JPEG, quality},
+                          angles, best_idx, scan_rc, jpeg, jpeg_len);
 }
 
 int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -765,8 +735,8 @@ int omr_deskew_with_projections_batch_streams_png(const uint8_t *const *streams,
                                                   double *angles, int32_t *best_idx, int32_t *scan_rc, uint8_t **png,
                                                   int64_t *png_len)
 {
-    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, compression, angles,
-                          best_idx, scan_rc, png, png_len, OUT_PNG);
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, OutFormat{OUT_PNG, compression},
+                          angles, best_idx, scan_rc, png, png_len);
 }
 
 int omr_deskew_with_projections_batch_streams_tiff(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -775,8 +745,8 @@ int omr_deskew_with_projections_batch_streams_tiff(const uint8_t *const *streams
                                                    int32_t rows_per_strip, int32_t dpi, double *angles, int32_t *best_idx,
                                                    int32_t *scan_rc, uint8_t **tiff, int64_t *tiff_len)
 {
-    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, threshold, angles,
-                          best_idx, scan_rc, tiff, tiff_len, OUT_TIFF, rows_per_strip, dpi);
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value,
+                          OutFormat{OUT_TIFF, threshold, 1, rows_per_strip, dpi}, angles, best_idx, scan_rc, tiff, tiff_len);
 }
 
 int omr_deskew_with_projections_batch_streams_tiff8(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -785,8 +755,8 @@ int omr_deskew_with_projections_batch_streams_tiff8(const uint8_t *const *stream
                                                     int32_t predictor, int32_t rows_per_strip, int32_t dpi, double *angles,
                                                     int32_t *best_idx, int32_t *scan_rc, uint8_t **tiff, int64_t *tiff_len)
 {
-    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value, compression, angles,
-                          best_idx, scan_rc, tiff, tiff_len, OUT_TIFF8, rows_per_strip, dpi, predictor);
+    return deskew_streams(streams, len, n, channels, max_angle, step, resize_scale, interp, border_value,
+                          OutFormat{OUT_TIFF8, compression, predictor, rows_per_strip, dpi}, angles, best_idx, scan_rc, tiff, tiff_len);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 
 #include "codec_stats.hpp"
 #include "jpeg.hpp"  // JpegSink: where a group's streams go (the protocol is the JPEG encoder's: place, then done)
+#include "tiff_head.hpp"
 
 namespace omr {
 
@@ -12,7 +13,7 @@ constexpr int TENC_MAX_SIDE = 1 << 20;  // imread's own limits, as the decoder's
 constexpr int64_t TENC_MAX_PIXELS = (int64_t)1 << 30;
 constexpr int TENC_CODES = 104;         // per colour, in tdec_code_tables' order: entry r for a run r < 64, 63 + m / 64 for a make-up run m
 constexpr int TENC_EOFB_BITS = 24;
-constexpr int TENC_HEAD_MAX = 8 + 2 + 12 * 13 + 4 + 16;  // header, the IFD with every tag, the two resolutions
+constexpr int TENC_HEAD_MAX = tiff_head_len(true, false, true, false);  // header, the IFD with every tag, the two resolutions: 186
 constexpr int TENC_HEAD_CAP = 208;      // room of TencImg::head: the 8-bit writer's head too (TENC8_HEAD_MAX, tiff_enc8.hpp)
 constexpr int64_t TENC_MAX_STRIP_BITS = ((int64_t)1 << 31) - 1;  // bit offsets inside a strip are 32 bits wide
 constexpr int64_t TENC_MAX_FILE = ((int64_t)1 << 32) - 1;        // classic TIFF's offsets
@@ -35,6 +36,16 @@ struct TencImg {
     int32_t data_at;   // the file offset of the first strip
     uint8_t head[TENC_HEAD_CAP];  // header, IFD and resolutions as the file begins, the two strip arrays' values left out
 };
+
+// the file's head (tiff_head.hpp) into m.head, and where it says the strip arrays and the first strip stand.  Only the
+// head's own bytes are written: m is a zeroed TencImg (both encoders memset theirs), so that the rest of m.head, which the
+// table's upload carries along, is zeros and not stale bytes
+static_assert(TENC_HEAD_MAX <= TENC_HEAD_CAP, "TencImg::head holds the Group 4 writer's head");
+inline void tenc_set_head(TencImg &m, const TiffHeadDesc &d)
+{
+    const TiffHead h = tiff_head(d, m.head);
+    m.head_len = h.head_len, m.off_pos = h.off_pos, m.cnt_pos = h.cnt_pos, m.data_at = h.data_at;
+}
 
 // what the device learns about an image
 struct TencDyn {

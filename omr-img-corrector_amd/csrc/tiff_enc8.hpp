@@ -14,7 +14,7 @@
 
 namespace omr {
 
-constexpr int TENC8_HEAD_MAX = 8 + 2 + 12 * 14 + 4 + 16 + 8;  // header, the IFD with every tag, the two resolutions, BitsPerSample's three
+constexpr int TENC8_HEAD_MAX = tiff_head_len(true, true, false, true);  // header, the IFD with every tag, the two resolutions, BitsPerSample's three: 206
 static_assert(TENC8_HEAD_MAX <= TENC_HEAD_CAP, "TencImg::head holds the 8-bit writer's head");
 constexpr int TENC8_DEFAULT_STRIP = 8192;  // libtiff's STRIP_SIZE_DEFAULT
 constexpr int TENC8_NONE = 1, TENC8_LZW = 5;  // Compression

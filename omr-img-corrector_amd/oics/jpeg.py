@@ -4,7 +4,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, i32p, lib, u8p
+from . import _codec
+from ._codec import _buf
+from ._lib import check, lib
 from ._lib import OmrImageOwned
 from .transfer import _mat, _take_owned, as_image
 
@@ -29,13 +31,8 @@ def encode_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, channe
     """omr_jpeg_encode_batch_device: n device-resident images in slots of rows x cols x channels (d_imgs, d_out: device
     addresses; sizes: None or int32 [n, 2] of (rows, cols) per image).  Returns out_len int64 [n]: stream i is
     out_len[i] bytes at d_out + i * out_stride_bytes (0: a 0 x 0 entry, slot untouched).  Synchronous."""
-    n = int(n)
-    out_len = np.zeros(max(n, 0), np.int64)
-    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
-    check(lib().omr_jpeg_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                             int(channels), None if sz is None else sz.ctypes.data_as(i32p), n, int(quality),
-                                             d_out, int(out_stride_bytes), out_len.ctypes.data_as(C.POINTER(C.c_int64))))
-    return out_len
+    return _codec.encode_batch_device(lib().omr_jpeg_encode_batch_device, d_imgs, img_stride_bytes, step_bytes, rows, cols, channels,
+                                      sizes, n, d_out, out_stride_bytes, quality)
 
 
 def encode(mat, quality=100):
@@ -43,19 +40,8 @@ def encode(mat, quality=100):
     holds the raw image's size plus the header, which all but noise at the highest qualities stays below; a stream that
     does not fit answers -4 with its length, and a second call encodes again into a buffer of that length."""
     a, im = as_image(_mat(mat))
-    n = C.c_int64()
-    L = lib()
-    buf = np.empty(min(im.rows * im.cols * im.channels + 1024, bound(im.rows, im.cols, im.channels)), np.uint8)
-    rc = L.omr_jpeg_encode(C.byref(im), int(quality), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    if rc == -4:
-        buf = np.empty(n.value, np.uint8)
-        rc = L.omr_jpeg_encode(C.byref(im), int(quality), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    check(rc)
-    return buf[: n.value].tobytes()
-
-
-def _buf(stream):
-    return np.frombuffer(bytes(stream), np.uint8)
+    first = min(im.rows * im.cols * im.channels + 1024, bound(im.rows, im.cols, im.channels))
+    return _codec.encode_retry(lib().omr_jpeg_encode, im, first, quality)
 
 
 def info(stream):
@@ -79,15 +65,7 @@ def decode_batch(streams, channels, d_out, out_stride_bytes, step_bytes, rows, c
     """omr_jpeg_decode_batch_device: host streams -> device-resident images, image i at the top left of the slot at
     d_out + i * out_stride_bytes (d_out: a device address).  Returns (out_size int32 [n, 2], rc int32 [n]): the images'
     (rows, cols), 0 x 0 where rc[i] != 0.  Synchronous."""
-    bufs = [_buf(s) for s in streams]
-    n = len(bufs)
-    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
-    lens = np.array([b.size for b in bufs], np.int64)
-    out_size, rc = np.zeros((max(n, 1), 2), np.int32), np.zeros(max(n, 1), np.int32)
-    check(lib().omr_jpeg_decode_batch_device(ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), d_out,
-                                             int(out_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                             out_size.ctypes.data_as(i32p), rc.ctypes.data_as(i32p)))
-    return out_size[:n], rc[:n]
+    return _codec.decode_batch_device(lib().omr_jpeg_decode_batch_device, streams, channels, d_out, out_stride_bytes, step_bytes, rows, cols)
 
 
 STAGES = ("upload and clearing", "un-stuffing", "synchronisation rounds", "coefficients", "inverse DCT", "colour")

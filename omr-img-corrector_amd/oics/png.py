@@ -1,15 +1,11 @@
 """PNG on the device (omr_png_*): decoding byte for byte what imread returns, and a lossless, deterministic encoder."""
 import ctypes as C
 
-import numpy as np
-
-from ._lib import check, i32p, lib, u8p
+from . import _codec
+from ._codec import _buf
+from ._lib import check, lib
 from ._lib import OmrImageOwned
 from .transfer import _mat, _take_owned, as_image
-
-
-def _buf(stream):
-    return np.frombuffer(bytes(stream), np.uint8)
 
 
 def info(stream):
@@ -33,15 +29,7 @@ def decode_batch_device(streams, channels, d_out, out_stride_bytes, step_bytes, 
     """omr_png_decode_batch_device: host streams -> device-resident images, image i at the top left of the slot at
     d_out + i * out_stride_bytes (d_out: a device address).  Returns (out_size int32 [n, 2], rc int32 [n]): the images'
     (rows, cols), 0 x 0 where rc[i] != 0.  Synchronous."""
-    bufs = [_buf(s) for s in streams]
-    n = len(bufs)
-    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
-    lens = np.array([b.size for b in bufs], np.int64)
-    out_size, rc = np.zeros((max(n, 1), 2), np.int32), np.zeros(max(n, 1), np.int32)
-    check(lib().omr_png_decode_batch_device(ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), d_out,
-                                            int(out_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                            out_size.ctypes.data_as(i32p), rc.ctypes.data_as(i32p)))
-    return out_size[:n], rc[:n]
+    return _codec.decode_batch_device(lib().omr_png_decode_batch_device, streams, channels, d_out, out_stride_bytes, step_bytes, rows, cols)
 
 
 STAGES = ("upload", "inflate", "Adler-32", "unfilter and convert")
@@ -50,10 +38,7 @@ STAGES = ("upload", "inflate", "Adler-32", "unfilter and convert")
 def stats(enable=True):
     """omr_png_decode_stats (measurement aid): what this thread's last decode took -> (groups, [ms per stage of STAGES]);
     then switches the collection on or off for the thread's next decodes."""
-    groups = C.c_int32()
-    ms = np.zeros(len(STAGES), np.float64)
-    check(lib().omr_png_decode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
-    return groups.value, [float(v) for v in ms]
+    return _codec.stage_stats(lib().omr_png_decode_stats, STAGES, enable)
 
 
 def bound(rows, cols, channels):
@@ -68,14 +53,8 @@ def encode_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, channe
     """omr_png_encode_batch_device: n device-resident images in slots of rows x cols x channels (d_imgs, d_out: device
     addresses; sizes: None or int32 [n, 2] of (rows, cols) per image).  Returns out_len int64 [n]: stream i is
     out_len[i] bytes at d_out + i * out_stride_bytes (0: a 0 x 0 entry, slot untouched).  Synchronous."""
-    n = int(n)
-    out_len = np.zeros(max(n, 0), np.int64)
-    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
-    check(lib().omr_png_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                            int(channels), None if sz is None else sz.ctypes.data_as(i32p), n,
-                                            int(compression), d_out, int(out_stride_bytes),
-                                            out_len.ctypes.data_as(C.POINTER(C.c_int64))))
-    return out_len
+    return _codec.encode_batch_device(lib().omr_png_encode_batch_device, d_imgs, img_stride_bytes, step_bytes, rows, cols, channels,
+                                      sizes, n, d_out, out_stride_bytes, compression)
 
 
 def encode(mat, compression=1):
@@ -83,15 +62,8 @@ def encode(mat, compression=1):
     buffer holds half the raw image's size, which sheets stay below; a stream that does not fit answers -4 with its
     length, and a second call encodes again into a buffer of that length."""
     a, im = as_image(_mat(mat))
-    n = C.c_int64()
-    L = lib()
-    buf = np.empty(min(im.rows * im.cols * im.channels // 2 + 1024, bound(im.rows, im.cols, im.channels)), np.uint8)
-    rc = L.omr_png_encode(C.byref(im), int(compression), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    if rc == -4:
-        buf = np.empty(n.value, np.uint8)
-        rc = L.omr_png_encode(C.byref(im), int(compression), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    check(rc)
-    return buf[: n.value].tobytes()
+    first = min(im.rows * im.cols * im.channels // 2 + 1024, bound(im.rows, im.cols, im.channels))
+    return _codec.encode_retry(lib().omr_png_encode, im, first, compression)
 
 
 STAGES_ENC = ("filter", "Adler-32", "matches and parse", "code sets and placement", "bit writer", "copy, CRC-32 and wrap")
@@ -100,7 +72,4 @@ STAGES_ENC = ("filter", "Adler-32", "matches and parse", "code sets and placemen
 def encode_stats(enable=True):
     """omr_png_encode_stats (measurement aid): what this thread's last encode took -> (groups, [ms per stage of
     STAGES_ENC]); then switches the collection on or off for the thread's next encodes."""
-    groups = C.c_int32()
-    ms = np.zeros(len(STAGES_ENC), np.float64)
-    check(lib().omr_png_encode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
-    return groups.value, [float(v) for v in ms]
+    return _codec.stage_stats(lib().omr_png_encode_stats, STAGES_ENC, enable)

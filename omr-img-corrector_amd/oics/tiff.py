@@ -6,12 +6,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import OMR_TIFF_CODES, OmrImageOwned, check, i32p, lib, u8p
+from . import _codec
+from ._codec import _buf
+from ._lib import OMR_TIFF_CODES, OmrImageOwned, check, i32p, lib
 from .transfer import _mat, _take_owned, as_image
-
-
-def _buf(stream):
-    return np.frombuffer(bytes(stream), np.uint8)
 
 
 def info(stream):
@@ -51,15 +49,7 @@ def decode_batch_device(streams, channels, d_out, out_stride_bytes, step_bytes, 
     """omr_tiff_decode_batch_device: host streams -> device-resident images, image i at the top left of the slot at
     d_out + i * out_stride_bytes (d_out: a device address).  Returns (out_size int32 [n, 2], rc int32 [n]): the images'
     (rows, cols), 0 x 0 where rc[i] != 0.  Synchronous."""
-    bufs = [_buf(s) for s in streams]
-    n = len(bufs)
-    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
-    lens = np.array([b.size for b in bufs], np.int64)
-    out_size, rc = np.zeros((max(n, 1), 2), np.int32), np.zeros(max(n, 1), np.int32)
-    check(lib().omr_tiff_decode_batch_device(ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64)), n, int(channels), d_out,
-                                             int(out_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                             out_size.ctypes.data_as(i32p), rc.ctypes.data_as(i32p)))
-    return out_size[:n], rc[:n]
+    return _codec.decode_batch_device(lib().omr_tiff_decode_batch_device, streams, channels, d_out, out_stride_bytes, step_bytes, rows, cols)
 
 
 STAGES = ("upload", "PackBits", "T.6", "unpack")
@@ -68,10 +58,7 @@ STAGES = ("upload", "PackBits", "T.6", "unpack")
 def stats(enable=True):
     """omr_tiff_decode_stats (measurement aid): what this thread's last decode took -> (groups, [ms per stage of STAGES]);
     then switches the collection on or off for the thread's next decodes."""
-    groups = C.c_int32()
-    ms = np.zeros(len(STAGES), np.float64)
-    check(lib().omr_tiff_decode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
-    return groups.value, [float(v) for v in ms]
+    return _codec.stage_stats(lib().omr_tiff_decode_stats, STAGES, enable)
 
 
 STAGES_EX = ("upload", "PackBits", "T.6", "LZW", "unpack", "finish8")
@@ -100,14 +87,8 @@ def encode_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, channe
     addresses; sizes: None or int32 [n, 2] of (rows, cols) per image) -> Group 4 TIFF files; a pixel is white iff its gray
     value is above `threshold`.  Returns out_len int64 [n]: file i is out_len[i] bytes at d_out + i * out_stride_bytes
     (0: a 0 x 0 entry, slot untouched).  Synchronous."""
-    n = int(n)
-    out_len = np.zeros(max(n, 0), np.int64)
-    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
-    check(lib().omr_tiff_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                             int(channels), None if sz is None else sz.ctypes.data_as(i32p), n,
-                                             int(threshold), int(rows_per_strip), int(dpi), d_out, int(out_stride_bytes),
-                                             out_len.ctypes.data_as(C.POINTER(C.c_int64))))
-    return out_len
+    return _codec.encode_batch_device(lib().omr_tiff_encode_batch_device, d_imgs, img_stride_bytes, step_bytes, rows, cols, channels,
+                                      sizes, n, d_out, out_stride_bytes, threshold, rows_per_strip, dpi)
 
 
 def encode(mat, threshold=127, rows_per_strip=0, dpi=0):
@@ -115,15 +96,8 @@ def encode(mat, threshold=127, rows_per_strip=0, dpi=0):
     thresholded at `threshold`.  One call in the usual case: the first buffer holds an eighth of the pixels, which pages
     stay far below; a file that does not fit answers -4 with its length, and a second call encodes into that."""
     a, im = as_image(_mat(mat))
-    n = C.c_int64()
-    L = lib()
-    buf = np.empty(min(im.rows * im.cols // 8 + 4096, bound(im.rows, im.cols, rows_per_strip)), np.uint8)
-    rc = L.omr_tiff_encode(C.byref(im), int(threshold), int(rows_per_strip), int(dpi), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    if rc == -4:
-        buf = np.empty(n.value, np.uint8)
-        rc = L.omr_tiff_encode(C.byref(im), int(threshold), int(rows_per_strip), int(dpi), buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    check(rc)
-    return buf[: n.value].tobytes()
+    first = min(im.rows * im.cols // 8 + 4096, bound(im.rows, im.cols, rows_per_strip))
+    return _codec.encode_retry(lib().omr_tiff_encode, im, first, threshold, rows_per_strip, dpi)
 
 
 STAGES_ENC = ("threshold and pack", "row coder", "placement", "head and bit merge")
@@ -132,10 +106,7 @@ STAGES_ENC = ("threshold and pack", "row coder", "placement", "head and bit merg
 def encode_stats(enable=True):
     """omr_tiff_encode_stats (measurement aid): what this thread's last encode took -> (groups, [ms per stage of
     STAGES_ENC]); then switches the collection on or off for the thread's next encodes."""
-    groups = C.c_int32()
-    ms = np.zeros(len(STAGES_ENC), np.float64)
-    check(lib().omr_tiff_encode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
-    return groups.value, [float(v) for v in ms]
+    return _codec.stage_stats(lib().omr_tiff_encode_stats, STAGES_ENC, enable)
 
 
 def bound8(rows, cols, channels=1, compression=5, rows_per_strip=0):
@@ -151,14 +122,8 @@ def encode8_batch_device(d_imgs, img_stride_bytes, step_bytes, rows, cols, chann
     addresses; sizes: None or int32 [n, 2] of (rows, cols) per image) -> 8-bit TIFF files, gray or RGB, uncompressed
     (compression 1) or LZW (5).  Returns out_len int64 [n]: file i is out_len[i] bytes at d_out + i * out_stride_bytes
     (0: a 0 x 0 entry, slot untouched).  Synchronous."""
-    n = int(n)
-    out_len = np.zeros(max(n, 0), np.int64)
-    sz = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
-    check(lib().omr_tiff8_encode_batch_device(d_imgs, int(img_stride_bytes), int(step_bytes), int(rows), int(cols),
-                                              int(channels), None if sz is None else sz.ctypes.data_as(i32p), n,
-                                              int(compression), int(predictor), int(rows_per_strip), int(dpi), d_out,
-                                              int(out_stride_bytes), out_len.ctypes.data_as(C.POINTER(C.c_int64))))
-    return out_len
+    return _codec.encode_batch_device(lib().omr_tiff8_encode_batch_device, d_imgs, img_stride_bytes, step_bytes, rows, cols, channels,
+                                      sizes, n, d_out, out_stride_bytes, compression, predictor, rows_per_strip, dpi)
 
 
 def encode8(mat, compression=5, predictor=1, rows_per_strip=0, dpi=0):
@@ -166,17 +131,8 @@ def encode8(mat, compression=5, predictor=1, rows_per_strip=0, dpi=0):
     call in the usual case: the first buffer holds the raw pixels and a page of head, which LZW passes only on noise; a file
     that does not fit answers -4 with its length, and a second call encodes into that."""
     a, im = as_image(_mat(mat))
-    n = C.c_int64()
-    L = lib()
-    args = (int(compression), int(predictor), int(rows_per_strip), int(dpi))
-    raw = im.rows * im.cols * im.channels
-    buf = np.empty(raw + 4096 + 8 * im.rows, np.uint8)
-    rc = L.omr_tiff8_encode(C.byref(im), *args, buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    if rc == -4:
-        buf = np.empty(n.value, np.uint8)
-        rc = L.omr_tiff8_encode(C.byref(im), *args, buf.ctypes.data_as(u8p), buf.size, C.byref(n))
-    check(rc)
-    return buf[: n.value].tobytes()
+    first = im.rows * im.cols * im.channels + 4096 + 8 * im.rows
+    return _codec.encode_retry(lib().omr_tiff8_encode, im, first, compression, predictor, rows_per_strip, dpi)
 
 
 STAGES_ENC8 = ("staging", "LZW", "placement", "head and strips")
@@ -185,7 +141,4 @@ STAGES_ENC8 = ("staging", "LZW", "placement", "head and strips")
 def encode8_stats(enable=True):
     """omr_tiff8_encode_stats (measurement aid): what this thread's last 8-bit encode took -> (groups, [ms per stage of
     STAGES_ENC8]); then switches the collection on or off for the thread's next encodes."""
-    groups = C.c_int32()
-    ms = np.zeros(len(STAGES_ENC8), np.float64)
-    check(lib().omr_tiff8_encode_stats(int(bool(enable)), C.byref(groups), ms.ctypes.data_as(C.POINTER(C.c_double))))
-    return groups.value, [float(v) for v in ms]
+    return _codec.stage_stats(lib().omr_tiff8_encode_stats, STAGES_ENC8, enable)

@@ -136,6 +136,7 @@ def test_cap_too_small():
             n = C.c_int64(-7)
             rc = L.omr_jpeg_encode(C.byref(im), 100, buf.ctypes.data_as(_lib.u8p), cap, C.byref(n))
             assert rc == -4 and n.value == len(want) and (buf == 0xA5).all(), (cn, cap, rc, n.value)
+            assert L.omr_last_error().decode() == "the stream takes %d bytes, the buffer holds %d" % (len(want), cap)
         buf = np.full(len(want) + 8, 0xA5, np.uint8)
         n = C.c_int64(-7)
         assert L.omr_jpeg_encode(C.byref(im), 100, buf.ctypes.data_as(_lib.u8p), len(want), C.byref(n)) == 0

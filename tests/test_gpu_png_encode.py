@@ -164,6 +164,7 @@ def test_host_form_and_front_doors():
     n = C.c_int64(-7)
     buf = np.full(64, 0xA5, np.uint8)
     assert oics.lib().omr_png_encode(C.byref(im), 1, buf.ctypes.data_as(_lib.u8p), 64, C.byref(n)) == -4
+    assert oics.lib().omr_last_error().decode() == "the stream takes %d bytes, the buffer holds 64" % len(s)
     assert n.value == len(s) and (buf == 0xA5).all()
     assert oics.lib().omr_png_encode(C.byref(im), 1, None, 0, C.byref(n)) == -4 and n.value == len(s)
     png.encode_stats(True)

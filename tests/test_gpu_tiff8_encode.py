@@ -211,6 +211,7 @@ def test_host_form_cap_rule_and_stats():
     buf = np.full(len(s) + 8, 0xA5, np.uint8)
     L = oics.lib()
     assert L.omr_tiff8_encode(C.byref(im), 5, 2, 8, 300, buf.ctypes.data_as(_lib.u8p), len(s) - 1, C.byref(n)) == -4
+    assert L.omr_last_error().decode() == "the file takes %d bytes, the buffer holds %d" % (len(s), len(s) - 1)
     assert n.value == len(s) and (buf == 0xA5).all()
     assert L.omr_tiff8_encode(C.byref(im), 5, 2, 8, 300, None, 0, C.byref(n)) == -4 and n.value == len(s)
     assert L.omr_tiff8_encode(C.byref(im), 5, 2, 8, 300, buf.ctypes.data_as(_lib.u8p), len(s), C.byref(n)) == 0

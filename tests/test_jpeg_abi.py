@@ -139,6 +139,17 @@ def test_batch_argument_errors_come_before_any_device_work():
     assert rc == 0 and (lens == -7).all()
 
 
+def test_bad_sizes_have_the_wording_all_four_encoders_share():
+    """the same four bad `sizes` stand in test_jpeg_abi, test_png_encode_abi, test_tiff_encode_abi and test_tiff8_encode_abi:
+    every encoder's batch entry point answers them with these words, to the letter"""
+    for sizes, text in [([[16, 24], [17, 24]], "sizes[1] = 17 x 24 does not fit the 16 x 24 slot"),
+                        ([[16, 25], [1, 1]], "sizes[0] = 16 x 25 does not fit the 16 x 24 slot"),
+                        ([[16, 24], [-1, 3]], "sizes[1] = -1 x 3 does not fit the 16 x 24 slot"),
+                        ([[0, 5], [1, 1]], "sizes[0] = 0 x 5 does not fit the 16 x 24 slot")]:
+        rc, lens = _batch(sizes=sizes)
+        assert rc == -5 and _err() == text and (lens == -7).all(), (sizes, rc, _err())
+
+
 def test_the_2_pow_32_bit_decision():
     """Bit offsets inside an image are 32-bit on the device, so a slot whose scan could exceed 2^32 bits is refused with
     -215 before any device work.  From omr_jpeg_bound's arithmetic: blocks x 1660 bits; 3 channels, 16 x 16 MCUs of 6."""

@@ -131,6 +131,17 @@ def test_batch_argument_errors_come_before_any_device_work():
         assert rc == -217 and (lens == -7).all()
 
 
+def test_bad_sizes_have_the_wording_all_four_encoders_share():
+    """the same four bad `sizes` stand in test_jpeg_abi, test_png_encode_abi, test_tiff_encode_abi and test_tiff8_encode_abi:
+    every encoder's batch entry point answers them with these words, to the letter"""
+    for sizes, text in [([[16, 24], [17, 24]], "sizes[1] = 17 x 24 does not fit the 16 x 24 slot"),
+                        ([[16, 25], [1, 1]], "sizes[0] = 16 x 25 does not fit the 16 x 24 slot"),
+                        ([[16, 24], [-1, 3]], "sizes[1] = -1 x 3 does not fit the 16 x 24 slot"),
+                        ([[0, 5], [1, 1]], "sizes[0] = 0 x 5 does not fit the 16 x 24 slot")]:
+        rc, lens = _batch(sizes=sizes)
+        assert rc == -5 and _err() == text and (lens == -7).all(), (sizes, rc, _err())
+
+
 def test_host_form_argument_errors_and_the_cap_rule():
     L = oics.lib()
     img = np.zeros((8, 12), np.uint8)
