@@ -17,7 +17,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -28,9 +27,11 @@
 #include "../../include/omrdeskew.h"
 #include "encode_any.hpp"
 #include "engine.hpp"
+#include "flow_frame.hpp"
 #include "hough_host.hpp"
 #include "host_threads.hpp"
 #include "jpeg_dec.hpp"
+#include "orient.hpp"
 #include "png_dec.hpp"
 #include "stream_sink.hpp"
 
@@ -324,29 +325,7 @@ int check_sheets(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_str
 
 namespace {
 
-// ---- the host-image form: contexts kept per (device, shape, parameters), transfers spread over host threads ---------
-struct HostArgs {
-    const omr_image *srcs;
-    uint16_t max_angle;
-    double step;
-    int32_t max_w, max_h;
-    double hmin, hgap;
-    double *angle;
-    int32_t *need_check, *scan_rc;
-    omr_image_owned *rotated;
-    int device;
-    // the JPEG form (omr_correct_default_batch_jpeg): streams instead of canvases
-    uint8_t **jpeg = nullptr;
-    int64_t *jpeg_len = nullptr;
-    OutFormat fmt{OUT_JPEG, 0};  // the PNG forms: OUT_PNG with the compression level
-    // the streams form (omr_correct_default_batch_streams): srcs carries the shapes only, the sheets are decoded on the device
-    const uint8_t *const *streams = nullptr;
-    const int64_t *stream_len = nullptr;
-    const JdecHeader *hdr = nullptr;
-    const PdecHeader *png_hdr = nullptr;  // sheet i is a PNG stream where is_png[i] != 0: png_hdr[i] holds, hdr[i] does not
-    const uint8_t *is_png = nullptr;
-};
-
+// ---- contexts kept per (device, shape, parameters) -------------------------------------------------------------------
 struct CtxKey {
     int device, rows, cols, cn;
     uint16_t max_angle;
@@ -361,156 +340,96 @@ struct CtxKey {
 };
 ContextCache<CtxKey, omr_correct_batch> g_ctx(4);
 
-// a context of kChunk sheets for this key: from the cache, or made and cached
+// a context of kAnglesChunk sheets for this key: from the cache, or made and cached
 int cached_context(const CtxKey &k, std::shared_ptr<omr_correct_batch> *out)
 {
     return g_ctx.get(k, [&](std::shared_ptr<omr_correct_batch> *sp) -> int {
         omr_correct_batch *raw = nullptr;
         int rc = omr_correct_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.max_w, k.max_h, k.hmin, k.hgap, k.device,
-                                          kChunk, &raw);
+                                          kAnglesChunk, &raw);
         if (rc == OMR_OK) sp->reset(raw, omr_correct_batch_destroy);
         return rc;
     }, out);
 }
 
-// Development aid (make debug, -DOMR_RUNS_DEBUG only; the release library reads no such switch): with
-// OMR_CORRECT_BATCH_TIMES set in the environment, every run of a bucket prints the wall time of its phases (context,
-// upload, device pipeline, canvases to host images) to stderr.
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// ---- the batch forms: the frame's walk (flow_frame.hpp) with this flow's few answers -------------------------------------
+struct Correct {
+    uint16_t max_angle;
+    double step;
+    int32_t max_w, max_h;
+    double hmin, hgap;
+};
 
-int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector<int> &idx)
+Flow correct_flow(const Correct &a)
 {
-#ifdef OMR_RUNS_DEBUG
-    static const bool times = getenv("OMR_CORRECT_BATCH_TIMES") != nullptr;
-#else
-    const bool times = false;
-#endif
-    double t0 = now_ms(), t_ctx = 0, t_up = 0, t_run = 0, t_down = 0;
-    const int m = (int)idx.size();
-    std::shared_ptr<omr_correct_batch> cbp;
-    int rc = cached_context(CtxKey{a.device, rows, cols, cn, a.max_angle, a.step, a.max_w, a.max_h, a.hmin, a.hgap}, &cbp);
-    if (rc == OMR_ERR_ASSERT) {  // the projection size truncates to 0 x n: the per-call function fails on each of these sheets
-        for (int i : idx) a.scan_rc[i] = rc, a.angle[i] = 0.0, a.need_check[i] = 0;
-        clear_error();
-        return OMR_OK;
-    }
-    if (rc) return rc;
-    omr_correct_batch *cb = cbp.get();
-    t_ctx = now_ms() - t0;
-    const int zmax = std::min(m, kChunk);
-    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    const int64_t out_step = (int64_t)cb->DC * cn, out_stride = out_step * cb->DR;
-    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
-    if ((rc = st.create())) return rc;
-    DevBuf din, dout;
-    OMR_HIP(din.alloc((size_t)zmax * in_stride));
-    const bool want_canvas = a.rotated || a.jpeg;
-    if (want_canvas) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
-    std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> chk((size_t)zmax), src((size_t)zmax), size(2 * (size_t)zmax);
-    std::vector<const uint8_t *> zs;
-    std::vector<int64_t> zlen;
-    std::vector<JdecHeader> zhdr;
-    std::vector<PdecHeader> zpng;
-    std::vector<int32_t> zskip, zskip_png, zrc;
-    for (int j0 = 0; j0 < m; j0 += zmax) {
-        const int z = std::min(zmax, m - j0);
-        double t1 = now_ms();
-        if (a.streams) {  // the chunk's streams -> BGR in the scan slots, decoded on the device
-            // a bucket may hold both kinds: each decoder fills its own members' slots and skips the other's
-            zs.resize((size_t)z), zlen.resize((size_t)z), zhdr.resize((size_t)z), zpng.resize((size_t)z);
-            zskip.assign((size_t)z, 0), zskip_png.assign((size_t)z, 0), zrc.assign((size_t)z, 0);
-            int pngs = 0;
-            for (int j = 0; j < z; j++) {
-                const int i = idx[(size_t)(j0 + j)];
-                zs[(size_t)j] = a.streams[i], zlen[(size_t)j] = a.stream_len[i];
-                if (a.is_png[i]) zpng[(size_t)j] = a.png_hdr[i], zskip[(size_t)j] = 1, pngs++;
-                else zhdr[(size_t)j] = a.hdr[i], zskip_png[(size_t)j] = 1;
-            }
-            if (pngs < z && (rc = jpeg_decode_device(zs.data(), zlen.data(), zhdr.data(), zskip.data(), z, cn, din.as<uint8_t>(),
-                                                     in_stride, row, zrc.data(), st.s)))
-                return rc;
-            if (pngs && (rc = png_decode_device(zs.data(), zlen.data(), zpng.data(), zskip_png.data(), z, cn, din.as<uint8_t>(),
-                                                in_stride, row, zrc.data(), st.s)))
-                return rc;
-        } else if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) {  // host memory -> device
-            return rc;
+    Flow f;
+    f.writes_early = true;
+    f.extra_refused = 0;  // need_check of a sheet with a code
+    f.accept = f.accept_parsed = [](const omr_image &im) { return check_image(&im, cn_correct_batch); };
+    f.canvas = [](int rows, int cols, int *R, int *C) {
+        canvas_of(rows, cols, R, C);
+        return (int)OMR_OK;
+    };
+    f.open = [a](int rows, int cols, int cn, bool, FlowBucket *b) -> int {
+        int dev = 0;
+        OMR_HIP(hipGetDevice(&dev));
+        std::shared_ptr<omr_correct_batch> cb;
+        int rc = cached_context(CtxKey{dev, rows, cols, cn, a.max_angle, a.step, a.max_w, a.max_h, a.hmin, a.hgap}, &cb);
+        if (rc == OMR_ERR_ASSERT) {  // the projection size truncates to 0 x n: the per-call function fails on each of these sheets
+            clear_error();
+            b->how = FlowBucket::ALL_CODE, b->code = rc;
+            return OMR_OK;
         }
-        double t2 = now_ms();
-        t_up += t2 - t1;
-        if ((rc = omr_correct_batch_run_device(cb, din.as<uint8_t>(), in_stride, row, z, ang.data(), chk.data(), src.data(),
-                                               want_canvas ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data())))
-            return rc;
-        if (a.streams)  // a sheet whose image data was damaged: its slot's content means nothing, its code and no output
-            for (int j = 0; j < z; j++)
-                if (zrc[(size_t)j]) src[(size_t)j] = zrc[(size_t)j], ang[(size_t)j] = 0.0, chk[(size_t)j] = 0;
-        for (int j = 0; j < z; j++) {
-            const int i = idx[(size_t)(j0 + j)];
-            a.angle[i] = ang[(size_t)j];
-            a.need_check[i] = chk[(size_t)j];
-            a.scan_rc[i] = src[(size_t)j];
-        }
-        double t3 = now_ms();
-        t_run += t3 - t2;
-        if (a.jpeg) {  // the canvases stay on the device: encoded there, only the streams come down
-            for (int j = 0; j < z; j++)
-                if (src[(size_t)j] != OMR_OK) size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
-            StreamSink sink(a.jpeg, a.jpeg_len, idx, j0);
-            if ((rc = a.fmt.encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, sink, st.s))) return rc;
-            t_down += now_ms() - t3;
-            continue;
-        }
-        if (!a.rotated) continue;
-        // canvases -> fresh host images, from several threads: packed on the device, then one staged copy each
-        rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), src.data(), idx, j0, z, a.rotated);
         if (rc) return rc;
-        t_down += now_ms() - t3;
-    }
-    if (times)
-        fprintf(stderr, "omr_correct_default_batch %d x %dx%dx%d: context %.2f ms, upload %.2f ms, device %.2f ms, canvases %.2f ms\n", m,
-                rows, cols, cn, t_ctx, t_up, t_run, t_down);
-    return OMR_OK;
+        b->chunk = kAnglesChunk, b->canvas_rows = cb->DR, b->canvas_cols = cb->DC, b->out_step = (int64_t)cb->DC * cn;
+        b->ctx = cb;
+        return OMR_OK;
+    };
+    f.run = [](const FlowBucket &b, const FlowSlots &s, double *ang, int32_t *chk, int32_t *src, int32_t *size) -> int {
+        return omr_correct_batch_run_device(static_cast<omr_correct_batch *>(b.ctx.get()), s.din, s.in_stride, s.row, s.z, ang, chk, src, s.dout,
+                                            s.out_stride, s.out_step, size);
+    };
+    return f;
 }
 
-// omr_correct_default_batch, its JPEG form and its streams form: buckets, contexts and results are the same; `rotated`
-// (may be null) receives the canvases, or `jpeg` / `jpeg_len` (null for the plain form) their streams.  The streams form
-// gives streams / stream_len / hdr per sheet and srcs[i] with that sheet's shape (its data is not read).
-int correct_default_host(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
-                         int32_t projection_max_width, int32_t projection_max_height, double hough_min_line_length,
-                         double hough_max_line_gap, double *rotate_angle, int32_t *need_check, int32_t *scan_rc,
-                         omr_image_owned *rotated, uint8_t **jpeg, int64_t *jpeg_len, const OutFormat &fmt,
-                         const uint8_t *const *streams = nullptr, const int64_t *stream_len = nullptr,
-                         const JdecHeader *hdr = nullptr, const PdecHeader *png_hdr = nullptr, const uint8_t *is_png = nullptr)
+// omr_correct_default_batch and its JPEG and PNG forms: `rotated` (may be null) receives the canvases, or `out` / `out_len`
+// (null for the plain form) their streams
+int correct_default_host(const omr_image *srcs, int32_t n, const Correct &a, double *rotate_angle, int32_t *need_check,
+                         int32_t *scan_rc, omr_image_owned *rotated, uint8_t **out, int64_t *out_len, const OutFormat &fmt)
 {
     if (!srcs || n < 1 || !rotate_angle || !need_check || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    ShapeBuckets b;
-    int rc = bucket_by_shape(srcs, n, [](const omr_image &im) { return check_image(&im, cn_correct_batch); }, &b);
-    if (rc) return rc;
-    if (rotated)
-        for (int i = 0; i < n; i++) rotated[i] = omr_image_owned{nullptr, 0, 0, 0, 0};
-    if (jpeg) {
-        for (int i = 0; i < n; i++) jpeg[i] = nullptr, jpeg_len[i] = 0;
-        // the encoder's bit offsets are 32-bit: a shape whose canvas slot could take more refuses the call, before any device work
-        for (const ImageShape &sh : b.shapes) {
-            int R, C;
-            canvas_of(sh.rows, sh.cols, &R, &C);
-            if ((rc = fmt.check_canvas(R, C, sh.cn))) return rc;
-        }
-    }
-    if ((rc = have_device())) return rc;
-    int dev = 0;
-    OMR_HIP(hipGetDevice(&dev));
-    HostArgs a{srcs, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
-               hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, dev};
-    a.jpeg = jpeg, a.jpeg_len = jpeg_len, a.fmt = fmt;
-    a.streams = streams, a.stream_len = stream_len, a.hdr = hdr, a.png_hdr = png_hdr, a.is_png = is_png;
-    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
-    if (rc && rotated)
-        for (int i = 0; i < n; i++) omr_image_free(&rotated[i]);
-    if (rc && jpeg)
-        for (int i = 0; i < n; i++) free(jpeg[i]), jpeg[i] = nullptr, jpeg_len[i] = 0;
-    return rc;
+    FlowSink sink;
+    if (out) sink.kind = FlowSink::STREAMS, sink.fmt = fmt;
+    else if (rotated) sink.kind = FlowSink::CANVASES;
+    FlowOut to;
+    to.angle = rotate_angle, to.extra = need_check, to.code = scan_rc, to.rotated = rotated, to.out = out, to.out_len = out_len;
+    return flow_host_call(correct_flow(a), sink, srcs, n, to);
+}
+
+// omr_correct_default_batch_streams and its PNG form: `out` receives the streams of either kind
+int correct_default_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, const Correct &a, const OutFormat &fmt,
+                            double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **out, int64_t *out_len)
+{
+    clear_error();
+    if (!streams || !len || n < 1 || !rotate_angle || !need_check || !scan_rc || !out || !out_len)
+        return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (int r = flow_check_streams(streams, len, n)) return r;
+    FlowSink sink;
+    sink.kind = FlowSink::STREAMS, sink.fmt = fmt;
+    FlowOut to;
+    to.angle = rotate_angle, to.extra = need_check, to.code = scan_rc, to.out = out, to.out_len = out_len;
+    // this flow's own header policy: a PNG, or a JPEG as omr_jpeg_decode takes it -- an EXIF orientation other than 1 is
+    // refused, and so is a TIFF (no JPEG).  A sheet the decoder refuses keeps its code and leaves the batch here
+    const auto parse = [](ImreadRun &run, const uint8_t *stream, int64_t l) {
+        run.jpeg.emplace_back(), run.png.emplace_back(), run.tiff.emplace_back();
+        const bool png = pdec_is_png(stream, l);
+        run.kind.push_back(png ? IMREAD_PNG : IMREAD_JPEG);
+        ImreadParsed ps;
+        ps.rc = png ? pdec_parse(stream, l, &run.png.back()) : jdec_parse(stream, l, &run.jpeg.back());
+        ps.rows = png ? run.png.back().rows : run.jpeg.back().rows, ps.cols = png ? run.png.back().cols : run.jpeg.back().cols;
+        return ps;
+    };
+    return flow_streams_call(correct_flow(a), sink, streams, len, n, 3, parse, to);
 }
 
 }  // namespace
@@ -640,9 +559,9 @@ int omr_correct_default_batch(const omr_image *srcs, int32_t n, uint16_t project
                               omr_image_owned *rotated)
 {
     clear_error();
-    return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
-                                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, rotated, nullptr,
-                                nullptr, OutFormat{OUT_JPEG, 0});
+    return correct_default_host(srcs, n, Correct{projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                                hough_min_line_length, hough_max_line_gap},
+                                rotate_angle, need_check, scan_rc, rotated, nullptr, nullptr, OutFormat{OUT_JPEG, 0});
 }
 
 int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
@@ -652,9 +571,9 @@ int omr_correct_default_batch_jpeg(const omr_image *srcs, int32_t n, uint16_t pr
 {
     clear_error();
     if (!jpeg || !jpeg_len) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
-                                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, jpeg,
-                                jpeg_len, OutFormat{OUT_JPEG, quality});
+    return correct_default_host(srcs, n, Correct{projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                                hough_min_line_length, hough_max_line_gap},
+                                rotate_angle, need_check, scan_rc, nullptr, jpeg, jpeg_len, OutFormat{OUT_JPEG, quality});
 }
 
 int omr_correct_default_batch_png(const omr_image *srcs, int32_t n, uint16_t projection_max_angle, double projection_angle_step,
@@ -664,71 +583,10 @@ int omr_correct_default_batch_png(const omr_image *srcs, int32_t n, uint16_t pro
 {
     clear_error();
     if (!png || !png_len) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    return correct_default_host(srcs, n, projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
-                                hough_min_line_length, hough_max_line_gap, rotate_angle, need_check, scan_rc, nullptr, png,
-                                png_len, OutFormat{OUT_PNG, compression});
+    return correct_default_host(srcs, n, Correct{projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                                hough_min_line_length, hough_max_line_gap},
+                                rotate_angle, need_check, scan_rc, nullptr, png, png_len, OutFormat{OUT_PNG, compression});
 }
-
-}  // extern "C"
-
-namespace {
-
-// omr_correct_default_batch_streams and its PNG form: `jpeg` receives the streams of either kind
-int correct_default_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
-                            double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
-                            double hough_min_line_length, double hough_max_line_gap, const OutFormat &fmt, double *rotate_angle,
-                            int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg, int64_t *jpeg_len)
-{
-    clear_error();
-    if (!streams || !len || n < 1 || !rotate_angle || !need_check || !scan_rc || !jpeg || !jpeg_len)
-        return fail(OMR_ERR_BADARG, "bad batch arguments");
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
-    // the headers, on the host: a sheet the decoder refuses keeps its code and leaves the batch here
-    std::vector<JdecHeader> hdr;
-    std::vector<PdecHeader> png_hdr;
-    std::vector<uint8_t> is_png;
-    std::vector<int> at;
-    std::vector<omr_image> views;
-    std::vector<const uint8_t *> zs;
-    std::vector<int64_t> zlen;
-    hdr.reserve((size_t)n);
-    for (int i = 0; i < n; i++) {
-        rotate_angle[i] = 0.0, need_check[i] = 0, jpeg[i] = nullptr, jpeg_len[i] = 0;
-        hdr.emplace_back(), png_hdr.emplace_back();
-        const bool png = pdec_is_png(streams[i], len[i]);
-        scan_rc[i] = png ? pdec_parse(streams[i], len[i], &png_hdr.back()) : jdec_parse(streams[i], len[i], &hdr.back());
-        if (scan_rc[i] != OMR_OK) {
-            hdr.pop_back(), png_hdr.pop_back();
-            continue;
-        }
-        const int rows = png ? png_hdr.back().rows : hdr.back().rows, cols = png ? png_hdr.back().cols : hdr.back().cols;
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]), is_png.push_back(png);
-        views.push_back(omr_image{streams[i], rows, cols, 3, (int64_t)cols * 3});
-    }
-    clear_error();
-    const int g = (int)at.size();
-    if (g == 0) return OMR_OK;  // every sheet refused: the codes are in scan_rc, there is no device work
-    std::vector<double> ang((size_t)g);
-    std::vector<int32_t> chk((size_t)g), src((size_t)g);
-    std::vector<uint8_t *> out((size_t)g);
-    std::vector<int64_t> out_len((size_t)g);
-    const int rc = correct_default_host(views.data(), g, projection_max_angle, projection_angle_step, projection_max_width,
-                                        projection_max_height, hough_min_line_length, hough_max_line_gap, ang.data(), chk.data(),
-                                        src.data(), nullptr, out.data(), out_len.data(), fmt, zs.data(), zlen.data(),
-                                        hdr.data(), png_hdr.data(), is_png.data());
-    if (rc) return rc;
-    for (int k = 0; k < g; k++) {
-        const int i = at[(size_t)k];
-        rotate_angle[i] = ang[(size_t)k], need_check[i] = chk[(size_t)k], scan_rc[i] = src[(size_t)k];
-        jpeg[i] = out[(size_t)k], jpeg_len[i] = out_len[(size_t)k];
-    }
-    return OMR_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, uint16_t projection_max_angle,
                                       double projection_angle_step, int32_t projection_max_width, int32_t projection_max_height,
@@ -736,9 +594,10 @@ int omr_correct_default_batch_streams(const uint8_t *const *streams, const int64
                                       double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **jpeg,
                                       int64_t *jpeg_len)
 {
-    return correct_default_streams(streams, len, n, projection_max_angle, projection_angle_step, projection_max_width,
-                                   projection_max_height, hough_min_line_length, hough_max_line_gap, OutFormat{OUT_JPEG, quality},
-                                   rotate_angle, need_check, scan_rc, jpeg, jpeg_len);
+    return correct_default_streams(streams, len, n,
+                                   Correct{projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                           hough_min_line_length, hough_max_line_gap},
+                                   OutFormat{OUT_JPEG, quality}, rotate_angle, need_check, scan_rc, jpeg, jpeg_len);
 }
 
 int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const int64_t *len, int32_t n,
@@ -748,9 +607,10 @@ int omr_correct_default_batch_streams_png(const uint8_t *const *streams, const i
                                           double *rotate_angle, int32_t *need_check, int32_t *scan_rc, uint8_t **png,
                                           int64_t *png_len)
 {
-    return correct_default_streams(streams, len, n, projection_max_angle, projection_angle_step, projection_max_width,
-                                   projection_max_height, hough_min_line_length, hough_max_line_gap, OutFormat{OUT_PNG, compression},
-                                   rotate_angle, need_check, scan_rc, png, png_len);
+    return correct_default_streams(streams, len, n,
+                                   Correct{projection_max_angle, projection_angle_step, projection_max_width, projection_max_height,
+                                           hough_min_line_length, hough_max_line_gap},
+                                   OutFormat{OUT_PNG, compression}, rotate_angle, need_check, scan_rc, png, png_len);
 }
 
 }  // extern "C"

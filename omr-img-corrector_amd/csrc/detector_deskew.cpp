@@ -23,6 +23,7 @@
 #include "detector_deskew.hpp"
 #include "encode_any.hpp"
 #include "engine.hpp"
+#include "flow_frame.hpp"
 #include "host_threads.hpp"
 #include "jpeg_dec.hpp"
 #include "orient.hpp"
@@ -32,9 +33,6 @@
 using namespace omr;
 
 namespace {
-
-const int kDeskewChunk = 32;  // scans of a shape per run when canvases are made: omr_deskew_with_projections_batch's bound
-const int kAnglesChunk = 64;  // ... when only the angles are asked for: the detectors' own host batches' bound
 
 // the flow on checked arguments.  skip (may be null): scans that are neither detected on nor rotated (their angle 0.0,
 // their code left to the caller).  rc is never null here.  max_rows x max_cols: detector_canvas's answer; d_out may be
@@ -107,55 +105,40 @@ int check_scan(const omr_image &im, int clip)
     return detector_canvas(im.rows, im.cols, clip, &mr, &mc);
 }
 
-// ---- host images -------------------------------------------------------------------------------------------------------
-struct HostArgs {
-    Detector d;
-    const omr_image *srcs;
+// ---- the batch forms: the frame's walk (flow_frame.hpp) with this flow's few answers -------------------------------------
+struct Rotate {
     int flags, border_mode;
     const uint8_t *border;
     int clip;
-    double *angles;
-    int32_t *rc;
-    omr_image_owned *rotated;
 };
 
-int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector<int> &idx)
+Flow detector_flow(const Detector &d, const Rotate &a)
 {
-    int mr = 0, mc = 0;
-    int rc = detector_canvas(rows, cols, a.clip, &mr, &mc);
-    if (rc) return rc;
-    // a run carries 32 scans: scan and slot of an A4 colour sheet are 26 + 55 MB on the device
-    const int m = (int)idx.size(), zmax = std::min(m, kDeskewChunk);
-    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    const int64_t out_step = ((int64_t)mc * cn + 3) & ~(int64_t)3, out_stride = out_step * mr;
-    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
-    if ((rc = st.create())) return rc;
-    DevBuf din, dout;
-    OMR_HIP(din.alloc((size_t)zmax * in_stride));
-    OMR_HIP(dout.alloc((size_t)zmax * out_stride));
-    std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> codes((size_t)zmax), size(2 * (size_t)zmax);
-    for (int j0 = 0; j0 < m; j0 += zmax) {
-        const int z = std::min(zmax, m - j0);
-        if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
+    Flow f;
+    f.accept = [a](const omr_image &im) { return check_scan(im, a.clip); };
+    f.canvas = [a](int rows, int cols, int *R, int *C) { return detector_canvas(rows, cols, a.clip, R, C); };
+    f.open = [a](int rows, int cols, int cn, bool canvases, FlowBucket *b) -> int {
+        int mr = 0, mc = 0;
+        if (canvases)
+            if (int rc = detector_canvas(rows, cols, a.clip, &mr, &mc)) return rc;
+        b->chunk = canvases ? kDeskewChunk : kDetectorAnglesChunk;
+        b->canvas_rows = mr, b->canvas_cols = mc, b->out_step = ((int64_t)mc * cn + 3) & ~(int64_t)3;
+        return OMR_OK;
+    };
+    f.run = [d, a](const FlowBucket &b, const FlowSlots &s, double *ang, int32_t *, int32_t *codes, int32_t *size) -> int {
+        // damaged image data: the slot's content means nothing.  Cleared, so that the detector finds a blank scan there
+        // whatever the slot held; its angle and canvas are not made
+        for (int j = 0; s.zrc && j < s.z; j++)
+            if (s.zrc[j]) OMR_HIP(hipMemsetAsync(s.din + (size_t)j * s.in_stride, 255, (size_t)s.in_stride, s.s));
         // BORDER_TRANSPARENT starts from zero-filled canvases, as omr_rotate_ex does
-        if (a.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(dout.p, 0, (size_t)z * out_stride, st.s));
-        if ((rc = deskew_run(a.d, din.as<uint8_t>(), z, in_stride, rows, cols, cn, row, a.flags, a.border_mode, a.border, a.clip, mr, mc,
-                             dout.as<uint8_t>(), out_stride, out_step, size.data(), ang.data(), codes.data(), nullptr, nullptr, st.s)))
-            return rc;
-        for (int j = 0; j < z; j++) {
-            const int i = idx[(size_t)(j0 + j)];
-            a.angles[i] = ang[(size_t)j], a.rc[i] = codes[(size_t)j];
-        }
-        // canvases -> fresh host images, from several threads; a scan without an angle has none
-        if ((rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), codes.data(), idx, j0, z, a.rotated)))
-            return rc;
-    }
-    return OMR_OK;
+        if (s.dout && a.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(s.dout, 0, (size_t)s.z * s.out_stride, s.s));
+        return deskew_run(d, s.din, s.z, s.in_stride, s.rows, s.cols, s.cn, s.row, a.flags, a.border_mode, a.border, a.clip, b.canvas_rows,
+                          b.canvas_cols, s.dout, s.out_stride, s.out_step, size, ang, codes, nullptr, s.zrc, s.s);
+    };
+    return f;
 }
 
-// both host forms: every image checked before any device work, then bucket by bucket; the caller's arrays are written only
-// when the whole call has succeeded
+// both host forms
 int host_form(const Detector &d, const omr_image *srcs, int n, int flags, int border_mode, const uint8_t *border, int clip,
               double *angles, int32_t *rc_out, omr_image_owned *rotated)
 {
@@ -163,87 +146,14 @@ int host_form(const Detector &d, const omr_image *srcs, int n, int flags, int bo
     if (!srcs || n < 1 || !border || !angles || !rotated || (!d.fft && !rc_out)) return fail(OMR_ERR_BADARG, "bad batch arguments");
     int rc = check_rotate_args(flags, border_mode, clip);
     if (rc) return rc;
-    ShapeBuckets b;
-    if ((rc = bucket_by_shape(srcs, n, [clip](const omr_image &im) { return check_scan(im, clip); }, &b))) return rc;
-    if ((rc = have_device())) return rc;
-    std::vector<double> ang((size_t)n, 0.0);
-    std::vector<int32_t> codes((size_t)n, OMR_OK);
-    std::vector<omr_image_owned> rot((size_t)n, omr_image_owned{nullptr, 0, 0, 0, 0});
-    const HostArgs a{d, srcs, flags, border_mode, border, clip, ang.data(), codes.data(), rot.data()};
-    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
-    if (rc) {
-        for (auto &o : rot) omr_image_free(&o);
-        return rc;
-    }
-    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
-    if (rc_out) memcpy(rc_out, codes.data(), sizeof(int32_t) * (size_t)n);
-    memcpy(rotated, rot.data(), sizeof(omr_image_owned) * (size_t)n);
-    return OMR_OK;
+    FlowSink sink;
+    sink.kind = FlowSink::CANVASES;
+    FlowOut to;
+    to.angle = angles, to.code = rc_out, to.rotated = rotated;
+    return flow_host_call(detector_flow(d, Rotate{flags, border_mode, border, clip}), sink, srcs, n, to);
 }
 
-// ---- file contents in, file contents out -------------------------------------------------------------------------------
-// Everything is indexed by the accepted sheets (those whose header parsed and whose canvas slot exists), in call order.
-struct StreamArgs {
-    Detector d;
-    const uint8_t *const *streams;
-    const int64_t *len;
-    ImreadHeaders hd;  // sheet k's header stands in the array of its kind, hd.kind[k]
-    int cn, flags, border_mode;
-    const uint8_t *border;
-    int clip;
-    OutFormat fmt;  // what writes the canvases
-    double *angles;
-    int32_t *scan_rc;
-    uint8_t **out;  // null (with out_len): the angles alone
-    int64_t *out_len;
-};
-
-int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<int> &idx)
-{
-    const int cn = a.cn;
-    int mr = 0, mc = 0, rc;
-    if (a.out && (rc = detector_canvas(rows, cols, a.clip, &mr, &mc))) return rc;
-    const int m = (int)idx.size(), zmax = std::min(m, a.out ? kDeskewChunk : kAnglesChunk);
-    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    const int64_t out_step = ((int64_t)mc * cn + 3) & ~(int64_t)3, out_stride = out_step * mr;
-    LeasedStream st;
-    if ((rc = st.create())) return rc;
-    DevBuf din, dout;
-    OMR_HIP(din.alloc((size_t)zmax * in_stride));
-    if (a.out) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
-    std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> codes((size_t)zmax), size(2 * (size_t)zmax, 0);
-    ImreadChunk ck;
-    for (int j0 = 0; j0 < m; j0 += zmax) {
-        const int z = std::min(zmax, m - j0);
-        // the chunk's streams -> the scan slots through the imread layer: each decoder fills its own members' slots, JPEG
-        // members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer and orient.hip
-        ck.gather(a.hd, a.streams, a.len, idx, j0, z);
-        if ((rc = imread_decode_device(ck.zs.data(), ck.zlen.data(), ck.hd.view(), nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, ck.zrc.data(), st.s)))
-            return rc;
-        // damaged image data: the slot's content means nothing.  Cleared, so that the detector finds a blank scan there
-        // whatever the slot held; its angle and canvas are not made
-        for (int j = 0; j < z; j++)
-            if (ck.zrc[(size_t)j]) OMR_HIP(hipMemsetAsync(din.as<uint8_t>() + (size_t)j * in_stride, 255, (size_t)in_stride, st.s));
-        if (a.out && a.border_mode == OMR_BORDER_TRANSPARENT) OMR_HIP(hipMemsetAsync(dout.p, 0, (size_t)z * out_stride, st.s));
-        if ((rc = deskew_run(a.d, din.as<uint8_t>(), z, in_stride, rows, cols, cn, row, a.flags, a.border_mode, a.border, a.clip, mr, mc,
-                             a.out ? dout.as<uint8_t>() : nullptr, out_stride, out_step, size.data(), ang.data(), codes.data(), nullptr,
-                             ck.zrc.data(), st.s)))
-            return rc;
-        for (int j = 0; j < z; j++) {
-            const int k = idx[(size_t)(j0 + j)];
-            a.scan_rc[k] = ck.zrc[(size_t)j] ? ck.zrc[(size_t)j] : codes[(size_t)j];
-            a.angles[k] = a.scan_rc[k] ? 0.0 : ang[(size_t)j];
-        }
-        if (!a.out) continue;
-        // the canvases stay on the device: encoded there, only the streams come down (a 0 x 0 canvas has none)
-        StreamSink sink(a.out, a.out_len, idx, j0);
-        if ((rc = a.fmt.encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, sink, st.s))) return rc;
-    }
-    return OMR_OK;
-}
-
+// file contents in, file contents out (out null, with out_len: the angles alone)
 int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, int32_t flags,
                  int32_t border_mode, const uint8_t *border, int32_t clip, int32_t format, int32_t level, double *angles,
                  int32_t *scan_rc, uint8_t **out, int64_t *out_len, int32_t rows_per_strip = 0, int32_t dpi = 0, int32_t predictor = 1)
@@ -256,70 +166,23 @@ int streams_form(const Detector &d, const uint8_t *const *streams, const int64_t
     if (format != OUT_JPEG && format != OUT_PNG && format != OUT_TIFF && format != OUT_TIFF8) return fail(OMR_ERR_BADARG, "format %d (0 = JPEG, 1 = PNG)", format);
     const OutFormat fmt{(OutKind)format, level, predictor, rows_per_strip, dpi};
     if (int r = fmt.check_params(channels)) return r;
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
+    if (int r = flow_check_streams(streams, len, n)) return r;
     int rc = check_rotate_args(flags, border_mode, clip);
     if (rc) return rc;
-    // the headers, on the host: a sheet its decoder refuses, or whose canvas slot leaves the image limit, keeps its code and
-    // leaves the batch here
-    std::vector<int32_t> code((size_t)n, OMR_OK);
-    ImreadRun run;
-    std::vector<int> at;
-    std::vector<omr_image> views;
-    std::vector<const uint8_t *> zs;
-    std::vector<int64_t> zlen;
-    run.reserve((size_t)n);
-    for (int i = 0; i < n; i++) {
-        // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
-        const ImreadParsed ps = run.append(streams[i], len[i], channels, false);
-        int r = ps.rc;
-        const int rows = ps.rows, cols = ps.cols;
+    FlowSink sink;
+    if (out) sink.kind = FlowSink::STREAMS, sink.fmt = fmt;
+    FlowOut to;
+    to.angle = angles, to.code = scan_rc, to.out = out, to.out_len = out_len;
+    // a sheet its decoder refuses, or whose canvas slot leaves the image limit, keeps its code (imread turns a JPEG by its
+    // EXIF orientation: the scan's shape is the turned one)
+    const bool canvases = out != nullptr;
+    const auto parse = [channels, clip, canvases](ImreadRun &run, const uint8_t *stream, int64_t l) {
+        ImreadParsed ps = run.append(stream, l, channels, false);
         int mr, mc;
-        if (!r) r = out ? detector_canvas(rows, cols, clip, &mr, &mc) : check_image_shape(rows, cols);
-        if ((code[(size_t)i] = r)) {
-            run.drop_last();
-            continue;
-        }
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]);
-        views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
-    }
-    clear_error();
-    const int g = (int)at.size();
-    std::vector<double> ang((size_t)g, 0.0);
-    std::vector<int32_t> src((size_t)g, OMR_OK);
-    std::vector<uint8_t *> bytes((size_t)g, nullptr);
-    std::vector<int64_t> bytes_len((size_t)g, 0);
-    if (g) {
-        ShapeBuckets b;
-        if ((rc = bucket_by_shape(views.data(), g, [](const omr_image &) { return (int)OMR_OK; }, &b))) return rc;
-        if (out) {  // the encoders' offsets inside an image are 32-bit: a shape whose canvas slot could exceed them refuses the
-                    // call, before any device work
-            for (const ImageShape &sh : b.shapes) {
-                int mr, mc;
-                if ((rc = detector_canvas(sh.rows, sh.cols, clip, &mr, &mc))) return rc;
-                if ((rc = fmt.check_canvas(mr, mc, sh.cn))) return rc;
-            }
-        }
-        if ((rc = have_device())) return rc;
-        const StreamArgs a{d, zs.data(), zlen.data(), run.view(), channels, flags, border_mode, border,
-                           clip, fmt, ang.data(), src.data(), out ? bytes.data() : nullptr, out ? bytes_len.data() : nullptr};
-        for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
-        if (rc) {
-            for (uint8_t *p : bytes) free(p);
-            return rc;
-        }
-    }
-    // every sheet is decided: the caller's arrays are written only now
-    for (int i = 0; i < n; i++) {
-        angles[i] = 0.0, scan_rc[i] = code[(size_t)i];
-        if (out) out[i] = nullptr, out_len[i] = 0;
-    }
-    for (int k = 0; k < g; k++) {
-        const int i = at[(size_t)k];
-        angles[i] = ang[(size_t)k], scan_rc[i] = src[(size_t)k];
-        if (out) out[i] = bytes[(size_t)k], out_len[i] = bytes_len[(size_t)k];
-    }
-    return OMR_OK;
+        if (!ps.rc) ps.rc = canvases ? detector_canvas(ps.rows, ps.cols, clip, &mr, &mc) : check_image_shape(ps.rows, ps.cols);
+        return ps;
+    };
+    return flow_streams_call(detector_flow(d, Rotate{flags, border_mode, border, clip}), sink, streams, len, n, channels, parse, to);
 }
 
 // a caller's format: anything but JPEG and PNG becomes a value streams_form refuses, the private one included

@@ -25,6 +25,7 @@
 #include "../../include/omrdeskew.h"
 #include "encode_any.hpp"
 #include "engine.hpp"
+#include "flow_frame.hpp"
 #include "host_threads.hpp"
 #include "hough_host.hpp"
 #include "jpeg_dec.hpp"
@@ -37,8 +38,6 @@ using namespace omr::hh;
 
 namespace {
 
-const int kChunk = 256;     // scans per run of the host form's contexts
-const int kDeskewChunk = 32;  // ... when the deskewed canvases come back with the angles
 const int kWarpChunk = 64;  // scans per launch of the deskew warp: bounds the tile records (2.4 MB per A4 colour scan's canvas)
 
 // scale_self's size and resize()'s dispatch for it, on the host (COPY: the working images are the scans)
@@ -205,7 +204,7 @@ int deskew_locked(omr_projection_batch *pb, const uint8_t *d_scans, int64_t scan
     return OMR_OK;
 }
 
-// ---- the host-image form: contexts kept per (device, shape, parameters) ----------------------------------------------
+// ---- contexts kept per (device, shape, parameters) -------------------------------------------------------------------
 struct CtxKey {
     int device, rows, cols, cn;
     uint16_t max_angle;
@@ -222,114 +221,169 @@ int cached_context(const CtxKey &k, std::shared_ptr<omr_projection_batch> *out)
 {
     return g_ctx.get(k, [&](std::shared_ptr<omr_projection_batch> *sp) -> int {
         omr_projection_batch *raw = nullptr;
-        int rc = omr_projection_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.scale, k.device, kChunk, &raw);
+        int rc = omr_projection_batch_create(k.rows, k.cols, k.cn, k.max_angle, k.step, k.scale, k.device, kAnglesChunk, &raw);
         if (rc == OMR_OK) sp->reset(raw, omr_projection_batch_destroy);
         return rc;
     }, out);
 }
 
-struct HostArgs {
-    const omr_image *srcs;
+// ---- the batch forms: the frame's walk (flow_frame.hpp) with this flow's few answers -------------------------------------
+struct Sweep {
     uint16_t max_angle;
     double step, scale;
     int N;
-    double *angles;
-    int32_t *best_idx;
-    int device;
-    // omr_deskew_with_projections_batch: the deskewed images as well (null: the angles alone)
-    omr_image_owned *rotated = nullptr;
-    int interp = OMR_INTER_NEAREST;
-    const uint8_t *border = nullptr;
+    int interp;
+    const uint8_t *border;
+    int cn = 0;                  // the streams forms: the channels every sheet is decoded to,
+    OutFormat fmt{OUT_JPEG, 0};  // and what writes the canvases
 };
 
+// a code of the per-call chain that belongs to its sheet (any other ends the call)
+bool sheet_code(int rc) { return rc == OMR_ERR_ASSERT || rc == OMR_ERR_BADARG || rc == OMR_ERR_NOTIMPL; }
+
 // the per-call function, image by image: the buckets a batch context does not take
-int bucket_per_call(const HostArgs &a, const std::vector<int> &idx)
+int host_per_call(const Sweep &a, const omr_image *srcs, const std::vector<int> &idx, const FlowOut &r)
 {
     for (int i : idx) {
-        int rc = omr_get_angle_with_projections(&a.srcs[i], a.max_angle, a.step, a.scale, 1, &a.angles[i]);
+        int rc = omr_get_angle_with_projections(&srcs[i], a.max_angle, a.step, a.scale, 1, &r.angle[i]);
         if (rc) return rc;
-        if (a.best_idx) a.best_idx[i] = (int32_t)llround(a.angles[i] / a.step) + a.N;
-        if (a.rotated && (rc = omr_rotate(&a.srcs[i], a.angles[i], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &a.rotated[i]))) return rc;
+        r.extra[i] = (int32_t)llround(r.angle[i] / a.step) + a.N;
+        if (r.rotated && (rc = omr_rotate(&srcs[i], r.angle[i], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &r.rotated[i]))) return rc;
     }
     return OMR_OK;
 }
 
-int host_bucket(const HostArgs &a, int rows, int cols, int cn, const std::vector<int> &idx)
+// the per-call chain from file contents, sheet by sheet; a sheet's own code stays with the sheet
+int streams_per_call(const Sweep &a, const FlowIn &in, const std::vector<int> &idx, const FlowOut &r)
 {
-    if (cn == 4) return bucket_per_call(a, idx);
-    std::shared_ptr<omr_projection_batch> pbp;
-    int rc = cached_context(CtxKey{a.device, rows, cols, cn, a.max_angle, a.step, a.scale}, &pbp);
-    if (rc == OMR_ERR_NOTIMPL || rc == OMR_ERR_BADARG || rc == OMR_ERR_ASSERT) {  // a sweep the batch context cannot plan
-        clear_error();
-        return bucket_per_call(a, idx);
-    }
-    if (rc) return rc;
-    omr_projection_batch *pb = pbp.get();
-    if (a.rotated && !pb->dk.count()) return bucket_per_call(a, idx);  // a canvas the warp's tables cannot hold
-    // with canvases a run carries 32 scans: scan and slot of an A4 colour sheet are 26 + 54 MB on the device
-    const int m = (int)idx.size(), zmax = std::min(m, a.rotated ? kDeskewChunk : kChunk);
-    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    const int64_t out_step = (int64_t)pb->dk.cols * cn, out_stride = out_step * pb->dk.rows;
-    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
-    if ((rc = st.create())) return rc;
-    DevBuf din, dout;
-    OMR_HIP(din.alloc((size_t)zmax * in_stride));
-    if (a.rotated) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
-    std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> best((size_t)zmax), size(2 * (size_t)zmax);
-    for (int j0 = 0; j0 < m; j0 += zmax) {
-        const int z = std::min(zmax, m - j0);
-        // host memory -> device, from several threads
-        if ((rc = upload_chunk(a.srcs, idx, j0, z, rows, row, din.as<uint8_t>(), in_stride))) return rc;
-        rc = a.rotated ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
-                                                            out_stride, out_step, size.data(), ang.data(), best.data())
-                       : omr_projection_batch_run_device(pb, din.as<uint8_t>(), in_stride, row, z, ang.data(), best.data(), nullptr, nullptr);
-        if (rc) return rc;
-        for (int j = 0; j < z; j++) {
-            const int i = idx[(size_t)(j0 + j)];
-            a.angles[i] = ang[(size_t)j];
-            if (a.best_idx) a.best_idx[i] = best[(size_t)j];
+    for (int k : idx) {
+        omr_image_owned img{nullptr, 0, 0, 0, 0}, rot{nullptr, 0, 0, 0, 0};
+        uint8_t *bytes = nullptr;
+        int64_t cap = 0, used = 0;
+        int rc = omr_imread(in.streams[k], in.len[k], a.cn, 0, &img);
+        const omr_image view{img.data, img.rows, img.cols, img.channels, img.step_bytes};
+        if (!rc) rc = omr_get_angle_with_projections(&view, a.max_angle, a.step, a.scale, 1, &r.angle[k]);
+        if (!rc && r.out) {
+            rc = omr_rotate(&view, r.angle[k], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &rot);
+            if (!rc) rc = a.fmt.bound(rot.rows, rot.cols, rot.channels, &cap);
+            if (!rc && !(bytes = (uint8_t *)malloc((size_t)cap))) rc = fail(OMR_ERR_NOMEM, "out of host memory");
+            const omr_image canvas{rot.data, rot.rows, rot.cols, rot.channels, rot.step_bytes};
+            if (!rc) rc = a.fmt.encode_host(&canvas, bytes, cap, &used);
         }
-        // canvases -> fresh host images, from several threads
-        if (a.rotated && (rc = download_canvases(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), nullptr, idx, j0, z, a.rotated)))
-            return rc;
+        omr_image_free(&img);
+        omr_image_free(&rot);
+        if (rc) {
+            free(bytes);
+            if (!sheet_code(rc)) return rc;
+            r.code[k] = rc, r.angle[k] = 0.0, r.extra[k] = -1;
+            continue;
+        }
+        r.extra[k] = (int32_t)llround(r.angle[k] / a.step) + a.N;
+        if (r.out) {
+            uint8_t *fit = (uint8_t *)realloc(bytes, (size_t)std::max<int64_t>(used, 1));  // the bound is several times the stream
+            r.out[k] = fit ? fit : bytes, r.out_len[k] = used;
+        }
     }
+    clear_error();
     return OMR_OK;
 }
 
-// both host forms: every image checked as the per-call function checks it, then bucket by bucket; the caller's arrays
-// are written only when the whole call has succeeded
+Flow projection_flow(const Sweep &a)
+{
+    Flow f;
+    f.extra_refused = -1;  // best_idx of a sheet with a code
+    // omr_get_angle_with_projections' checks
+    f.accept = [a](const omr_image &im) -> int {
+        Working w;
+        int rc = check_image(&im, cn_gray_source);
+        return rc ? rc : working_size(im.rows, im.cols, a.scale, &w);
+    };
+    f.canvas = [a](int rows, int cols, int *R, int *C) -> int {
+        const int A = candidate_count(a.max_angle, a.step, nullptr);
+        std::vector<double> cand((size_t)A);
+        for (int i = 0; i < A; i++) cand[(size_t)i] = (double)(i - a.N) * a.step;
+        DeskewTables dk;
+        if (dk.plan(rows, cols, cand.data(), A)) clear_error(), *R = 0;  // (a shape without a canvas goes sheet by sheet)
+        else *R = dk.rows, *C = dk.cols;
+        return OMR_OK;
+    };
+    f.open = [a](int rows, int cols, int cn, bool canvases, FlowBucket *b) -> int {
+        b->how = FlowBucket::PER_SHEET;
+        if (cn == 4) return OMR_OK;
+        int dev = 0;
+        OMR_HIP(hipGetDevice(&dev));
+        std::shared_ptr<omr_projection_batch> pb;
+        int rc = cached_context(CtxKey{dev, rows, cols, cn, a.max_angle, a.step, a.scale}, &pb);
+        if (rc == OMR_ERR_NOTIMPL || rc == OMR_ERR_BADARG || rc == OMR_ERR_ASSERT) {  // a sweep the batch context cannot plan
+            clear_error();
+            return OMR_OK;
+        }
+        if (rc) return rc;
+        if (canvases && !pb->dk.count()) return OMR_OK;  // a canvas the warp's tables cannot hold
+        b->how = FlowBucket::RUN, b->chunk = canvases ? kDeskewChunk : kAnglesChunk;
+        b->canvas_rows = pb->dk.rows, b->canvas_cols = pb->dk.cols, b->out_step = (int64_t)pb->dk.cols * cn;
+        b->ctx = pb;
+        return OMR_OK;
+    };
+    f.run = [a](const FlowBucket &b, const FlowSlots &s, double *ang, int32_t *best, int32_t *, int32_t *size) -> int {
+        omr_projection_batch *pb = static_cast<omr_projection_batch *>(b.ctx.get());
+        return s.dout ? omr_projection_batch_deskew_device(pb, s.din, s.in_stride, s.row, s.z, a.interp, a.border, s.dout, s.out_stride,
+                                                           s.out_step, size, ang, best)
+                      : omr_projection_batch_run_device(pb, s.din, s.in_stride, s.row, s.z, ang, best, nullptr, nullptr);
+    };
+    f.per_sheet = [a](const FlowIn &in, const std::vector<int> &idx, const FlowOut &r) -> int {
+        return in.streams ? streams_per_call(a, in, idx, r) : host_per_call(a, in.imgs, idx, r);
+    };
+    return f;
+}
+
+// both host forms
 int host_form(const omr_image *srcs, int n, uint16_t max_angle, double step, double scale, double *angles, int32_t *best_idx,
               omr_image_owned *rotated, int interp, const uint8_t *border)
 {
     int N = 0;
     if (candidate_count(max_angle, step, &N) <= 0)
         return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
-    ShapeBuckets b;
-    // omr_get_angle_with_projections' checks, for every image before any device work
-    int rc = bucket_by_shape(srcs, n, [&](const omr_image &im) -> int {
+    FlowSink sink;
+    if (rotated) sink.kind = FlowSink::CANVASES;
+    FlowOut to;
+    to.angle = angles, to.extra = best_idx, to.rotated = rotated;
+    return flow_host_call(projection_flow(Sweep{max_angle, step, scale, N, interp, border}), sink, srcs, n, to);
+}
+
+// omr_deskew_with_projections_batch_streams and its PNG and TIFF forms: `out` receives the streams
+// of any kind
+int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, uint16_t max_angle, double step,
+                   double scale, int32_t interp, const uint8_t *border, const OutFormat &fmt, double *angles, int32_t *best_idx,
+                   int32_t *scan_rc, uint8_t **out, int64_t *out_len)
+{
+    clear_error();
+    if (int r = fmt.check_params(channels == 1 ? 1 : 3)) return r;  // a bad channel count has its own refusal below
+    if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
+    if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
+    if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
+    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "channels must be 1 or 3, got %d", channels);
+    if (int r = flow_check_streams(streams, len, n)) return r;
+    int N = 0;
+    if (candidate_count(max_angle, step, &N) <= 0)
+        return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
+    if (!isfinite(scale) || scale <= 0.0) return fail(OMR_ERR_BADARG, "resize_scale must be finite and positive");
+    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
+        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
+    FlowSink sink;
+    if (out) sink.kind = FlowSink::STREAMS, sink.fmt = fmt;
+    FlowOut to;
+    to.angle = angles, to.extra = best_idx, to.code = scan_rc, to.out = out, to.out_len = out_len;
+    // a sheet its decoder refuses, or for which the per-call function would fail, keeps its code (imread turns a JPEG by its
+    // EXIF orientation: the scan's shape is the turned one)
+    const auto parse = [channels, scale](ImreadRun &run, const uint8_t *stream, int64_t l) {
+        ImreadParsed ps = run.append(stream, l, channels, false);
         Working w;
-        int rc = check_image(&im, cn_gray_source);
-        return rc ? rc : working_size(im.rows, im.cols, scale, &w);
-    }, &b);
-    if (rc || (rc = have_device())) return rc;
-    int dev = 0;
-    OMR_HIP(hipGetDevice(&dev));
-    std::vector<double> ang((size_t)n);
-    std::vector<int32_t> best((size_t)n);
-    std::vector<omr_image_owned> rot(rotated ? (size_t)n : 0, omr_image_owned{nullptr, 0, 0, 0, 0});
-    HostArgs a{srcs, max_angle, step, scale, N, ang.data(), best.data(), dev};
-    a.rotated = rotated ? rot.data() : nullptr, a.interp = interp, a.border = border;
-    for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++)
-        rc = host_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.shapes[k].cn, b.members[k]);
-    if (rc) {
-        for (auto &o : rot) omr_image_free(&o);
-        return rc;
-    }
-    memcpy(angles, ang.data(), sizeof(double) * (size_t)n);
-    if (best_idx) memcpy(best_idx, best.data(), sizeof(int32_t) * (size_t)n);
-    if (rotated) memcpy(rotated, rot.data(), sizeof(omr_image_owned) * (size_t)n);
-    return OMR_OK;
+        if (!ps.rc) ps.rc = working_size(ps.rows, ps.cols, scale, &w);
+        return ps;
+    };
+    return flow_streams_call(projection_flow(Sweep{max_angle, step, scale, N, interp, border, channels, fmt}), sink, streams, len, n,
+                             channels, parse, to);
 }
 
 }  // namespace
@@ -507,218 +561,6 @@ int omr_deskew_with_projections_batch(const omr_image *srcs, int32_t n, uint16_t
         return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
     return host_form(srcs, n, max_angle, step, resize_scale, angles, best_idx, rotated, interp, border_value);
 }
-
-}  // extern "C"
-
-namespace {
-
-// ---- the streams form: file contents in, file contents out --------------------------------------
-// Everything is indexed by the accepted sheets (those whose header parsed and whose working size exists), in call order.
-struct StreamArgs {
-    const uint8_t *const *streams;
-    const int64_t *len;
-    ImreadHeaders hd;  // sheet k's header stands in the array of its kind, hd.kind[k]
-    int cn;
-    uint16_t max_angle;
-    double step, scale;
-    int N;
-    int interp;
-    const uint8_t *border;
-    OutFormat fmt;  // what writes the canvases
-    double *angles;
-    int32_t *best_idx, *scan_rc;
-    uint8_t **out;  // null (with out_len): the angles alone
-    int64_t *out_len;
-    int device;
-};
-
-// a code of the per-call chain that belongs to its sheet (any other ends the call)
-bool sheet_code(int rc) { return rc == OMR_ERR_ASSERT || rc == OMR_ERR_BADARG || rc == OMR_ERR_NOTIMPL; }
-
-// the per-call chain, sheet by sheet: the buckets a batch context does not take
-int streams_per_call(const StreamArgs &a, const std::vector<int> &idx)
-{
-    for (int k : idx) {
-        omr_image_owned img{nullptr, 0, 0, 0, 0}, rot{nullptr, 0, 0, 0, 0};
-        uint8_t *bytes = nullptr;
-        int64_t cap = 0, used = 0;
-        int rc = omr_imread(a.streams[k], a.len[k], a.cn, 0, &img);
-        const omr_image view{img.data, img.rows, img.cols, img.channels, img.step_bytes};
-        if (!rc) rc = omr_get_angle_with_projections(&view, a.max_angle, a.step, a.scale, 1, &a.angles[k]);
-        if (!rc && a.out) {
-            rc = omr_rotate(&view, a.angles[k], 1.0, a.interp, a.border, OMR_CLIP_CONTAIN, &rot);
-            if (!rc) rc = a.fmt.bound(rot.rows, rot.cols, rot.channels, &cap);
-            if (!rc && !(bytes = (uint8_t *)malloc((size_t)cap))) rc = fail(OMR_ERR_NOMEM, "out of host memory");
-            const omr_image canvas{rot.data, rot.rows, rot.cols, rot.channels, rot.step_bytes};
-            if (!rc) rc = a.fmt.encode_host(&canvas, bytes, cap, &used);
-        }
-        omr_image_free(&img);
-        omr_image_free(&rot);
-        if (rc) {
-            free(bytes);
-            if (!sheet_code(rc)) return rc;
-            a.scan_rc[k] = rc, a.angles[k] = 0.0, a.best_idx[k] = -1;
-            continue;
-        }
-        a.best_idx[k] = (int32_t)llround(a.angles[k] / a.step) + a.N;
-        if (a.out) {
-            uint8_t *fit = (uint8_t *)realloc(bytes, (size_t)std::max<int64_t>(used, 1));  // the bound is several times the stream
-            a.out[k] = fit ? fit : bytes, a.out_len[k] = used;
-        }
-    }
-    clear_error();
-    return OMR_OK;
-}
-
-int streams_bucket(const StreamArgs &a, int rows, int cols, const std::vector<int> &idx)
-{
-    const int cn = a.cn;
-    std::shared_ptr<omr_projection_batch> pbp;
-    int rc = cached_context(CtxKey{a.device, rows, cols, cn, a.max_angle, a.step, a.scale}, &pbp);
-    if (rc == OMR_ERR_NOTIMPL || rc == OMR_ERR_BADARG || rc == OMR_ERR_ASSERT) {  // a sweep the batch context cannot plan
-        clear_error();
-        return streams_per_call(a, idx);
-    }
-    if (rc) return rc;
-    omr_projection_batch *pb = pbp.get();
-    if (a.out && !pb->dk.count()) return streams_per_call(a, idx);  // a canvas the warp's tables cannot hold
-    const int m = (int)idx.size(), zmax = std::min(m, a.out ? kDeskewChunk : kChunk);
-    const int64_t row = (int64_t)cols * cn, in_stride = (row * rows + 255) & ~(int64_t)255;
-    const int64_t out_step = (int64_t)pb->dk.cols * cn, out_stride = out_step * pb->dk.rows;
-    LeasedStream st;  // the batch's device buffers come from the block cache and return to it when the call ends
-    if ((rc = st.create())) return rc;
-    DevBuf din, dout;
-    OMR_HIP(din.alloc((size_t)zmax * in_stride));
-    if (a.out) OMR_HIP(dout.alloc((size_t)zmax * out_stride));
-    std::vector<double> ang((size_t)zmax);
-    std::vector<int32_t> best((size_t)zmax), size(2 * (size_t)zmax);
-    ImreadChunk ck;
-    for (int j0 = 0; j0 < m; j0 += zmax) {
-        const int z = std::min(zmax, m - j0);
-        // the chunk's streams -> the scan slots, decoded on the device; a bucket may hold both kinds: each decoder fills
-        // its own members' slots and skips the other's
-        // (JPEG members that imread turns -- the bucket's shape is their turned one -- go through a scratch buffer of the
-        // chunk, which one launch turns into their slots)
-        ck.gather(a.hd, a.streams, a.len, idx, j0, z);
-        if ((rc = imread_decode_device(ck.zs.data(), ck.zlen.data(), ck.hd.view(), nullptr, z, cn, false, din.as<uint8_t>(), in_stride, row, ck.zrc.data(), st.s)))
-            return rc;
-        rc = a.out ? omr_projection_batch_deskew_device(pb, din.as<uint8_t>(), in_stride, row, z, a.interp, a.border, dout.as<uint8_t>(),
-                                                        out_stride, out_step, size.data(), ang.data(), best.data())
-                   : omr_projection_batch_run_device(pb, din.as<uint8_t>(), in_stride, row, z, ang.data(), best.data(), nullptr, nullptr);
-        if (rc) return rc;
-        for (int j = 0; j < z; j++) {
-            const int k = idx[(size_t)(j0 + j)];
-            if (ck.zrc[(size_t)j]) {  // damaged image data: the slot's content means nothing; its code and no output
-                a.scan_rc[k] = ck.zrc[(size_t)j], a.angles[k] = 0.0, a.best_idx[k] = -1;
-                size[2 * (size_t)j] = size[2 * (size_t)j + 1] = 0;
-            } else {
-                a.angles[k] = ang[(size_t)j], a.best_idx[k] = best[(size_t)j];
-            }
-        }
-        if (!a.out) continue;
-        // the canvases stay on the device: encoded there, only the streams come down
-        StreamSink sink(a.out, a.out_len, idx, j0);
-        if ((rc = a.fmt.encode_device(dout.as<uint8_t>(), out_stride, out_step, cn, size.data(), z, sink, st.s))) return rc;
-    }
-    return OMR_OK;
-}
-
-// omr_deskew_with_projections_batch_streams and its PNG and TIFF forms: `out` receives the streams of any kind
-int deskew_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels, uint16_t max_angle, double step,
-                   double scale, int32_t interp, const uint8_t *border, const OutFormat &fmt, double *angles, int32_t *best_idx,
-                   int32_t *scan_rc, uint8_t **out, int64_t *out_len)
-{
-    clear_error();
-    if (int r = fmt.check_params(channels == 1 ? 1 : 3)) return r;  // a bad channel count has its own refusal below
-    if (!streams || !len || n < 1 || !angles || !scan_rc) return fail(OMR_ERR_BADARG, "bad batch arguments");
-    if (!out != !out_len) return fail(OMR_ERR_BADARG, "the streams and their lengths are returned together, or neither");
-    if (out && !border) return fail(OMR_ERR_BADARG, "null border_value");
-    if (channels != 1 && channels != 3) return fail(OMR_ERR_BADARG, "channels must be 1 or 3, got %d", channels);
-    for (int i = 0; i < n; i++)
-        if (!streams[i] || len[i] < 0) return fail(OMR_ERR_BADARG, "streams[%d] is null or has a negative length", i);
-    int N = 0;
-    if (candidate_count(max_angle, step, &N) <= 0)
-        return fail(OMR_ERR_BADARG, "empty candidate range (the reference indexes [0] and panics)");
-    if (!isfinite(scale) || scale <= 0.0) return fail(OMR_ERR_BADARG, "resize_scale must be finite and positive");
-    if (interp != OMR_INTER_NEAREST && interp != OMR_INTER_LINEAR)
-        return fail(OMR_ERR_NOTIMPL, "interpolation flag %d is not implemented", interp);
-    // the headers, on the host: a sheet its decoder refuses, or for which the per-call function would fail, keeps its
-    // code and leaves the batch here
-    std::vector<int32_t> code((size_t)n, OMR_OK);
-    ImreadRun run;
-    std::vector<int> at;
-    std::vector<omr_image> views;
-    std::vector<const uint8_t *> zs;
-    std::vector<int64_t> zlen;
-    run.reserve((size_t)n);
-    for (int i = 0; i < n; i++) {
-        // imread turns a JPEG by its EXIF orientation: the scan's shape is the turned one
-        const ImreadParsed ps = run.append(streams[i], len[i], channels, false);
-        int rc = ps.rc;
-        const int rows = ps.rows, cols = ps.cols;
-        Working w;
-        if (!rc) rc = working_size(rows, cols, scale, &w);
-        if ((code[(size_t)i] = rc)) {
-            run.drop_last();
-            continue;
-        }
-        at.push_back(i), zs.push_back(streams[i]), zlen.push_back(len[i]);
-        views.push_back(omr_image{streams[i], rows, cols, channels, (int64_t)cols * channels});
-    }
-    clear_error();
-    const int g = (int)at.size();
-    std::vector<double> ang((size_t)g, 0.0);
-    std::vector<int32_t> best((size_t)g, -1), src((size_t)g, OMR_OK);
-    std::vector<uint8_t *> bytes((size_t)g, nullptr);
-    std::vector<int64_t> bytes_len((size_t)g, 0);
-    int rc = OMR_OK;
-    if (g) {
-        ShapeBuckets b;
-        if ((rc = bucket_by_shape(views.data(), g, [](const omr_image &) { return (int)OMR_OK; }, &b))) return rc;
-        if (out) {  // the encoders' offsets inside an image are 32-bit: a shape whose canvas slot could exceed them refuses the
-                    // call, before any device work (a shape without a canvas goes sheet by sheet)
-            const int A = candidate_count(max_angle, step, nullptr);
-            std::vector<double> cand((size_t)A);
-            for (int i = 0; i < A; i++) cand[(size_t)i] = (double)(i - N) * step;
-            for (const ImageShape &sh : b.shapes) {
-                DeskewTables dk;
-                if (dk.plan(sh.rows, sh.cols, cand.data(), A)) {
-                    clear_error();
-                    continue;
-                }
-                if ((rc = fmt.check_canvas(dk.rows, dk.cols, sh.cn))) return rc;
-            }
-        }
-        if ((rc = have_device())) return rc;
-        int dev = 0;
-        OMR_HIP(hipGetDevice(&dev));
-        StreamArgs a{zs.data(), zlen.data(), run.view(), channels, max_angle, step, scale, N, interp,
-                     border, fmt, ang.data(), best.data(), src.data(), out ? bytes.data() : nullptr,
-                     out ? bytes_len.data() : nullptr, dev};
-        for (size_t k = 0; k < b.shapes.size() && rc == OMR_OK; k++) rc = streams_bucket(a, b.shapes[k].rows, b.shapes[k].cols, b.members[k]);
-        if (rc) {
-            for (uint8_t *p : bytes) free(p);
-            return rc;
-        }
-    }
-    // every sheet is decided: the caller's arrays are written only now
-    for (int i = 0; i < n; i++) {
-        angles[i] = 0.0, scan_rc[i] = code[(size_t)i];
-        if (best_idx) best_idx[i] = -1;
-        if (out) out[i] = nullptr, out_len[i] = 0;
-    }
-    for (int k = 0; k < g; k++) {
-        const int i = at[(size_t)k];
-        angles[i] = ang[(size_t)k], scan_rc[i] = src[(size_t)k];
-        if (best_idx) best_idx[i] = best[(size_t)k];
-        if (out) out[i] = bytes[(size_t)k], out_len[i] = bytes_len[(size_t)k];
-    }
-    return OMR_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int omr_deskew_with_projections_batch_streams(const uint8_t *const *streams, const int64_t *len, int32_t n, int32_t channels,
                                               uint16_t max_angle, double step, double resize_scale, int32_t interp,

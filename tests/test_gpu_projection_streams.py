@@ -157,7 +157,7 @@ def test_gray_channel_form_and_the_angles_alone():
 
 
 def _deskew_chunk():
-    src = open(os.path.join(ROOT, "omr-img-corrector_amd", "csrc", "projection_batch.cpp")).read()
+    src = open(os.path.join(ROOT, "omr-img-corrector_amd", "csrc", "flow_frame.hpp")).read()
     return int(re.search(r"const int kDeskewChunk = (\d+);", src).group(1))
 
 

@@ -96,7 +96,7 @@ def legs(streams, channels):
 
 
 def deskew_chunk():
-    src = open(os.path.join(ROOT, "omr-img-corrector_amd", "csrc", "projection_batch.cpp")).read()
+    src = open(os.path.join(ROOT, "omr-img-corrector_amd", "csrc", "flow_frame.hpp")).read()
     return int(re.search(r"const int kDeskewChunk = (\d+);", src).group(1))
 
 
