@@ -6,7 +6,7 @@
 //   sweep       the context's omr_batch_ctx at the resize scale (quirk B4), black_max 127 (omr.rs:129-139); the scores
 //               go to the host, where omr_select_projection_result decides every sheet (omr.rs:147-221)
 //   Hough       only the sheets that are not Believed: one batched Canny + HoughLinesP pass on a gather of their
-//               colour sheets, then line_angles -> vote_counts -> select_omr_rs and the omr.rs:351-399 decision per sheet
+//               colour sheets with its omr.rs vote (edges_detection_device), then the omr.rs:351-399 decision per sheet
 //   warp        the batch colour warp (deskew.hip) with a per-call candidate set made of the decided angles: NEAREST,
 //               white border, CONTAIN, scale 1.  The Believed sheets' warp runs on a stream of its own while the Hough
 //               pass runs.
@@ -246,9 +246,7 @@ int run_locked(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_strid
     // 4. Hough on a gather of the other sheets (packed, at most kChunk at a time), omr.rs:351-399 per sheet
     if (!rest.empty()) {
         const int64_t row = (int64_t)cb->cols * cb->cn, gstride = row * cb->rows;
-        HoughParams hp;
-        hp.min_line_length = cb->hough_min;
-        hp.max_line_gap = cb->hough_gap;
+        const HoughParams hp = hough_params(cb->hough_min, cb->hough_gap);
         std::vector<int> decided;
         for (size_t j0 = 0; j0 < rest.size(); j0 += kChunk) {
             const int m = (int)std::min(rest.size() - j0, (size_t)kChunk);
@@ -257,46 +255,29 @@ int run_locked(omr_correct_batch *cb, const uint8_t *d_scans, int64_t scan_strid
                 OMR_HIP(hipMemcpy2DAsync(cb->gather.as<uint8_t>() + (size_t)j * gstride, (size_t)row,
                                          d_scans + (size_t)rest[j0 + j] * scan_stride, (size_t)step, (size_t)row, (size_t)cb->rows,
                                          hipMemcpyDeviceToDevice, cb->s));
-            std::vector<std::vector<int32_t>> lines;
-            std::vector<int> sheet_rc((size_t)m, OMR_OK);
-            {
-                PoolScope scratch(cb->s);  // the pass's own buffers come from the block cache
-                rc = edges_lines_device(cb->gather.as<uint8_t>(), gstride, row, cb->rows, cb->cols, cb->cn, m, hp, cb->s, &lines);
-                if (rc == OMR_ERR_NOMEM) {  // a sheet with more segments than the buffer holds: the per-call function fails on that
-                    lines.assign((size_t)m, {});  // sheet alone, so the chunk is redone sheet by sheet
-                    for (int j = 0; j < m; j++) {
-                        std::vector<std::vector<int32_t>> one;
-                        const int r1 = edges_lines_device(cb->gather.as<uint8_t>() + (size_t)j * gstride, gstride, row, cb->rows,
-                                                          cb->cols, cb->cn, 1, hp, cb->s, &one);
-                        if (r1 == OMR_ERR_NOMEM) sheet_rc[(size_t)j] = r1;
-                        else if (r1) return r1;
-                        else lines[(size_t)j] = std::move(one[0]);
-                    }
-                    rc = OMR_OK;
+            std::vector<double> ea((size_t)m);
+            std::vector<int32_t> nl((size_t)m), sheet_rc((size_t)m, OMR_OK);
+            uint8_t *g = cb->gather.as<uint8_t>();
+            // the pass's own buffers come from the block cache: edges_detection_device holds a PoolScope on cb->s
+            rc = edges_detection_device(g, m, gstride, row, cb->rows, cb->cols, cb->cn, hp, ea.data(), nullptr, nl.data(), cb->s);
+            if (rc == OMR_ERR_NOMEM)  // a sheet with more segments than the buffer holds: the per-call function fails on that
+                for (int j = 0; j < m; j++) {  // sheet alone, so the chunk is redone sheet by sheet, the same stages with n = 1
+                    rc = edges_detection_device(g + (size_t)j * gstride, 1, gstride, row, cb->rows, cb->cols, cb->cn, hp, &ea[(size_t)j],
+                                                nullptr, &nl[(size_t)j], cb->s);
+                    if (rc == OMR_ERR_NOMEM) sheet_rc[(size_t)j] = rc, rc = OMR_OK;
+                    if (rc) return rc;
                 }
-                if (rc) return rc;
-            }
+            if (rc) return rc;
             for (int j = 0; j < m; j++) {
                 const int i = rest[j0 + j];
-                std::vector<float> ang;
-                std::vector<int32_t> cnt;
-                double ea = 0;
-                int32_t est = 0, en = 0;
-                if (sheet_rc[(size_t)j] == OMR_OK) {
-                    line_angles(lines[(size_t)j], &ang);
-                    {
-                        PoolScope scratch(cb->s);
-                        if ((rc = vote_counts(ang, true, cb->s, &cnt))) return rc;
-                    }
-                    sheet_rc[(size_t)j] = select_omr_rs(ang, cnt, &ea, &est, nullptr, 0, &en);  // no segment: -215 (quirk B11)
-                }
+                if (sheet_rc[(size_t)j] == OMR_OK && nl[(size_t)j] == 0) sheet_rc[(size_t)j] = OMR_ERR_ASSERT;  // no segment: -215 (quirk B11)
                 if (sheet_rc[(size_t)j] != OMR_OK) {
                     scan_rc[i] = sheet_rc[(size_t)j];
                     rotate_angle[i] = 0.0;
                     need_check[i] = 0;
                     continue;
                 }
-                omr_correct_default_decision(pa[i], pst[i], &pc[(size_t)i * (A + 1)], std::min<int32_t>(pn[i], A + 1), ea,
+                omr_correct_default_decision(pa[i], pst[i], &pc[(size_t)i * (A + 1)], std::min<int32_t>(pn[i], A + 1), ea[(size_t)j],
                                              &rotate_angle[i], &need_check[i]);
                 decided.push_back(i);
             }

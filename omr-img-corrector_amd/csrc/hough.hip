@@ -897,55 +897,28 @@ hipError_t launch_ppht(const PphtArgs &a, int in_flight, hipStream_t s)
 }
 
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void angle_votes_kernel(const float *__restrict__ ang, int n, int as_f64,
-                                                          int32_t *__restrict__ counts)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float ai = ang[i];
-    int c = 0;
-    if (as_f64) {
-        const double di = (double)ai;
-        for (int j = 0; j < n; j++) c += fabs(di - (double)ang[j]) < 0.1;
-    } else {
-        for (int j = 0; j < n; j++) c += fabsf(__fsub_rn(ai, ang[j])) < 0.1f;
-    }
-    counts[i] = c;
-}
-
+// omr.rs:278-284 per scan: counts[o + i] = #{ j : |a_i - a_j| < 0.1 } in f64 on the widened f32 angles of scan
+// blockIdx.y, which owns [off[y], off[y + 1]) of the flat lists; a thread per angle
 __global__ __launch_bounds__(256) void angle_votes_batch_kernel(const float *__restrict__ ang,
-                                                                const int64_t *__restrict__ off, int as_f64,
+                                                                const int32_t *__restrict__ off,
                                                                 int32_t *__restrict__ counts)
 {
-    const int64_t o = off[blockIdx.y];
-    const int n = (int)(off[blockIdx.y + 1] - o);
+    const int o = off[blockIdx.y];
+    const int n = off[blockIdx.y + 1] - o;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float *a = ang + o;
-    const float ai = a[i];
+    const double di = (double)a[i];
     int c = 0;
-    if (as_f64) {
-        const double di = (double)ai;
-        for (int j = 0; j < n; j++) c += fabs(di - (double)a[j]) < 0.1;
-    } else {
-        for (int j = 0; j < n; j++) c += fabsf(__fsub_rn(ai, a[j])) < 0.1f;
-    }
+    for (int j = 0; j < n; j++) c += fabs(di - (double)a[j]) < 0.1;
     counts[o + i] = c;
 }
 
-hipError_t launch_angle_votes_batch(const float *d_angles, const int64_t *d_off, int n_scans, int max_n, int as_f64,
-                                    int32_t *d_counts, hipStream_t s)
+hipError_t launch_angle_votes_batch(const float *d_angles, const int32_t *d_off, int n_scans, int max_n, int32_t *d_counts,
+                                    hipStream_t s)
 {
     if (n_scans <= 0 || max_n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(angle_votes_batch_kernel, dim3((max_n + 255) / 256, n_scans), dim3(256), 0, s, d_angles, d_off,
-                       as_f64, d_counts);
-    return hipGetLastError();
-}
-
-hipError_t launch_angle_votes(const float *d_angles, int n, int as_f64, int32_t *d_counts, hipStream_t s)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(angle_votes_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_angles, n, as_f64, d_counts);
+    hipLaunchKernelGGL(angle_votes_batch_kernel, dim3((max_n + 255) / 256, n_scans), dim3(256), 0, s, d_angles, d_off, d_counts);
     return hipGetLastError();
 }
 

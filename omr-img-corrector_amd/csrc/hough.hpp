@@ -72,14 +72,12 @@ hipError_t launch_ppht(const PphtArgs &a, int in_flight, hipStream_t s);
 hipError_t debug_ppht_stamps(unsigned long long out[12], bool reset);
 #endif
 
-// counts[i] = #{ j : |a[i] - a[j]| < 0.1 } in f32 (hough.rs:77-83) or in f64 on widened values
-// (omr.rs:278-284)
-hipError_t launch_angle_votes(const float *d_angles, int n, int as_f64, int32_t *d_counts, hipStream_t s);
-// the same for a batch: scan k owns angles / counts [off[k], off[k + 1]); max_n = the longest list
-hipError_t launch_angle_votes_batch(const float *d_angles, const int64_t *d_off, int n_scans, int max_n, int as_f64,
-                                    int32_t *d_counts, hipStream_t s);
+// omr.rs:278-284 per scan: counts[i] = #{ j of i's scan : |a[i] - a[j]| < 0.1 } in f64 on the widened f32 angles; scan k
+// owns angles / counts [off[k], off[k + 1]) (d_off below), max_n = the longest list
+hipError_t launch_angle_votes_batch(const float *d_angles, const int32_t *d_off, int n_scans, int max_n, int32_t *d_counts,
+                                    hipStream_t s);
 
-// ---- a batch's segments stay on the device (omr_hough_angles_batch_device)
+// ---- the segments stay on the device for the votes and the line pictures
 // d_off[0 .. n] = exclusive scan of min(n_lines[i], cap) -- with d_packed below the form lined.hip and the vote take.
 // d_flag (two words, zeroed by the caller): [0] = the largest count that exceeds cap, [1] = 1 when the total leaves the
 // 32-bit range.

@@ -1,9 +1,8 @@
-// hough_host.hpp -- host-side building blocks of the Hough-line path (oics_hough.cpp), shared with
-// the FFT path (oics_fft.cpp), which ends in the same Canny -> HoughLinesP -> vote chain.
+// hough_host.hpp -- the host-side stages of the Hough-line path (oics_hough.cpp), shared with the FFT path
+// (oics_fft.cpp) and correct_default's batches (correct_batch.cpp).  One chain serves every entry point, per call (n = 1
+// on an uploaded image) and per batch:  Canny -> segments (BatchSegments) -> vote -> line pictures.
 #pragma once
 #include <stdint.h>
-
-#include <math.h>
 
 #include <algorithm>
 #include <memory>
@@ -12,11 +11,10 @@
 
 #include "../../include/omrdeskew.h"
 #include "engine.hpp"
+#include "hough_select.hpp"  // line_angles, select_omr_rs, select_fft_rs: the pure host rules
 
 namespace omr {
 namespace hh {
-
-constexpr double kPi = 3.14159265358979323846;
 
 struct HoughParams {
     double low = 50.0, high = 150.0;  // hough.rs:27, omr.rs:239
@@ -24,56 +22,19 @@ struct HoughParams {
     int threshold = 0;
     double min_line_length = 0, max_line_gap = 0;
 };
+inline HoughParams hough_params(double min_line_length, double max_line_gap)
+{
+    HoughParams hp;
+    hp.min_line_length = min_line_length, hp.max_line_gap = max_line_gap;
+    return hp;
+}
 
 // a host image into a fresh packed device buffer
 int upload(const omr_image *im, DevBuf *buf, hipStream_t s);
 // Canny on n device-resident scans of one shape -> d_map holds the edges (0 / 255), packed;
-// d_rowcnt (n x rows) receives the edge pixels per row (what ppht_device starts from)
+// d_rowcnt (n x rows) receives the edge pixels per row (what segments_from_edges starts from)
 int canny_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int rows, int cols, int cn, int n, double low_t,
                  double high_t, uint8_t *d_map, int *d_flag, hipStream_t s, int32_t *d_rowcnt);
-// HoughLinesP on n device-resident edge images (packed)
-int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, const HoughParams &hp, hipStream_t s,
-                std::vector<std::vector<int32_t>> *lines_out);
-// keep_edges (may be null): receives a copy of the edge maps, which HoughLinesP consumes
-int edges_lines_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int rows, int cols, int cn, int n,
-                       const HoughParams &hp, hipStream_t s, std::vector<std::vector<int32_t>> *lines,
-                       DevBuf *keep_edges = nullptr);
-// the detectors' line picture (lined.hip): GRAY2BGR of a packed device edge map with `n_lines` host segments
-// (x0, y0, x1, y1) drawn on in list order, as a fresh host image; synchronises `s`
-extern const uint8_t kLinedBgr[3];
-int lined_to_host(const uint8_t *d_edges, int rows, int cols, const int32_t *lines, int n_lines, const uint8_t bgr[3],
-                  hipStream_t s, omr_image_owned *picture);
-void line_angles(const std::vector<int32_t> &l, std::vector<float> *ang);
-int vote_counts(const std::vector<float> &ang, bool as_f64, hipStream_t s, std::vector<int32_t> *counts);
-int select_omr_rs(const std::vector<float> &ang, const std::vector<int32_t> &cnt, double *angle, int32_t *status,
-                  double *candidates, int32_t cand_cap, int32_t *cand_len);
-
-// fft.rs:197-247 on n segments (x1, y1, x2, y2): f64 angles (libm atan2) folded into [-45, 45]; the inner loop re-reads
-// line i (quirk B10, fft.rs:231), so line i collects n - 1 votes iff its raw angle is within 0.1 of its folded angle,
-// else none.  No segment, or no line with a vote: 0.0.  The one statement of the rule, for the per-call and batch forms
-inline void select_fft_rs(const int32_t *l, int n, double *angle_out)
-{
-    double average_angle = 0.0;
-    int max_votes = 0;
-    for (int i = 0; i < n; i++) {
-        const double x1 = l[4 * i], y1 = l[4 * i + 1], x2 = l[4 * i + 2], y2 = l[4 * i + 3];
-        const double raw = (atan2(y2 - y1, x2 - x1) * 180.0) / kPi;
-        const double angle = raw < -45.0 ? raw + 90.0 : (raw > 45.0 ? raw - 90.0 : raw);
-        int votes = 0;
-        for (int j = 0; j < n; j++) {
-            if (i == j) continue;
-            if (fabs(raw - angle) < 0.1) votes++;
-        }
-        if (votes > max_votes) {
-            max_votes = votes;
-            average_angle = angle;
-        }
-        if (max_votes == n - 1 && n > 1) break;  // nothing can beat n - 1 with a strict '>'
-    }
-    *angle_out = average_angle;
-}
-
-// ---- the batch forms' shared stages (oics_hough.cpp)
 
 // fn(lo, hi) over [0, count) in contiguous pieces on a few host threads (the caller's alone for a small count)
 template <class Fn>
@@ -93,30 +54,59 @@ void host_fan_out(size_t count, size_t min_piece, Fn fn)
 int hough_batch_check(const void *d_scans, int n, int64_t stride, int rows, int cols, int cn, int64_t step, bool have_outputs,
                       const void *d_lined, int64_t lstride, int64_t lstep);
 
-// What the segment stage of a batch leaves: Canny and HoughLinesP of n scans of one shape, the segments packed in scan
-// order -- scan i owns segments off[i] .. off[i + 1] -- on the device (d_packed: null when the batch has no segment at
-// all) and on the host (lines, four ints a segment).  edges: the edge maps as Canny left them (packed n x rows x cols),
-// copied before HoughLinesP erased the points it used; filled only when asked for
+// HoughLinesP's output, the only form it has: the segments of n scans of one shape packed in scan order -- scan i owns
+// segments off[i] .. off[i + 1] -- on the device (d_off; d_packed: null when there is no segment at all) and on the host
+// (off, lines: four ints a segment).  edges: the edge maps as Canny left them (packed n x rows x cols), copied before
+// HoughLinesP erased the points it used; filled only when asked for
 struct BatchSegments {
     DevBuf edges, d_off, d_packed;
     std::vector<int32_t> off, lines;
+    int scans() const { return (int)off.size() - 1; }
     size_t total() const { return (size_t)off.back(); }
     int count(int i) const { return off[(size_t)i + 1] - off[(size_t)i]; }
+    int max_count() const
+    {
+        int m = 0;
+        for (int i = 0; i < scans(); i++) m = std::max(m, count(i));
+        return m;
+    }
 };
-// arguments already checked.  Synchronises `s` on success.  The caller holds a PoolScope on `s` (or drains `s` itself
-// before it lets go of `seg`): the stage's own buffers go back on every return, and it is the block cache's drain of
-// their stream that keeps an error return from freeing what queued work still uses.
+// The segment stage.  segments_from_edges: HoughLinesP on n packed device edge images (consumed; d_rowcnt as Canny or
+// launch_edges_rowcount filled it) -> slots -> offsets -> packed list, two downloads.  batch_segments_device: Canny,
+// the kept edges, then that.  A scan whose segments exceed its slot fails the call with OMR_ERR_NOMEM.
+// Arguments already checked.  Both synchronise `s` on success.  The caller holds a PoolScope on `s` (a LeasedStream
+// carries one) or drains `s` itself before it lets go of `seg`: the stage's own buffers go back on every return, and it
+// is the block cache's drain of their stream that keeps an error return from freeing what queued work still uses.
+int segments_from_edges(uint8_t *d_edges, int32_t *d_rowcnt, int n, int rows, int cols, const HoughParams &hp, hipStream_t s,
+                        BatchSegments *seg);
 int batch_segments_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
                           const HoughParams &hp, bool keep_edges, hipStream_t s, BatchSegments *seg);
-// the line pictures of n packed edge maps (lined.hip); arguments already checked, a null d_lines only with no segment.
+
+// The vote stage of omr.rs (:257-284): the f32 angles of the whole packed list (host threads, libm) and per angle the
+// f64 count of its scan's angles within 0.1, one launch indexed by seg.d_off.  Synchronises `s`.  (hough.rs's vote is
+// vote_select_kernel alone, fft.rs's is select_fft_rs.)
+int omr_rs_votes(const BatchSegments &seg, hipStream_t s, std::vector<float> *ang, std::vector<int32_t> *cnt);
+// omr.rs:231-302 for n device-resident scans of one shape: segments, votes, select_omr_rs per scan; a scan without a
+// segment reports 0.0 and OMR_STATUS_NOT_A_RESULT.  status, n_lines and the candidate outputs -- scan 0's -- may be null.
+// Arguments already checked.  Synchronises `s`
+int edges_detection_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
+                           const HoughParams &hp, double *angles, int32_t *status, int32_t *n_lines, hipStream_t s,
+                           double *candidates = nullptr, int32_t cand_cap = 0, int32_t *cand_len = nullptr);
+// the per-call form: one packed scan, and no segment is the reference's panic (quirk B11), OMR_ERR_ASSERT; the outputs
+// are written on success only
+int edges_detection_one(const uint8_t *d_src, int rows, int cols, int cn, const HoughParams &hp, hipStream_t s, double *angle,
+                        int32_t *status, double *candidates, int32_t cand_cap, int32_t *cand_len);
+
+// the detectors' line pictures (lined.hip) of n packed edge maps: GRAY2BGR with picture i's device segments
+// d_lines[off[i] .. off[i + 1]) drawn on in list order; arguments already checked, a null d_lines only with no segment.
 // Synchronises `s`
+extern const uint8_t kLinedBgr[3];
 int lined_device(const uint8_t *d_edges, int n, int64_t estride, int64_t estep, int rows, int cols, const int32_t *d_lines,
                  const int32_t *off, const uint8_t bgr[3], uint8_t *d_out, int64_t ostride, int64_t ostep, hipStream_t s);
-// the body of omr_edges_detection_batch_device (omr.rs:231-302 per scan); arguments already checked.  Synchronises `s`
-int edges_detection_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
-                           const HoughParams &hp, double *angles, int32_t *status, int32_t *n_lines, hipStream_t s);
-// pictures (packed, `pic` bytes each, rows x cols x 3) of a chunk's scans -> fresh host images lined[members[j0 + j]], from
-// several threads, one staged copy each; skip[j] != 0 leaves scan j without one (skip may be null)
+// a packed device picture (rows x cols x 3) as a fresh host image, one staged copy; synchronises `s`
+int picture_to_host(const uint8_t *d_pic, int rows, int cols, hipStream_t s, omr_image_owned *picture);
+// the pictures of a chunk's scans -> lined[members[j0 + j]], from several threads; skip[j] != 0 leaves scan j without one
+// (skip may be null)
 int download_pictures(const uint8_t *d_pics, int m, int rows, int cols, const std::vector<int> &members, int j0,
                       const int32_t *skip, omr_image_owned *lined);
 

@@ -510,6 +510,29 @@ int fft_angles_device(const uint8_t *d_scans, int n, int64_t stride, int64_t ste
     return OMR_OK;
 }
 
+// omr.rs:314-330 for n device-resident colour scans of one shape: RGB2GRAY, the log spectra, Canny(weak, strong) on them
+// -> `edges` (packed n x rows x cols: the edge pictures take the gray scans' place, which the transform has read by then).
+// Arguments already checked.  Synchronises `s`, on the error returns too
+int fourier_front(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn, double weak,
+                  double strong, hipStream_t s, DevBuf *edges)
+{
+    const size_t img = (size_t)rows * cols;
+    FftWork w;
+    DevBuf logs, flag, rowcnt;
+    DrainOnExit drain{s};
+    OMR_HIP(edges->alloc((size_t)n * img));
+    for (int i = 0; i < n; i++)  // per scan: a stack of scans may exceed a launch's 65535 rows
+        OMR_HIP(launch_rgb2gray(d_scans + (int64_t)i * stride, step, rows, cols, cn, edges->as<uint8_t>() + (size_t)i * img, cols, s));
+    int rc = w.create(rows, cols, s, fft_group(n, rows, cols));
+    if (rc) return rc;
+    OMR_HIP(logs.alloc((size_t)n * img));
+    if ((rc = log_pictures(w, edges->as<uint8_t>(), n, (int64_t)img, cols, logs.as<uint8_t>(), s))) return rc;
+    OMR_HIP(flag.alloc(sizeof(int)));
+    OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
+    return canny_device(logs.as<uint8_t>(), (int64_t)img, cols, rows, cols, 1, n, weak, strong, edges->as<uint8_t>(), flag.as<int>(), s,
+                        rowcnt.as<int32_t>());
+}
+
 // one bucket of omr_get_angles_with_fft_batch: `members` index same-shape images of `grays`; at most FB_SCANS go to the
 // device at a time (6 bytes a pixel there, plus the HoughLinesP state and the FFT workspace)
 int fft_host_bucket(const omr_image *grays, const std::vector<int> &members, const HoughParams &hp, double *angles,
@@ -626,12 +649,8 @@ int omr_fft_spectrum_raw(const omr_image *gray, float *row_pass, float *magnitud
 int omr_fft_image_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows, int32_t cols,
                                int64_t step_bytes, uint8_t *d_magnitude_log, void *stream)
 {
-    clear_error();
-    if (!d_scans || !d_magnitude_log || n <= 0) return fail(OMR_ERR_BADARG, "null pointer or empty batch");
-    if (rows <= 0 || cols <= 0 || rows >= 32767 || cols >= 32767) return fail(OMR_ERR_ASSERT, "bad image shape");
-    if (step_bytes < cols) return fail(OMR_ERR_BADARG, "step_bytes too small");
-    int rc = have_device();
-    if (rc) return rc;
+    int rc = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, 1, step_bytes, d_magnitude_log != nullptr, nullptr, 0, 0);
+    if (rc || (rc = have_device())) return rc;
     hipStream_t s = (hipStream_t)stream;
     FftWork w;
     DrainOnExit drain{s};  // the workspace is released on return, error returns included
@@ -654,23 +673,17 @@ static int angle_with_fft(const omr_image *gray, double canny_threshold_1, doubl
     LeasedStream st;
     if ((rc = st.create())) return rc;
     const int rows = gray->rows, cols = gray->cols;
-    DevBuf in, m8, l8;
+    const int64_t pic = (int64_t)cols * 3 * rows;
+    DevBuf in, d_pic;
     if ((rc = upload(gray, &in, st.s))) return rc;
-    FftWork w;
-    if ((rc = w.create(rows, cols, st.s))) return rc;
-    OMR_HIP(m8.alloc((size_t)rows * cols));
-    OMR_HIP(l8.alloc((size_t)rows * cols));
-    if ((rc = w.run(in.as<uint8_t>(), cols, m8.as<uint8_t>(), l8.as<uint8_t>(), st.s))) return rc;
-    const HoughParams hp = fft_hough_params(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap);
-    std::vector<std::vector<int32_t>> lines;
-    DevBuf edges;  // the picture's background: the edges of the log spectrum as Canny left them
-    if ((rc = edges_lines_device(l8.as<uint8_t>(), 0, cols, rows, cols, 1, 1, hp, st.s, &lines, lined ? &edges : nullptr)))
+    if (lined) OMR_HIP(d_pic.alloc((size_t)pic));
+    double angle = 0.0;  // the batch body with n = 1; no segment: 0.0 and the bare edges
+    if ((rc = fft_angles_device(in.as<uint8_t>(), 1, 0, cols, rows, cols,
+                                fft_hough_params(canny_threshold_1, canny_threshold_2, min_line_length, max_line_gap), &angle, nullptr,
+                                d_pic.as<uint8_t>(), pic, (int64_t)cols * 3, st.s)))
         return rc;
-    const std::vector<int32_t> &l = lines[0];
-    const int n = (int)(l.size() / 4);
-    select_fft_rs(l.data(), n, angle_out);  // fft.rs:197-247
-    if (!lined) return OMR_OK;
-    return lined_to_host(edges.as<uint8_t>(), rows, cols, l.data(), n, kLinedBgr, st.s, lined);  // no segment: the bare edges
+    *angle_out = angle;
+    return lined ? picture_to_host(d_pic.as<uint8_t>(), rows, cols, st.s, lined) : OMR_OK;
 }
 
 int omr_get_angle_with_fft(const omr_image *gray, double canny_threshold_1, double canny_threshold_2,
@@ -751,34 +764,15 @@ int omr_get_result_from_fourier_transform(const omr_image *src, double canny_thr
     LeasedStream st;
     if ((rc = st.create())) return rc;
     const int rows = src->rows, cols = src->cols;
-    DevBuf in, gray, m8, l8, edges, flag, rowcnt;
+    DevBuf in, edges;
     if ((rc = upload(src, &in, st.s))) return rc;
-    OMR_HIP(gray.alloc((size_t)rows * cols));
-    OMR_HIP(launch_rgb2gray(in.as<uint8_t>(), (int64_t)cols * src->channels, rows, cols, src->channels, gray.as<uint8_t>(),
-                            cols, st.s));
-    FftWork w;
-    if ((rc = w.create(rows, cols, st.s))) return rc;
-    OMR_HIP(m8.alloc((size_t)rows * cols));
-    OMR_HIP(l8.alloc((size_t)rows * cols));
-    if ((rc = w.run(gray.as<uint8_t>(), cols, m8.as<uint8_t>(), l8.as<uint8_t>(), st.s))) return rc;
-    // omr.rs:323-330 Canny(weak, strong) on the log picture, then get_result_from_edges_detection on the
-    // EDGE picture: Canny(50, 150) once more (omr.rs:236-240), HoughLinesP threshold 0, the omr.rs vote
-    OMR_HIP(edges.alloc((size_t)rows * cols));
-    OMR_HIP(flag.alloc(sizeof(int)));
-    OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)rows));
-    if ((rc = canny_device(l8.as<uint8_t>(), 0, cols, rows, cols, 1, 1, canny_threshold_weak, canny_threshold_strong,
-                           edges.as<uint8_t>(), flag.as<int>(), st.s, rowcnt.as<int32_t>())))
+    // omr.rs:314-330 the front, then get_result_from_edges_detection on the EDGE picture: Canny(50, 150) once more
+    // (omr.rs:236-240), HoughLinesP threshold 0, the omr.rs vote
+    if ((rc = fourier_front(in.as<uint8_t>(), 1, 0, (int64_t)cols * src->channels, rows, cols, src->channels, canny_threshold_weak,
+                            canny_threshold_strong, st.s, &edges)))
         return rc;
-    HoughParams hp;
-    hp.min_line_length = fourier_min_line_length;
-    hp.max_line_gap = fourier_max_line_gap;
-    std::vector<std::vector<int32_t>> lines;
-    if ((rc = edges_lines_device(edges.as<uint8_t>(), 0, cols, rows, cols, 1, 1, hp, st.s, &lines))) return rc;
-    std::vector<float> ang;
-    std::vector<int32_t> cnt;
-    line_angles(lines[0], &ang);
-    if ((rc = vote_counts(ang, true, st.s, &cnt))) return rc;
-    return select_omr_rs(ang, cnt, angle, status, candidates, cand_cap, cand_len);
+    return edges_detection_one(edges.as<uint8_t>(), rows, cols, 1, hough_params(fourier_min_line_length, fourier_max_line_gap), st.s,
+                               angle, status, candidates, cand_cap, cand_len);
 }
 
 int omr_fourier_transform_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,
@@ -793,29 +787,13 @@ int omr_fourier_transform_batch_device(const uint8_t *d_scans, int32_t n, int64_
     if ((rc = have_device())) return rc;
     hipStream_t s = (hipStream_t)stream;
     PoolScope scope(s);
-    const size_t img = (size_t)rows * cols;
-    FftWork w;
-    DevBuf gray, logs, flag, rowcnt;
+    DevBuf edges;
     DrainOnExit drain{s};
-    OMR_HIP(gray.alloc((size_t)n * img));
-    for (int i = 0; i < n; i++)  // omr.rs:314 per scan (a stack of scans may exceed a launch's 65535 rows)
-        OMR_HIP(launch_rgb2gray(d_scans + (int64_t)i * scan_stride_bytes, step_bytes, rows, cols, channels,
-                                gray.as<uint8_t>() + (size_t)i * img, cols, s));
-    if ((rc = w.create(rows, cols, s, fft_group(n, rows, cols)))) return rc;
-    OMR_HIP(logs.alloc((size_t)n * img));
-    if ((rc = log_pictures(w, gray.as<uint8_t>(), n, (int64_t)img, cols, logs.as<uint8_t>(), s))) return rc;
-    // omr.rs:323-330 Canny(weak, strong) on the log pictures -- the edge pictures take the gray scans' place, which the
-    // transform has read by then -- and get_result_from_edges_detection on the EDGE pictures
-    uint8_t *edges = gray.as<uint8_t>();
-    OMR_HIP(flag.alloc(sizeof(int)));
-    OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
-    if ((rc = canny_device(logs.as<uint8_t>(), (int64_t)img, cols, rows, cols, 1, n, canny_threshold_weak, canny_threshold_strong,
-                           edges, flag.as<int>(), s, rowcnt.as<int32_t>())))
+    if ((rc = fourier_front(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels, canny_threshold_weak,
+                            canny_threshold_strong, s, &edges)))
         return rc;
-    HoughParams hp;
-    hp.min_line_length = fourier_min_line_length;
-    hp.max_line_gap = fourier_max_line_gap;
-    return edges_detection_device(edges, n, (int64_t)img, cols, rows, cols, 1, hp, angles, status, n_lines, s);
+    return edges_detection_device(edges.as<uint8_t>(), n, (int64_t)rows * cols, cols, rows, cols, 1,
+                                  hough_params(fourier_min_line_length, fourier_max_line_gap), angles, status, n_lines, s);
 }
 
 }  // extern "C"

@@ -6,17 +6,17 @@
 //   oics::omr::correct_default                   packages/lib/src/omr.rs:339-448 (minus imread / imwrite)
 //   imgproc::canny / imgproc::hough_lines_p      call sites hough.rs:27-43, omr.rs:236-253
 //
-// The image work (Canny, point list, progressive probabilistic Hough, the O(n^2) vote of large line
-// sets) runs on the GPU (hough.hip).  The host builds the 180-entry trigonometric / walk tables
-// (double cos / sin -> float, exactly hough.cpp's expressions), turns the segments into angles with
-// libm atan2f / fmodf (what Rust's f32::atan2 and % call) and applies the reference's selection
-// rules.  No CPU fallback: without a HIP device every entry point returns -217.
+// One chain of stages (hough_host.hpp) serves every entry point; a per-call form is
+// the batch form with n = 1 on an uploaded image.  The image work (Canny, point list, progressive
+// probabilistic Hough, the O(n^2) votes) runs on the GPU (hough.hip).  The host builds the 180-entry
+// trigonometric / walk tables (double cos / sin -> float, exactly hough.cpp's expressions), turns the
+// segments into angles with libm (hough_select.hpp) and applies omr.rs's selection rule.  No CPU
+// fallback: without a HIP device every entry point returns -217.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
-#include <thread>
 #include <vector>
 
 #include "../../include/omrdeskew.h"
@@ -32,7 +32,7 @@ using namespace omr::hh;
 namespace omr {
 namespace hh {
 
-// omr_hough_set_scans_in_flight(): 0 = the default (see ppht_device)
+// omr_hough_set_scans_in_flight(): 0 = the default (launch_ppht: one workgroup per scan)
 std::atomic<int> g_scans_in_flight{0};
 
 const uint8_t kLinedBgr[3] = {186, 88, 255};  // Scalar(186, 88, 255, 0): hough.rs:59, fft.rs:209
@@ -176,109 +176,38 @@ static int ppht_launch(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, 
     return OMR_OK;
 }
 
-// HoughLinesP on n device-resident edge images -> per-scan segments on the host
-int ppht_device(uint8_t *d_edges, int32_t *d_rowcnt, int rows, int cols, int n, const HoughParams &hp, hipStream_t s,
-                std::vector<std::vector<int32_t>> *lines_out)
+// HoughLinesP -> packed segment list (hough_host.hpp).  d_over and the PPHT run are released on every return without a
+// wait of their own: the caller's PoolScope makes that a drain of `s`
+int segments_from_edges(uint8_t *d_edges, int32_t *d_rowcnt, int n, int rows, int cols, const HoughParams &hp, hipStream_t s,
+                        BatchSegments *seg)
 {
     PphtRun run;
     int rc = ppht_launch(d_edges, d_rowcnt, rows, cols, n, hp, s, &run);
     if (rc) return rc;
-    const DevBuf &lines = run.lines, &nlines = run.nlines;
-    const int cap = run.cap;
-    std::vector<int32_t> nl((size_t)n);
-    OMR_HIP(hipMemcpyAsync(nl.data(), nlines.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    // slots -> offsets (one small download) -> packed list (one download)
+    DevBuf d_over;
+    DevBuf &d_off = seg->d_off, &d_packed = seg->d_packed;
+    std::vector<int32_t> &off = seg->off;
+    off.assign((size_t)n + 1, 0);
+    seg->lines.clear();
+    int32_t over[2] = {0, 0};
+    OMR_HIP(d_off.alloc(sizeof(int32_t) * off.size()));
+    OMR_HIP(d_over.alloc(sizeof(over)));
+    OMR_HIP(hipMemsetAsync(d_over.p, 0, sizeof(over), s));
+    OMR_HIP(launch_ppht_offsets(run.nlines.as<int32_t>(), n, run.cap, d_off.as<int32_t>(), d_over.as<int32_t>(), s));
+    OMR_HIP(hipMemcpyAsync(off.data(), d_off.p, sizeof(int32_t) * off.size(), hipMemcpyDeviceToHost, s));
+    OMR_HIP(hipMemcpyAsync(over, d_over.p, sizeof(over), hipMemcpyDeviceToHost, s));
     OMR_HIP(hipStreamSynchronize(s));
-    lines_out->assign((size_t)n, {});
-    for (int i = 0; i < n; i++) {
-        if (nl[i] > cap) return fail(OMR_ERR_NOMEM, "HoughLinesP: %d segments exceed the buffer of %d", nl[i], cap);
-        (*lines_out)[i].resize((size_t)nl[i] * 4);
-        if (nl[i])
-            OMR_HIP(hipMemcpyAsync((*lines_out)[i].data(), lines.as<int32_t>() + (size_t)i * cap * 4,
-                                   sizeof(int32_t) * 4 * (size_t)nl[i], hipMemcpyDeviceToHost, s));
+    if (over[0]) return fail(OMR_ERR_NOMEM, "HoughLinesP: %d segments exceed the buffer of %d", over[0], run.cap);
+    if (over[1]) return fail(OMR_ERR_NOMEM, "HoughLinesP: the batch's segments exceed a list of 2^31 - 1");
+    const size_t total = seg->total();
+    if (total > 0) {
+        seg->lines.resize(total * 4);
+        OMR_HIP(d_packed.alloc(sizeof(int32_t) * 4 * total));
+        OMR_HIP(launch_ppht_pack(run.lines.as<int32_t>(), run.cap, d_off.as<int32_t>(), n, seg->max_count(), d_packed.as<int32_t>(), s));
+        OMR_HIP(hipMemcpyAsync(seg->lines.data(), d_packed.p, sizeof(int32_t) * 4 * total, hipMemcpyDeviceToHost, s));
+        OMR_HIP(hipStreamSynchronize(s));
     }
-    OMR_HIP(hipStreamSynchronize(s));
-    return OMR_OK;
-}
-
-// hough.rs:50-68 / omr.rs:257-267
-static void line_angles(const int32_t *l, size_t n, float *ang)
-{
-    const float pi32 = 3.14159274101257324f;  // std::f32::consts::PI
-    for (size_t i = 0; i < n; i++) {
-        const float x1 = (float)l[4 * i], y1 = (float)l[4 * i + 1], x2 = (float)l[4 * i + 2], y2 = (float)l[4 * i + 3];
-        float angle = atan2f(y2 - y1, x2 - x1) * 180.0f / pi32;
-        ang[i] = fmodf(angle, 45.0f);
-    }
-}
-void line_angles(const std::vector<int32_t> &l, std::vector<float> *ang)
-{
-    ang->resize(l.size() / 4);
-    line_angles(l.data(), l.size() / 4, ang->data());
-}
-
-// counts[i] = #{j : |a_i - a_j| < 0.1}: on the host for small sets, on the GPU otherwise
-int vote_counts(const std::vector<float> &ang, bool as_f64, hipStream_t s, std::vector<int32_t> *counts)
-{
-    const int n = (int)ang.size();
-    counts->assign((size_t)n, 0);
-    if (n <= 2048) {
-        for (int i = 0; i < n; i++) {
-            int c = 0;
-            if (as_f64) {
-                for (int j = 0; j < n; j++) c += fabs((double)ang[i] - (double)ang[j]) < 0.1;
-            } else {
-                for (int j = 0; j < n; j++) c += fabsf(ang[i] - ang[j]) < 0.1f;
-            }
-            (*counts)[i] = c;
-        }
-        return OMR_OK;
-    }
-    DevBuf da, dc;
-    OMR_HIP(da.alloc(sizeof(float) * (size_t)n));
-    OMR_HIP(dc.alloc(sizeof(int32_t) * (size_t)n));
-    OMR_HIP(hipMemcpyAsync(da.p, ang.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-    OMR_HIP(launch_angle_votes(da.as<float>(), n, as_f64 ? 1 : 0, dc.as<int32_t>(), s));
-    OMR_HIP(hipMemcpyAsync(counts->data(), dc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    OMR_HIP(hipStreamSynchronize(s));
-    return OMR_OK;
-}
-
-// hough.rs:70-92: strict ">" keeps the first maximum
-int select_hough_rs(const std::vector<float> &ang, const std::vector<int32_t> &cnt, double *angle)
-{
-    if (ang.empty()) return fail(OMR_ERR_ASSERT, "no line segment found (the reference panics on angles[0], hough.rs:74)");
-    float target = ang[0];
-    int best = 0;
-    for (size_t i = 0; i < ang.size(); i++)
-        if (cnt[i] > best) {
-            target = ang[i];
-            best = cnt[i];
-        }
-    *angle = (double)target;
-    return OMR_OK;
-}
-
-// omr.rs:268-301
-int select_omr_rs(const std::vector<float> &ang, const std::vector<int32_t> &cnt, double *angle, int32_t *status,
-                  double *candidates, int32_t cand_cap, int32_t *cand_len)
-{
-    if (ang.empty()) return fail(OMR_ERR_ASSERT, "no line segment found (the reference panics on angles[0], omr.rs:272)");
-    double target = (double)ang[0];
-    int best = 0, nc = 0;
-    for (size_t i = 0; i < ang.size(); i++) {
-        if (cnt[i] > best) {
-            target = (double)ang[i];
-            best = cnt[i];
-            if (candidates && cand_cap > 0) candidates[0] = target;
-            nc = 1;
-        } else if (cnt[i] == best) {
-            if (candidates && nc < cand_cap) candidates[nc] = (double)ang[i];
-            nc++;
-        }
-    }
-    *angle = target;
-    if (cand_len) *cand_len = nc;
-    if (status) *status = nc == 0 ? OMR_STATUS_NOT_A_RESULT : (nc == 1 ? OMR_STATUS_BELIEVED : OMR_STATUS_NEED_CHECK);
     return OMR_OK;
 }
 
@@ -288,25 +217,6 @@ int upload(const omr_image *im, DevBuf *buf, hipStream_t s)
     const size_t row = (size_t)im->cols * im->channels;
     OMR_HIP(buf->alloc(row * (size_t)im->rows));
     return upload_rows(buf->p, row, im->data, (size_t)im->step_bytes, row, (size_t)im->rows, s);
-}
-
-// Canny + HoughLinesP of n device-resident scans -> per-scan segments.  keep_edges: receives a copy of the edge maps
-// (packed, n x rows x cols), taken before HoughLinesP, which erases the points it has used from its input
-int edges_lines_device(const uint8_t *d_src, int64_t scan_stride, int64_t step, int rows, int cols, int cn, int n,
-                       const HoughParams &hp, hipStream_t s, std::vector<std::vector<int32_t>> *lines, DevBuf *keep_edges)
-{
-    DevBuf map, flag, rowcnt;
-    OMR_HIP(map.alloc((size_t)n * rows * cols));
-    OMR_HIP(flag.alloc(sizeof(int)));
-    OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
-    int rc = canny_device(d_src, scan_stride, step, rows, cols, cn, n, hp.low, hp.high, map.as<uint8_t>(), flag.as<int>(), s,
-                          rowcnt.as<int32_t>());
-    if (rc) return rc;
-    if (keep_edges) {
-        OMR_HIP(keep_edges->alloc(map.bytes));
-        OMR_HIP(hipMemcpyAsync(keep_edges->p, map.p, (size_t)n * rows * cols, hipMemcpyDeviceToDevice, s));
-    }
-    return ppht_device(map.as<uint8_t>(), rowcnt.as<int32_t>(), rows, cols, n, hp, s, lines);
 }
 
 // ---- the line picture (lined.hip): every argument rule of the omr_lined_picture* entry points, before any device work
@@ -366,27 +276,14 @@ int lined_device(const uint8_t *d_edges, int n, int64_t estride, int64_t estep, 
     return OMR_OK;
 }
 
-// the picture of one packed device edge map with host segments, as a fresh host image
-int lined_to_host(const uint8_t *d_edges, int rows, int cols, const int32_t *lines, int n_lines, const uint8_t bgr[3],
-                  hipStream_t s, omr_image_owned *picture)
+// a packed device picture as a fresh host image
+int picture_to_host(const uint8_t *d_pic, int rows, int cols, hipStream_t s, omr_image_owned *picture)
 {
-    const int32_t off[2] = {0, n_lines};
-    DevBuf dl, out;
-    if (n_lines > 0) {
-        OMR_HIP(dl.alloc(sizeof(int32_t) * 4 * (size_t)n_lines));
-        OMR_HIP(hipMemcpyAsync(dl.p, lines, sizeof(int32_t) * 4 * (size_t)n_lines, hipMemcpyHostToDevice, s));
-    }
     const size_t row = (size_t)cols * 3;
-    OMR_HIP(out.alloc(row * rows));
-    int rc = lined_device(d_edges, 1, 0, cols, rows, cols, dl.as<int32_t>(), off, bgr, out.as<uint8_t>(), 0, (int64_t)row, s);
-    if (rc) return rc;
-    picture->rows = rows;
-    picture->cols = cols;
-    picture->channels = 3;
-    picture->step_bytes = (int64_t)row;
-    picture->data = (uint8_t *)malloc(row * rows);
-    if (!picture->data) return fail(OMR_ERR_NOMEM, "out of host memory");
-    rc = staged_d2h(picture->data, out.p, row * rows, s);
+    uint8_t *data = (uint8_t *)malloc(row * rows);
+    if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
+    *picture = omr_image_owned{data, rows, cols, 3, (int64_t)row};
+    int rc = staged_d2h(data, d_pic, row * rows, s);
     if (rc) omr_image_free(picture);
     return rc;
 }
@@ -412,14 +309,12 @@ int hough_batch_check(const void *d_scans, int n, int64_t stride, int rows, int 
     return OMR_OK;
 }
 
-// Canny -> HoughLinesP -> packed segment list of a batch (hough_host.hpp).  map, flag, rowcnt, d_over and the PPHT run
-// are released on every return without a wait of their own: the caller's PoolScope makes that a drain of `s`
+// Canny -> the kept edges -> the segment stage (hough_host.hpp).  map, flag and rowcnt are released as that stage's buffers
 int batch_segments_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
                           const HoughParams &hp, bool keep_edges, hipStream_t s, BatchSegments *seg)
 {
     const size_t img = (size_t)rows * cols;
     DevBuf map, flag, rowcnt;
-    DevBuf &edges = seg->edges, &d_off = seg->d_off, &d_packed = seg->d_packed;
     OMR_HIP(map.alloc((size_t)n * img));
     OMR_HIP(flag.alloc(sizeof(int)));
     OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)n * rows));
@@ -427,36 +322,22 @@ int batch_segments_device(const uint8_t *d_scans, int n, int64_t stride, int64_t
                           rowcnt.as<int32_t>());
     if (rc) return rc;
     if (keep_edges) {  // the pictures' background: HoughLinesP erases the points it has used from its input
-        OMR_HIP(edges.alloc(map.bytes));
-        OMR_HIP(hipMemcpyAsync(edges.p, map.p, (size_t)n * img, hipMemcpyDeviceToDevice, s));
+        OMR_HIP(seg->edges.alloc(map.bytes));
+        OMR_HIP(hipMemcpyAsync(seg->edges.p, map.p, (size_t)n * img, hipMemcpyDeviceToDevice, s));
     }
-    PphtRun run;
-    if ((rc = ppht_launch(map.as<uint8_t>(), rowcnt.as<int32_t>(), rows, cols, n, hp, s, &run))) return rc;
-    // slots -> offsets (one small download) -> packed list (one download)
-    DevBuf d_over;
-    std::vector<int32_t> &off = seg->off;
-    off.assign((size_t)n + 1, 0);
-    seg->lines.clear();
-    int32_t over[2] = {0, 0};
-    OMR_HIP(d_off.alloc(sizeof(int32_t) * off.size()));
-    OMR_HIP(d_over.alloc(sizeof(over)));
-    OMR_HIP(hipMemsetAsync(d_over.p, 0, sizeof(over), s));
-    OMR_HIP(launch_ppht_offsets(run.nlines.as<int32_t>(), n, run.cap, d_off.as<int32_t>(), d_over.as<int32_t>(), s));
-    OMR_HIP(hipMemcpyAsync(off.data(), d_off.p, sizeof(int32_t) * off.size(), hipMemcpyDeviceToHost, s));
-    OMR_HIP(hipMemcpyAsync(over, d_over.p, sizeof(over), hipMemcpyDeviceToHost, s));
-    OMR_HIP(hipStreamSynchronize(s));
-    if (over[0]) return fail(OMR_ERR_NOMEM, "HoughLinesP: %d segments exceed the buffer of %d", over[0], run.cap);
-    if (over[1]) return fail(OMR_ERR_NOMEM, "HoughLinesP: the batch's segments exceed a list of 2^31 - 1");
-    const size_t total = seg->total();
-    int max_n = 0;
-    for (int i = 0; i < n; i++) max_n = std::max(max_n, seg->count(i));
-    if (total > 0) {
-        seg->lines.resize(total * 4);
-        OMR_HIP(d_packed.alloc(sizeof(int32_t) * 4 * total));
-        OMR_HIP(launch_ppht_pack(run.lines.as<int32_t>(), run.cap, d_off.as<int32_t>(), n, max_n, d_packed.as<int32_t>(), s));
-        OMR_HIP(hipMemcpyAsync(seg->lines.data(), d_packed.p, sizeof(int32_t) * 4 * total, hipMemcpyDeviceToHost, s));
-        OMR_HIP(hipStreamSynchronize(s));
-    }
+    return segments_from_edges(map.as<uint8_t>(), rowcnt.as<int32_t>(), n, rows, cols, hp, s, seg);
+}
+
+// the f32 angles of the whole packed list: on the host (libm atan2f / fmodf, as the reference: the device's are not the
+// host's bit for bit), then uploaded for the vote.  Enqueues only; nothing to do without a segment
+static int segment_angles(const BatchSegments &seg, hipStream_t s, std::vector<float> *ang, DevBuf *d_ang)
+{
+    const size_t total = seg.total();
+    ang->resize(total);
+    if (total == 0) return OMR_OK;
+    host_fan_out(total, 4096, [&](size_t lo, size_t hi) { line_angles(seg.lines.data() + 4 * lo, hi - lo, ang->data() + lo); });
+    OMR_HIP(d_ang->alloc(sizeof(float) * total));
+    OMR_HIP(hipMemcpyAsync(d_ang->p, ang->data(), sizeof(float) * total, hipMemcpyHostToDevice, s));
     return OMR_OK;
 }
 
@@ -470,18 +351,14 @@ static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, in
     BatchSegments seg;
     int rc = batch_segments_device(d_scans, n, stride, step, rows, cols, cn, hp, d_lined != nullptr, s, &seg);
     if (rc) return rc;
-    const std::vector<int32_t> &off = seg.off, &lines = seg.lines;
+    const std::vector<int32_t> &off = seg.off;
     const DevBuf &edges = seg.edges, &d_off = seg.d_off, &d_packed = seg.d_packed;
-    const size_t total = seg.total();
     std::vector<int32_t> win((size_t)n, -1);
-    std::vector<float> ang(total);
-    if (total > 0) {
-        // the angles on the host (libm atan2f / fmodf, as the reference: the device's are not the host's bit for bit)
-        host_fan_out(total, 4096, [&](size_t lo, size_t hi) { line_angles(lines.data() + 4 * lo, hi - lo, ang.data() + lo); });
-        DevBuf d_ang, d_win;
-        OMR_HIP(d_ang.alloc(sizeof(float) * total));
+    std::vector<float> ang;
+    DevBuf d_ang, d_win;
+    if ((rc = segment_angles(seg, s, &ang, &d_ang))) return rc;
+    if (seg.total() > 0) {  // hough.rs:70-92 is vote_select_kernel alone
         OMR_HIP(d_win.alloc(sizeof(int32_t) * (size_t)n));
-        OMR_HIP(hipMemcpyAsync(d_ang.p, ang.data(), sizeof(float) * total, hipMemcpyHostToDevice, s));
         OMR_HIP(launch_vote_select(d_ang.as<float>(), d_off.as<int32_t>(), n, d_win.as<int32_t>(), s));
         OMR_HIP(hipMemcpyAsync(win.data(), d_win.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
         OMR_HIP(hipStreamSynchronize(s));
@@ -516,57 +393,55 @@ static int hough_angles_device(const uint8_t *d_scans, int n, int64_t stride, in
     return OMR_OK;
 }
 
-// omr.rs:231-302 for n device-resident scans of one shape: the body of omr_edges_detection_batch_device (and, on the
-// edge pictures of the log spectra, the last stage of omr_fourier_transform_batch_device)
-int edges_detection_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
-                           const HoughParams &hp, double *angles, int32_t *status, int32_t *n_lines, hipStream_t s)
+// omr.rs's vote stage (hough_host.hpp)
+int omr_rs_votes(const BatchSegments &seg, hipStream_t s, std::vector<float> *ang, std::vector<int32_t> *cnt)
 {
-    std::vector<std::vector<int32_t>> lines;
-    int rc;
-    if ((rc = edges_lines_device(d_scans, stride, step, rows, cols, cn, n, hp, s, &lines))) return rc;
-    // angles on host threads (libm atan2f, as the reference), one vote launch for the whole batch
-    std::vector<std::vector<float>> ang((size_t)n);
-    {
-        const int nt = (int)std::max(1u, std::min<unsigned>((unsigned)n, std::min(std::thread::hardware_concurrency(), 32u)));
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; t++)
-            pool.emplace_back([&, t]() {
-                for (int i = t; i < n; i += nt) line_angles(lines[i], &ang[i]);
-            });
-        for (auto &th : pool) th.join();
+    const size_t total = seg.total();
+    DevBuf d_ang, d_cnt;
+    int rc = segment_angles(seg, s, ang, &d_ang);
+    if (rc) return rc;
+    cnt->resize(total);
+    if (total == 0) return OMR_OK;
+    OMR_HIP(d_cnt.alloc(sizeof(int32_t) * total));
+    OMR_HIP(launch_angle_votes_batch(d_ang.as<float>(), seg.d_off.as<int32_t>(), seg.scans(), seg.max_count(), d_cnt.as<int32_t>(), s));
+    OMR_HIP(hipMemcpyAsync(cnt->data(), d_cnt.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, s));
+    OMR_HIP(hipStreamSynchronize(s));
+    return OMR_OK;
+}
+
+// omr.rs:231-302 per scan (hough_host.hpp)
+int edges_detection_device(const uint8_t *d_scans, int n, int64_t stride, int64_t step, int rows, int cols, int cn,
+                           const HoughParams &hp, double *angles, int32_t *status, int32_t *n_lines, hipStream_t s,
+                           double *candidates, int32_t cand_cap, int32_t *cand_len)
+{
+    PoolScope scope(s);
+    BatchSegments seg;
+    std::vector<float> ang;
+    std::vector<int32_t> cnt;
+    int rc = batch_segments_device(d_scans, n, stride, step, rows, cols, cn, hp, false, s, &seg);
+    if (rc || (rc = omr_rs_votes(seg, s, &ang, &cnt))) return rc;
+    for (int i = 0; i < n; i++) {  // no segment: the reference would panic (quirk B11), select_omr_rs says "not a result"
+        const size_t o = (size_t)seg.off[(size_t)i];
+        if (n_lines) n_lines[i] = seg.count(i);
+        select_omr_rs(ang.data() + o, cnt.data() + o, seg.count(i), &angles[i], status ? &status[i] : nullptr,
+                      i == 0 ? candidates : nullptr, cand_cap, i == 0 ? cand_len : nullptr);
     }
-    std::vector<int64_t> off((size_t)n + 1, 0);
-    int max_n = 0;
-    for (int i = 0; i < n; i++) {
-        off[i + 1] = off[i] + (int64_t)ang[i].size();
-        max_n = std::max(max_n, (int)ang[i].size());
-    }
-    std::vector<int32_t> cnt_all((size_t)off[n]);
-    if (off[n] > 0) {
-        std::vector<float> flat((size_t)off[n]);
-        for (int i = 0; i < n; i++) std::copy(ang[i].begin(), ang[i].end(), flat.begin() + off[i]);
-        DevBuf da, dc, doff;
-        OMR_HIP(da.alloc(sizeof(float) * flat.size()));
-        OMR_HIP(dc.alloc(sizeof(int32_t) * flat.size()));
-        OMR_HIP(doff.alloc(sizeof(int64_t) * off.size()));
-        OMR_HIP(hipMemcpyAsync(da.p, flat.data(), sizeof(float) * flat.size(), hipMemcpyHostToDevice, s));
-        OMR_HIP(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, s));
-        OMR_HIP(launch_angle_votes_batch(da.as<float>(), doff.as<int64_t>(), n, max_n, 1, dc.as<int32_t>(), s));
-        OMR_HIP(hipMemcpyAsync(cnt_all.data(), dc.p, sizeof(int32_t) * flat.size(), hipMemcpyDeviceToHost, s));
-        OMR_HIP(hipStreamSynchronize(s));
-    }
-    for (int i = 0; i < n; i++) {
-        if (n_lines) n_lines[i] = (int32_t)ang[i].size();
-        if (ang[i].empty()) {  // the reference would panic (quirk B11): report "not a result"
-            angles[i] = 0.0;
-            if (status) status[i] = OMR_STATUS_NOT_A_RESULT;
-            continue;
-        }
-        std::vector<int32_t> cnt(cnt_all.begin() + off[i], cnt_all.begin() + off[i + 1]);
-        int32_t st = 0, nc = 0;
-        if ((rc = select_omr_rs(ang[i], cnt, &angles[i], &st, nullptr, 0, &nc))) return rc;
-        if (status) status[i] = st;
-    }
+    return OMR_OK;
+}
+
+int edges_detection_one(const uint8_t *d_src, int rows, int cols, int cn, const HoughParams &hp, hipStream_t s, double *angle,
+                        int32_t *status, double *candidates, int32_t cand_cap, int32_t *cand_len)
+{
+    double a = 0;
+    int32_t st = 0, nl = 0, nc = 0;
+    std::vector<double> cand((size_t)std::max(cand_cap, 0));
+    int rc = edges_detection_device(d_src, 1, 0, (int64_t)cols * cn, rows, cols, cn, hp, &a, &st, &nl, s, cand.data(), cand_cap, &nc);
+    if (rc) return rc;
+    if (nl == 0) return fail(OMR_ERR_ASSERT, "no line segment found (the reference panics on angles[0], omr.rs:272)");
+    *angle = a;
+    if (status) *status = st;
+    if (cand_len) *cand_len = nc;
+    if (candidates) std::copy_n(cand.begin(), std::min(nc, std::max(cand_cap, 0)), candidates);
     return OMR_OK;
 }
 
@@ -578,12 +453,7 @@ int download_pictures(const uint8_t *d_pics, int m, int rows, int cols, const st
     return on_threads(m, [&](hipStream_t s, int lo, int hi) -> int {
         for (int j = lo; j < hi; j++) {
             if (skip && skip[j] != OMR_OK) continue;
-            omr_image_owned &o = lined[members[(size_t)(j0 + j)]];
-            uint8_t *data = (uint8_t *)malloc(pic);
-            if (!data) return fail(OMR_ERR_NOMEM, "out of host memory");
-            o = omr_image_owned{data, rows, cols, 3, (int64_t)cols * 3};
-            int rc1 = staged_d2h(o.data, d_pics + (size_t)j * pic, pic, s);
-            if (rc1) return rc1;
+            if (int rc1 = picture_to_host(d_pics + (size_t)j * pic, rows, cols, s, &lined[members[(size_t)(j0 + j)]])) return rc1;
         }
         return OMR_OK;
     });
@@ -642,17 +512,15 @@ int omr_hough_lines_p(const omr_image *edges, double rho, double theta, int32_t 
     if ((rc = upload(edges, &img, st.s))) return rc;
     OMR_HIP(rowcnt.alloc(sizeof(int32_t) * (size_t)edges->rows));
     OMR_HIP(launch_edges_rowcount(img.as<uint8_t>(), edges->rows, edges->cols, 1, 0, rowcnt.as<int32_t>(), st.s));
-    HoughParams hp;
+    HoughParams hp = hough_params(min_line_length, max_line_gap);
     hp.rho = rho;
     hp.theta = theta;
     hp.threshold = threshold;
-    hp.min_line_length = min_line_length;
-    hp.max_line_gap = max_line_gap;
-    std::vector<std::vector<int32_t>> out;
-    if ((rc = ppht_device(img.as<uint8_t>(), rowcnt.as<int32_t>(), edges->rows, edges->cols, 1, hp, st.s, &out))) return rc;
-    const int n = (int)(out[0].size() / 4);
+    BatchSegments seg;  // the segment stage's edges half, n = 1
+    if ((rc = segments_from_edges(img.as<uint8_t>(), rowcnt.as<int32_t>(), 1, edges->rows, edges->cols, hp, st.s, &seg))) return rc;
+    const int n = seg.count(0);
     *n_lines = n;
-    if (lines && cap > 0) memcpy(lines, out[0].data(), sizeof(int32_t) * 4 * (size_t)std::min(n, (int)cap));
+    if (lines && cap > 0 && n > 0) memcpy(lines, seg.lines.data(), sizeof(int32_t) * 4 * (size_t)std::min(n, (int)cap));
     return OMR_OK;
 }
 
@@ -668,23 +536,21 @@ static int angle_with_hough(const omr_image *gray, double min_line_length, doubl
     if ((rc = have_device())) return rc;
     LeasedStream st;
     if ((rc = st.create())) return rc;
-    DevBuf in;
+    const int rows = gray->rows, cols = gray->cols;
+    const int64_t pic = (int64_t)cols * 3 * rows;
+    DevBuf in, d_pic;
     if ((rc = upload(gray, &in, st.s))) return rc;
-    HoughParams hp;
-    hp.min_line_length = min_line_length;
-    hp.max_line_gap = max_line_gap;
-    std::vector<std::vector<int32_t>> lines;
-    DevBuf edges;  // the picture's background: the edge map as Canny left it
-    if ((rc = edges_lines_device(in.as<uint8_t>(), 0, (int64_t)gray->cols * gray->channels, gray->rows, gray->cols,
-                                 gray->channels, 1, hp, st.s, &lines, lined ? &edges : nullptr)))
+    if (lined) OMR_HIP(d_pic.alloc((size_t)pic));
+    double angle = 0.0;
+    int32_t code = OMR_OK;
+    if ((rc = hough_angles_device(in.as<uint8_t>(), 1, 0, (int64_t)cols * gray->channels, rows, cols, gray->channels,
+                                  hough_params(min_line_length, max_line_gap), &angle, &code, nullptr, d_pic.as<uint8_t>(), pic,
+                                  (int64_t)cols * 3, st.s)))
         return rc;
-    std::vector<float> ang;
-    std::vector<int32_t> cnt;
-    line_angles(lines[0], &ang);
-    if ((rc = vote_counts(ang, false, st.s, &cnt))) return rc;
-    if ((rc = select_hough_rs(ang, cnt, angle_out)) || !lined) return rc;  // no segment: the reference panics before its imwrite
-    return lined_to_host(edges.as<uint8_t>(), gray->rows, gray->cols, lines[0].data(), (int)(lines[0].size() / 4), kLinedBgr,
-                         st.s, lined);
+    if (code)  // the reference panics before its imwrite: no picture
+        return fail(code, "no line segment found (the reference panics on angles[0], hough.rs:74)");
+    *angle_out = angle;
+    return lined ? picture_to_host(d_pic.as<uint8_t>(), rows, cols, st.s, lined) : OMR_OK;
 }
 
 int omr_get_angle_with_hough(const omr_image *gray, double min_line_length, double max_line_gap, double *angle_out)
@@ -706,11 +572,9 @@ int omr_hough_angles_batch_device(const uint8_t *d_scans, int32_t n, int64_t sca
     int err = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, angles && rc, d_lined,
                                 lined_stride_bytes, lined_step);
     if (err || (err = have_device())) return err;
-    HoughParams hp;
-    hp.min_line_length = min_line_length;
-    hp.max_line_gap = max_line_gap;
-    return hough_angles_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels, hp, angles, rc, n_lines, d_lined,
-                               lined_stride_bytes, lined_step, (hipStream_t)stream);
+    return hough_angles_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels,
+                               hough_params(min_line_length, max_line_gap), angles, rc, n_lines, d_lined, lined_stride_bytes,
+                               lined_step, (hipStream_t)stream);
 }
 
 // the Hough leg of the reference's benchmark on device-resident scans: gray, this file's batch detector, rotate_mat of the
@@ -784,9 +648,7 @@ int omr_get_angles_with_hough_batch(const omr_image *grays, int32_t n, double mi
     // omr_get_angle_with_hough's checks, for every image before any device work
     int err = bucket_by_shape(grays, n, [](const omr_image &im) { return check_image(&im, cn_canny); }, &b);
     if (err || (err = have_device())) return err;
-    HoughParams hp;
-    hp.min_line_length = min_line_length;
-    hp.max_line_gap = max_line_gap;
+    const HoughParams hp = hough_params(min_line_length, max_line_gap);
     // angles and codes go to the caller's arrays only when the whole call has succeeded
     std::vector<double> ang((size_t)n);
     std::vector<int32_t> rcs((size_t)n);
@@ -838,9 +700,18 @@ int omr_lined_picture(const omr_image *edges, const int32_t *lines, int32_t n_li
     if ((rc = have_device())) return rc;
     LeasedStream st;
     if ((rc = st.create())) return rc;
-    DevBuf in;
+    const int32_t off[2] = {0, n_lines};
+    DevBuf in, d_lines, d_pic;
     if ((rc = upload(edges, &in, st.s))) return rc;
-    return lined_to_host(in.as<uint8_t>(), edges->rows, edges->cols, lines, n_lines, bgr, st.s, picture);
+    if (n_lines > 0) {
+        OMR_HIP(d_lines.alloc(sizeof(int32_t) * 4 * (size_t)n_lines));
+        OMR_HIP(hipMemcpyAsync(d_lines.p, lines, sizeof(int32_t) * 4 * (size_t)n_lines, hipMemcpyHostToDevice, st.s));
+    }
+    OMR_HIP(d_pic.alloc((size_t)edges->cols * 3 * edges->rows));
+    if ((rc = lined_device(in.as<uint8_t>(), 1, 0, edges->cols, edges->rows, edges->cols, d_lines.as<int32_t>(), off, bgr,
+                           d_pic.as<uint8_t>(), 0, (int64_t)edges->cols * 3, st.s)))
+        return rc;
+    return picture_to_host(d_pic.as<uint8_t>(), edges->rows, edges->cols, st.s, picture);
 }
 
 int omr_get_result_from_edges_detection(const omr_image *src, double edges_min_line_length, double edges_max_line_gap,
@@ -856,36 +727,19 @@ int omr_get_result_from_edges_detection(const omr_image *src, double edges_min_l
     if ((rc = st.create())) return rc;
     DevBuf in;
     if ((rc = upload(src, &in, st.s))) return rc;
-    HoughParams hp;
-    hp.min_line_length = edges_min_line_length;
-    hp.max_line_gap = edges_max_line_gap;
-    std::vector<std::vector<int32_t>> lines;
-    if ((rc = edges_lines_device(in.as<uint8_t>(), 0, (int64_t)src->cols * src->channels, src->rows, src->cols,
-                                 src->channels, 1, hp, st.s, &lines)))
-        return rc;
-    std::vector<float> ang;
-    std::vector<int32_t> cnt;
-    line_angles(lines[0], &ang);
-    if ((rc = vote_counts(ang, true, st.s, &cnt))) return rc;
-    return select_omr_rs(ang, cnt, angle, status, candidates, cand_cap, cand_len);
+    return edges_detection_one(in.as<uint8_t>(), src->rows, src->cols, src->channels,
+                               hough_params(edges_min_line_length, edges_max_line_gap), st.s, angle, status, candidates, cand_cap,
+                               cand_len);
 }
 
 int omr_edges_detection_batch_device(const uint8_t *d_scans, int32_t n, int64_t scan_stride_bytes, int32_t rows,
                                      int32_t cols, int32_t channels, int64_t step_bytes, double min_line_length,
                                      double max_line_gap, double *angles, int32_t *status, int32_t *n_lines, void *stream)
 {
-    clear_error();
-    if (!d_scans || !angles || n <= 0) return fail(OMR_ERR_BADARG, "null pointer or empty batch");
-    if (rows <= 0 || cols <= 0 || rows >= 32767 || cols >= 32767) return fail(OMR_ERR_ASSERT, "bad image shape");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(OMR_ERR_ASSERT, "1, 3 or 4 channels");
-    if (step_bytes < (int64_t)cols * channels) return fail(OMR_ERR_BADARG, "step_bytes too small");
-    int rc = have_device();
-    if (rc) return rc;
-    HoughParams hp;
-    hp.min_line_length = min_line_length;
-    hp.max_line_gap = max_line_gap;
-    return edges_detection_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels, hp, angles, status, n_lines,
-                                  (hipStream_t)stream);
+    int rc = hough_batch_check(d_scans, n, scan_stride_bytes, rows, cols, channels, step_bytes, angles != nullptr, nullptr, 0, 0);
+    if (rc || (rc = have_device())) return rc;
+    return edges_detection_device(d_scans, n, scan_stride_bytes, step_bytes, rows, cols, channels,
+                                  hough_params(min_line_length, max_line_gap), angles, status, n_lines, (hipStream_t)stream);
 }
 
 // omr.rs:351-399
@@ -943,20 +797,10 @@ int omr_correct_default(const omr_image *src, uint16_t projection_max_angle, dou
         *rotate_angle = pa;
         *need_check = 0;
     } else {  // omr.rs:361-402
-        HoughParams hp;
-        hp.min_line_length = hough_min_line_length;
-        hp.max_line_gap = hough_max_line_gap;
-        std::vector<std::vector<int32_t>> lines;
-        if ((rc = edges_lines_device(d_src, 0, (int64_t)src->cols * src->channels, src->rows, src->cols, src->channels, 1, hp,
-                                     st.s, &lines)))
-            return rc;
-        std::vector<float> ang;
-        std::vector<int32_t> cnt;
-        line_angles(lines[0], &ang);
-        if ((rc = vote_counts(ang, true, st.s, &cnt))) return rc;
         double ea = 0;
-        int32_t est = 0, en = 0;
-        if ((rc = select_omr_rs(ang, cnt, &ea, &est, nullptr, 0, &en))) return rc;
+        if ((rc = edges_detection_one(d_src, src->rows, src->cols, src->channels, hough_params(hough_min_line_length, hough_max_line_gap),
+                                      st.s, &ea, nullptr, nullptr, 0, nullptr)))
+            return rc;
         omr_correct_default_decision(pa, pst, pc.data(), std::min<int32_t>(pn, (int32_t)pc.size()), ea, rotate_angle,
                                      need_check);
     }

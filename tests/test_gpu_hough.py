@@ -182,8 +182,57 @@ def test_entry_points_are_reentrant(oracle):
     assert not errs, errs
 
 
+def _same_result(r, want):
+    ea, es, ec = want[:3]
+    assert np.float64(r.angle).view(np.uint64) == np.float64(ea).view(np.uint64) and int(r.status) == es
+    assert r.candidates.size == ec.size and (r.candidates.view(np.uint64) == ec.view(np.uint64)).all()
+
+
+def test_per_call_forms_on_many_segment_cards_against_the_oracle(oracle):
+    """The per-call forms run the batch stages with n = 1, so "batch == per call" alone would compare the code with
+    itself: on the (60, 4) cards of test_gpu_hough_batch (dozens of crossing segments a card, 200 x 253) both per-call
+    forms are held to the CPU oracle's Canny -> HoughLinesP -> vote -- hough.rs's angle bits, omr.rs's angle bits,
+    status and candidate list -- and the blank sheet to -215 from both."""
+    from test_gpu_hough_batch import BATCH, SHAPES, make_scan
+    rows, cols = SHAPES["odd"]
+    counts = []
+    for what in BATCH:
+        img = make_scan(rows, cols, 1, what)
+        lines = oracle.hough_lines_p(oracle.canny(img, 50.0, 150.0), 60.0, 4.0)
+        counts.append(len(lines))
+        if len(lines) == 0:
+            for call in (hough.get_angle_with_hough, omr.get_result_from_edges_detection):
+                with pytest.raises(oics.OmrError) as e:
+                    call(img, 60.0, 4.0)
+                assert e.value.code == -215
+            continue
+        e_ang, e_n = oracle.get_angle_with_hough(img, 60.0, 4.0)
+        assert e_n == len(lines)
+        assert np.float64(hough.get_angle_with_hough(img, 60.0, 4.0)).view(np.uint64) == np.float64(e_ang).view(np.uint64), what
+        want = oracle.get_result_from_edges_detection(img, 60.0, 4.0)
+        assert want[3] == len(lines)
+        _same_result(omr.get_result_from_edges_detection(img, 60.0, 4.0), want)
+    assert counts[0] == 0 and sum(1 for c in counts if c >= 16) >= 4, counts
+
+
+def test_more_than_2048_segments_of_one_scan_through_the_omr_rs_count(oracle):
+    """256 x 320 noise with (3, 1): 2980 segments on the CPU oracle, 950 of them candidates -- one scan's list is longer
+    than anything a host loop ever counted (2048).  Per call, and as scan 0 of a device batch of two beside a blank
+    sheet, against the oracle."""
+    import torch
+    rows, cols = 256, 320
+    img = np.random.Generator(np.random.PCG64(7)).integers(0, 256, size=(rows, cols), dtype=np.uint8)
+    want = oracle.get_result_from_edges_detection(img, 3.0, 1.0)
+    assert want[3] > 2048 and want[2].size > 2
+    _same_result(omr.get_result_from_edges_detection(img, 3.0, 1.0), want)
+    d = torch.from_numpy(np.stack([img, np.full((rows, cols), 255, np.uint8)])).to("cuda:0")
+    ang, st, nl = omr.edges_detection_batch_device(d.data_ptr(), 2, rows * cols, rows, cols, 1, cols, 3.0, 1.0)
+    assert list(nl) == [want[3], 0] and list(st) == [want[1], int(ResultStatus.NotAResult)]
+    assert np.float64(ang[0]).view(np.uint64) == np.float64(want[0]).view(np.uint64) and np.float64(ang[1]).view(np.uint64) == 0
+
+
 def test_large_line_sets_use_the_device_vote(oracle):
-    """More than 2048 segments: the O(n^2) +-0.1 degree vote runs on the GPU (angle_votes_kernel)."""
+    """More than 2048 segments: the O(n^2) +-0.1 degree votes run on the GPU (angle_votes_batch_kernel, vote_select_kernel)."""
     img, _ = card(1754, 1240, 12)
     ea, es, ec, en = oracle.get_result_from_edges_detection(img, 60.0, 20.0)
     assert en > 2048

@@ -123,7 +123,7 @@ def test_device_batch_votes():
 
 
 def test_large_segment_set_votes_on_the_device():
-    """more than 2048 segments: the count of angle_votes_kernel against the float64 vote"""
+    """more than 2048 segments: the count of angle_votes_batch_kernel against the float64 vote"""
     img = hc.dense_dashes()
     L, G = 5.0, 1.0
     E = hough.canny(img)
